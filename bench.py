@@ -10,6 +10,10 @@ filter) over the rank's shard of parameter draws, inputs already resident in HBM
 (N > 1) by the RCCL all-gather of per-draw logp/status.  Per-GPU shard is fixed (weak scaling):
 4096 draws of the SW-shaped workload (n = 40 variables, 7 shocks, 7 observables, T = 200;
 BASELINE.json configs[2]).  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the steps and prints the headline line.  `--full` adds everything else
+(CPU baseline and parity, the extra legs, the sustained run, per-kernel durations and the roofline block).
+`--dump-outputs DIR` writes the per-draw logp and status of the last timed step as DIR/logp.npy, DIR/status.npy.
 """
 from __future__ import annotations
 
@@ -393,11 +397,11 @@ def gensys_roofline(eng, call, nloc, n, n_lead):
 
 
 def second_order_leg(timeout=900):
-    """BASELINE configs[4] as a leg of the default line: a CHILD process runs `bench.py --workload sw_second_order` (1024 draws)
+    """BASELINE configs[4] as a leg of the --full line: a CHILD process runs `bench.py --workload sw_second_order` (1024 draws)
     before this process touches the GPU and its JSON line is embedded; None if it fails."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "sw_second_order", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "sw_second_order", "--steps", "3", "--warmup", "1", "--full",
            "--cpu-sample", "0", "--no-extras"]
     try:
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, check=False)
@@ -413,6 +417,27 @@ def second_order_leg(timeout=900):
         return leg
     except (subprocess.TimeoutExpired, OSError, ValueError) as exc:
         return {"error": str(exc)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per per-draw output of the last timed step.  A batch whose outputs would exceed
+    DUMP_LIMIT_BYTES in all is written as a fixed, seeded sample of draws, whose indices go to DIR/draw_index.npy."""
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as fh:  # a directory made here never shows up in `git status`
+            fh.write("*\n")
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (8 * (len(arrays) + 1))
+        idx = np.sort(np.random.default_rng(20261016).choice(n, keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["draw_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def spawn_ranks(n_ranks, argv, shared_gpu=False, timeout=None):
@@ -465,16 +490,23 @@ def main():
                     help="timed steps (default 800: ~1.2 s of timed region at 1.5 ms per step, long enough for an outside "
                          "observer -- rocm-smi sampling -- to see the GPU busy)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: CPU baseline and parity, the extra legs (full recursion, "
+                         "gensys, observe_jumps, conservative, gradient, two_streams, second_order, n80), the sustained run, "
+                         "per-kernel durations and the roofline block.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (per-draw logp and status, float64) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--batch-per-gpu", type=int, default=None,
                     help="draws per GPU; default: 4096 at --gpus 1 (BASELINE configs[2]), 8192 at --gpus N > 1 (configs[3]: "
                          "65 536 draws over 8 GPUs), 1024 for --workload sw_second_order (configs[4])")
-    ap.add_argument("--cpu-sample", type=int, default=192, help="evaluations timed on the host cores (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=192, help="with --full: evaluations timed on the host cores (0 = skip)")
     ap.add_argument("--profile-reps", type=int, default=3)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--max-iter", type=int, default=1000)
     ap.add_argument("--workload", default="sw_shaped", choices=["sw_shaped", "rbc", "full_nk", "sw_second_order"])
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the two extra legs of the default line (full recursion: kalman_steady_tol = 0; solver = gensys)")
+                    help="with --full: skip the extra legs (full recursion: kalman_steady_tol = 0; solver = gensys; ...)")
     ap.add_argument("--solver", default="cycle_reduction", choices=["cycle_reduction", "gensys"])
     ap.add_argument("--from-theta", action="store_true",
                     help="rbc workload only: start each step from the parameter draws (generated Jacobian kernel on the "
@@ -484,6 +516,8 @@ def main():
                     help="functional check on a box with fewer devices than ranks: rank r uses device r %% device_count "
                          "and the gather runs over gloo (the JSON line says so; not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher of its N rank processes.  It never
@@ -524,7 +558,7 @@ def main():
 
     cpu = None
     cpu_logp = None
-    if rank == 0 and args.cpu_sample > 0:  # (also at N > 1: rank 0's shard; the other ranks wait in the rendezvous)
+    if args.full and rank == 0 and args.cpu_sample > 0:  # (also at N > 1: rank 0's shard; the other ranks wait in the rendezvous)
         try:  # one worker per PHYSICAL core: with SMT siblings as workers the per-core rate halves and says nothing more
             import psutil
 
@@ -545,7 +579,7 @@ def main():
 
     # checker samples of the extra legs (rank 0, N = 1, default line only): the oracle with solver = gensys, and with the
     # observation model of the realistic-structure leg (seven observed JUMP variables) -- also before the GPU is touched
-    want_extras = (world == 1 and not args.no_extras and not args.from_theta and args.workload == "sw_shaped"
+    want_extras = (args.full and world == 1 and not args.no_extras and not args.from_theta and args.workload == "sw_shaped"
                    and args.solver == "cycle_reduction")
     cpu_gensys = cpu_jumps = om_j = b80 = om80 = cpu_n80 = om_c = cpu_cons = grad_fd = None
     if want_extras:
@@ -664,12 +698,14 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logp": logp_all.cpu().numpy(), "status": stat_all.cpu().numpy()})
 
     # When the caller's --steps make the timed region shorter than a second (the driver's 20 steps are 30 ms), the same step runs
     # on for >= 1.2 s OUTSIDE the headline timer: an outside observer (rocm-smi sampling) then sees the GPU busy, and the
     # sustained rate corroborates `value` (same loop, same buffers; never reported as `value`).
     sustained = None
-    if dt < 1.0:
+    if args.full and dt < 1.0:
         n_sus = int(np.ceil(1.2 / (dt / args.steps)))
         torch.cuda.synchronize()
         barrier()
@@ -935,10 +971,12 @@ def main():
         torch.cuda.synchronize()
 
     # per-kernel durations, HIP events on the launch stream (rank 0's shard)
-    kms = eng.profile_kernels(dA, dB, dC, dD, dq, dZ, dy, Hdiag=dH, q_mode=1, tol=args.tol, max_iter=args.max_iter,
-                              reps=args.profile_reps, n_state_hint=hints[0], z_selector_hint=hints[1],
-                              solver=args.solver, n_lead_hint=n_lead)
-    torch.cuda.synchronize()
+    kms = {}
+    if args.full:
+        kms = eng.profile_kernels(dA, dB, dC, dD, dq, dZ, dy, Hdiag=dH, q_mode=1, tol=args.tol, max_iter=args.max_iter,
+                                  reps=args.profile_reps, n_state_hint=hints[0], z_selector_hint=hints[1],
+                                  solver=args.solver, n_lead_hint=n_lead)
+        torch.cuda.synchronize()
 
     # structure statistics of rank 0's shard (one untimed pass): CR iterations, first steady-state step
     import ctypes  # noqa: F401
@@ -946,7 +984,7 @@ def main():
     from geconpy_amd import _lib
 
     stats = {}
-    if rank == 0 and args.workload == "sw_shaped":
+    if args.full and rank == 0 and args.workload == "sw_shaped":
         lib = _lib.load()
         it_buf = torch.zeros(nloc, dtype=torch.int32, device=device)
         st_buf = torch.zeros(nloc, dtype=torch.int32, device=device)
@@ -970,80 +1008,84 @@ def main():
         del T_buf
 
     if rank == 0:
-        # hardware counters of the same command, collected by tools/pmc_collect.py on an MI355X and committed under
-        # profiles/ (rocprofv3 cannot profile the process it runs in): FP64 VALU instruction counts and HBM bytes per
-        # launch.  Only valid for the default workload / batch / solver; the JSON line names the file.
-        pmc, pmc_src = {}, None
-        default_cfg = (per_gpu == 4096 and hints[1] and args.workload == "sw_shaped" and args.solver == "cycle_reduction"
-                       and not args.no_hints)
-        if default_cfg:
-            pmc, pmc_src = load_pmc()
-        cr_it = stats.get("cr_iters_mean", 7.0)
-        flops = algorithmic_flops(n, k, p, T_len, cr_iters=cr_it)
-        # contract flops by the kernel that does the work (the Lyapunov solve now runs inside the Kalman kernel)
-        # (selection: R comes out of the cycle-reduction kernel's final elimination unless --solver gensys)
-        fused_sel = args.solver == "cycle_reduction"
-        contract = {"solver": flops["solver"] + (flops["selection"] if fused_sel else 0.0),
-                    "assemble": 2.0 * n * n * k if fused_sel else flops["selection"],
-                    "kalman": flops["kalman"] + flops["lyapunov"]}
-        s_cols = hints[0] or n
-        u_dim = min(n, s_cols + p) if not hints[1] else int(np.count_nonzero((shard["A"][0] != 0).any(axis=0)
-                                                                             | (om["Z"] != 0).any(axis=0)))
         h_defl = deflated_static(n, shard["A"][0], shard["C"][0]) if args.solver == "cycle_reduction" else 0
-        ex = executed_flops(n, k, p, T_len, s_cols, stats.get("lead_columns", n), u_dim, cr_it,
-                            stats.get("full_steps_mean", T_len), 8, selector=bool(hints[1]), h=h_defl)
-        bs_n, bs_d = (n + 7) // 8, (n - h_defl + 7) // 8
-        np_lo = 8 * (((hints[0] if 0 < (hints[0] or 0) < n else n) + 7) // 8)  # launch_kalman.hip::kalman_folds_rqr
-        folds_rqr = bool(args.solver == "cycle_reduction" and hints[1] and p <= 8 and 1 <= k <= 16
-                         and not (p <= 3 and 0 < (hints[0] or 0) and (hints[0] or 0) + p <= 6)
-                         and n * ((k + 1) & ~1) <= np_lo * (np_lo + 2))
-        nd_ = n - h_defl
-        ncol_ = h_defl + 3 * nd_ + k  # launch_cr_fused: two columns of the QR per lane up to 128, three up to 192
-        one_launch = (h_defl and nd_ + k <= 64 and
-                      ((ncol_ <= 128 and (bs_n, bs_d) in {(3, 2), (3, 3), (4, 3), (4, 4), (5, 4), (6, 4), (6, 5)}) or
-                       (128 < ncol_ <= 192 and (bs_n, bs_d) in {(6, 5), (7, 5), (7, 6), (8, 6)})))
-        mf_default = __import__('geconpy_amd._lib', fromlist=['make_options']).make_options().kalman_mfma == 2
-        names = {"solver": ((f"dsge::cr_fused_kernel{'_occ2' if bs_d == 4 and ncol_ <= 128 else ''}<{bs_n},{bs_d}> (static-variable deflation {n} -> {nd_}: "
-                             "QR of the static columns + cycle reduction + back-substitution, one launch)") if one_launch else
-                            (f"dsge::cr_deflate_kernel<{bs_n}> + cr_compact_kernel<{bs_d}> + cr_inflate_kernel<{bs_d}> (static-variable "
-                             f"deflation {n} -> {nd_}, three launches)") if h_defl else f"dsge::cr_compact_kernel<{bs_n}>")
-                 if args.solver == "cycle_reduction" else ("dsge::gensys_reduce_kernel + gensys_qzwin_kernel + gensys_post_kernel (window path, three launches)"
-                                if n > 16 else "dsge::gensys_kernel"),
-                 "assemble": (("none: sym(R Q R')[U,U] is formed in the prologue of the Kalman kernel (rqr_kernel<16> only for "
-                               "draws handed on to the general filter)") if folds_rqr else
-                              "dsge::rqr_kernel<16>" if (args.solver == "cycle_reduction" and k <= 16)
-                              else f"dsge::assemble_kernel<{(n + 7) // 8}>"),
-                 "kalman": ((f"dsge::kalman_mf_kernel<5,{5 if u_dim <= 20 else 7}> (covariance in the tile layout of v_mfma_f64_4x4x4f64: downdate "
-                             f"and both prediction products on the FP64 matrix core)")
-                            if (hints[1] and p <= 8 and 17 <= hints[0] <= 20 and u_dim <= 28 and mf_default) else
-                            f"dsge::kalman_nt_kernel<{(u_dim + 7) // 8}>" if hints[1] and p <= 8
-                            else f"dsge::kalman_sel_kernel<{(u_dim + 7) // 8},{'true' if hints[1] else 'false'}>")}
-        kern = {}
-        for key in ("solver", "assemble", "kalman"):
-            sec = kms[key] * 1e-3
-            leg = pmc.get(key, {})
-            kern[key] = {
-                "kernel": names[key],
-                "ms": round(kms[key], 4),
-                "contract_mflop_per_eval": round(contract[key] / 1e6, 3),
-                "contract_tflops": round(contract[key] * nloc / sec / 1e12, 3),
-                "model_mflop_per_eval": round(ex[key] / 1e6, 3),
-                "model_tflops": round(ex[key] * nloc / sec / 1e12, 3),
-                "counted_mflop_per_eval": round(leg["fp64_flops"] / nloc / 1e6, 3) if leg else None,
-                "counted_tflops": round(leg["fp64_flops"] / sec / 1e12, 3) if leg else None,
-                "hbm_bytes_per_launch": round(leg["hbm_bytes"]) if leg else None,
-                "lds_conflict_share": round(leg["lds_conflict_share"], 3) if leg else None,
-                # FP64 matrix-core evidence from the committed counters (north_star: "MFMA only for the F P F' products of the
-                # Kalman recursion"): wave-level MFMA instructions per launch, their share of the VALU instruction stream, and the
-                # busy share of the 1024 SIMDs' matrix pipes over the committed launch duration at 2.4 GHz
-                "mfma_insts_per_launch": round(leg["mfma_insts"]) if leg else None,
-                "mfma_share_of_valu_insts": round(leg["mfma_insts"] / leg["valu_insts"], 4) if leg and leg.get("valu_insts") else None,
-                "mfma_busy": (round(leg["mfma_busy_cycles"] / (1024 * leg["avg_ns"] * 2.4), 4)
-                              if leg and leg.get("avg_ns") else None),
-            }
-        dom = max(kern, key=lambda k_: kern[k_]["ms"])
-        total_kernel_s = sum(kms.values()) * 1e-3
-        b_eval = algorithmic_bytes(n, k, p)
+        roofline = None
+        if args.full:
+            # hardware counters of the same command, collected by tools/pmc_collect.py on an MI355X and committed under
+            # profiles/ (rocprofv3 cannot profile the process it runs in): FP64 VALU instruction counts and HBM bytes per
+            # launch.  Only valid for the default workload / batch / solver; the JSON line names the file.
+            pmc, pmc_src = {}, None
+            default_cfg = (per_gpu == 4096 and hints[1] and args.workload == "sw_shaped" and args.solver == "cycle_reduction"
+                           and not args.no_hints)
+            if default_cfg:
+                pmc, pmc_src = load_pmc()
+            cr_it = stats.get("cr_iters_mean", 7.0)
+            flops = algorithmic_flops(n, k, p, T_len, cr_iters=cr_it)
+            # contract flops by the kernel that does the work (the Lyapunov solve now runs inside the Kalman kernel)
+            # (selection: R comes out of the cycle-reduction kernel's final elimination unless --solver gensys)
+            fused_sel = args.solver == "cycle_reduction"
+            contract = {"solver": flops["solver"] + (flops["selection"] if fused_sel else 0.0),
+                        "assemble": 2.0 * n * n * k if fused_sel else flops["selection"],
+                        "kalman": flops["kalman"] + flops["lyapunov"]}
+            s_cols = hints[0] or n
+            u_dim = min(n, s_cols + p) if not hints[1] else int(np.count_nonzero((shard["A"][0] != 0).any(axis=0)
+                                                                                 | (om["Z"] != 0).any(axis=0)))
+            ex = executed_flops(n, k, p, T_len, s_cols, stats.get("lead_columns", n), u_dim, cr_it,
+                                stats.get("full_steps_mean", T_len), 8, selector=bool(hints[1]), h=h_defl)
+            bs_n, bs_d = (n + 7) // 8, (n - h_defl + 7) // 8
+            np_lo = 8 * (((hints[0] if 0 < (hints[0] or 0) < n else n) + 7) // 8)  # launch_kalman.hip::kalman_folds_rqr
+            folds_rqr = bool(args.solver == "cycle_reduction" and hints[1] and p <= 8 and 1 <= k <= 16
+                             and not (p <= 3 and 0 < (hints[0] or 0) and (hints[0] or 0) + p <= 6)
+                             and n * ((k + 1) & ~1) <= np_lo * (np_lo + 2))
+            nd_ = n - h_defl
+            ncol_ = h_defl + 3 * nd_ + k  # launch_cr_fused: two columns of the QR per lane up to 128, three up to 192
+            one_launch = (h_defl and nd_ + k <= 64 and
+                          ((ncol_ <= 128 and (bs_n, bs_d) in {(3, 2), (3, 3), (4, 3), (4, 4), (5, 4), (6, 4), (6, 5)}) or
+                           (128 < ncol_ <= 192 and (bs_n, bs_d) in {(6, 5), (7, 5), (7, 6), (8, 6)})))
+            mf_default = __import__('geconpy_amd._lib', fromlist=['make_options']).make_options().kalman_mfma == 2
+            names = {"solver": ((f"dsge::cr_fused_kernel{'_occ2' if bs_d == 4 and ncol_ <= 128 else ''}<{bs_n},{bs_d}> (static-variable deflation {n} -> {nd_}: "
+                                 "QR of the static columns + cycle reduction + back-substitution, one launch)") if one_launch else
+                                (f"dsge::cr_deflate_kernel<{bs_n}> + cr_compact_kernel<{bs_d}> + cr_inflate_kernel<{bs_d}> (static-variable "
+                                 f"deflation {n} -> {nd_}, three launches)") if h_defl else f"dsge::cr_compact_kernel<{bs_n}>")
+                     if args.solver == "cycle_reduction" else ("dsge::gensys_reduce_kernel + gensys_qzwin_kernel + gensys_post_kernel (window path, three launches)"
+                                    if n > 16 else "dsge::gensys_kernel"),
+                     "assemble": (("none: sym(R Q R')[U,U] is formed in the prologue of the Kalman kernel (rqr_kernel<16> only for "
+                                   "draws handed on to the general filter)") if folds_rqr else
+                                  "dsge::rqr_kernel<16>" if (args.solver == "cycle_reduction" and k <= 16)
+                                  else f"dsge::assemble_kernel<{(n + 7) // 8}>"),
+                     "kalman": ((f"dsge::kalman_mf_kernel<5,{5 if u_dim <= 20 else 7}> (covariance in the tile layout of v_mfma_f64_4x4x4f64: downdate "
+                                 f"and both prediction products on the FP64 matrix core)")
+                                if (hints[1] and p <= 8 and 17 <= hints[0] <= 20 and u_dim <= 28 and mf_default) else
+                                f"dsge::kalman_nt_kernel<{(u_dim + 7) // 8}>" if hints[1] and p <= 8
+                                else f"dsge::kalman_sel_kernel<{(u_dim + 7) // 8},{'true' if hints[1] else 'false'}>")}
+            kern = {}
+            for key in ("solver", "assemble", "kalman"):
+                sec = kms[key] * 1e-3
+                leg = pmc.get(key, {})
+                kern[key] = {
+                    "kernel": names[key],
+                    "ms": round(kms[key], 4),
+                    "contract_mflop_per_eval": round(contract[key] / 1e6, 3),
+                    "contract_tflops": round(contract[key] * nloc / sec / 1e12, 3),
+                    "model_mflop_per_eval": round(ex[key] / 1e6, 3),
+                    "model_tflops": round(ex[key] * nloc / sec / 1e12, 3),
+                    "counted_mflop_per_eval": round(leg["fp64_flops"] / nloc / 1e6, 3) if leg else None,
+                    "counted_tflops": round(leg["fp64_flops"] / sec / 1e12, 3) if leg else None,
+                    "hbm_bytes_per_launch": round(leg["hbm_bytes"]) if leg else None,
+                    "lds_conflict_share": round(leg["lds_conflict_share"], 3) if leg else None,
+                    # FP64 matrix-core evidence from the committed counters (north_star: "MFMA only for the F P F' products of the
+                    # Kalman recursion"): wave-level MFMA instructions per launch, their share of the VALU instruction stream, and the
+                    # busy share of the 1024 SIMDs' matrix pipes over the committed launch duration at 2.4 GHz
+                    "mfma_insts_per_launch": round(leg["mfma_insts"]) if leg else None,
+                    "mfma_share_of_valu_insts": round(leg["mfma_insts"] / leg["valu_insts"], 4) if leg and leg.get("valu_insts") else None,
+                    "mfma_busy": (round(leg["mfma_busy_cycles"] / (1024 * leg["avg_ns"] * 2.4), 4)
+                                  if leg and leg.get("avg_ns") else None),
+                }
+            dom = max(kern, key=lambda k_: kern[k_]["ms"])
+            total_kernel_s = sum(kms.values()) * 1e-3
+            b_eval = algorithmic_bytes(n, k, p)
+            roofline = roofline_block(kern, dom, kms, pmc_src, flops, ex, nloc, total_kernel_s, b_eval, hints, u_dim, h_defl,
+                                      stats)
         value = global_batch * args.steps / dt
         out = {
             "metric": "solve+Kalman-logp evals/sec, Smets-Wouters n~40 T=200",
@@ -1082,8 +1124,7 @@ def main():
                                     else "workgroups in descending order of a persistence key of T (power iteration)") + " (slow draws first; outputs stay in draw order)",
                 "parallelism": f"draw-sharded x{world}, one all_gather of packed (logp,status) records" if world > 1 else "single GPU",
             },
-            "roofline": roofline_block(kern, dom, kms, pmc_src, flops, ex, nloc, total_kernel_s, b_eval, hints, u_dim, h_defl,
-                                       stats),
+            **({"roofline": roofline} if roofline else {}),
             "failed_draws": n_fail,
             **({"sustained": sustained} if sustained else {}),
             **extras,
@@ -1127,7 +1168,7 @@ def main_second_order(args, world, rank, local_rank):
     om = wl.sw_shaped_observation_model()
     cpu = None
     cpu_logp = None
-    if rank == 0 and args.cpu_sample > 0:
+    if args.full and rank == 0 and args.cpu_sample > 0:
         try:
             import psutil
 
@@ -1203,19 +1244,22 @@ def main_second_order(args, world, rank, local_rank):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     logp_host = logp_all.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logp": logp_host, "status": stat_all.cpu().numpy()})
     n_fail = int((stat_all != 0).sum().item())
     ginfo = gather_info(dist, world, rank, device)
     # stage durations (HIP events on the launch stream inside the library) and the number of full filter steps per draw
-    ms = (ctypes.c_float * 4)()
-    at = torch.full((nloc,), -1, dtype=torch.int32, device=device)
-    eng.record_steady_steps(at)
-    local_eval(0, nloc, stage_ms=ms)
-    torch.cuda.synchronize()
-    eng.record_steady_steps(None)
-    at_h = at.cpu().numpy()
-    n_full = np.where(at_h < 0, T_len, at_h).astype(np.float64)
+    if args.full:
+        ms = (ctypes.c_float * 4)()
+        at = torch.full((nloc,), -1, dtype=torch.int32, device=device)
+        eng.record_steady_steps(at)
+        local_eval(0, nloc, stage_ms=ms)
+        torch.cuda.synchronize()
+        eng.record_steady_steps(None)
+        at_h = at.cpu().numpy()
+        n_full = np.where(at_h < 0, T_len, at_h).astype(np.float64)
     full = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         ms_f = (ctypes.c_float * 4)()
         lp_h = logp_buf.clone()
         local_eval(0, nloc, stage_ms=ms_f, options={"kalman_steady_tol": 0.0})
@@ -1226,17 +1270,37 @@ def main_second_order(args, world, rank, local_rank):
         local_eval(0, nloc)
         torch.cuda.synchronize()
     if rank == 0:
-        mp16 = 16 * ((m + 15) // 16)
-        kq = k + s * k + k * (k + 1) // 2
-        # the prediction step's two products (unpadded): W' = P Az' in full, X = W Az' on and above the diagonal only (it is
-        # symmetric: so_gemm_sym multiplies m (m + 1) / 2 of its m^2 entries)
-        flops_step = 2.0 * m ** 3 + 2.0 * m * (m * (m + 1) / 2)
-        flops_filter = float(n_full.sum()) * flops_step
-        filt_s = ms[3] * 1e-3
         value = global_batch * args.steps / dt
-        soc = so_counters(f"so_filter_kernel<{mp16 // 16}>", nloc)
-        mfma_frac = flops_filter / filt_s / 1e12 / FP64_PEAK_TFLOPS
-        hbm_frac = (soc["traffic"] / filt_s / 1e9 / HBM_PEAK_GBS) if soc.get("traffic") else None
+        roofline = None
+        if args.full:
+            mp16 = 16 * ((m + 15) // 16)
+            kq = k + s * k + k * (k + 1) // 2
+            # the prediction step's two products (unpadded): W' = P Az' in full, X = W Az' on and above the diagonal only (it is
+            # symmetric: so_gemm_sym multiplies m (m + 1) / 2 of its m^2 entries)
+            flops_step = 2.0 * m ** 3 + 2.0 * m * (m * (m + 1) / 2)
+            flops_filter = float(n_full.sum()) * flops_step
+            filt_s = ms[3] * 1e-3
+            soc = so_counters(f"so_filter_kernel<{mp16 // 16}>", nloc)
+            mfma_frac = flops_filter / filt_s / 1e12 / FP64_PEAK_TFLOPS
+            hbm_frac = (soc["traffic"] / filt_s / 1e9 / HBM_PEAK_GBS) if soc.get("traffic") else None
+            roofline = {
+                "kernel": f"dsge::so_filter_kernel<{mp16 // 16}> (512 threads per draw; v_mfma_f64_16x16x4_f64 on {mp16 // 16} x {mp16 // 16} tiles)",
+                # the bound is read off the counters: whichever of the two fractions is larger (committed HBM traffic over the
+                # duration measured here vs useful matrix-core flops over the same duration)
+                "bound": "hbm" if (hbm_frac is not None and hbm_frac > mfma_frac) else "mfma",
+                "hbm_frac": round(hbm_frac, 4) if hbm_frac is not None else None, "mfma_frac": round(mfma_frac, 4),
+                "unit": "TFLOP/s", "peak": FP64_PEAK_TFLOPS,
+                "achieved": round(flops_filter / filt_s / 1e12, 3),
+                "frac": round(flops_filter / filt_s / 1e12 / FP64_PEAK_TFLOPS, 5),
+                "flops_source": f"2 m^3 (W' = P Az') + m^2 (m + 1) (the symmetric X = W Az', upper half only) with m = {m}, unpadded, per "
+                                f"full filter step x the measured number of full steps per draw (mean {n_full.mean():.1f} of {T_len}); "
+                                "duration: HIP events around the kernel in this run",
+                **soc,
+                "stage_ms": {"first_order_solver": round(ms[0], 3), "second_order_setup": round(ms[1], 3),
+                             "stationary_covariance": round(ms[2], 3), "filter": round(ms[3], 3)},
+                "full_steps_mean": float(n_full.mean()), "never_steady": int((at_h < 0).sum()),
+                "qz_product_K": kq,
+            }
         out = {
             "metric": "second-order solve + pruned-state-space Kalman-logp evals/sec, Smets-Wouters-shaped n=40 T=200",
             "value": round(value, 2), "unit": "evals/s", "n_gpus": world,
@@ -1255,24 +1319,7 @@ def main_second_order(args, world, rank, local_rank):
                                "oracle/second_order.py, parity unpinned by construction",
                 "parallelism": f"draw-sharded x{world}, one all_gather of packed (logp,status) records" if world > 1 else "single GPU",
             },
-            "roofline": {
-                "kernel": f"dsge::so_filter_kernel<{mp16 // 16}> (512 threads per draw; v_mfma_f64_16x16x4_f64 on {mp16 // 16} x {mp16 // 16} tiles)",
-                # the bound is read off the counters: whichever of the two fractions is larger (committed HBM traffic over the
-                # duration measured here vs useful matrix-core flops over the same duration)
-                "bound": "hbm" if (hbm_frac is not None and hbm_frac > mfma_frac) else "mfma",
-                "hbm_frac": round(hbm_frac, 4) if hbm_frac is not None else None, "mfma_frac": round(mfma_frac, 4),
-                "unit": "TFLOP/s", "peak": FP64_PEAK_TFLOPS,
-                "achieved": round(flops_filter / filt_s / 1e12, 3),
-                "frac": round(flops_filter / filt_s / 1e12 / FP64_PEAK_TFLOPS, 5),
-                "flops_source": f"2 m^3 (W' = P Az') + m^2 (m + 1) (the symmetric X = W Az', upper half only) with m = {m}, unpadded, per "
-                                f"full filter step x the measured number of full steps per draw (mean {n_full.mean():.1f} of {T_len}); "
-                                "duration: HIP events around the kernel in this run",
-                **soc,
-                "stage_ms": {"first_order_solver": round(ms[0], 3), "second_order_setup": round(ms[1], 3),
-                             "stationary_covariance": round(ms[2], 3), "filter": round(ms[3], 3)},
-                "full_steps_mean": float(n_full.mean()), "never_steady": int((at_h < 0).sum()),
-                "qz_product_K": kq,
-            },
+            **({"roofline": roofline} if roofline else {}),
             "failed_draws": n_fail,
         }
         if full is not None:

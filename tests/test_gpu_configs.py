@@ -256,7 +256,7 @@ def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` without torch.distributed.run: the launcher starts two rank processes (before anything
     touches the GPU) and rank 0 prints one JSON line with n_gpus = 2 -- a COMPLETE line: roofline, cpu_baseline and parity
     (rank 0 computes them on its shard before it touches the GPU), so that a multi-GPU driver run counts as measured."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--batch-per-gpu", "512", "--cpu-sample", "8", "--profile-reps", "1", "--allow-shared-gpu"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
@@ -273,6 +273,31 @@ def test_bench_launches_its_own_ranks():
     # line says exactly that (on a multi-GPU node: "nccl", distinct_devices == world)
     g = out["gather"]
     assert g["world"] == 2 and g["backend"] == "gloo" and [e["rank"] for e in g["ranks"]] == [0, 1] and g["distinct_devices"] == 1
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full: one headline line (value, ms_per_step of the --steps timed steps) and none
+    of the --full blocks; --dump-outputs writes the per-draw logp / status of the last timed step, which are the batch's logp."""
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch-per-gpu", "256", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["unit"] == "evals/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["failed_draws"] == 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 256) <= 0.01 * 256  # value = draws per timed step / ms_per_step
+    assert not {"roofline", "cpu_baseline", "parity", "sustained", "gensys", "gradient"} & set(out)
+    logp, status = np.load(out_dir / "logp.npy"), np.load(out_dir / "status.npy")
+    assert logp.dtype == status.dtype == np.float64 and logp.shape == status.shape == (256,)
+    assert (status == 0).all()
+    b = wl.sw_shaped_batch(256)
+    om = wl.sw_shaped_observation_model()
+    ref = batched.solve_kalman_logp_batched(b["A"], b["B"], b["C"], b["D"], b["sigma"] ** 2, om["Z"], om["y"],
+                                            Hdiag=om["Hdiag"], tol=1e-8, max_iter=1000)
+    assert_allclose(logp, ref["logp"], rtol=LOGP_RTOL, atol=0)
 
 
 def test_bench_sizes_a_multi_gpu_run_as_configs3():

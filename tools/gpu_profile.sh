@@ -6,7 +6,7 @@ TAG=${1:-prof}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o kt -- python3 bench.py --steps 5 --warmup 2 --cpu-sample 0 "$@" > "$OUT/bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o kt -- python3 bench.py --full --steps 5 --warmup 2 --cpu-sample 0 "$@" > "$OUT/bench.log" 2>&1
 grep '^{' "$OUT/bench.log" > "$OUT/bench.json"
 find "$OUT" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
 # the full trace is large; keep only the stats

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/$C" -o pmc -- python3 bench.py --steps 1 --warmup 1 --cpu-sample 0 --profile-reps 1 > "$OUT/$C.log" 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/$C" -o pmc -- python3 bench.py --full --steps 1 --warmup 1 --cpu-sample 0 --profile-reps 1 > "$OUT/$C.log" 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys, collections

@@ -5,7 +5,7 @@ TAG=${1:-kseq}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o kt -- python3 bench.py --steps 1 --warmup 1 --cpu-sample 0 --no-extras --profile-reps 1 "$@" > "$OUT/run.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o kt -- python3 bench.py --full --steps 1 --warmup 1 --cpu-sample 0 --no-extras --profile-reps 1 "$@" > "$OUT/run.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)

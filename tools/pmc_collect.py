@@ -44,7 +44,7 @@ def main():
     extra = sys.argv[sys.argv.index("--") + 1:] if "--" in sys.argv else []
     os.makedirs(out, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
              "--profile-reps", "1", *extra]
     if "--script" in sys.argv:  # counters of another driver, e.g. --script tools/grad_rate.py (the gradient pipeline)
         bench = ["python3", os.path.join(ROOT, sys.argv[sys.argv.index("--script") + 1])]

@@ -7,19 +7,19 @@ RND=${2:-r6}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-python3 bench.py --solver gensys --cpu-sample 0 > "$OUT/bench_gensys.json" 2>/dev/null
+python3 bench.py --full --solver gensys --cpu-sample 0 > "$OUT/bench_gensys.json" 2>/dev/null
 # (the ordered QZ for every draw: the library default is gensys by spectral division since round 5; DSGE_GENSYS_DOUBLING is read at load)
-DSGE_GENSYS_DOUBLING=0 python3 bench.py --solver gensys --cpu-sample 0 --no-extras > "$OUT/bench_gensys_qz.json" 2>/dev/null
-python3 bench.py --from-theta --cpu-sample 0 > "$OUT/bench_sw_from_theta.json" 2>/dev/null
-python3 bench.py --workload rbc --cpu-sample 0 > "$OUT/bench_rbc.json" 2>/dev/null
-python3 bench.py --workload full_nk --cpu-sample 0 > "$OUT/bench_full_nk.json" 2>/dev/null
-python3 bench.py --batch-per-gpu 8192 --cpu-sample 0 --no-extras > "$OUT/bench_8192_per_gpu.json" 2>/dev/null
+DSGE_GENSYS_DOUBLING=0 python3 bench.py --full --solver gensys --cpu-sample 0 --no-extras > "$OUT/bench_gensys_qz.json" 2>/dev/null
+python3 bench.py --full --from-theta --cpu-sample 0 > "$OUT/bench_sw_from_theta.json" 2>/dev/null
+python3 bench.py --full --workload rbc --cpu-sample 0 > "$OUT/bench_rbc.json" 2>/dev/null
+python3 bench.py --full --workload full_nk --cpu-sample 0 > "$OUT/bench_full_nk.json" 2>/dev/null
+python3 bench.py --full --batch-per-gpu 8192 --cpu-sample 0 --no-extras > "$OUT/bench_8192_per_gpu.json" 2>/dev/null
 for V in default gensys gensys_qz sw_second_order; do
   ARGS="--no-extras"; [ "$V" = gensys ] && ARGS="--solver gensys --no-extras"; [ "$V" = gensys_qz ] && ARGS="--solver gensys --no-extras"
   [ "$V" = sw_second_order ] && ARGS="--workload sw_second_order --no-extras --steps 2 --warmup 1"
   unset DSGE_GENSYS_DOUBLING; [ "$V" = gensys_qz ] && export DSGE_GENSYS_DOUBLING=0
   rm -rf "$OUT/kt_$V"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$V" -o kt -- python3 bench.py --steps 5 --warmup 2 --cpu-sample 0 $ARGS > "$OUT/kt_$V.log" 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$V" -o kt -- python3 bench.py --full --steps 5 --warmup 2 --cpu-sample 0 $ARGS > "$OUT/kt_$V.log" 2>&1
   find "$OUT/kt_$V" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats_$V.csv" \;
   rm -rf "$OUT/kt_$V" "$OUT/kt_$V.log"
 done
@@ -34,8 +34,8 @@ rm -rf "$OUT/pmc_default" "$OUT/pmc_gensys" "$OUT/pmc_gensys_sd" "$OUT/pmc_so"
 # the roofline blocks quote flops / traffic from the counters committed under profiles/: take the lines after they are refreshed
 mkdir -p profiles/$RND
 cp "$OUT/pmc_counters_sw_second_order.json" "$OUT/pmc_counters.json" "$OUT/pmc_counters_gensys.json" "$OUT/pmc_counters_gensys_spectral_division.json" profiles/$RND/ 2>/dev/null
-python3 bench.py --workload sw_second_order > "$OUT/bench_sw_second_order.json" 2> "$OUT/bench_sw_second_order.err"
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full --workload sw_second_order > "$OUT/bench_sw_second_order.json" 2> "$OUT/bench_sw_second_order.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 # (the window kernels run on every draw only with the ordered QZ for every draw: under the default route the phase counters of draw 0 stay zero)
 DSGE_GENSYS_DOUBLING=0 python3 tools/gensys_window_phases.py > "$OUT/gensys_window_phases.txt" 2>&1
 python3 tools/kalman_phases.py > "$OUT/kalman_phases.txt" 2>&1
