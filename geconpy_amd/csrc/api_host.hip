@@ -1,0 +1,859 @@
+// Host twins of the C ABI (include/dsge_hip.h: every *_host entry point): host pointers in, host pointers out.  A twin
+// checks its arguments, declares its buffers to a HostCall, calls the device-pointer entry point (dsge_api.hip) on the
+// calling thread's stream and copies the outputs back.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "dsge_host.hpp"
+
+using namespace dsge_host;
+
+namespace {
+
+// ---- staging arenas -------------------------------------------------------------------------------------------------------
+// Host threads call the twins concurrently (ctypes releases the GIL: PyMC / nutpie chains in threads, two pytensor Ops),
+// so a twin LEASES a staging arena for the duration of its call from a pool that grows to the number of concurrent
+// callers; arenas are never shared between two calls in flight and never freed while leased.
+struct Arena {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  int dev = -1;
+  bool leased = false;
+};
+constexpr int MAX_DEV = 16;
+std::mutex g_stage_mutex;
+std::vector<Arena*> g_stage_pool;
+
+// One call of a host twin: the calling thread's two streams, the leased arena and the list of buffers the call stages.
+//
+//   HostCall hc;
+//   if ((rc = hc.begin())) return rc;            // device check, streams
+//   hc.in(&dA, A, nn); hc.out(&dT, T_out, nn);   // one line per buffer; a null host pointer declares nothing (dX = nullptr)
+//   if ((rc = hc.stage())) return rc;            // sizes and leases the arena, fills dA, dT, ..., enqueues the uploads
+//   if ((rc = dsge_..._batched(dA, ..., dT, hc.stream()))) return rc;
+//   return hc.finish();                          // enqueues the downloads, synchronises
+//
+// The arena is sized from the declared list, so it cannot be smaller than what the list carves.  A call that leaves
+// between stage() and the end of finish() (a refusal of the device entry such as DSGE_ERR_TOO_LARGE, a HIP error) has
+// copies or kernels in flight on the thread's streams: the destructor waits for them BEFORE it gives the arena back,
+// since another host thread may lease it at once.
+class HostCall {
+ public:
+  HostCall() = default;
+  HostCall(const HostCall&) = delete;
+  HostCall& operator=(const HostCall&) = delete;
+  ~HostCall() {
+    if (pending_) {  // first: nothing of this call may still touch the arena ...
+      for (hipStream_t s : s_) (void)hipStreamSynchronize(s);
+      (void)hipGetLastError();  // (clear the sticky error, as HIP_TRY does)
+    }
+    if (arena_) {  // ... then: the arena is free for the next caller
+      std::lock_guard<std::mutex> lk(g_stage_mutex);
+      arena_->leased = false;
+    }
+  }
+
+  int begin() {
+    int rc = ensure_device();
+    if (rc) return rc;
+    return twin_streams(&s_[0], &s_[1]);
+  }
+  hipStream_t stream(int i = 0) const { return s_[i]; }
+
+  // Declarations, in the order the arena is carved.  *dev is null at once for a null host pointer and the device address
+  // after stage() otherwise.
+  template <typename T>
+  void in(const T** dev, const T* host, size_t count) {  // uploaded by stage()
+    declare(dev, host, host, nullptr, count * sizeof(T));
+  }
+  template <typename T>
+  void out(T** dev, T* host, size_t count) {  // downloaded by finish()
+    declare(dev, host, nullptr, host, count * sizeof(T));
+  }
+  template <typename T>
+  void io(T** dev, T* host, size_t count) {  // both
+    declare(dev, host, host, host, count * sizeof(T));
+  }
+  template <typename T>
+  void space(T** dev, size_t count) {  // device space only: the caller copies, or nobody does
+    declare(dev, dev, nullptr, nullptr, count * sizeof(T));
+  }
+
+  // Ends the declarations: leases an arena that holds every declared buffer (each rounded up to 256 bytes), assigns the
+  // addresses in declaration order and enqueues the uploads on stream 0.
+  int stage() {
+    size_t bytes = TAIL_PAD;
+    for (const Buf& b : bufs_) bytes += align256(b.bytes);
+    void* base = nullptr;
+    int rc = lease(bytes, &base);
+    if (rc) return rc;
+    pending_ = true;
+    size_t off = 0;
+    for (const Buf& b : bufs_) {
+      void* p = (char*)base + off;
+      off += align256(b.bytes);
+      std::memcpy(b.slot, &p, sizeof p);  // (the caller's typed pointer)
+      if (b.up) HIP_TRY(hipMemcpyAsync(p, b.up, b.bytes, hipMemcpyHostToDevice, s_[0]));
+    }
+    return DSGE_SUCCESS;
+  }
+
+  // After the device entry: every declared output back on stream 0, then wait for it.
+  int finish() {
+    for (const Buf& b : bufs_)
+      if (b.down) {
+        void* p = nullptr;
+        std::memcpy(&p, b.slot, sizeof p);
+        HIP_TRY(hipMemcpyAsync(b.down, p, b.bytes, hipMemcpyDeviceToHost, s_[0]));
+      }
+    HIP_TRY(hipStreamSynchronize(s_[0]));
+    pending_ = false;
+    return DSGE_SUCCESS;
+  }
+
+ private:
+  struct Buf {
+    void* slot;  // address of the caller's device pointer
+    const void* up;
+    void* down;
+    size_t bytes;
+  };
+  // Added to every total.  The hand-counted totals this class replaced carried undocumented slack of 4096, 8192 or 16384
+  // bytes depending on the twin (and + 8 / + 64 inside some terms); whether a kernel reads a few bytes past its last
+  // input was never established, so the largest of them stays behind the last buffer of every call.
+  static constexpr size_t TAIL_PAD = 16384;
+  static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+  template <typename P>
+  void declare(P** dev, const void* present, const void* up, void* down, size_t bytes) {
+    *dev = nullptr;
+    if (present) bufs_.push_back(Buf{(void*)dev, up, down, bytes});
+  }
+
+  int lease(size_t bytes, void** out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= MAX_DEV) return fail(DSGE_ERR_INVALID, "device index out of range");
+    Arena* a = nullptr;
+    {
+      std::lock_guard<std::mutex> lk(g_stage_mutex);
+      for (Arena* c : g_stage_pool)  // the largest free arena of this device
+        if (!c->leased && c->dev == dev && (!a || c->cap > a->cap)) a = c;
+      if (!a) {
+        a = new Arena();
+        a->dev = dev;
+        g_stage_pool.push_back(a);
+      }
+      a->leased = true;
+    }
+    arena_ = a;
+    if (a->cap < bytes) {  // only this call holds the arena: nothing of it is in flight
+      if (a->ptr) {
+        HIP_TRY(hipFree(a->ptr));
+        a->ptr = nullptr;
+        a->cap = 0;
+      }
+      const size_t cap = bytes + bytes / 4 + 4096;
+      HIP_TRY(hipMalloc(&a->ptr, cap));
+      a->cap = cap;
+    }
+    *out = a->ptr;
+    return DSGE_SUCCESS;
+  }
+
+  hipStream_t s_[2] = {nullptr, nullptr};
+  Arena* arena_ = nullptr;
+  bool pending_ = false;  // staged, and finish() has not synchronised yet
+  std::vector<Buf> bufs_;
+};
+
+int cr_host(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol, double* T_out,
+            int32_t* status, int32_t* n_iter, int scan_mode) {
+  int rc = check_common(batch, n, DSGE_MAX_N_BIG);
+  if (rc) return rc;
+  if (!A || !B || !C || !T_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n;
+  const double *dA, *dB, *dC;
+  double* dT;
+  int32_t *dS, *dI;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.out(&dT, T_out, nn);
+  hc.out(&dS, status, batch);
+  hc.out(&dI, n_iter, batch);
+  if ((rc = hc.stage())) return rc;
+  rc = scan_mode ? dsge_scan_cycle_reduction_batched(dA, dB, dC, batch, n, max_iter, tol, dT, dS, dI, hc.stream())
+                 : dsge_cycle_reduction_batched(dA, dB, dC, batch, n, max_iter, tol, dT, dS, dI, hc.stream());
+  if (rc) return rc;
+  return hc.finish();
+}
+
+// the two gradient twins: dense_z selects the entry point with the design matrix's adjoint (Z_bar, optional)
+int grad_host(const double* A, const double* B, const double* C, const double* D, const double* q, int q_batched,
+              const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+              const double* y, int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter, double jitter,
+              double missing_fill, int n_filter_hint, int n_lead_hint, double* logp_out, int32_t* status_out, double* A_bar,
+              double* B_bar, double* C_bar, double* D_bar, double* q_bar, double* d_bar, double* h_bar, bool dense_z,
+              double* Z_bar) {
+  int rc = check_common(batch, n, 56);
+  if (rc) return rc;
+  if (dense_z && n + p > 56)
+    return fail(DSGE_ERR_INVALID, "gradient path with a dense design matrix: n + p must not exceed 56");
+  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0) return fail(DSGE_ERR_INVALID, "bad sizes");
+  if (!A || !B || !C || !D || !q || !Z || !y || !logp_out || !status_out || !A_bar || !B_bar || !C_bar || !D_bar || !q_bar)
+    return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  if (q_batched < 0 || q_batched > 3) return fail(DSGE_ERR_INVALID, "gradient path: q_batched is a DSGE_Q_* mode (0..3)");
+  const size_t qstride = (q_batched >= 2) ? (size_t)k * k : (size_t)k;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = (size_t)((q_batched & 1) ? batch : 1) * qstride;
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, bp = (size_t)batch * p;
+  const double *dA, *dB, *dC, *dD, *dq, *dZ, *dd, *dH, *dy;
+  double *dL, *gA, *gB, *gC, *gD, *gq, *gd, *gh, *gZ;
+  int32_t* dS;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, D, nk);
+  hc.in(&dq, q, nq);
+  hc.in(&dZ, Z, nz);
+  hc.in(&dd, d, nd);
+  hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.out(&dL, logp_out, batch);
+  hc.out(&dS, status_out, batch);
+  hc.out(&gA, A_bar, nn);
+  hc.out(&gB, B_bar, nn);
+  hc.out(&gC, C_bar, nn);
+  hc.out(&gD, D_bar, nk);
+  hc.out(&gq, q_bar, (size_t)batch * qstride);
+  hc.out(&gd, d_bar, bp);
+  hc.out(&gh, h_bar, bp);
+  hc.out(&gZ, dense_z ? Z_bar : nullptr, (size_t)batch * p * n);
+  if ((rc = hc.stage())) return rc;
+  rc = dense_z ? dsge_solve_kalman_logp_grad_dense_z_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH,
+                                                             h_batched, dy, batch, n, k, p, T_len, solver, tol, max_iter,
+                                                             jitter, missing_fill, n_filter_hint, n_lead_hint, dL, dS, gA, gB,
+                                                             gC, gD, gq, gd, gh, gZ, hc.stream())
+               : dsge_solve_kalman_logp_grad_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH, h_batched,
+                                                     dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
+                                                     n_filter_hint, n_lead_hint, dL, dS, gA, gB, gC, gD, gq, gd, gh,
+                                                     hc.stream());
+  if (rc) return rc;
+  return hc.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsge_cycle_reduction_batched_host(const double* A, const double* B, const double* C, int batch, int n,
+                                      int max_iter, double tol, double* T_out, int32_t* status, int32_t* n_iter) {
+  return cr_host(A, B, C, batch, n, max_iter, tol, T_out, status, n_iter, 0);
+}
+
+int dsge_scan_cycle_reduction_batched_host(const double* A, const double* B, const double* C, int batch, int n,
+                                           int max_iter, double tol, double* T_out, int32_t* status,
+                                           int32_t* n_steps) {
+  return cr_host(A, B, C, batch, n, max_iter, tol, T_out, status, n_steps, 1);
+}
+
+int dsge_gensys_batched_host(const double* A, const double* B, const double* C, const double* D, int batch, int n,
+                             int k, double tol, int n_lead_hint, double* T_out, double* R_out, int32_t* eu_out,
+                             int32_t* status) {
+  int rc = check_common(batch, n, (big_size(n) && opt().gensys_doubling != 0) ? DSGE_MAX_N_BIG : DSGE_MAX_N_GENSYS - 1);
+  if (rc) return rc;
+  if (!A || !B || !C || !T_out || !eu_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (R_out && (!D || k < 1 || k > n)) return fail(DSGE_ERR_INVALID, "R_out requires D and 1 <= k <= n");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * (R_out ? k : 0);
+  const double *dA, *dB, *dC, *dD;
+  double *dT, *dR;
+  int32_t *dE, *dS;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, R_out ? D : nullptr, nk);  // (D is read for R_out only)
+  hc.out(&dT, T_out, nn);
+  hc.out(&dR, R_out, nk);
+  hc.out(&dE, eu_out, (size_t)batch * 3);
+  hc.out(&dS, status, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_gensys_batched(dA, dB, dC, dD, batch, n, k, tol, n_lead_hint, dT, dR, dE, dS, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_gensys_pencil_batched_host(const double* g0, const double* g1, const double* c, const double* psi, const double* pi,
+                                    int batch, int N, int k, int n_eta, double tol, double* G1_out, double* C_out,
+                                    double* impact_out, double* gev_out, int32_t* eu_out, int32_t* status) {
+  return dsge_gensys_pencil_full_batched_host(g0, g1, c, psi, pi, batch, N, k, n_eta, tol, G1_out, C_out, impact_out, gev_out,
+                                              eu_out, status, nullptr);
+}
+
+int dsge_gensys_pencil_full_batched_host(const double* g0, const double* g1, const double* c, const double* psi,
+                                         const double* pi, int batch, int N, int k, int n_eta, double tol, double* G1_out,
+                                         double* C_out, double* impact_out, double* gev_out, int32_t* eu_out,
+                                         int32_t* status, const dsge_gensys_forward* forward) {
+  int rc = check_common(batch, N, DSGE_MAX_N_GENSYS);
+  if (rc) return rc;
+  if (k < 1 || n_eta < 0 || n_eta + k + 1 > 64) return fail(DSGE_ERR_INVALID, "need k >= 1, n_eta >= 0, n_eta + k + 1 <= 64");
+  if (!g0 || !g1 || !psi || (n_eta > 0 && !pi) || !G1_out || !C_out || !impact_out || !gev_out || !eu_out || !status)
+    return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * N * N, nk = (size_t)batch * N * k, ne = (size_t)batch * N * (n_eta > 0 ? n_eta : 1),
+               nv = (size_t)batch * N;
+  const dsge_gensys_forward fh = forward ? *forward : dsge_gensys_forward{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  const double *d0, *d1, *dc, *dps, *dpi;
+  double *dG, *dC, *dI, *dV;
+  int32_t *dE, *dS;
+  dsge_gensys_forward fd{nullptr, nullptr, nullptr, nullptr, nullptr, fh.pi_raw};  // the same struct of device pointers
+  hc.in(&d0, g0, nn);
+  hc.in(&d1, g1, nn);
+  hc.in(&dc, c, nv);
+  hc.in(&dps, psi, nk);
+  hc.in(&dpi, pi, (size_t)batch * N * n_eta);
+  hc.out(&dG, G1_out, nn);
+  hc.out(&dC, C_out, nv);
+  hc.out(&dI, impact_out, nk);
+  hc.out(&dV, gev_out, nv * 4);
+  hc.out(&dE, eu_out, (size_t)batch * 3);
+  hc.out(&dS, status, batch);
+  hc.out(&fd.f_mat, fh.f_mat, nn * 2);
+  hc.out(&fd.f_wt, fh.f_wt, nk * 2);
+  hc.out(&fd.y_wt, fh.y_wt, nn * 2);
+  hc.out(&fd.loose, fh.loose, ne);
+  hc.out(&fd.n_unstable, fh.n_unstable, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_gensys_pencil_full_batched(d0, d1, dc, dps, dpi, batch, N, k, n_eta, tol, dG, dC, dI, dV, dE, dS,
+                                            forward ? &fd : nullptr, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_bk_eigenvalues_batched_host(const double* A, const double* B, const double* C, int batch, int n, double tol,
+                                     double* eig_re, double* eig_im, int32_t* n_eig, int32_t* n_forward,
+                                     int32_t* n_unstable, int32_t* status) {
+  int rc = check_common(batch, n, DSGE_MAX_N_GENSYS - 1);
+  if (rc) return rc;
+  if (!A || !B || !C || !eig_re || !eig_im || !n_eig || !n_forward || !n_unstable || !status)
+    return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, ne = (size_t)batch * 2 * n;
+  const double *dA, *dB, *dC;
+  double *dRe, *dIm;
+  int32_t *dNe, *dNf, *dNu, *dS;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.out(&dRe, eig_re, ne);
+  hc.out(&dIm, eig_im, ne);
+  hc.out(&dNe, n_eig, batch);
+  hc.out(&dNf, n_forward, batch);
+  hc.out(&dNu, n_unstable, batch);
+  hc.out(&dS, status, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_bk_eigenvalues_batched(dA, dB, dC, batch, n, tol, dRe, dIm, dNe, dNf, dNu, dS, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_selection_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
+                                int batch, int n, int k, double* R_out, double* resid_out) {
+  int rc = check_common(batch, n, DSGE_MAX_N_BIG);
+  if (rc) return rc;
+  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
+  if (!B || !C || !D || !T || !R_out) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
+  const double *dA, *dB, *dC, *dD, *dT;
+  double *dR, *dRes;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, D, nk);
+  hc.in(&dT, T, nn);
+  hc.out(&dR, R_out, nk);
+  hc.out(&dRes, resid_out, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_selection_batched(dA, dB, dC, dD, dT, batch, n, k, dR, dRes, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_selection_adjoints_batched_host(const double* B, const double* C, const double* T, const double* R,
+                                         const double* R_bar, int batch, int n, int k, double* B_bar, double* C_bar,
+                                         double* D_bar, double* T_bar) {
+  int rc = check_common(batch, n, 56);
+  if (rc) return rc;
+  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
+  if (!B || !C || !T || !R || !R_bar || !B_bar || !C_bar || !D_bar || !T_bar) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
+  const double *dB, *dC, *dT, *dR, *dRb;
+  double *dBb, *dCb, *dDb, *dTb;
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dT, T, nn);
+  hc.in(&dR, R, nk);
+  hc.in(&dRb, R_bar, nk);
+  hc.out(&dBb, B_bar, nn);
+  hc.out(&dCb, C_bar, nn);
+  hc.out(&dDb, D_bar, nk);
+  hc.out(&dTb, T_bar, nn);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_selection_adjoints_batched(dB, dC, dT, dR, dRb, batch, n, k, dBb, dCb, dDb, dTb, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_policy_adjoints_batched_host(const double* B, const double* C, const double* T, const double* T_bar,
+                                      int batch, int n, double* A_bar, double* B_bar, double* C_bar, int32_t* status) {
+  int rc = check_common(batch, n, 56);
+  if (rc) return rc;
+  if (!B || !C || !T || !T_bar || !A_bar || !B_bar || !C_bar || !status) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n;
+  const double *dB, *dC, *dT, *dTb;
+  double *dAb, *dBb, *dCb;
+  int32_t* dS;
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dT, T, nn);
+  hc.in(&dTb, T_bar, nn);
+  hc.out(&dAb, A_bar, nn);
+  hc.out(&dBb, B_bar, nn);
+  hc.out(&dCb, C_bar, nn);
+  hc.out(&dS, status, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_policy_adjoints_batched(dB, dC, dT, dTb, batch, n, dAb, dBb, dCb, dS, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_second_order_logp_batched_host(const double* A, const double* B, const double* C, const double* D,
+                                        const int32_t* hess_idx, int nnz, const double* hess_val, const double* q,
+                                        int q_batched, const double* Z, const double* d, const double* Hdiag, const double* y,
+                                        int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
+                                        double jitter, double missing_fill, const int32_t* state_idx, int n_state,
+                                        const int32_t* lead_idx, int n_lead, const int32_t* ret_idx, int n_ret,
+                                        double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* gyy_out,
+                                        double* gyu_out, double* guu_out, double* gss_out) {
+  int rc = check_common(batch, n, DSGE_MAX_N_CR);
+  if (rc) return rc;
+  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0 || nnz < 0 || n_state < 1 || n_state > 24)
+    return fail(DSGE_ERR_INVALID, "second order: size out of range");
+  if (!A || !B || !C || !D || (nnz > 0 && (!hess_idx || !hess_val)) || !q || !Z || !y || !logp_out || !status_out ||
+      !state_idx || !ret_idx || (n_lead > 0 && !lead_idx))
+    return fail(DSGE_ERR_INVALID, "null pointer");
+  // the structure arguments are host arrays here as in the device entry point: validated BEFORE anything is staged
+  if (n_lead < 0 || n_lead > n || n_ret < n_state || n_ret > n) return fail(DSGE_ERR_INVALID, "second order: n_lead / n_ret out of range");
+  for (int i = 0; i < n_state; ++i)
+    if (state_idx[i] < 0 || state_idx[i] >= n) return fail(DSGE_ERR_INVALID, "state_idx out of range");
+  for (int i = 0; i < n_lead; ++i)
+    if (lead_idx[i] < 0 || lead_idx[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
+  for (int i = 0; i < n_ret; ++i)
+    if (ret_idx[i] < 0 || ret_idx[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nv = (size_t)batch * nnz, ss = (size_t)n_state * n_state;
+  const double *dA, *dB, *dC, *dD, *dHv, *dq, *dZ, *dd, *dH, *dy;
+  const int32_t* dHi;
+  double *dlp, *dT, *dR, *dgyy, *dgyu, *dguu, *dgss;
+  int32_t* dst;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, D, nk);
+  hc.in(&dHi, hess_idx, (size_t)nnz * 3);
+  hc.in(&dHv, hess_val, nv);
+  hc.in(&dq, q, q_batched ? (size_t)batch * k : (size_t)k);
+  hc.in(&dZ, Z, (size_t)p * n);
+  hc.in(&dd, d, p);
+  hc.in(&dH, Hdiag, p);
+  hc.in(&dy, y, (size_t)T_len * p);
+  hc.out(&dlp, logp_out, batch);
+  hc.out(&dst, status_out, batch);
+  hc.out(&dT, T_out, nn);
+  hc.out(&dR, R_out, nk);
+  hc.out(&dgyy, gyy_out, (size_t)batch * n * ss);
+  hc.out(&dgyu, gyu_out, (size_t)batch * n * n_state * k);
+  hc.out(&dguu, guu_out, (size_t)batch * n * k * k);
+  hc.out(&dgss, gss_out, (size_t)batch * n);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_second_order_logp_batched(dA, dB, dC, dD, dHi, nnz, dHv, dq, q_batched, dZ, dd, dH, dy, batch, n, k, p, T_len,
+                                           solver, tol, max_iter, jitter, missing_fill, state_idx, n_state, lead_idx, n_lead,
+                                           ret_idx, n_ret, dlp, dst, dT, dR, dgyy, dgyu, dguu, dgss, nullptr, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                            int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                            const double* y, int batch, int m, int k, int p, int T_len, double jitter,
+                                            double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
+                                            double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m || p < 1 || p > DSGE_MAX_P || T_len < 0 || q_mode < 0 || q_mode > 3)
+    return fail(DSGE_ERR_INVALID, "size out of range");
+  if (!T || !R || !Q || !Z || !y || !ll_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, tm = (size_t)batch * T_len * m,
+               tc = full_cov ? tm * m : tm;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  double *dll, *dap, *daf, *dpp, *dpf;
+  int32_t* dS;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, mk);
+  hc.in(&dQ, Q, nq);
+  hc.in(&dZ, Z, nz);
+  hc.in(&dd, d, nd);
+  hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.io(&dS, status_io, batch);
+  hc.out(&dll, ll_out, (size_t)batch * T_len);
+  hc.out(&dap, a_pred_out, tm);
+  hc.out(&daf, a_filt_out, tm);
+  hc.out(&dpp, p_pred_out, tc);
+  hc.out(&dpf, p_filt_out, tc);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_kalman_filter_outputs_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k, p,
+                                               T_len, jitter, missing_fill, dll, dap, daf, dpp, dpf, full_cov, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_policy_norms_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
+                                   const double* R, const int32_t* state_mask, int batch, int n, int k,
+                                   double* det_norm_out, double* stoch_norm_out) {
+  int rc = check_common(batch, n, 56);
+  if (rc) return rc;
+  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
+  if (!A || !B || !C || !D || !T || !R || !state_mask || !det_norm_out || !stoch_norm_out)
+    return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
+  const double *dA, *dB, *dC, *dD, *dT, *dR;
+  const int32_t* dM;
+  double *d1, *d2;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, D, nk);
+  hc.in(&dT, T, nn);
+  hc.in(&dR, R, nk);
+  hc.in(&dM, state_mask, n);
+  hc.out(&d1, det_norm_out, batch);
+  hc.out(&d2, stoch_norm_out, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_policy_norms_batched(dA, dB, dC, dD, dT, dR, dM, batch, n, k, d1, d2, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_backward_direct_batched_host(const double* A, const double* B, const double* D, int batch, int n, int k,
+                                      double* T_out, double* R_out) {
+  int rc = check_common(batch, n, DSGE_MAX_N_CR);
+  if (rc) return rc;
+  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
+  if (!A || !B || !D || !T_out || !R_out) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
+  const double *dA, *dB, *dD;
+  double *dT, *dR;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dD, D, nk);
+  hc.out(&dT, T_out, nn);
+  hc.out(&dR, R_out, nk);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_backward_direct_batched(dA, dB, dD, batch, n, k, dT, dR, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_lyapunov_batched_host(const double* T, const double* R, const double* Q, int q_mode, int batch, int m, int k,
+                               double* P0_out, double* RQR_out, int32_t* status) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!T || !R || !Q || !P0_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const double *dT, *dR, *dQ;
+  double *dP, *dX;
+  int32_t* dS;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, mk);
+  hc.in(&dQ, Q, nq);
+  hc.out(&dP, P0_out, mm);
+  hc.out(&dX, RQR_out, mm);
+  hc.out(&dS, status, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_lyapunov_batched(dT, dR, dQ, q_mode, batch, m, k, dP, dX, dS, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_solve_kalman_logp_augmented_batched_host(const double* A, const double* B, const double* C, const double* D,
+                                                  const double* Q, int q_mode, const double* Z, int z_batched,
+                                                  const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                                  const double* y, int batch, int n, int k, int p, int T_len, int solver,
+                                                  double tol, int max_iter, double jitter, double missing_fill, int m,
+                                                  const int32_t* inv_var_order, int n_links, const int32_t* link_rows,
+                                                  const int32_t* link_cols, int n_state_hint, int z_selector_hint,
+                                                  int n_lead_hint, double* logp_out, int32_t* status_out,
+                                                  double* T_aug_out, double* R_aug_out, double* resid_out) {
+  int rc = check_common(batch, n, DSGE_MAX_N);
+  if (rc) return rc;
+  if (m < n || m > DSGE_MAX_N_BIG || k < 1 || k > n || p < 1 || p > DSGE_MAX_P || T_len < 0 || n_links < 0)
+    return fail(DSGE_ERR_INVALID, "bad sizes");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
+  const double *dA, *dB, *dC, *dD, *dQ, *dZ, *dd, *dH, *dy;
+  const int32_t *dinv, *dlr, *dlc;
+  double *dL, *dTa, *dRa, *dRes;
+  int32_t* dS;
+  hc.in(&dA, A, nn);
+  hc.in(&dB, B, nn);
+  hc.in(&dC, C, nn);
+  hc.in(&dD, D, nk);
+  hc.in(&dQ, Q, nq);
+  hc.in(&dZ, Z, nz);
+  hc.in(&dd, d, nd);
+  hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.in(&dinv, inv_var_order, n);
+  hc.in(&dlr, link_rows, n_links);
+  hc.in(&dlc, link_cols, n_links);
+  hc.out(&dL, logp_out, batch);
+  hc.out(&dS, status_out, batch);
+  hc.out(&dTa, T_aug_out, mm);
+  hc.out(&dRa, R_aug_out, mk);
+  hc.out(&dRes, resid_out, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_solve_kalman_logp_augmented_batched(dA, dB, dC, dD, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched,
+                                                     dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
+                                                     m, dinv, n_links, dlr, dlc, n_state_hint, z_selector_hint, n_lead_hint,
+                                                     dL, dS, dTa, dRa, dRes, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_solve_kalman_logp_grad_batched_host(const double* A, const double* B, const double* C, const double* D,
+                                             const double* q, int q_batched, const double* Z, int z_batched,
+                                             const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                             const double* y, int batch, int n, int k, int p, int T_len, int solver,
+                                             double tol, int max_iter, double jitter, double missing_fill,
+                                             int n_filter_hint, int n_lead_hint, double* logp_out, int32_t* status_out,
+                                             double* A_bar, double* B_bar, double* C_bar, double* D_bar, double* q_bar,
+                                             double* d_bar, double* h_bar) {
+  return grad_host(A, B, C, D, q, q_batched, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver, tol,
+                   max_iter, jitter, missing_fill, n_filter_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar, D_bar,
+                   q_bar, d_bar, h_bar, false, nullptr);
+}
+
+int dsge_solve_kalman_logp_grad_dense_z_batched_host(const double* A, const double* B, const double* C, const double* D,
+                                                     const double* q, int q_batched, const double* Z, int z_batched,
+                                                     const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                                     const double* y, int batch, int n, int k, int p, int T_len, int solver,
+                                                     double tol, int max_iter, double jitter, double missing_fill,
+                                                     int n_filter_hint, int n_lead_hint, double* logp_out,
+                                                     int32_t* status_out, double* A_bar, double* B_bar, double* C_bar,
+                                                     double* D_bar, double* q_bar, double* d_bar, double* h_bar,
+                                                     double* Z_bar) {
+  return grad_host(A, B, C, D, q, q_batched, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver, tol,
+                   max_iter, jitter, missing_fill, n_filter_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar, D_bar,
+                   q_bar, d_bar, h_bar, true, Z_bar);
+}
+
+int dsge_autocorrelation_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                      const double* Hdiag, int batch, int m, int k, int p, int n_lags, int lag_step,
+                                      int correlation, double* acf_out, double* Sigma_out, int32_t* status) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (n_lags < 0 || lag_step < 1) return fail(DSGE_ERR_INVALID, "n_lags >= 0 and lag_step >= 1 required");
+  if (Z && (p < 1 || p > DSGE_MAX_P)) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
+  if (!T || !R || !Q || !acf_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const int dim = Z ? p : m;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const size_t no = (size_t)batch * (n_lags + 1) * dim * dim;
+  const double *dT, *dR, *dQ, *dZ, *dH;
+  double *dSig, *dO;
+  int32_t* dS;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, mk);
+  hc.in(&dQ, Q, nq);
+  hc.in(&dZ, Z, (size_t)p * m);
+  hc.in(&dH, Hdiag, p);
+  if (Sigma_out)  // (the device entry always writes the state covariance)
+    hc.out(&dSig, Sigma_out, mm);
+  else
+    hc.space(&dSig, mm);
+  hc.out(&dO, acf_out, no);
+  hc.out(&dS, status, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_autocorrelation_batched(dT, dR, dQ, q_mode, dZ, dH, batch, m, k, p, n_lags, lag_step, correlation, dO,
+                                         dSig, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_kalman_logp_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                  int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                  const double* y, int batch, int m, int k, int p, int T_len, double jitter,
+                                  double missing_fill, int n_state_hint, int z_selector_hint, double* logp_out,
+                                  int32_t* status_io) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
+  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!T || !R || !Q || !Z || !y || !logp_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  double* dL;
+  int32_t* dS;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, mk);
+  hc.in(&dQ, Q, nq);
+  hc.in(&dZ, Z, nz);
+  hc.in(&dd, d, nd);
+  hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.io(&dS, status_io, batch);
+  hc.out(&dL, logp_out, batch);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_kalman_logp_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k,
+                                     p, T_len, jitter, missing_fill, n_state_hint, z_selector_hint, dL, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_solve_kalman_logp_batched_host(const double* A, const double* B, const double* C, const double* D,
+                                        const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
+                                        int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
+                                        int n, int k, int p, int T_len, int solver, double tol, int max_iter,
+                                        double jitter, double missing_fill, int n_state_hint, int z_selector_hint,
+                                        int n_lead_hint, double* logp_out, int32_t* status_out, double* T_out,
+                                        double* R_out, double* resid_out, int32_t* n_iter_out) {
+  const int solver_code = solver & ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
+  int rc = check_common(batch, n, (solver_code == DSGE_SOLVER_CYCLE_REDUCTION || solver_code == DSGE_SOLVER_SCAN_CYCLE_REDUCTION ||
+                                   (solver_code == DSGE_SOLVER_GENSYS && opt().gensys_doubling != 0))
+                                      ? DSGE_MAX_N_BIG
+                                      : DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
+  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
+  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
+  // Shared inputs first (stream 0, by stage()), then the batch in chunks on two streams: while the kernels of chunk c run,
+  // the host stages chunk c+1 (pageable memory: hipMemcpyAsync returns once the runtime has staged the buffer), so
+  // the PCIe transfer of the Jacobians overlaps the compute.  Outputs come back in one go at the end.
+  const bool q_b = (q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED);
+  const bool d_b = d && d_batched, h_b = Hdiag && h_batched;
+  // (per draw: space only, uploaded chunk by chunk below -- as are Q, Z, d, Hdiag when they are batched)
+  const double *dA, *dB, *dC, *dD, *dQ, *dZ, *dd, *dH, *dy;
+  double *dL, *dT, *dR, *dRes;
+  int32_t *dS, *dI;
+  hc.space(&dA, nn);
+  hc.space(&dB, nn);
+  hc.space(&dC, nn);
+  hc.space(&dD, nk);
+  q_b ? hc.space(&dQ, nq) : hc.in(&dQ, Q, nq);
+  z_batched ? hc.space(&dZ, nz) : hc.in(&dZ, Z, nz);
+  d_b ? hc.space(&dd, nd) : hc.in(&dd, d, nd);
+  h_b ? hc.space(&dH, nh) : hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.out(&dL, logp_out, batch);
+  hc.out(&dS, status_out, batch);
+  hc.out(&dT, T_out, nn);
+  hc.out(&dR, R_out, nk);
+  hc.out(&dRes, resid_out, batch);
+  hc.out(&dI, n_iter_out, batch);
+  if ((rc = hc.stage())) return rc;
+  HIP_TRY(hipStreamSynchronize(hc.stream(0)));
+  const int n_chunks = (batch >= 2048) ? 4 : (batch >= 512 ? 2 : 1);
+  const int per = (batch + n_chunks - 1) / n_chunks;
+  const size_t qk = (q_mode == DSGE_Q_FULL_BATCHED) ? (size_t)k * k : (size_t)k;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int c0 = c * per;
+    const int nb = (batch - c0 < per) ? batch - c0 : per;
+    if (nb <= 0) break;
+    hipStream_t st = hc.stream(c & 1);
+    const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k, oq = c0 * qk, oz = (size_t)c0 * p * n, op = (size_t)c0 * p;
+    auto up = [st](const double* dev, const double* host, size_t count) {  // a slice of a space-only buffer
+      return hipMemcpyAsync(const_cast<double*>(dev), host, count * sizeof(double), hipMemcpyHostToDevice, st);
+    };
+    HIP_TRY(up(dA + o2, A + o2, (size_t)nb * n * n));
+    HIP_TRY(up(dB + o2, B + o2, (size_t)nb * n * n));
+    HIP_TRY(up(dC + o2, C + o2, (size_t)nb * n * n));
+    HIP_TRY(up(dD + ok, D + ok, (size_t)nb * n * k));
+    if (q_b) HIP_TRY(up(dQ + oq, Q + oq, (size_t)nb * qk));
+    if (z_batched) HIP_TRY(up(dZ + oz, Z + oz, (size_t)nb * p * n));
+    if (d_b) HIP_TRY(up(dd + op, d + op, (size_t)nb * p));
+    if (h_b) HIP_TRY(up(dH + op, Hdiag + op, (size_t)nb * p));
+    // (pipeline_unchunked, not the public entry: that one would chunk again under dsge_options.pipeline_chunks)
+    if ((rc = pipeline_unchunked(dA + o2, dB + o2, dC + o2, dD + ok, q_b ? dQ + oq : dQ, q_mode, z_batched ? dZ + oz : dZ,
+                                 z_batched, d_b ? dd + op : dd, d_batched, h_b ? dH + op : dH, h_batched, dy, nb, n, k, p,
+                                 T_len, solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
+                                 dL + c0, dS + c0, dT ? dT + o2 : nullptr, dR ? dR + ok : nullptr,
+                                 dRes ? dRes + c0 : nullptr, dI ? dI + c0 : nullptr, st, 1, nullptr)))
+      return rc;
+  }
+  for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamSynchronize(hc.stream(i)));
+  return hc.finish();
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // C ABI of libdsge_hip.so (declared in include/dsge_hip.h): argument checking, kernel
-// dispatch on the tile size BS = ceil(n/8), library-owned scratch, host staging twins.
+// dispatch on the tile size BS = ceil(n/8), library-owned scratch.  The *_host twins are in api_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -35,18 +35,12 @@ static Options defaults_from_environment() {
 }
 const Options g_defaults = defaults_from_environment();
 thread_local const Options* t_call_options = nullptr;  // options of the call running on this thread
-}  // namespace dsge_host
-
-using namespace dsge_host;
 
 namespace {
-
-
-
-
 bool g_device_checked = false;
 int g_device_ok = 0;
 std::mutex g_mutex;
+}  // namespace
 
 // Lazy device check (fork-aware: nothing touches HIP before the first call).
 int ensure_device() {
@@ -67,62 +61,11 @@ int ensure_device() {
   g_device_ok = 1;
   return DSGE_SUCCESS;
 }
+}  // namespace dsge_host
 
-// ---- library-owned device scratch (grown on demand, one arena per device) ----------------
-struct Arena {
-  void* ptr = nullptr;
-  size_t cap = 0;
-  int dev = -1;
-  bool leased = false;
-};
-constexpr int MAX_DEV = 16;
+using namespace dsge_host;
 
-// Host-twin staging.  Host threads call the twins concurrently (ctypes releases the GIL: PyMC / nutpie chains in threads,
-// two pytensor Ops), so a twin LEASES a staging arena for the duration of its call from a pool that grows to the number of
-// concurrent callers; arenas are never shared between two calls in flight and never freed while leased.
-std::mutex g_stage_mutex;
-std::vector<Arena*> g_stage_pool;
-
-struct StageLease {
-  Arena* a = nullptr;
-  ~StageLease() {
-    if (a) {
-      std::lock_guard<std::mutex> lk(g_stage_mutex);
-      a->leased = false;
-    }
-  }
-  int reserve(size_t bytes, void** out) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= MAX_DEV) return fail(DSGE_ERR_INVALID, "device index out of range");
-    {
-      std::lock_guard<std::mutex> lk(g_stage_mutex);
-      for (Arena* c : g_stage_pool)  // the largest free arena of this device
-        if (!c->leased && c->dev == dev && (!a || c->cap > a->cap)) a = c;
-      if (!a) {
-        a = new Arena();
-        a->dev = dev;
-        g_stage_pool.push_back(a);
-      }
-      a->leased = true;
-    }
-    if (a->cap < bytes) {  // only this call holds the arena: nothing of it is in flight
-      if (a->ptr) {
-        HIP_TRY(hipFree(a->ptr));
-        a->ptr = nullptr;
-        a->cap = 0;
-      }
-      const size_t cap = bytes + bytes / 4 + 4096;
-      HIP_TRY(hipMalloc(&a->ptr, cap));
-      a->cap = cap;
-    }
-    *out = a->ptr;
-    return DSGE_SUCCESS;
-  }
-};
-#define STAGE_RESERVE(bytes, out) \
-  StageLease stage_lease_;        \
-  if ((rc = stage_lease_.reserve((bytes), (out)))) return rc
+namespace {
 
 // Installs the options of one call on the calling thread (see dsge_host.hpp); nests.
 struct OptionsGuard {
@@ -286,7 +229,7 @@ int twin_streams(hipStream_t* s0, hipStream_t* s1) {
 }  // namespace dsge_host
 
 namespace {
-// The stream the verdict of gensys by spectral division runs on, next to the filter on the caller's stream (pipeline(), round 6):
+// The stream the verdict of gensys by spectral division runs on, next to the filter on the caller's stream (pipeline_unchunked(), round 6):
 // one per host thread and device, with its fork / join events; released when the thread exits.
 struct VerdictStream {
   hipStream_t s = nullptr;
@@ -340,6 +283,9 @@ struct Carver {
   }
 };
 
+}  // namespace
+
+namespace dsge_host {
 int check_common(int batch, int n, int n_max) {
   if (batch < 0) return fail(DSGE_ERR_INVALID, "batch < 0");
   if (n < 1 || n > n_max) return fail(DSGE_ERR_INVALID, "n out of range (1.." + std::to_string(n_max) + ")");
@@ -355,15 +301,7 @@ size_t q_elems(int q_mode, int batch, int k) {
     default: return 0;
   }
 }
-
-// host staging helpers ---------------------------------------------------------------------
-struct Stage {
-  Carver carver;
-  std::vector<std::pair<void*, std::pair<const void*, size_t>>> ups;
-  explicit Stage(void* base) : carver(base) {}
-};
-
-}  // namespace
+}  // namespace dsge_host
 
 extern "C" {
 
@@ -791,14 +729,16 @@ static int pipeline_big(const double* A, const double* B, const double* C, const
   return DSGE_SUCCESS;
 }
 
-static int pipeline(const double* A, const double* B, const double* C, const double* D, const double* Q, int q_mode,
-                    const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                    const double* y, int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
-                    double jitter, double missing_fill, int n_state_hint, int z_selector_hint, int n_lead_hint,
-                    double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* resid_out,
-                    int32_t* n_iter_out, hipStream_t st, int reps, float* ms_out, int arena_id = 0,
-                    void* scratch_slice = nullptr) {
-  (void)arena_id;  // (scratch is keyed by stream now; the chunked host path runs its chunks on two streams)
+}  // extern "C"
+
+// (declared in dsge_host.hpp: the fused host twin calls it chunk by chunk)
+int dsge_host::pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const double* Q,
+                                  int q_mode, const double* Z, int z_batched, const double* d, int d_batched,
+                                  const double* Hdiag, int h_batched, const double* y, int batch, int n, int k, int p,
+                                  int T_len, int solver, double tol, int max_iter, double jitter, double missing_fill,
+                                  int n_state_hint, int z_selector_hint, int n_lead_hint, double* logp_out,
+                                  int32_t* status_out, double* T_out, double* R_out, double* resid_out, int32_t* n_iter_out,
+                                  hipStream_t st, int reps, float* ms_out, void* scratch_slice) {
   const bool zero_T_on_failure = (solver & DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE) != 0;
   solver &= ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
   const bool is_cr = solver == DSGE_SOLVER_CYCLE_REDUCTION || solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION;
@@ -971,6 +911,8 @@ static int pipeline(const double* A, const double* B, const double* C, const dou
   return DSGE_SUCCESS;
 }
 
+extern "C" {
+
 int dsge_solve_kalman_logp_batched(const double* A, const double* B, const double* C, const double* D, const double* Q,
                                    int q_mode, const double* Z, int z_batched, const double* d, int d_batched,
                                    const double* Hdiag, int h_batched, const double* y, int batch, int n, int k, int p,
@@ -983,9 +925,9 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
   // Kalman launch busy for up to 200 full steps (1.5 ms) while the rest of the GPU has long finished; with two chunk
   // pipelines in flight that tail overlaps the cycle-reduction launch of the next chunk instead of being idle time.
   if (opt().pipeline_chunks < 2 || batch < 1024 || batch / opt().pipeline_chunks < 256)
-    return pipeline(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                    tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint, logp_out, status_out,
-                    T_out, R_out, resid_out, n_iter_out, (hipStream_t)stream, 1, nullptr);
+    return pipeline_unchunked(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len,
+                              solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
+                              logp_out, status_out, T_out, R_out, resid_out, n_iter_out, (hipStream_t)stream, 1, nullptr);
   int rc = ensure_device();
   if (rc) return rc;
   constexpr int MAXS = 8;
@@ -1014,12 +956,13 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
     const int c0 = c * per;
     const int nb = (batch - c0 < per) ? batch - c0 : per;
     const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k;
-    rc = pipeline(A + o2, B + o2, C + o2, D + ok, q_b ? Q + c0 * qk : Q, q_mode, z_batched ? Z + (size_t)c0 * p * n : Z,
-                  z_batched, (d && d_batched) ? d + (size_t)c0 * p : d, d_batched,
-                  (Hdiag && h_batched) ? Hdiag + (size_t)c0 * p : Hdiag, h_batched, y, nb, n, k, p, T_len, solver, tol,
-                  max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint, logp_out + c0, status_out + c0,
-                  T_out ? T_out + o2 : nullptr, R_out ? R_out + ok : nullptr, resid_out ? resid_out + c0 : nullptr,
-                  n_iter_out ? n_iter_out + c0 : nullptr, s_str[c % n_str], 1, nullptr, 0, (char*)base + slice * c);
+    rc = pipeline_unchunked(A + o2, B + o2, C + o2, D + ok, q_b ? Q + c0 * qk : Q, q_mode,
+                            z_batched ? Z + (size_t)c0 * p * n : Z, z_batched, (d && d_batched) ? d + (size_t)c0 * p : d,
+                            d_batched, (Hdiag && h_batched) ? Hdiag + (size_t)c0 * p : Hdiag, h_batched, y, nb, n, k, p, T_len,
+                            solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
+                            logp_out + c0, status_out + c0, T_out ? T_out + o2 : nullptr, R_out ? R_out + ok : nullptr,
+                            resid_out ? resid_out + c0 : nullptr, n_iter_out ? n_iter_out + c0 : nullptr, s_str[c % n_str], 1,
+                            nullptr, (char*)base + slice * c);
     if (rc) break;
   }
   for (int i = 0; i < n_str; ++i) {
@@ -1351,64 +1294,9 @@ int dsge_profile_pipeline(const double* A, const double* B, const double* C, con
                           int n_state_hint, int z_selector_hint, int n_lead_hint, double* logp_out,
                           int32_t* status_out, int reps, float* ms_out, void* stream) {
   if (!ms_out || reps < 1) return fail(DSGE_ERR_INVALID, "ms_out null or reps < 1");
-  return pipeline(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                  tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint, logp_out, status_out,
-                  nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, reps, ms_out);
-}
-
-// ------------------------------------------------------------------------------------------
-// Host twins: stage through library-owned device buffers on the default stream.
-// ------------------------------------------------------------------------------------------
-#define UP(dst, src, count, type)                                                                   \
-  type* dst = nullptr;                                                                              \
-  if (src) {                                                                                        \
-    dst = cv.take<type>(count);                                                                     \
-    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(type) * (count), hipMemcpyHostToDevice, tw_st));      \
-  }
-#define OUTBUF(dst, host, count, type) type* dst = (host) ? cv.take<type>(count) : nullptr;
-#define DOWN(host, dev, count, type)                                                                \
-  if (host) HIP_TRY(hipMemcpyAsync(host, dev, sizeof(type) * (count), hipMemcpyDeviceToHost, tw_st));
-
-static int cr_host(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol,
-                   double* T_out, int32_t* status, int32_t* n_iter, int scan_mode);
-
-int dsge_cycle_reduction_batched_host(const double* A, const double* B, const double* C, int batch, int n,
-                                      int max_iter, double tol, double* T_out, int32_t* status, int32_t* n_iter) {
-  return cr_host(A, B, C, batch, n, max_iter, tol, T_out, status, n_iter, 0);
-}
-
-int dsge_scan_cycle_reduction_batched_host(const double* A, const double* B, const double* C, int batch, int n,
-                                           int max_iter, double tol, double* T_out, int32_t* status,
-                                           int32_t* n_steps) {
-  return cr_host(A, B, C, batch, n, max_iter, tol, T_out, status, n_steps, 1);
-}
-
-static int cr_host(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol,
-                   double* T_out, int32_t* status, int32_t* n_iter, int scan_mode) {
-  int rc = check_common(batch, n, DSGE_MAX_N_BIG);
-  if (rc) return rc;
-  if (!A || !B || !C || !T_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n;
-  void* base = nullptr;
-  STAGE_RESERVE(4 * align256(nn * 8) + 2 * align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  OUTBUF(dT, T_out, nn, double);
-  OUTBUF(dS, status, batch, int32_t);
-  OUTBUF(dI, n_iter, batch, int32_t);
-  if ((rc = cr_entry(dA, dB, dC, batch, n, max_iter, tol, dT, dS, dI, tw_st, scan_mode))) return rc;
-  DOWN(T_out, dT, nn, double);
-  DOWN(status, dS, batch, int32_t);
-  DOWN(n_iter, dI, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
+  return pipeline_unchunked(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
+                            tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint, logp_out,
+                            status_out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, reps, ms_out);
 }
 
 // Debug hook: when enabled, kalman_sel_kernel accumulates the shader cycles draw 0 spends in each
@@ -1506,819 +1394,6 @@ int dsge_debug_gensys_window_phases(int enable, long long* cycles_out) {
     (void)hipFree(g_gensys_win_dbg);
     g_gensys_win_dbg = nullptr;
   }
-  return DSGE_SUCCESS;
-}
-
-int dsge_gensys_batched_host(const double* A, const double* B, const double* C, const double* D, int batch, int n,
-                             int k, double tol, int n_lead_hint, double* T_out, double* R_out, int32_t* eu_out,
-                             int32_t* status) {
-  int rc = check_common(batch, n, (big_size(n) && opt().gensys_doubling != 0) ? DSGE_MAX_N_BIG : DSGE_MAX_N_GENSYS - 1);
-  if (rc) return rc;
-  if (!A || !B || !C || !T_out || !eu_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (R_out && (!D || k < 1 || k > n)) return fail(DSGE_ERR_INVALID, "R_out requires D and 1 <= k <= n");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * (R_out ? k : 0);
-  void* base = nullptr;
-  STAGE_RESERVE(4 * align256(nn * 8) + 2 * align256(nk * 8) + 2 * align256((size_t)batch * 12) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  const double* dDp = nullptr;
-  if (R_out) {
-    UP(dD, D, nk, double);
-    dDp = dD;
-  }
-  OUTBUF(dT, T_out, nn, double);
-  OUTBUF(dR, R_out, nk, double);
-  OUTBUF(dE, eu_out, (size_t)batch * 3, int32_t);
-  OUTBUF(dS, status, batch, int32_t);
-  if ((rc = dsge_gensys_batched(dA, dB, dC, dDp, batch, n, k, tol, n_lead_hint, dT, dR, dE, dS, tw_st))) return rc;
-  DOWN(T_out, dT, nn, double);
-  DOWN(R_out, dR, nk, double);
-  DOWN(eu_out, dE, (size_t)batch * 3, int32_t);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_gensys_pencil_batched_host(const double* g0, const double* g1, const double* c, const double* psi, const double* pi,
-                                    int batch, int N, int k, int n_eta, double tol, double* G1_out, double* C_out,
-                                    double* impact_out, double* gev_out, int32_t* eu_out, int32_t* status) {
-  return dsge_gensys_pencil_full_batched_host(g0, g1, c, psi, pi, batch, N, k, n_eta, tol, G1_out, C_out, impact_out, gev_out,
-                                              eu_out, status, nullptr);
-}
-
-int dsge_gensys_pencil_full_batched_host(const double* g0, const double* g1, const double* c, const double* psi,
-                                         const double* pi, int batch, int N, int k, int n_eta, double tol, double* G1_out,
-                                         double* C_out, double* impact_out, double* gev_out, int32_t* eu_out,
-                                         int32_t* status, const dsge_gensys_forward* forward) {
-  int rc = check_common(batch, N, DSGE_MAX_N_GENSYS);
-  if (rc) return rc;
-  if (k < 1 || n_eta < 0 || n_eta + k + 1 > 64) return fail(DSGE_ERR_INVALID, "need k >= 1, n_eta >= 0, n_eta + k + 1 <= 64");
-  if (!g0 || !g1 || !psi || (n_eta > 0 && !pi) || !G1_out || !C_out || !impact_out || !gev_out || !eu_out || !status)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * N * N, nk = (size_t)batch * N * k, ne = (size_t)batch * N * (n_eta > 0 ? n_eta : 1),
-               nv = (size_t)batch * N;
-  void* base = nullptr;
-  const dsge_gensys_forward fh = forward ? *forward : dsge_gensys_forward{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  STAGE_RESERVE(3 * align256(nn * 8) + 2 * align256(nk * 8) + align256(ne * 8) + 2 * align256(nv * 8) + align256(nv * 32) +
-                    2 * align256((size_t)batch * 12) + (fh.f_mat ? align256(nn * 16) : 0) + (fh.y_wt ? align256(nn * 16) : 0) +
-                    (fh.f_wt ? align256(nk * 16) : 0) + (fh.loose ? align256(ne * 8) : 0) + align256((size_t)batch * 4) + 8192,
-                &base);
-  Carver cv(base);
-  UP(d0, g0, nn, double);
-  UP(d1, g1, nn, double);
-  UP(dc, c, nv, double);
-  UP(dps, psi, nk, double);
-  UP(dpi, pi, (size_t)batch * N * n_eta, double);
-  OUTBUF(dG, G1_out, nn, double);
-  OUTBUF(dC, C_out, nv, double);
-  OUTBUF(dI, impact_out, nk, double);
-  OUTBUF(dV, gev_out, nv * 4, double);
-  OUTBUF(dE, eu_out, (size_t)batch * 3, int32_t);
-  OUTBUF(dS, status, batch, int32_t);
-  OUTBUF(dFm, fh.f_mat, nn * 2, double);
-  OUTBUF(dFw, fh.f_wt, nk * 2, double);
-  OUTBUF(dYw, fh.y_wt, nn * 2, double);
-  OUTBUF(dLo, fh.loose, ne, double);
-  OUTBUF(dNu, fh.n_unstable, batch, int32_t);
-  const dsge_gensys_forward fd{dFm, dFw, dYw, dLo, dNu, fh.pi_raw};
-  if ((rc = dsge_gensys_pencil_full_batched(d0, d1, dc, dps, dpi, batch, N, k, n_eta, tol, dG, dC, dI, dV, dE, dS,
-                                            forward ? &fd : nullptr, tw_st)))
-    return rc;
-  DOWN(fh.f_mat, dFm, nn * 2, double);
-  DOWN(fh.f_wt, dFw, nk * 2, double);
-  DOWN(fh.y_wt, dYw, nn * 2, double);
-  DOWN(fh.loose, dLo, ne, double);
-  DOWN(fh.n_unstable, dNu, batch, int32_t);
-  DOWN(G1_out, dG, nn, double);
-  DOWN(C_out, dC, nv, double);
-  DOWN(impact_out, dI, nk, double);
-  DOWN(gev_out, dV, nv * 4, double);
-  DOWN(eu_out, dE, (size_t)batch * 3, int32_t);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_bk_eigenvalues_batched_host(const double* A, const double* B, const double* C, int batch, int n, double tol,
-                                     double* eig_re, double* eig_im, int32_t* n_eig, int32_t* n_forward,
-                                     int32_t* n_unstable, int32_t* status) {
-  int rc = check_common(batch, n, DSGE_MAX_N_GENSYS - 1);
-  if (rc) return rc;
-  if (!A || !B || !C || !eig_re || !eig_im || !n_eig || !n_forward || !n_unstable || !status)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, ne = (size_t)batch * 2 * n;
-  void* base = nullptr;
-  STAGE_RESERVE(3 * align256(nn * 8) + 2 * align256(ne * 8) + 4 * align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  OUTBUF(dRe, eig_re, ne, double);
-  OUTBUF(dIm, eig_im, ne, double);
-  OUTBUF(dNe, n_eig, batch, int32_t);
-  OUTBUF(dNf, n_forward, batch, int32_t);
-  OUTBUF(dNu, n_unstable, batch, int32_t);
-  OUTBUF(dS, status, batch, int32_t);
-  if ((rc = dsge_bk_eigenvalues_batched(dA, dB, dC, batch, n, tol, dRe, dIm, dNe, dNf, dNu, dS, tw_st))) return rc;
-  DOWN(eig_re, dRe, ne, double);
-  DOWN(eig_im, dIm, ne, double);
-  DOWN(n_eig, dNe, batch, int32_t);
-  DOWN(n_forward, dNf, batch, int32_t);
-  DOWN(n_unstable, dNu, batch, int32_t);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_selection_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
-                                int batch, int n, int k, double* R_out, double* resid_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N_BIG);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (!B || !C || !D || !T || !R_out) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = nullptr;
-  STAGE_RESERVE(4 * align256(nn * 8) + 2 * align256(nk * 8) + align256((size_t)batch * 8) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dT, T, nn, double);
-  OUTBUF(dR, R_out, nk, double);
-  OUTBUF(dRes, resid_out, batch, double);
-  if ((rc = dsge_selection_batched(dA, dB, dC, dD, dT, batch, n, k, dR, dRes, tw_st))) return rc;
-  DOWN(R_out, dR, nk, double);
-  DOWN(resid_out, dRes, batch, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_selection_adjoints_batched_host(const double* B, const double* C, const double* T, const double* R,
-                                         const double* R_bar, int batch, int n, int k, double* B_bar, double* C_bar,
-                                         double* D_bar, double* T_bar) {
-  int rc = check_common(batch, n, 56);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (!B || !C || !T || !R || !R_bar || !B_bar || !C_bar || !D_bar || !T_bar) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = nullptr;
-  STAGE_RESERVE(6 * align256(nn * 8) + 3 * align256(nk * 8) + 4096, &base);
-  Carver cv(base);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dT, T, nn, double);
-  UP(dR, R, nk, double);
-  UP(dRb, R_bar, nk, double);
-  OUTBUF(dBb, B_bar, nn, double);
-  OUTBUF(dCb, C_bar, nn, double);
-  OUTBUF(dDb, D_bar, nk, double);
-  OUTBUF(dTb, T_bar, nn, double);
-  if ((rc = dsge_selection_adjoints_batched(dB, dC, dT, dR, dRb, batch, n, k, dBb, dCb, dDb, dTb, tw_st))) return rc;
-  DOWN(B_bar, dBb, nn, double);
-  DOWN(C_bar, dCb, nn, double);
-  DOWN(D_bar, dDb, nk, double);
-  DOWN(T_bar, dTb, nn, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_policy_adjoints_batched_host(const double* B, const double* C, const double* T, const double* T_bar,
-                                      int batch, int n, double* A_bar, double* B_bar, double* C_bar, int32_t* status) {
-  int rc = check_common(batch, n, 56);
-  if (rc) return rc;
-  if (!B || !C || !T || !T_bar || !A_bar || !B_bar || !C_bar || !status) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n;
-  void* base = nullptr;
-  STAGE_RESERVE(7 * align256(nn * 8) + align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dT, T, nn, double);
-  UP(dTb, T_bar, nn, double);
-  OUTBUF(dAb, A_bar, nn, double);
-  OUTBUF(dBb, B_bar, nn, double);
-  OUTBUF(dCb, C_bar, nn, double);
-  OUTBUF(dS, status, batch, int32_t);
-  if ((rc = dsge_policy_adjoints_batched(dB, dC, dT, dTb, batch, n, dAb, dBb, dCb, dS, tw_st))) return rc;
-  DOWN(A_bar, dAb, nn, double);
-  DOWN(B_bar, dBb, nn, double);
-  DOWN(C_bar, dCb, nn, double);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_second_order_logp_batched_host(const double* A, const double* B, const double* C, const double* D,
-                                        const int32_t* hess_idx, int nnz, const double* hess_val, const double* q,
-                                        int q_batched, const double* Z, const double* d, const double* Hdiag, const double* y,
-                                        int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
-                                        double jitter, double missing_fill, const int32_t* state_idx, int n_state,
-                                        const int32_t* lead_idx, int n_lead, const int32_t* ret_idx, int n_ret,
-                                        double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* gyy_out,
-                                        double* gyu_out, double* guu_out, double* gss_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N_CR);
-  if (rc) return rc;
-  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0 || nnz < 0 || n_state < 1 || n_state > 24)
-    return fail(DSGE_ERR_INVALID, "second order: size out of range");
-  if (!A || !B || !C || !D || (nnz > 0 && (!hess_idx || !hess_val)) || !q || !Z || !y || !logp_out || !status_out ||
-      !state_idx || !ret_idx || (n_lead > 0 && !lead_idx))
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  // the structure arguments are host arrays here as in the device entry point: validated BEFORE anything is staged
-  if (n_lead < 0 || n_lead > n || n_ret < n_state || n_ret > n) return fail(DSGE_ERR_INVALID, "second order: n_lead / n_ret out of range");
-  for (int i = 0; i < n_state; ++i)
-    if (state_idx[i] < 0 || state_idx[i] >= n) return fail(DSGE_ERR_INVALID, "state_idx out of range");
-  for (int i = 0; i < n_lead; ++i)
-    if (lead_idx[i] < 0 || lead_idx[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
-  for (int i = 0; i < n_ret; ++i)
-    if (ret_idx[i] < 0 || ret_idx[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nv = (size_t)batch * nnz, ss = (size_t)n_state * n_state;
-  void* base = nullptr;
-  STAGE_RESERVE(5 * align256(nn * 8) + 4 * align256(nk * 8) + align256(nv * 8) + align256((size_t)nnz * 12) +
-                    align256((size_t)batch * k * 8) + align256(nn / n * ss * 8 + 64) + align256(nk * n_state * 8 + 64) +
-                    align256((size_t)batch * n * k * k * 8 + 64) + align256((size_t)batch * n * 8) +
-                    align256((size_t)p * n * 8) + 2 * align256((size_t)p * 8) + align256((size_t)T_len * p * 8 + 8) +
-                    2 * align256((size_t)batch * 8) + 16384,
-                &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dHi, hess_idx, (size_t)nnz * 3, int32_t);
-  UP(dHv, hess_val, nv, double);
-  UP(dq, q, q_batched ? (size_t)batch * k : (size_t)k, double);
-  UP(dZ, Z, (size_t)p * n, double);
-  UP(dd, d, p, double);
-  UP(dH, Hdiag, p, double);
-  UP(dy, y, (size_t)T_len * p, double);
-  OUTBUF(dlp, logp_out, batch, double);
-  OUTBUF(dst, status_out, batch, int32_t);
-  OUTBUF(dT, T_out, nn, double);
-  OUTBUF(dR, R_out, nk, double);
-  OUTBUF(dgyy, gyy_out, (size_t)batch * n * ss, double);
-  OUTBUF(dgyu, gyu_out, (size_t)batch * n * n_state * k, double);
-  OUTBUF(dguu, guu_out, (size_t)batch * n * k * k, double);
-  OUTBUF(dgss, gss_out, (size_t)batch * n, double);
-  if ((rc = dsge_second_order_logp_batched(dA, dB, dC, dD, dHi, nnz, dHv, dq, q_batched, dZ, dd, dH, dy, batch, n, k, p, T_len,
-                                           solver, tol, max_iter, jitter, missing_fill, state_idx, n_state, lead_idx, n_lead,
-                                           ret_idx, n_ret, dlp, dst, dT, dR, dgyy, dgyu, dguu, dgss, nullptr, tw_st)))
-    return rc;
-  DOWN(logp_out, dlp, batch, double);
-  DOWN(status_out, dst, batch, int32_t);
-  DOWN(T_out, dT, nn, double);
-  DOWN(R_out, dR, nk, double);
-  DOWN(gyy_out, dgyy, (size_t)batch * n * ss, double);
-  DOWN(gyu_out, dgyu, (size_t)batch * n * n_state * k, double);
-  DOWN(guu_out, dguu, (size_t)batch * n * k * k, double);
-  DOWN(gss_out, dgss, (size_t)batch * n, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
-                                            int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                                            const double* y, int batch, int m, int k, int p, int T_len, double jitter,
-                                            double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
-                                            double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > m || p < 1 || p > DSGE_MAX_P || T_len < 0 || q_mode < 0 || q_mode > 3)
-    return fail(DSGE_ERR_INVALID, "size out of range");
-  if (!T || !R || !Q || !Z || !y || !ll_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr;
-  if ((rc = twin_streams(&tw_st, nullptr))) return rc;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, tm = (size_t)batch * T_len * m,
-               tc = full_cov ? tm * m : tm;
-  void* base = nullptr;
-  STAGE_RESERVE(align256(mm * 8) + align256(mk * 8) + align256(nq * 8) + align256(nz * 8) + align256(nd * 8) + align256(nh * 8) +
-                    align256(ny * 8) + align256((size_t)batch * T_len * 8) + 2 * align256(tm * 8) + 2 * align256(tc * 8) +
-                    align256((size_t)batch * 4) + 8192,
-                &base);
-  Carver cv(base);
-  UP(dT, T, mm, double);
-  UP(dR, R, mk, double);
-  UP(dQ, Q, nq, double);
-  UP(dZ, Z, nz, double);
-  UP(dd, d, nd, double);
-  UP(dH, Hdiag, nh, double);
-  UP(dy, y, ny, double);
-  UP(dS, status_io, batch, int32_t);
-  OUTBUF(dll, ll_out, (size_t)batch * T_len, double);
-  OUTBUF(dap, a_pred_out, tm, double);
-  OUTBUF(daf, a_filt_out, tm, double);
-  OUTBUF(dpp, p_pred_out, tc, double);
-  OUTBUF(dpf, p_filt_out, tc, double);
-  if ((rc = dsge_kalman_filter_outputs_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k, p,
-                                               T_len, jitter, missing_fill, dll, dap, daf, dpp, dpf, full_cov, dS, tw_st)))
-    return rc;
-  DOWN(ll_out, dll, (size_t)batch * T_len, double);
-  DOWN(a_pred_out, dap, tm, double);
-  DOWN(a_filt_out, daf, tm, double);
-  DOWN(p_pred_out, dpp, tc, double);
-  DOWN(p_filt_out, dpf, tc, double);
-  DOWN(status_io, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_policy_norms_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
-                                   const double* R, const int32_t* state_mask, int batch, int n, int k,
-                                   double* det_norm_out, double* stoch_norm_out) {
-  int rc = check_common(batch, n, 56);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (!A || !B || !C || !D || !T || !R || !state_mask || !det_norm_out || !stoch_norm_out)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = nullptr;
-  STAGE_RESERVE(4 * align256(nn * 8) + 2 * align256(nk * 8) + 2 * align256((size_t)batch * 8) +
-                                       align256((size_t)n * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dT, T, nn, double);
-  UP(dR, R, nk, double);
-  UP(dM, state_mask, (size_t)n, int32_t);
-  OUTBUF(d1, det_norm_out, batch, double);
-  OUTBUF(d2, stoch_norm_out, batch, double);
-  if ((rc = dsge_policy_norms_batched(dA, dB, dC, dD, dT, dR, dM, batch, n, k, d1, d2, tw_st))) return rc;
-  DOWN(det_norm_out, d1, batch, double);
-  DOWN(stoch_norm_out, d2, batch, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_backward_direct_batched_host(const double* A, const double* B, const double* D, int batch, int n, int k,
-                                      double* T_out, double* R_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N_CR);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (!A || !B || !D || !T_out || !R_out) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = nullptr;
-  STAGE_RESERVE(3 * align256(nn * 8) + 2 * align256(nk * 8) + 4096, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dD, D, nk, double);
-  OUTBUF(dT, T_out, nn, double);
-  OUTBUF(dR, R_out, nk, double);
-  if ((rc = dsge_backward_direct_batched(dA, dB, dD, batch, n, k, dT, dR, tw_st))) return rc;
-  DOWN(T_out, dT, nn, double);
-  DOWN(R_out, dR, nk, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_lyapunov_batched_host(const double* T, const double* R, const double* Q, int q_mode, int batch, int m, int k,
-                               double* P0_out, double* RQR_out, int32_t* status) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !P0_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  void* base = nullptr;
-  STAGE_RESERVE(3 * align256(mm * 8) + align256(mk * 8) + align256(nq * 8) +
-                                       align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dT, T, mm, double);
-  UP(dR, R, mk, double);
-  UP(dQ, Q, nq, double);
-  OUTBUF(dP, P0_out, mm, double);
-  OUTBUF(dX, RQR_out, mm, double);
-  OUTBUF(dS, status, batch, int32_t);
-  if ((rc = dsge_lyapunov_batched(dT, dR, dQ, q_mode, batch, m, k, dP, dX, dS, tw_st))) return rc;
-  DOWN(P0_out, dP, mm, double);
-  DOWN(RQR_out, dX, mm, double);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_solve_kalman_logp_augmented_batched_host(const double* A, const double* B, const double* C, const double* D,
-                                                  const double* Q, int q_mode, const double* Z, int z_batched,
-                                                  const double* d, int d_batched, const double* Hdiag, int h_batched,
-                                                  const double* y, int batch, int n, int k, int p, int T_len, int solver,
-                                                  double tol, int max_iter, double jitter, double missing_fill, int m,
-                                                  const int32_t* inv_var_order, int n_links, const int32_t* link_rows,
-                                                  const int32_t* link_cols, int n_state_hint, int z_selector_hint,
-                                                  int n_lead_hint, double* logp_out, int32_t* status_out,
-                                                  double* T_aug_out, double* R_aug_out, double* resid_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N);
-  if (rc) return rc;
-  if (m < n || m > DSGE_MAX_N_BIG || k < 1 || k > n || p < 1 || p > DSGE_MAX_P || T_len < 0 || n_links < 0)
-    return fail(DSGE_ERR_INVALID, "bad sizes");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
-  void* base = nullptr;
-  STAGE_RESERVE(3 * align256(nn * 8) + align256(nk * 8) + align256(nq * 8) + align256(nz * 8) +
-                                       align256(nd * 8) + align256(nh * 8) + align256(ny * 8 + 8) + align256(mm * 8) +
-                                       align256(mk * 8) + 3 * align256((size_t)batch * 8) +
-                                       align256((size_t)n * 4) + 2 * align256((size_t)n_links * 4 + 4) + 8192, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dQ, Q, nq, double);
-  UP(dZ, Z, nz, double);
-  UP(dd, d, nd, double);
-  UP(dH, Hdiag, nh, double);
-  UP(dy, y, ny, double);
-  UP(dinv, inv_var_order, (size_t)n, int32_t);
-  UP(dlr, link_rows, (size_t)n_links, int32_t);
-  UP(dlc, link_cols, (size_t)n_links, int32_t);
-  OUTBUF(dL, logp_out, batch, double);
-  OUTBUF(dS, status_out, batch, int32_t);
-  OUTBUF(dTa, T_aug_out, mm, double);
-  OUTBUF(dRa, R_aug_out, mk, double);
-  OUTBUF(dRes, resid_out, batch, double);
-  if ((rc = dsge_solve_kalman_logp_augmented_batched(dA, dB, dC, dD, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched,
-                                                     dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
-                                                     m, dinv, n_links, dlr, dlc, n_state_hint, z_selector_hint, n_lead_hint,
-                                                     dL, dS, dTa, dRa, dRes, tw_st)))
-    return rc;
-  DOWN(logp_out, dL, batch, double);
-  DOWN(status_out, dS, batch, int32_t);
-  DOWN(T_aug_out, dTa, mm, double);
-  DOWN(R_aug_out, dRa, mk, double);
-  DOWN(resid_out, dRes, batch, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_solve_kalman_logp_grad_batched_host(const double* A, const double* B, const double* C, const double* D,
-                                             const double* q, int q_batched, const double* Z, int z_batched,
-                                             const double* d, int d_batched, const double* Hdiag, int h_batched,
-                                             const double* y, int batch, int n, int k, int p, int T_len, int solver,
-                                             double tol, int max_iter, double jitter, double missing_fill,
-                                             int n_filter_hint, int n_lead_hint, double* logp_out, int32_t* status_out,
-                                             double* A_bar, double* B_bar, double* C_bar, double* D_bar, double* q_bar,
-                                             double* d_bar, double* h_bar) {
-  int rc = check_common(batch, n, 56);
-  if (rc) return rc;
-  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0) return fail(DSGE_ERR_INVALID, "bad sizes");
-  if (!A || !B || !C || !D || !q || !Z || !y || !logp_out || !status_out || !A_bar || !B_bar || !C_bar || !D_bar || !q_bar)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  if (q_batched < 0 || q_batched > 3) return fail(DSGE_ERR_INVALID, "gradient path: q_batched is a DSGE_Q_* mode (0..3)");
-  const size_t qstride = (q_batched >= 2) ? (size_t)k * k : (size_t)k;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = (size_t)((q_batched & 1) ? batch : 1) * qstride;
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, bp = (size_t)batch * p;
-  void* base = nullptr;
-  STAGE_RESERVE(6 * align256(nn * 8) + 2 * align256(nk * 8) + align256(nq * 8) + align256(nz * 8) +
-                                       align256(nd * 8) + align256(nh * 8) + align256(ny * 8 + 8) +
-                                       2 * align256(bp * 8) + align256((size_t)batch * qstride * 8) +
-                                       2 * align256((size_t)batch * 8) + 8192, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dq, q, nq, double);
-  UP(dZ, Z, nz, double);
-  UP(dd, d, nd, double);
-  UP(dH, Hdiag, nh, double);
-  UP(dy, y, ny, double);
-  OUTBUF(dL, logp_out, batch, double);
-  OUTBUF(dS, status_out, batch, int32_t);
-  OUTBUF(gA, A_bar, nn, double);
-  OUTBUF(gB, B_bar, nn, double);
-  OUTBUF(gC, C_bar, nn, double);
-  OUTBUF(gD, D_bar, nk, double);
-  OUTBUF(gq, q_bar, (size_t)batch * qstride, double);
-  OUTBUF(gd, d_bar, bp, double);
-  OUTBUF(gh, h_bar, bp, double);
-  if ((rc = dsge_solve_kalman_logp_grad_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH, h_batched,
-                                                dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
-                                                n_filter_hint, n_lead_hint, dL, dS, gA, gB, gC, gD, gq, gd, gh, tw_st)))
-    return rc;
-  DOWN(logp_out, dL, batch, double);
-  DOWN(status_out, dS, batch, int32_t);
-  DOWN(A_bar, gA, nn, double);
-  DOWN(B_bar, gB, nn, double);
-  DOWN(C_bar, gC, nn, double);
-  DOWN(D_bar, gD, nk, double);
-  DOWN(q_bar, gq, (size_t)batch * qstride, double);
-  DOWN(d_bar, gd, bp, double);
-  DOWN(h_bar, gh, bp, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_solve_kalman_logp_grad_dense_z_batched_host(const double* A, const double* B, const double* C, const double* D,
-                                             const double* q, int q_batched, const double* Z, int z_batched,
-                                             const double* d, int d_batched, const double* Hdiag, int h_batched,
-                                             const double* y, int batch, int n, int k, int p, int T_len, int solver,
-                                             double tol, int max_iter, double jitter, double missing_fill,
-                                             int n_filter_hint, int n_lead_hint, double* logp_out, int32_t* status_out,
-                                             double* A_bar, double* B_bar, double* C_bar, double* D_bar, double* q_bar,
-                                             double* d_bar, double* h_bar, double* Z_bar) {
-  int rc = check_common(batch, n, 56);
-  if (rc) return rc;
-  if (n + p > 56) return fail(DSGE_ERR_INVALID, "gradient path with a dense design matrix: n + p must not exceed 56");
-  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0) return fail(DSGE_ERR_INVALID, "bad sizes");
-  if (!A || !B || !C || !D || !q || !Z || !y || !logp_out || !status_out || !A_bar || !B_bar || !C_bar || !D_bar || !q_bar)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  if (q_batched < 0 || q_batched > 3) return fail(DSGE_ERR_INVALID, "gradient path: q_batched is a DSGE_Q_* mode (0..3)");
-  const size_t qstride = (q_batched >= 2) ? (size_t)k * k : (size_t)k;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = (size_t)((q_batched & 1) ? batch : 1) * qstride;
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, bp = (size_t)batch * p;
-  void* base = nullptr;
-  STAGE_RESERVE(6 * align256(nn * 8) + 2 * align256(nk * 8) + align256(nq * 8) + align256(nz * 8) +
-                                       align256(nd * 8) + align256(nh * 8) + align256(ny * 8 + 8) +
-                                       2 * align256(bp * 8) + align256((size_t)batch * qstride * 8) + align256((size_t)batch * p * n * 8) +
-                                       2 * align256((size_t)batch * 8) + 8192, &base);
-  Carver cv(base);
-  UP(dA, A, nn, double);
-  UP(dB, B, nn, double);
-  UP(dC, C, nn, double);
-  UP(dD, D, nk, double);
-  UP(dq, q, nq, double);
-  UP(dZ, Z, nz, double);
-  UP(dd, d, nd, double);
-  UP(dH, Hdiag, nh, double);
-  UP(dy, y, ny, double);
-  OUTBUF(dL, logp_out, batch, double);
-  OUTBUF(dS, status_out, batch, int32_t);
-  OUTBUF(gA, A_bar, nn, double);
-  OUTBUF(gB, B_bar, nn, double);
-  OUTBUF(gC, C_bar, nn, double);
-  OUTBUF(gD, D_bar, nk, double);
-  OUTBUF(gq, q_bar, (size_t)batch * qstride, double);
-  OUTBUF(gd, d_bar, bp, double);
-  OUTBUF(gh, h_bar, bp, double);
-  OUTBUF(gZ, Z_bar, (size_t)batch * p * n, double);
-  if ((rc = dsge_solve_kalman_logp_grad_dense_z_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH, h_batched,
-                                                dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
-                                                n_filter_hint, n_lead_hint, dL, dS, gA, gB, gC, gD, gq, gd, gh, gZ, tw_st)))
-    return rc;
-  DOWN(logp_out, dL, batch, double);
-  DOWN(status_out, dS, batch, int32_t);
-  DOWN(A_bar, gA, nn, double);
-  DOWN(B_bar, gB, nn, double);
-  DOWN(C_bar, gC, nn, double);
-  DOWN(D_bar, gD, nk, double);
-  DOWN(q_bar, gq, (size_t)batch * qstride, double);
-  DOWN(d_bar, gd, bp, double);
-  DOWN(h_bar, gh, bp, double);
-  DOWN(Z_bar, gZ, (size_t)batch * p * n, double);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_autocorrelation_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
-                                      const double* Hdiag, int batch, int m, int k, int p, int n_lags, int lag_step,
-                                      int correlation, double* acf_out, double* Sigma_out, int32_t* status) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (n_lags < 0 || lag_step < 1) return fail(DSGE_ERR_INVALID, "n_lags >= 0 and lag_step >= 1 required");
-  if (Z && (p < 1 || p > DSGE_MAX_P)) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (!T || !R || !Q || !acf_out || !status) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const int dim = Z ? p : m;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t no = (size_t)batch * (n_lags + 1) * dim * dim;
-  void* base = nullptr;
-  STAGE_RESERVE(2 * align256(mm * 8) + align256(mk * 8) + align256(nq * 8) + align256(no * 8) +
-                                       align256((size_t)p * m * 8) + align256((size_t)p * 8) +
-                                       align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dT, T, mm, double);
-  UP(dR, R, mk, double);
-  UP(dQ, Q, nq, double);
-  UP(dZ, Z, (size_t)p * m, double);
-  UP(dH, Hdiag, (size_t)p, double);
-  double* dSig = cv.take<double>(mm);
-  OUTBUF(dO, acf_out, no, double);
-  OUTBUF(dS, status, batch, int32_t);
-  if ((rc = dsge_autocorrelation_batched(dT, dR, dQ, q_mode, dZ, dH, batch, m, k, p, n_lags, lag_step, correlation, dO,
-                                         dSig, dS, tw_st)))
-    return rc;
-  DOWN(acf_out, dO, no, double);
-  DOWN(Sigma_out, dSig, mm, double);
-  DOWN(status, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_kalman_logp_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
-                                  int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                                  const double* y, int batch, int m, int k, int p, int T_len, double jitter,
-                                  double missing_fill, int n_state_hint, int z_selector_hint, double* logp_out,
-                                  int32_t* status_io) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !Z || !y || !logp_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
-  void* base = nullptr;
-  STAGE_RESERVE(align256(mm * 8) + align256(mk * 8) + align256(nq * 8) + align256(nz * 8) +
-                              align256(nd * 8) + align256(nh * 8) + align256(ny * 8) + align256((size_t)batch * 8) +
-                              align256((size_t)batch * 4) + 4096, &base);
-  Carver cv(base);
-  UP(dT, T, mm, double);
-  UP(dR, R, mk, double);
-  UP(dQ, Q, nq, double);
-  UP(dZ, Z, nz, double);
-  UP(dd, d, nd, double);
-  UP(dH, Hdiag, nh, double);
-  UP(dy, y, ny, double);
-  UP(dS, status_io, batch, int32_t);
-  OUTBUF(dL, logp_out, batch, double);
-  if ((rc = dsge_kalman_logp_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k,
-                                     p, T_len, jitter, missing_fill, n_state_hint, z_selector_hint, dL, dS, tw_st)))
-    return rc;
-  DOWN(logp_out, dL, batch, double);
-  DOWN(status_io, dS, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  return DSGE_SUCCESS;
-}
-
-int dsge_solve_kalman_logp_batched_host(const double* A, const double* B, const double* C, const double* D,
-                                        const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
-                                        int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
-                                        int n, int k, int p, int T_len, int solver, double tol, int max_iter,
-                                        double jitter, double missing_fill, int n_state_hint, int z_selector_hint,
-                                        int n_lead_hint, double* logp_out, int32_t* status_out, double* T_out,
-                                        double* R_out, double* resid_out, int32_t* n_iter_out) {
-  const int solver_code = solver & ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
-  int rc = check_common(batch, n, (solver_code == DSGE_SOLVER_CYCLE_REDUCTION || solver_code == DSGE_SOLVER_SCAN_CYCLE_REDUCTION ||
-                                   (solver_code == DSGE_SOLVER_GENSYS && opt().gensys_doubling != 0))
-                                      ? DSGE_MAX_N_BIG
-                                      : DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((rc = ensure_device())) return rc;
-  hipStream_t tw_st = nullptr, tw_st1 = nullptr;
-  if ((rc = twin_streams(&tw_st, &tw_st1))) return rc;
-  (void)tw_st1;
-  if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
-  void* base = nullptr;
-  STAGE_RESERVE(4 * align256(nn * 8) + 2 * align256(nk * 8) + align256(nq * 8) + align256(nz * 8) +
-                              align256(nd * 8) + align256(nh * 8) + align256(ny * 8) + 2 * align256((size_t)batch * 8) +
-                              2 * align256((size_t)batch * 4) + 8192, &base);
-  Carver cv(base);
-  // Shared inputs first (default stream), then the batch in chunks on two streams: while the kernels of chunk c run,
-  // the host stages chunk c+1 (pageable memory: hipMemcpyAsync returns once the runtime has staged the buffer), so
-  // the PCIe transfer of the Jacobians overlaps the compute.  Outputs come back in one go at the end.
-  double *dA = cv.take<double>(nn), *dB = cv.take<double>(nn), *dC = cv.take<double>(nn), *dD = cv.take<double>(nk);
-  const bool q_b = (q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED);
-  double* dQ = cv.take<double>(nq);
-  double* dZ = cv.take<double>(nz);
-  double* dd = d ? cv.take<double>(nd) : nullptr;
-  double* dH = Hdiag ? cv.take<double>(nh) : nullptr;
-  double* dy = cv.take<double>(ny);
-  OUTBUF(dL, logp_out, batch, double);
-  OUTBUF(dS, status_out, batch, int32_t);
-  OUTBUF(dT, T_out, nn, double);
-  OUTBUF(dR, R_out, nk, double);
-  OUTBUF(dRes, resid_out, batch, double);
-  OUTBUF(dI, n_iter_out, batch, int32_t);
-  if (!q_b) HIP_TRY(hipMemcpyAsync(dQ, Q, nq * 8, hipMemcpyHostToDevice, tw_st));
-  if (!z_batched) HIP_TRY(hipMemcpyAsync(dZ, Z, nz * 8, hipMemcpyHostToDevice, tw_st));
-  if (d && !d_batched) HIP_TRY(hipMemcpyAsync(dd, d, nd * 8, hipMemcpyHostToDevice, tw_st));
-  if (Hdiag && !h_batched) HIP_TRY(hipMemcpyAsync(dH, Hdiag, nh * 8, hipMemcpyHostToDevice, tw_st));
-  HIP_TRY(hipMemcpyAsync(dy, y, ny * 8, hipMemcpyHostToDevice, tw_st));
-  HIP_TRY(hipStreamSynchronize(tw_st));
-  hipStream_t s_str[2] = {tw_st, tw_st1};
-  const int n_chunks = (batch >= 2048) ? 4 : (batch >= 512 ? 2 : 1);
-  const int per = (batch + n_chunks - 1) / n_chunks;
-  const size_t qk = (q_mode == DSGE_Q_FULL_BATCHED) ? (size_t)k * k : (size_t)k;
-  for (int c = 0; c < n_chunks; ++c) {
-    const int c0 = c * per;
-    const int nb = (batch - c0 < per) ? batch - c0 : per;
-    if (nb <= 0) break;
-    hipStream_t st = s_str[c & 1];
-    const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k;
-    HIP_TRY(hipMemcpyAsync(dA + o2, A + o2, (size_t)nb * n * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dB + o2, B + o2, (size_t)nb * n * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dC + o2, C + o2, (size_t)nb * n * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dD + ok, D + ok, (size_t)nb * n * k * 8, hipMemcpyHostToDevice, st));
-    if (q_b) HIP_TRY(hipMemcpyAsync(dQ + c0 * qk, Q + c0 * qk, (size_t)nb * qk * 8, hipMemcpyHostToDevice, st));
-    if (z_batched)
-      HIP_TRY(hipMemcpyAsync(dZ + (size_t)c0 * p * n, Z + (size_t)c0 * p * n, (size_t)nb * p * n * 8, hipMemcpyHostToDevice, st));
-    if (d && d_batched) HIP_TRY(hipMemcpyAsync(dd + (size_t)c0 * p, d + (size_t)c0 * p, (size_t)nb * p * 8, hipMemcpyHostToDevice, st));
-    if (Hdiag && h_batched)
-      HIP_TRY(hipMemcpyAsync(dH + (size_t)c0 * p, Hdiag + (size_t)c0 * p, (size_t)nb * p * 8, hipMemcpyHostToDevice, st));
-    if ((rc = pipeline(dA + o2, dB + o2, dC + o2, dD + ok, q_b ? dQ + c0 * qk : dQ, q_mode, z_batched ? dZ + (size_t)c0 * p * n : dZ,
-                       z_batched, (dd && d_batched) ? dd + (size_t)c0 * p : dd, d_batched,
-                       (dH && h_batched) ? dH + (size_t)c0 * p : dH, h_batched, dy, nb, n, k, p, T_len, solver, tol, max_iter, jitter,
-                       missing_fill, n_state_hint, z_selector_hint, n_lead_hint, dL + c0, dS + c0, dT ? dT + o2 : nullptr,
-                       dR ? dR + ok : nullptr, dRes ? dRes + c0 : nullptr, dI ? dI + c0 : nullptr, st, 1, nullptr, c & 1)))
-      return rc;
-  }
-  for (auto& x : s_str) HIP_TRY(hipStreamSynchronize(x));
-  DOWN(logp_out, dL, batch, double);
-  DOWN(status_out, dS, batch, int32_t);
-  DOWN(T_out, dT, nn, double);
-  DOWN(R_out, dR, nk, double);
-  DOWN(resid_out, dRes, batch, double);
-  DOWN(n_iter_out, dI, batch, int32_t);
-  HIP_TRY(hipStreamSynchronize(tw_st));
   return DSGE_SUCCESS;
 }
 

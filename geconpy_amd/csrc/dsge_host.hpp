@@ -56,6 +56,20 @@ void stream_arenas_release(hipStream_t st);  // every pool of the library (dsge_
 // arenas released -- when the thread exits): two host threads in two twins never share a stream, hence never an arena.
 int twin_streams(hipStream_t* s0, hipStream_t* s1);
 
+// Shared by the device entry points (dsge_api.hip) and their host twins (api_host.hip)
+int ensure_device();                          // lazy check for a gfx950 device: nothing touches HIP before the first call
+int check_common(int batch, int n, int n_max);
+size_t q_elems(int q_mode, int batch, int k);  // elements of a shock covariance in layout DSGE_Q_*
+// The fused solve + filter pipeline of ONE batch on ONE stream: what dsge_solve_kalman_logp_batched runs when it does not
+// split the batch (dsge_options.pipeline_chunks), with the stage timing of dsge_profile_pipeline (reps, ms_out) and an
+// optional slice of a scratch arena the caller reserved (chunks in flight on several streams).  Arguments as the public entry.
+int pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const double* Q, int q_mode,
+                       const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                       const double* y, int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
+                       double jitter, double missing_fill, int n_state_hint, int z_selector_hint, int n_lead_hint,
+                       double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* resid_out,
+                       int32_t* n_iter_out, hipStream_t st, int reps, float* ms_out, void* scratch_slice = nullptr);
+
 // hipEvent_t that destroys itself: stage-timing events must not leak on the early returns of HIP_TRY
 struct EventGuard {
   hipEvent_t e = nullptr;

@@ -126,6 +126,10 @@ def test_big_failed_draw_and_too_many_filtered_variables():
     with pytest.raises(_lib.DsgeTooLargeError):
         batched.solve_kalman_logp_batched(wide["A"], wide["B"], wide["C"], wide["D"], wide["sigma"] ** 2, omw["Z"], omw["y"],
                                           Hdiag=omw["Hdiag"], tol=1e-8, max_iter=1000)
+    # (the refusal comes after the host twin has staged its inputs: the next call of this thread is the same call as before, to the bit)
+    again = batched.solve_kalman_logp_batched(A, b["B"], b["C"], b["D"], b["sigma"] ** 2, om["Z"], om["y"], Hdiag=om["Hdiag"],
+                                              tol=1e-8, max_iter=1000)
+    assert np.array_equal(again["status"], r["status"]) and np.array_equal(again["logp"], r["logp"])
     # the ordered QZ keeps n + #lead <= 64 (gensys beyond that exists by spectral division only: test_big_gensys_*)
     with pytest.raises(_lib.DsgeHipError):
         batched.solve_kalman_logp_batched(b["A"], b["B"], b["C"], b["D"], b["sigma"] ** 2, om["Z"], om["y"], Hdiag=om["Hdiag"],
