@@ -25,7 +25,7 @@ int fail(int code, const std::string& msg) {
 // environment variable DSGE_GENSYS_DOUBLING = 0 | 1 | 2 | 3 replaces the default of dsge_options.gensys_doubling (a site that wants the
 // ordered QZ for every draw everywhere without touching its callers; the test suite runs its gensys tests under both values).
 static Options defaults_from_environment() {
-  Options o{};
+  Options o;
   if (const char* e = std::getenv("DSGE_GENSYS_DOUBLING"))
     if ((e[0] >= '0' && e[0] <= '3') && e[1] == '\0') o.gensys_doubling = e[0] - '0';
   // (A/B switch of the round-6 fused assembly + adjoint launch of the gradient pipeline; not part of dsge_options)
@@ -71,37 +71,10 @@ namespace {
 struct OptionsGuard {
   Options local;
   const Options* prev;
-  explicit OptionsGuard(const dsge_options* o) : prev(t_call_options) {
+  // (grad_fused_adjoint is an internal switch, not in dsge_options: it keeps the process-level value)
+  explicit OptionsGuard(const dsge_options* o) : local(g_defaults), prev(t_call_options) {
     if (!o) return;
-    local.grad_fused_adjoint = g_defaults.grad_fused_adjoint;  // (an internal switch, not in dsge_options: the process-level value)
-    local.cr_compact = o->cr_compact;
-    local.cr_fused_selection = o->cr_fused_selection;
-    local.cr_deflation = o->cr_deflation;
-    local.cr_two_waves = o->cr_two_waves;
-    local.n_static_hint = o->n_static_hint;
-    local.kalman_order = o->kalman_order;
-    local.kalman_tiny = o->kalman_tiny;
-    local.kalman_block = o->kalman_block;
-    local.kalman_mfma = o->kalman_mfma;
-    local.pipeline_chunks = o->pipeline_chunks;
-    local.gensys_split = o->gensys_split;
-    local.kalman_steady_tol = o->kalman_steady_tol;
-    local.kalman_nt_products = o->kalman_nt_products;
-    local.cr_fused_deflation = o->cr_fused_deflation;
-    local.cr_four_waves = o->cr_four_waves;
-    local.gensys_real_stage = o->gensys_real_stage;
-    local.gensys_pairs = o->gensys_pairs;
-    local.gensys_shape_cache = o->gensys_shape_cache;
-    local.kalman_narrow = o->kalman_narrow;
-    local.gensys_direct_blocks = o->gensys_direct_blocks;
-    local.kalman_head_draws = o->kalman_head_draws;
-    local.gensys_doubling = o->gensys_doubling;
-    local.kalman_grad_split = o->kalman_grad_split;
-    local.ll_constant = o->ll_constant;
-    local.mask_d = o->mask_d;
-    local.joseph = o->joseph;
-    local.jitter_F = o->jitter_F;
-    local.jitter_P = o->jitter_P;
+    static_cast<dsge_options&>(local) = *o;
     t_call_options = &local;
   }
   ~OptionsGuard() { t_call_options = prev; }
@@ -194,95 +167,109 @@ void stream_arenas_release(hipStream_t st) {
   for (StreamArenaPool* p : pool_registry()) p->release(st);
 }
 
-namespace {
-struct ThreadStreams {
-  hipStream_t s[2] = {nullptr, nullptr};
-  int dev = -1;
-  void drop() {
-    for (auto& x : s)
-      if (x) {
-        (void)hipStreamSynchronize(x);
-        stream_arenas_release(x);
-        (void)hipStreamDestroy(x);
-        x = nullptr;
-      }
-    (void)hipGetLastError();
-  }
-  ~ThreadStreams() { drop(); }
-};
-thread_local ThreadStreams t_streams;
-}  // namespace
+// ---- ScratchLayout (dsge_host.hpp) ----
+size_t ScratchLayout::bytes() const {
+  size_t b = PAD;
+  for (int i = 0; i < n_ && i < MAX_BUFS; ++i) b += align256(bufs_[i].bytes);
+  return b;
+}
 
-int twin_streams(hipStream_t* s0, hipStream_t* s1) {
+int ScratchLayout::reserve(StreamArenaPool& pool, hipStream_t st, void* slice) {
+  if (n_ > MAX_BUFS) return fail(DSGE_ERR_INVALID, "ScratchLayout: more buffers declared than MAX_BUFS");
+  void* base = slice;
+  if (!base) {
+    int rc = pool.reserve(bytes(), st, &base);
+    if (rc) return rc;
+  }
+  char* p = (char*)base;
+  for (int i = 0; i < n_; ++i) {
+    std::memcpy(bufs_[i].slot, &p, sizeof(p));  // (the slot is some T*: every object pointer has this representation)
+    p += align256(bufs_[i].bytes);
+  }
+  return DSGE_SUCCESS;
+}
+
+// ---- ThreadStream (dsge_host.hpp) ----
+int ThreadStream::ensure() {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  if (t_streams.dev != dev) {  // (streams belong to a device; recreate after a device switch)
-    t_streams.drop();
-    for (auto& x : t_streams.s) HIP_TRY(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-    t_streams.dev = dev;
+  if (dev_ == dev && s_ && ev_[0] && ev_[1]) return DSGE_SUCCESS;
+  // another device than last time, or a creation that failed half-way: drop what exists, then create all three -- a failure
+  // leaves a partially filled record behind that the next call (or the destructor) drops
+  drop();
+  dev_ = dev;
+  HIP_TRY(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+  for (auto& e : ev_) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return DSGE_SUCCESS;
+}
+
+void ThreadStream::drop() {  // (idempotent; the owning device is made current for the destroy calls and the caller's restored)
+  if (!s_ && !ev_[0] && !ev_[1]) return;
+  int cur = 0;
+  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+  if (dev_ >= 0) (void)hipSetDevice(dev_);
+  if (s_) {
+    (void)hipStreamSynchronize(s_);
+    stream_arenas_release(s_);
+    (void)hipStreamDestroy(s_);
+    s_ = nullptr;
   }
-  *s0 = t_streams.s[0];
-  if (s1) *s1 = t_streams.s[1];
+  for (auto& e : ev_) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+  open_ = false;
+  if (have_cur) (void)hipSetDevice(cur);
+  (void)hipGetLastError();
+}
+
+int ThreadStream::fork(hipStream_t from) {
+  int rc = ensure();
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(ev_[0], from));
+  HIP_TRY(hipStreamWaitEvent(s_, ev_[0], 0));
+  open_ = true;
+  return DSGE_SUCCESS;
+}
+
+int ThreadStream::join(hipStream_t into) {
+  HIP_TRY(hipEventRecord(ev_[1], s_));
+  HIP_TRY(hipStreamWaitEvent(into, ev_[1], 0));
+  open_ = false;
+  return DSGE_SUCCESS;
+}
+
+void ThreadStream::close(hipStream_t into) {
+  if (!open_) return;
+  if (hipEventRecord(ev_[1], s_) != hipSuccess || hipStreamWaitEvent(into, ev_[1], 0) != hipSuccess)
+    (void)hipStreamSynchronize(s_);
+  (void)hipGetLastError();
+  open_ = false;
+}
+
+int twin_streams(hipStream_t* s0, hipStream_t* s1) {
+  static thread_local ThreadStream t_twin[2];
+  for (auto& t : t_twin) {
+    int rc = t.ensure();
+    if (rc) return rc;
+  }
+  *s0 = t_twin[0].stream();
+  if (s1) *s1 = t_twin[1].stream();
   return DSGE_SUCCESS;
 }
 
 }  // namespace dsge_host
 
 namespace {
-// The stream the verdict of gensys by spectral division runs on, next to the filter on the caller's stream (pipeline_unchunked(), round 6):
-// one per host thread and device, with its fork / join events; released when the thread exits.
-struct VerdictStream {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  int dev = -1;
-  void release() {
-    if (!s && !fork && !join) return;
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    if (dev >= 0) (void)hipSetDevice(dev);
-    if (join) (void)hipEventDestroy(join);
-    if (fork) (void)hipEventDestroy(fork);
-    if (s) (void)hipStreamDestroy(s);
-    s = nullptr;
-    fork = join = nullptr;
-    if (have_cur) (void)hipSetDevice(cur);
-  }
-  ~VerdictStream() { release(); }
-};
-thread_local VerdictStream t_verdict;
-int verdict_stream(VerdictStream** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (t_verdict.dev != dev || !t_verdict.s || !t_verdict.fork || !t_verdict.join) {
-    t_verdict.release();
-    t_verdict.dev = dev;
-    HIP_TRY(hipStreamCreateWithFlags(&t_verdict.s, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&t_verdict.fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&t_verdict.join, hipEventDisableTiming));
-  }
-  *out = &t_verdict;
-  return DSGE_SUCCESS;
-}
+// The stream the verdict of gensys by spectral division runs on, next to the filter on the caller's stream (pipeline_unchunked(),
+// round 6), and the streams the chunks of dsge_options.pipeline_chunks alternate over
+thread_local ThreadStream t_verdict;
+constexpr int MAX_CHUNK_STREAMS = 8;
+thread_local ThreadStream t_chunk[MAX_CHUNK_STREAMS];
 
 // Scratch of the device entry points (one arena per (device, stream), StreamArenaPool)
 StreamArenaPool g_scratch_pool;
 StreamArenaPool g_aug_big_pool;  // the gathered model of the augmented route beyond 64 states
-int scratch_reserve(hipStream_t st, size_t bytes, void** out) { return g_scratch_pool.reserve(bytes, st, out); }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t count) {
-    T* p = (T*)(base + off);
-    off += align256(count * sizeof(T));
-    return p;
-  }
-};
-
 }  // namespace
 
 namespace dsge_host {
@@ -308,40 +295,27 @@ extern "C" {
 int dsge_abi_version(void) { return DSGE_ABI_VERSION; }
 const char* dsge_last_error(void) { return g_last_error.c_str(); }
 
-int dsge_debug_cr_phases(int enable, long long* cycles_out) {
+// The debug counter hooks: enable = 1 allocates (zeroed) the device buffer *slot of `count` int64 the kernels of one family
+// stamp, cycles_out (host, may be NULL) reads it back behind a device synchronisation, enable = 0 frees it.
+static int debug_counters(long long** slot, int count, int enable, long long* cycles_out) {
   int rc = ensure_device();
   if (rc) return rc;
-  if (enable && !g_cr_dbg) {
-    HIP_TRY(hipMalloc((void**)&g_cr_dbg, 8 * sizeof(long long)));
-    HIP_TRY(hipMemset(g_cr_dbg, 0, 8 * sizeof(long long)));
+  if (enable && !*slot) {
+    HIP_TRY(hipMalloc((void**)slot, count * sizeof(long long)));
+    HIP_TRY(hipMemset(*slot, 0, count * sizeof(long long)));
   }
-  if (cycles_out && g_cr_dbg) {
+  if (cycles_out && *slot) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cycles_out, g_cr_dbg, 8 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cycles_out, *slot, count * sizeof(long long), hipMemcpyDeviceToHost));
   }
-  if (!enable && g_cr_dbg) {
-    (void)hipFree(g_cr_dbg);
-    g_cr_dbg = nullptr;
+  if (!enable && *slot) {
+    (void)hipFree(*slot);
+    *slot = nullptr;
   }
   return DSGE_SUCCESS;
 }
-int dsge_debug_second_order_phases(int enable, long long* cycles_out) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (enable && !g_so_dbg) {
-    HIP_TRY(hipMalloc((void**)&g_so_dbg, 8 * sizeof(long long)));
-    HIP_TRY(hipMemset(g_so_dbg, 0, 8 * sizeof(long long)));
-  }
-  if (cycles_out && g_so_dbg) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cycles_out, g_so_dbg, 8 * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  if (!enable && g_so_dbg) {
-    (void)hipFree(g_so_dbg);
-    g_so_dbg = nullptr;
-  }
-  return DSGE_SUCCESS;
-}
+int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_dbg, 8, enable, cycles_out); }
+int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
 int dsge_debug_adjoint_refine(int mode) {
   if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
   g_adj_refine_mode = mode;
@@ -557,9 +531,9 @@ int dsge_autocorrelation_batched(const double* T, const double* R, const double*
   hipStream_t st = (hipStream_t)stream;
   double* Sigma = Sigma_out;
   if (!Sigma) {
-    void* base = nullptr;
-    if ((rc = scratch_reserve(st, align256((size_t)batch * m * m * sizeof(double)) + 4096, &base))) return rc;
-    Sigma = (double*)base;
+    ScratchLayout lay;
+    lay.add(&Sigma, (size_t)batch * m * m);
+    if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   }
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * batch, st));
   if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, nullptr,
@@ -584,11 +558,11 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   const size_t mm = (size_t)batch * m * m;
-  void* base = nullptr;
-  if ((rc = scratch_reserve(st, 2 * align256(mm * 8) + 4096, &base))) return rc;
-  Carver cv(base);
-  double* RQR = cv.take<double>(mm);
-  double* P0 = cv.take<double>(mm);
+  double *RQR = nullptr, *P0 = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, mm);
+  lay.add(&P0, mm);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, RQR, P0,
                             status_io, 0, 1, st)))
     return rc;
@@ -611,12 +585,12 @@ int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, 
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  void* base = nullptr;
   const size_t mm = (size_t)batch * m * m;
-  if ((rc = scratch_reserve(st, 2 * align256(mm * sizeof(double)) + 4096, &base))) return rc;
-  Carver cv(base);
-  double* RQR = cv.take<double>(mm);
-  double* P0 = cv.take<double>(mm);
+  double *RQR = nullptr, *P0 = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, mm);
+  lay.add(&P0, mm);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, RQR, P0,
                             status_io, 0, 2, st)))
     return rc;
@@ -624,14 +598,41 @@ int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, 
                        missing_fill, n_state_hint, z_selector_hint, logp_out, status_io, st);
 }
 
-inline size_t pipeline_scratch_bytes(int batch, int n, int k) {
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  size_t b = 3 * align256(nn * 8) + align256(nk * 8) + align256((size_t)batch * 12) + 3 * align256((size_t)batch * 4) +
-             align256((size_t)batch * 8) + 4096;
-  if (n > 64)  // pipeline_big: the gathered model (T_r, R_r, Z_r at 64 filtered variables) next to the full-size T, R
-    b += align256((size_t)batch * 64 * 64 * 8) + align256((size_t)batch * 64 * k * 8) +
-         align256((size_t)batch * DSGE_MAX_P * 64 * 8) + 1024;
-  return b;
+// The scratch of the fused pipeline for one batch, declared once for both of its routes: pipeline_unchunked and pipeline_big
+// take their pointers from it, the chunked entry asks it for the bytes of one chunk first.  T, R and the iteration counts are
+// the caller's outputs where given.
+struct PipelineScratch {
+  double *Tw, *Rw, *RQR, *P0;
+  int32_t *eu_w, *it_w;
+  int32_t *key_w, *vst_w;     // n <= 64: dispatch key of the Kalman launch; status words of an overlapped gensys verdict
+  unsigned long long* cm_w;   // n <= 64: non-zero columns of T, from the solver
+  double *T_r, *R_r, *Z_r;    // n > 64: the gathered model at 64 filtered variables
+  int32_t* park_w;            // n > 64
+};
+static void pipeline_declare(ScratchLayout& lay, PipelineScratch& s, int batch, int n, int k, int z_batched, double* T_out,
+                             double* R_out, int32_t* n_iter_out) {
+  const size_t b = (size_t)batch, nn = b * n * n, uu = b * 64 * 64;
+  s = PipelineScratch{};
+  if (!(s.Tw = T_out)) lay.add(&s.Tw, nn);
+  if (!(s.Rw = R_out)) lay.add(&s.Rw, b * n * k);
+  if (big_size(n)) {  // pipeline_big
+    lay.add(&s.T_r, uu);
+    lay.add(&s.R_r, b * 64 * k);
+    lay.add(&s.Z_r, (z_batched ? b : 1) * DSGE_MAX_P * 64);  // (not p: the chunked entry sizes a chunk before p is checked)
+    lay.add(&s.RQR, uu);
+    lay.add(&s.P0, uu);
+    if (!(s.it_w = n_iter_out)) lay.add(&s.it_w, b);
+    lay.add(&s.park_w, b);
+    lay.add(&s.eu_w, b * 3);  // (gensys: the certificate's eu codes)
+    return;
+  }
+  lay.add(&s.RQR, nn);
+  lay.add(&s.P0, nn);
+  lay.add(&s.eu_w, b * 3);
+  if (!(s.it_w = n_iter_out)) lay.add(&s.it_w, b);  // cycle-reduction iterations
+  lay.add(&s.key_w, b);
+  lay.add(&s.cm_w, b);
+  lay.add(&s.vst_w, b);
 }
 
 // ---- 65 .. 96 variables (dsge_big.hpp): cycle reduction with one workgroup per draw, then the EXISTING filter kernels on the
@@ -645,20 +646,12 @@ static int pipeline_big(const double* A, const double* B, const double* C, const
                         int32_t* status_out, double* T_out, double* R_out, double* resid_out, int32_t* n_iter_out, hipStream_t st,
                         int reps, float* ms_out, void* scratch_slice) {
   int rc;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = scratch_slice;
-  if (!base && (rc = scratch_reserve(st, pipeline_scratch_bytes(batch, n, k), &base))) return rc;
-  Carver cv(base);
-  double* Tw = T_out ? T_out : cv.take<double>(nn);
-  double* Rw = R_out ? R_out : cv.take<double>(nk);
-  double* T_r = cv.take<double>((size_t)batch * 64 * 64);
-  double* R_r = cv.take<double>((size_t)batch * 64 * k);
-  double* Z_r = cv.take<double>(z_batched ? (size_t)batch * p * 64 : (size_t)p * 64);
-  double* RQR = cv.take<double>((size_t)batch * 64 * 64);
-  double* P0 = cv.take<double>((size_t)batch * 64 * 64);
-  int32_t* it_w = n_iter_out ? n_iter_out : cv.take<int32_t>((size_t)batch);
-  int32_t* park_w = cv.take<int32_t>((size_t)batch);
-  int32_t* eu_w = cv.take<int32_t>((size_t)batch * 3);  // (gensys: the certificate's eu codes)
+  ScratchLayout lay;
+  PipelineScratch s;
+  pipeline_declare(lay, s, batch, n, k, z_batched, T_out, R_out, n_iter_out);
+  if ((rc = lay.reserve(g_scratch_pool, st, scratch_slice))) return rc;
+  double *Tw = s.Tw, *Rw = s.Rw, *T_r = s.T_r, *R_r = s.R_r, *Z_r = s.Z_r, *RQR = s.RQR, *P0 = s.P0;
+  int32_t *it_w = s.it_w, *park_w = s.park_w, *eu_w = s.eu_w;
   // F depends on A and Z only: measured FIRST (one small launch, a 72-byte read-back, one stream synchronisation per call -- not
   // per repetition), so that a model with more than 64 state + observed variables is refused before anything is enqueued and
   // before any output of this call is touched (DSGE_ERR_TOO_LARGE: "nothing computed", include/dsge_hip.h)
@@ -762,26 +755,19 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
                         park_failures, tol, max_iter, jitter, missing_fill, z_selector_hint, logp_out, status_out, T_out, R_out,
                         resid_out, n_iter_out, st, reps, ms_out, scratch_slice);
 
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = scratch_slice;  // (a slice of an arena the caller reserved: chunks in flight on several streams)
-  if (!base &&
-      (rc = scratch_reserve(st, pipeline_scratch_bytes(batch, n, k), &base)))
-    return rc;
-  Carver cv(base);
-  double* Tw = T_out ? T_out : cv.take<double>(nn);
-  double* Rw = R_out ? R_out : cv.take<double>(nk);
-  double* RQR = cv.take<double>(nn);
-  double* P0 = cv.take<double>(nn);
-  int32_t* eu_w = cv.take<int32_t>((size_t)batch * 3);
-  int32_t* it_w = n_iter_out ? n_iter_out : cv.take<int32_t>((size_t)batch);  // cycle-reduction iterations
-  int32_t* key_w = cv.take<int32_t>((size_t)batch);                            // dispatch key of the Kalman launch
-  unsigned long long* cm_w = cv.take<unsigned long long>((size_t)batch);       // non-zero columns of T, from the solver
-  int32_t* vst_w = cv.take<int32_t>((size_t)batch);                            // status words of an overlapped gensys verdict
+  ScratchLayout lay;
+  PipelineScratch s;
+  pipeline_declare(lay, s, batch, n, k, z_batched, T_out, R_out, n_iter_out);
+  // (scratch_slice: a slice of an arena the caller reserved -- chunks in flight on several streams)
+  if ((rc = lay.reserve(g_scratch_pool, st, scratch_slice))) return rc;
+  double *Tw = s.Tw, *Rw = s.Rw, *RQR = s.RQR, *P0 = s.P0;
+  int32_t *eu_w = s.eu_w, *it_w = s.it_w, *key_w = s.key_w, *vst_w = s.vst_w;
+  unsigned long long* cm_w = s.cm_w;
 
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  EventGuard ev[4];
   float acc_ms[3] = {0.f, 0.f, 0.f};
   if (ms_out)
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : ev) HIP_TRY(e.create());
   const int n_rep = ms_out ? reps : 1;
   for (int rep = 0; rep < n_rep; ++rep) {
     if (ms_out) HIP_TRY(hipEventRecord(ev[0], st));
@@ -792,7 +778,7 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
     int gensys_key = 0;  // 1: the gensys launches have written the Kalman dispatch key
     const int32_t* gensys_qz_marks = nullptr;  // gensys by spectral division: Rw already holds R of the unmarked draws
     dsge_host::GensysOverlap gov;              // ... with the verdict on a second stream (used = 1: join, merge, second filter pass below)
-    hipEvent_t gov_join = nullptr;
+    ForkGuard verdict_guard{nullptr, st};      // (armed in front of launch_gensys: joins the verdict on every return before the join below)
     if (is_cr) {
       int deflated = 0;
       // static variables deflated first (the iteration then runs on n - h variables); not when the caller asks for the
@@ -818,17 +804,13 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
       const bool q_diag_ = q_mode == DSGE_Q_DIAG_SHARED || q_mode == DSGE_Q_DIAG_BATCHED;
       const bool want_overlap = opt().gensys_doubling == 1 && !ms_out && !resid_out && !park_failures && !capturing && batch >= 256 &&
                                 q_diag_ && n <= 64 && kalman_folds_rqr(n, p, k, n_state_hint, z_selector_hint);
-      VerdictStream* vs = nullptr;
       if (want_overlap) {
-        if ((rc = verdict_stream(&vs))) return rc;
-        gov.st = vs->s;
-        gov.fork = vs->fork;
+        gov.side = verdict_guard.side = &t_verdict;
         gov.status = vst_w;
       }
       rc = launch_gensys(A, B, C, batch, n, tol, n_lead_hint, Tw, eu_w, status_out, st, nullptr,
                          (opt().kalman_order != 0 && batch >= 512) ? key_w : nullptr, &gensys_key, D, k, Rw, n_state_hint,
                          &gensys_qz_marks, want_overlap ? &gov : nullptr);
-      if (!rc && gov.used) gov_join = vs->join;
     } else {
       HIP_TRY(hipMemsetAsync(status_out, 0, sizeof(int32_t) * batch, st));
       if (n_iter_out) HIP_TRY(hipMemsetAsync(n_iter_out, 0, sizeof(int32_t) * batch, st));
@@ -880,8 +862,7 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
     if (gov.used) {
       // join the verdict; R of the draws the ordered QZ solved (explicit selection, marked draws only, by the verdict's status);
       // their status words; their filter (every launch a second pass)
-      HIP_TRY(hipEventRecord(gov_join, gov.st));
-      HIP_TRY(hipStreamWaitEvent(st, gov_join, 0));
+      if ((rc = gov.side->join(st))) return rc;
       if ((rc = launch_assemble(A, B, C, D, Tw, nullptr, Q, q_mode, batch, n, k, Rw, nullptr, nullptr, nullptr, gov.status, 1, 0, st,
                                 gov.marks)))
         return rc;
@@ -904,10 +885,8 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
       }
     }
   }
-  if (ms_out) {
+  if (ms_out)
     for (int i = 0; i < 3; ++i) ms_out[i] = acc_ms[i] / (float)n_rep;
-    for (auto& e : ev) HIP_TRY(hipEventDestroy(e));
-  }
   return DSGE_SUCCESS;
 }
 
@@ -930,26 +909,25 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
                               logp_out, status_out, T_out, R_out, resid_out, n_iter_out, (hipStream_t)stream, 1, nullptr);
   int rc = ensure_device();
   if (rc) return rc;
-  constexpr int MAXS = 8;
-  static thread_local hipStream_t s_str[MAXS] = {};
-  static thread_local hipEvent_t s_ev[MAXS + 1] = {};
-  static thread_local int s_dev = -1;
-  int dev_now = 0;
-  HIP_TRY(hipGetDevice(&dev_now));
-  if (s_dev != dev_now) {
-    for (auto& x : s_str) HIP_TRY(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-    for (auto& e : s_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    s_dev = dev_now;
-  }
   hipStream_t caller = (hipStream_t)stream;
   const int n_chunks = opt().pipeline_chunks;
-  const int n_str = n_chunks < MAXS ? n_chunks : MAXS;
+  const int n_str = n_chunks < MAX_CHUNK_STREAMS ? n_chunks : MAX_CHUNK_STREAMS;
   const int per = ((batch + n_chunks - 1) / n_chunks + 63) & ~63;
-  const size_t slice = (pipeline_scratch_bytes(per, n, k) + 255) & ~(size_t)255;
+  size_t slice;  // bytes of one chunk's layout (a multiple of 256)
+  {
+    ScratchLayout one;
+    PipelineScratch unused;
+    pipeline_declare(one, unused, per, n, k, z_batched, T_out, R_out, n_iter_out);
+    slice = one.bytes();
+  }
   void* base = nullptr;
-  if ((rc = scratch_reserve(caller, slice * n_chunks, &base))) return rc;
-  HIP_TRY(hipEventRecord(s_ev[MAXS], caller));
-  for (int i = 0; i < n_str; ++i) HIP_TRY(hipStreamWaitEvent(s_str[i], s_ev[MAXS], 0));
+  if ((rc = g_scratch_pool.reserve(slice * n_chunks, caller, &base))) return rc;
+  ForkGuard open[MAX_CHUNK_STREAMS];  // (whatever ends the chunk loop early: the caller's stream waits for every chunk stream)
+  for (int i = 0; i < n_str; ++i) {
+    open[i].side = &t_chunk[i];
+    open[i].into = caller;
+    if ((rc = t_chunk[i].fork(caller))) return rc;
+  }
   const bool q_b = (q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED);
   const size_t qk = (q_mode == DSGE_Q_FULL_BATCHED) ? (size_t)k * k : (size_t)k;
   for (int c = 0; c * per < batch; ++c) {
@@ -961,15 +939,13 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
                             d_batched, (Hdiag && h_batched) ? Hdiag + (size_t)c0 * p : Hdiag, h_batched, y, nb, n, k, p, T_len,
                             solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
                             logp_out + c0, status_out + c0, T_out ? T_out + o2 : nullptr, R_out ? R_out + ok : nullptr,
-                            resid_out ? resid_out + c0 : nullptr, n_iter_out ? n_iter_out + c0 : nullptr, s_str[c % n_str], 1,
-                            nullptr, (char*)base + slice * c);
-    if (rc) break;
+                            resid_out ? resid_out + c0 : nullptr, n_iter_out ? n_iter_out + c0 : nullptr,
+                            t_chunk[c % n_str].stream(), 1, nullptr, (char*)base + slice * c);
+    if (rc) return rc;
   }
-  for (int i = 0; i < n_str; ++i) {
-    HIP_TRY(hipEventRecord(s_ev[i], s_str[i]));
-    HIP_TRY(hipStreamWaitEvent(caller, s_ev[i], 0));
-  }
-  return rc;
+  for (int i = 0; i < n_str; ++i)
+    if ((rc = t_chunk[i].join(caller))) return rc;
+  return DSGE_SUCCESS;
 }
 
 int dsge_second_order_logp_batched(const double* A, const double* B, const double* C, const double* D,
@@ -1000,14 +976,14 @@ int dsge_second_order_logp_batched(const double* A, const double* B, const doubl
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
-  void* base = nullptr;
-  if ((rc = scratch_reserve(st, align256(nn * 8) + align256(nk * 8) + 2 * align256((size_t)batch * 12) + 4096, &base)))
-    return rc;
-  Carver cv(base);
-  double* Tw = T_out ? T_out : cv.take<double>(nn);
-  double* Rw = R_out ? R_out : cv.take<double>(nk);
-  int32_t* eu_w = cv.take<int32_t>((size_t)batch * 3);
-  int32_t* it_w = cv.take<int32_t>((size_t)batch);
+  double *Tw = T_out, *Rw = R_out;
+  int32_t *eu_w = nullptr, *it_w = nullptr;
+  ScratchLayout lay;
+  if (!Tw) lay.add(&Tw, nn);
+  if (!Rw) lay.add(&Rw, nk);
+  lay.add(&eu_w, (size_t)batch * 3);
+  lay.add(&it_w, (size_t)batch);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   EventGuard e0, e1;  // (destroyed on every return path)
   if (stage_ms) {
     HIP_TRY(e0.create());
@@ -1062,19 +1038,17 @@ int dsge_solve_kalman_logp_augmented_batched(const double* A, const double* B, c
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
-  void* base = nullptr;
-  if ((rc = scratch_reserve(st, align256(nn * 8) + align256(nk * 8) + 3 * align256(mm * 8) + align256(mk * 8) +
-                                         align256((size_t)batch * 12) + 4096,
-                          &base)))
-    return rc;
-  Carver cv(base);
-  double* Tw = cv.take<double>(nn);
-  double* Rw = cv.take<double>(nk);
-  double* Ta = T_aug_out ? T_aug_out : cv.take<double>(mm);
-  double* Ra = R_aug_out ? R_aug_out : cv.take<double>(mk);
-  double* RQR = cv.take<double>(mm);
-  double* P0 = cv.take<double>(mm);
-  int32_t* eu_w = cv.take<int32_t>((size_t)batch * 3);
+  double *Tw = nullptr, *Rw = nullptr, *Ta = T_aug_out, *Ra = R_aug_out, *RQR = nullptr, *P0 = nullptr;
+  int32_t* eu_w = nullptr;
+  ScratchLayout lay;
+  lay.add(&Tw, nn);
+  lay.add(&Rw, nk);
+  if (!Ta) lay.add(&Ta, mm);
+  if (!Ra) lay.add(&Ra, mk);
+  lay.add(&RQR, mm);
+  lay.add(&P0, mm);
+  lay.add(&eu_w, (size_t)batch * 3);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   if (is_cr) {
     rc = launch_cr(A, B, C, batch, n, max_iter, tol, Tw, status_out, nullptr, st, solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION);
   } else if (solver == DSGE_SOLVER_GENSYS) {
@@ -1103,18 +1077,15 @@ int dsge_solve_kalman_logp_augmented_batched(const double* A, const double* B, c
       return fail(DSGE_ERR_TOO_LARGE, "augmented solve + Kalman with m > 64: " + std::to_string(u) +
                                           " state (incl. chain) and observed variables, the filter kernels take at most 64");
     if (u < 1) return fail(DSGE_ERR_INVALID, "augmented solve + Kalman with m > 64: no state and no observed variable");
-    void* b2 = nullptr;
     const size_t uu = (size_t)batch * 64 * 64;
-    if ((rc = g_aug_big_pool.reserve(3 * align256(uu * 8) + align256((size_t)batch * 64 * k * 8) +
-                                         align256((size_t)batch * DSGE_MAX_P * 64 * 8) + 1024,
-                                     st, &b2)))
-      return rc;
-    Carver c2(b2);
-    double* T_r = c2.take<double>(uu);
-    double* RQR_r = c2.take<double>(uu);
-    double* P0_r = c2.take<double>(uu);
-    double* R_r = c2.take<double>((size_t)batch * 64 * k);
-    double* Z_r = c2.take<double>(z_batched ? (size_t)batch * p * 64 : (size_t)p * 64);
+    double *T_r = nullptr, *RQR_r = nullptr, *P0_r = nullptr, *R_r = nullptr, *Z_r = nullptr;
+    ScratchLayout gathered;
+    gathered.add(&T_r, uu);
+    gathered.add(&RQR_r, uu);
+    gathered.add(&P0_r, uu);
+    gathered.add(&R_r, (size_t)batch * 64 * k);
+    gathered.add(&Z_r, z_batched ? (size_t)batch * p * 64 : (size_t)p * 64);
+    if ((rc = gathered.reserve(g_aug_big_pool, st))) return rc;
     if ((rc = launch_big_compress(Ta, Ra, Z, z_batched, batch, m, k, p, idx, u, T_r, R_r, Z_r, st))) return rc;
     if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T_r, R_r, Q, q_mode, batch, u, k, nullptr, nullptr, RQR_r, P0_r,
                               status_out, 0, 2, st)))
@@ -1163,32 +1134,29 @@ static int grad_pipeline(const double* A, const double* B, const double* C, cons
   if (chunk < 1) chunk = 1;
   if (chunk > (size_t)batch) chunk = (size_t)batch;
   const size_t nn = chunk * n * n, nk = chunk * n * k;
-  void* base = nullptr;
   const size_t mm = chunk * (size_t)m * m, mk = chunk * (size_t)m * k;
-  if ((rc = scratch_reserve(st, 4 * align256(nn * 8) + align256(nk * 8) + align256(chunk * 12) + 2 * align256(chunk * 4) +
-                                         align256(chunk * per_draw + 8) + 8192 +
-                                         (dense_z ? 4 * align256(mm * 8) + align256(mk * 8) + align256((size_t)p * m * 8) : 0),
-                          &base)))
-    return rc;
-  Carver cv(base);
-  double* Tw = cv.take<double>(nn);
-  double* Rw = cv.take<double>(nk);
-  double* RQR = cv.take<double>(nn);
-  double* Tbar = cv.take<double>(nn);
-  double* Gbar = cv.take<double>(nn);
-  int32_t* eu_w = cv.take<int32_t>(chunk * 3);
-  int32_t* it_w = cv.take<int32_t>(chunk);   // cycle-reduction iterations = dispatch key of the reverse-sweep launch
-  int32_t* ord_w = cv.take<int32_t>(chunk);
-  double* store = cv.take<double>(chunk * per_draw / sizeof(double) + 1);
+  double *Tw = nullptr, *Rw = nullptr, *RQR = nullptr, *Tbar = nullptr, *Gbar = nullptr, *store = nullptr;
+  int32_t *eu_w = nullptr, *it_w = nullptr, *ord_w = nullptr;
   double *Ta = nullptr, *Ra = nullptr, *RQRa = nullptr, *Tbar_a = nullptr, *Gbar_a = nullptr, *Zaug = nullptr;
+  ScratchLayout lay;
+  lay.add(&Tw, nn);
+  lay.add(&Rw, nk);
+  lay.add(&RQR, nn);
+  lay.add(&Tbar, nn);
+  lay.add(&Gbar, nn);
+  lay.add(&eu_w, chunk * 3);
+  lay.add(&it_w, chunk);  // cycle-reduction iterations = dispatch key of the reverse-sweep launch
+  lay.add(&ord_w, chunk);
+  lay.add(&store, chunk * per_draw / sizeof(double) + 1);
   if (dense_z) {
-    Ta = cv.take<double>(mm);
-    Ra = cv.take<double>(mk);
-    RQRa = cv.take<double>(mm);
-    Tbar_a = cv.take<double>(mm);
-    Gbar_a = cv.take<double>(mm);
-    Zaug = cv.take<double>((size_t)p * m);
+    lay.add(&Ta, mm);
+    lay.add(&Ra, mk);
+    lay.add(&RQRa, mm);
+    lay.add(&Tbar_a, mm);
+    lay.add(&Gbar_a, mm);
+    lay.add(&Zaug, (size_t)p * m);
   }
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   for (size_t c0 = 0; c0 < (size_t)batch; c0 += chunk) {
     const int nb = (int)(((size_t)batch - c0 < chunk) ? (size_t)batch - c0 : chunk);
     const double *Ac = A + c0 * n * n, *Bc = B + c0 * n * n, *Cc = C + c0 * n * n, *Dc = D + c0 * n * k;
@@ -1302,44 +1270,12 @@ int dsge_profile_pipeline(const double* A, const double* B, const double* C, con
 // Debug hook: when enabled, kalman_sel_kernel accumulates the shader cycles draw 0 spends in each
 // of its five per-step phases, [5] = cycles in steady-state steps, [6] = number of steady-state steps,
 // [7] = total; dsge_debug_kalman_phases(0/1 enable, out[8]) reads them back.
-int dsge_debug_kalman_phases(int enable, long long* cycles_out) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (enable && !g_kalman_dbg) {
-    HIP_TRY(hipMalloc((void**)&g_kalman_dbg, 16 * sizeof(long long)));
-    HIP_TRY(hipMemset(g_kalman_dbg, 0, 16 * sizeof(long long)));
-  }
-  if (cycles_out && g_kalman_dbg) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cycles_out, g_kalman_dbg, 16 * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  if (!enable && g_kalman_dbg) {
-    (void)hipFree(g_kalman_dbg);
-    g_kalman_dbg = nullptr;
-  }
-  return DSGE_SUCCESS;
-}
+int dsge_debug_kalman_phases(int enable, long long* cycles_out) { return debug_counters(&g_kalman_dbg, 16, enable, cycles_out); }
 
 // Debug hook: cr_big_kernel (n > 64) accumulates the shader cycles workgroup 0 spends on its first draw: [0] register-block loads,
 // [1] eliminations, [2] row scatters, [3] the four products and norms, [4] iterations, [5] total (with the final solve);
 // [8..12] inside the eliminations (thread 0): candidates + column, first barrier, pivot row, second barrier, update.  16 values.
-int dsge_debug_big_phases(int enable, long long* cycles_out) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (enable && !g_big_dbg) {
-    HIP_TRY(hipMalloc((void**)&g_big_dbg, 16 * sizeof(long long)));
-    HIP_TRY(hipMemset(g_big_dbg, 0, 16 * sizeof(long long)));
-  }
-  if (cycles_out && g_big_dbg) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cycles_out, g_big_dbg, 16 * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  if (!enable && g_big_dbg) {
-    (void)hipFree(g_big_dbg);
-    g_big_dbg = nullptr;
-  }
-  return DSGE_SUCCESS;
-}
+int dsge_debug_big_phases(int enable, long long* cycles_out) { return debug_counters(&g_big_dbg, 16, enable, cycles_out); }
 
 // Debug hook (not part of the drop-in surface): shader-clock stamps of draw 0 at the phase
 // boundaries of gensys_kernel: [start, after Hessenberg-triangular, after QZ, after reordering,
@@ -1380,57 +1316,13 @@ int dsge_debug_gensys_stage_ms(int enable, float* ms_out) {
 }
 
 int dsge_debug_gensys_window_phases(int enable, long long* cycles_out) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (enable && !g_gensys_win_dbg) {
-    HIP_TRY(hipMalloc((void**)&g_gensys_win_dbg, 32 * sizeof(long long)));
-    HIP_TRY(hipMemset(g_gensys_win_dbg, 0, 32 * sizeof(long long)));
-  }
-  if (cycles_out && g_gensys_win_dbg) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(cycles_out, g_gensys_win_dbg, 32 * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  if (!enable && g_gensys_win_dbg) {
-    (void)hipFree(g_gensys_win_dbg);
-    g_gensys_win_dbg = nullptr;
-  }
-  return DSGE_SUCCESS;
+  return debug_counters(&g_gensys_win_dbg, 32, enable, cycles_out);
 }
 
 // ---- per-call options (include/dsge_hip.h: dsge_options) --------------------------------------------------------------
 int dsge_options_init(dsge_options* o) {
   if (!o) return fail(DSGE_ERR_INVALID, "null pointer");
-  const Options& d = g_defaults;
-  std::memset(o, 0, sizeof(*o));
-  o->struct_size = (uint32_t)sizeof(dsge_options);
-  o->cr_compact = d.cr_compact;
-  o->cr_fused_selection = d.cr_fused_selection;
-  o->cr_deflation = d.cr_deflation;
-  o->cr_two_waves = d.cr_two_waves;
-  o->n_static_hint = d.n_static_hint;
-  o->kalman_order = d.kalman_order;
-  o->kalman_tiny = d.kalman_tiny;
-  o->kalman_block = d.kalman_block;
-  o->kalman_mfma = d.kalman_mfma;
-  o->pipeline_chunks = d.pipeline_chunks;
-  o->gensys_split = d.gensys_split;
-  o->gensys_real_stage = d.gensys_real_stage;
-  o->kalman_steady_tol = d.kalman_steady_tol;
-  o->kalman_nt_products = d.kalman_nt_products;
-  o->cr_fused_deflation = d.cr_fused_deflation;
-  o->cr_four_waves = d.cr_four_waves;
-  o->gensys_pairs = d.gensys_pairs;
-  o->gensys_shape_cache = d.gensys_shape_cache;
-  o->kalman_narrow = d.kalman_narrow;
-  o->gensys_direct_blocks = d.gensys_direct_blocks;
-  o->kalman_head_draws = d.kalman_head_draws;
-  o->gensys_doubling = d.gensys_doubling;
-  o->kalman_grad_split = d.kalman_grad_split;
-  o->ll_constant = d.ll_constant;
-  o->mask_d = d.mask_d;
-  o->joseph = d.joseph;
-  o->jitter_F = d.jitter_F;
-  o->jitter_P = d.jitter_P;
+  *o = g_defaults;  // (the dsge_options part: struct_size set, reserved_ zero -- struct Options, dsge_host.hpp)
   return DSGE_SUCCESS;
 }
 

@@ -28,8 +28,8 @@ int fail(int code, const std::string& msg);  // records the message for dsge_las
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
 // Library-owned device scratch: ONE arena per (device, stream) and pool -- the library is re-entrant per stream:
-// two calls enqueued on two streams never share intermediates.  Slots are created on demand (a host thread's twin streams
-// release theirs when the thread exits: stream_arenas_release); beyond MAX_SLOTS live (device, stream) pairs the least
+// two calls enqueued on two streams never share intermediates.  Slots are created on demand (a host thread's library streams
+// release theirs when the thread exits: ThreadStream, stream_arenas_release); beyond MAX_SLOTS live (device, stream) pairs the least
 // recently used slot is recycled after a device-wide synchronisation, and it changes owner -- the former stream gets a
 // fresh slot on its next call, so no two streams ever hold the same memory.
 class StreamArenaPool {
@@ -52,8 +52,68 @@ class StreamArenaPool {
   unsigned long long clock_ = 0;
 };
 void stream_arenas_release(hipStream_t st);  // every pool of the library (dsge_api.hip)
-// The two streams the host twins of the CALLING THREAD run on (created on first use per device, destroyed -- and their
-// arenas released -- when the thread exits): two host threads in two twins never share a stream, hence never an arena.
+
+// The scratch buffers of one entry point, declared ONCE: add() names a typed pointer slot and its element count, reserve() sizes
+// the arena from that list (every buffer rounded to 256 bytes, PAD bytes behind the last), takes it from `pool` for the stream --
+// or places it into a slice of an arena the caller reserved -- and fills the slots.  What is carved can therefore never exceed
+// what was reserved.  An output pointer the caller supplied declares nothing: `double* Tw = T_out; if (!Tw) lay.add(&Tw, nn);`.
+// Fixed capacity, no heap: the fused entry only enqueues.
+class ScratchLayout {
+ public:
+  static constexpr size_t PAD = 8192;
+  template <typename T>
+  void add(T** slot, size_t count) {
+    if (n_ < MAX_BUFS) bufs_[n_] = Buf{(void*)slot, count * sizeof(T)};
+    ++n_;
+  }
+  size_t bytes() const;  // of the whole arena
+  int reserve(StreamArenaPool& pool, hipStream_t st, void* slice = nullptr);
+ private:
+  struct Buf {
+    void* slot;  // address of the caller's T*
+    size_t bytes;
+  };
+  static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+  static constexpr int MAX_BUFS = 16;
+  Buf bufs_[MAX_BUFS];
+  int n_ = 0;
+};
+
+// A library stream of the CALLING THREAD on its current device (non-blocking), with a fork and a join event: created on first
+// use, dropped and created again when the thread's device changed or an earlier creation stopped half-way.  When the thread
+// exits, the stream is synchronised, its arenas are released (stream_arenas_release) and stream and events are destroyed with
+// the owning device made current.  Two host threads never share one, hence never an arena.  `thread_local` instances only.
+class ThreadStream {
+ public:
+  ThreadStream() = default;
+  ThreadStream(const ThreadStream&) = delete;
+  ThreadStream& operator=(const ThreadStream&) = delete;
+  ~ThreadStream() { drop(); }
+  int ensure();                      // the stream exists on the current device
+  hipStream_t stream() const { return s_; }
+  int fork(hipStream_t from);        // ensure(); this stream waits for what is enqueued on `from`
+  int join(hipStream_t into);        // `into` waits for what is enqueued on this stream
+  // no fork stays open: enqueues the join if one is owed and synchronises this stream if that fails; reports nothing
+  void close(hipStream_t into);
+ private:
+  void drop();
+  hipStream_t s_ = nullptr;
+  hipEvent_t ev_[2] = {nullptr, nullptr};  // fork, join
+  int dev_ = -1;
+  bool open_ = false;                // forked, join not enqueued yet
+};
+// Around a forked section: whichever way the scope is left (the early returns of HIP_TRY included), the caller's stream `into`
+// waits for the side stream, so an error code never comes back with work in flight on buffers the caller may free.  On the
+// success path the section enqueues side->join(into) itself, where the order of work wants it; the guard then does nothing.
+// It never touches the error being returned.
+struct ForkGuard {
+  ThreadStream* side = nullptr;  // null = nothing was (or will be) forked
+  hipStream_t into = nullptr;
+  ~ForkGuard() {
+    if (side) side->close(into);
+  }
+};
+// The two streams the host twins of the calling thread run on
 int twin_streams(hipStream_t* s0, hipStream_t* s1);
 
 // Shared by the device entry points (dsge_api.hip) and their host twins (api_host.hip)
@@ -195,8 +255,7 @@ int launch_grad_assemble(const double* B, const double* C, const double* T, cons
 int gensys_caps(int n, int n_lead_hint, int* n_cap, int* l_cap);
 // gensys by spectral division with the verdict next to the filter (round 6; launch_gensys.hip::launch_gensys_doubling)
 struct GensysOverlap {
-  hipStream_t st = nullptr;       // in: the verdict's stream (a library stream of the calling thread)
-  hipEvent_t fork = nullptr;      // in: event the verdict stream waits for (recorded on the caller's stream behind the iteration)
+  ThreadStream* side = nullptr;   // in: the verdict's stream, forked from the caller's stream behind the iteration
   int32_t* status = nullptr;      // in: [batch] status words the verdict works on
   const int32_t* marks = nullptr; // out: [batch], non-zero = the verdict re-solved (or rejected) the draw
   int used = 0;                   // out: 1 = the verdict was forked
@@ -244,37 +303,42 @@ extern int32_t* g_kalman_steady_at;   // debug: device buffer [batch], first ste
 // for the duration of the call on the calling thread (launching is synchronous on the host, every kernel argument is
 // passed by value at launch), so two host threads -- two PyMC chains, two streams -- never see each other's settings.
 // Calls without options use the compiled-in defaults (g_defaults is never written: ABI 8 removed the dsge_set_* setters).
-struct Options {
-  int cr_compact = 1;          // 0 = dense cycle-reduction kernel only
-  int cr_fused_selection = 1;  // fused pipeline: R from the cycle-reduction kernel's final elimination
-  int cr_deflation = 1;        // static-variable deflation in front of cycle reduction
-  int cr_two_waves = 1;        // 4 x 4-tile compact kernel built for two waves per SIMD
-  int n_static_hint = -1;      // static variables (zero columns of A and C): -1 = measure on the device, >= 0 caller's bound
-  int kalman_order = 1;        // Kalman workgroups slow-draws-first (1 = CR iteration count / persistence key, 2 = key, 0 = index)
-  int kalman_tiny = 1;         // thread-per-draw kernel for small models
-  int kalman_block = 0;        // steady tail handed to kalman_tail_kernel
-  int kalman_mfma = 2;         // prediction products on the FP64 matrix core: 2 = 4 x 4 x 4 blocks in the NT kernel (round 6), 1 = 16 x 16 x 4 (round 2, slower), 0 = VALU
-  int cr_four_waves = 1;       // n = 49..64: cr_wide_kernel (256 threads per draw) instead of cr_compact_kernel<7|8>
-  int cr_fused_deflation = 1;  // deflation + cycle reduction + inflation in one launch (dsge_cr_fused.hpp)
-  int kalman_nt_products = 1;  // selector fast path: kalman_nt_kernel (NT prediction products, 16-byte LDS loads); 0 = kalman_sel_kernel
-  int pipeline_chunks = 0;     // fused device call in chunks over library-owned streams
-  int gensys_split = 1;        // 0 = single-launch gensys kernel, 1 = window path unless small, 2 = always
-  int gensys_real_stage = 1;   // window path: real double-shift sweeps in front of the complex single-shift iteration
-  double kalman_steady_tol = 1e-14;  // steady-state switch of the fast Kalman kernel (0 = never)
-  int gensys_pairs = 1;        // window path: two draws per wavefront in the real double-shift sweeps (dsge_gensys_pair.hpp)
-  int gensys_shape_cache = 1;  // window path: capacity record measured once per model size
-  int gensys_direct_blocks = 1;  // window path: isolated 2 x 2 blocks triangularised in closed form in front of the complex iteration
-  int kalman_narrow = 1;       // fast filter: the SK = 20 instance of the 32-wide tile when the state block fits
-  int gensys_doubling = 1;     // gensys by spectral division: cycle reduction + certificate, ordered QZ only for uncertified draws (0: QZ for all)
-  int kalman_grad_split = 2;   // gradient: forward sweep by a logp kernel with record output, reverse sweep by kalman_grad_kernel<BS, true>; 2: + kalman_grad_tail_kernel
+// The fields ARE the public dsge_options (one list, include/dsge_hip.h); the constructor is the only place their defaults are
+// written: dsge_options_init hands out a copy, a call with options installs a copy of the caller's struct.
+struct Options : dsge_options {
   int grad_fused_adjoint = 1;  // gradient pipeline: reverse of the assembly + policy adjoints in one launch (internal; DSGE_GRAD_FUSED_ADJOINT=0 switches it off)
-  int kalman_head_draws = 0;   // fast filter: this many draws at the head of the dispatch order on the two-wavefront kernel (-1 = all)
-  // conventions of the filter step (third party: pymc_extras; include/dsge_hip.h "Filter conventions")
-  int ll_constant = DSGE_LL_CONST_P;
-  int mask_d = 0;
-  int joseph = 1;
-  double jitter_F = -1.0;      // < 0: the call's `jitter` argument
-  double jitter_P = -1.0;
+  Options() : dsge_options{} {   // (reserved_ stays zero)
+    struct_size = (uint32_t)sizeof(dsge_options);
+    cr_compact = 1;          // 0 = dense cycle-reduction kernel only
+    cr_fused_selection = 1;  // fused pipeline: R from the cycle-reduction kernel's final elimination
+    cr_deflation = 1;        // static-variable deflation in front of cycle reduction
+    cr_two_waves = 1;        // 4 x 4-tile compact kernel built for two waves per SIMD
+    n_static_hint = -1;      // static variables (zero columns of A and C): -1 = measure on the device, >= 0 caller's bound
+    kalman_order = 1;        // Kalman workgroups slow-draws-first (1 = CR iteration count / persistence key, 2 = key, 0 = index)
+    kalman_tiny = 1;         // thread-per-draw kernel for small models
+    kalman_block = 0;        // steady tail handed to kalman_tail_kernel
+    kalman_mfma = 2;         // prediction products on the FP64 matrix core: 2 = 4 x 4 x 4 blocks in the NT kernel (round 6), 1 = 16 x 16 x 4 (round 2, slower), 0 = VALU
+    cr_four_waves = 1;       // n = 49..64: cr_wide_kernel (256 threads per draw) instead of cr_compact_kernel<7|8>
+    cr_fused_deflation = 1;  // deflation + cycle reduction + inflation in one launch (dsge_cr_fused.hpp)
+    kalman_nt_products = 1;  // selector fast path: kalman_nt_kernel (NT prediction products, 16-byte LDS loads); 0 = kalman_sel_kernel
+    pipeline_chunks = 0;     // fused device call in chunks over library-owned streams
+    gensys_split = 1;        // 0 = single-launch gensys kernel, 1 = window path unless small, 2 = always
+    gensys_real_stage = 1;   // window path: real double-shift sweeps in front of the complex single-shift iteration
+    kalman_steady_tol = 1e-14;  // steady-state switch of the fast Kalman kernel (0 = never)
+    gensys_pairs = 1;        // window path: two draws per wavefront in the real double-shift sweeps (dsge_gensys_pair.hpp)
+    gensys_shape_cache = 1;  // window path: capacity record measured once per model size
+    gensys_direct_blocks = 1;  // window path: isolated 2 x 2 blocks triangularised in closed form in front of the complex iteration
+    kalman_narrow = 1;       // fast filter: the SK = 20 instance of the 32-wide tile when the state block fits
+    gensys_doubling = 1;     // gensys by spectral division: cycle reduction + certificate, ordered QZ only for uncertified draws (0: QZ for all)
+    kalman_grad_split = 2;   // gradient: forward sweep by a logp kernel with record output, reverse sweep by kalman_grad_kernel<BS, true>; 2: + kalman_grad_tail_kernel
+    kalman_head_draws = 0;   // fast filter: this many draws at the head of the dispatch order on the two-wavefront kernel (-1 = all)
+    // conventions of the filter step (third party: pymc_extras; include/dsge_hip.h "Filter conventions")
+    ll_constant = DSGE_LL_CONST_P;
+    mask_d = 0;
+    joseph = 1;
+    jitter_F = -1.0;         // < 0: the call's `jitter` argument
+    jitter_P = -1.0;
+  }
 };
 extern const Options g_defaults;
 extern thread_local const Options* t_call_options;

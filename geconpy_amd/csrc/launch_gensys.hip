@@ -284,7 +284,7 @@ int launch_gensys_bk(const double* A, const double* B, const double* C, int batc
 // *done = 0: not applicable (sizes) -- the caller runs the QZ path on the whole batch.
 // Round 6, `ov` (optional): the VERDICT -- certificate, compaction, the ordered QZ of the draws without a certificate -- runs on a
 // second stream next to what the caller enqueues behind this call on `st` (the filter of every draw with the doubling iteration's T
-// and R): ov->st is forked from `st` behind the iteration, works on ov->status (a copy of the iteration's status words: the filter
+// and R): ov->side is forked from `st` behind the iteration, works on ov->status (a copy of the iteration's status words: the filter
 // reads and writes `status` meanwhile) and leaves in ov->marks which draws it re-solved.  The caller joins, merges the two status
 // arrays and re-runs the filter on the marked draws (dsge_api.hip::pipeline).
 static int launch_gensys_doubling(const double* A, const double* B, const double* C, const double* D, int k, double* R_tmp,
@@ -326,15 +326,14 @@ static int launch_gensys_doubling(const double* A, const double* B, const double
   // can use at once)
   hipStream_t vst = st;
   int32_t* vstatus = status;
-  if (ov && ov->st && ov->status && ov->fork && deflated) {
+  if (ov && ov->side && ov->status && deflated) {
     HIP_TRY(hipMemcpyAsync(ov->status, status, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     if (key_out) {  // (the filter's dispatch key is needed on the caller's stream, before the verdict)
       HIP_TRY(hipMemcpyAsync(key_out, it, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
       if (key_written) *key_written = 1;
     }
-    HIP_TRY(hipEventRecord(ov->fork, st));
-    HIP_TRY(hipStreamWaitEvent(ov->st, ov->fork, 0));
-    vst = ov->st;
+    if ((rc = ov->side->fork(st))) return rc;
+    vst = ov->side->stream();
     vstatus = ov->status;
     ov->used = 1;
     ov->marks = mark;

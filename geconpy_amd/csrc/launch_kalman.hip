@@ -23,40 +23,7 @@ namespace {
 // The stream the two-wavefront head launch runs on, next to the caller's stream (fork / join by events): one per host thread and
 // device, created on first use.  Two calls of one thread on two caller streams share it -- their heads then run one after the
 // other, which is correct (events order them) and rare.
-struct HeadStream {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  int dev = -1;
-  void release() {  // (idempotent; the owning device is made current for the destroy calls and the caller's restored)
-    if (!s && !fork && !join) return;
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    if (dev >= 0) (void)hipSetDevice(dev);
-    if (join) (void)hipEventDestroy(join);
-    if (fork) (void)hipEventDestroy(fork);
-    if (s) (void)hipStreamDestroy(s);
-    s = nullptr;
-    fork = join = nullptr;
-    if (have_cur) (void)hipSetDevice(cur);
-  }
-  ~HeadStream() { release(); }  // thread exit: the stream and both events go with the thread
-};
-thread_local HeadStream t_head;
-int head_stream(HeadStream** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (t_head.dev != dev || !t_head.s || !t_head.fork || !t_head.join) {
-    // another device than last time, or a creation that failed half-way: drop what exists, then create all three -- a failure
-    // leaves a partially filled record behind that the next call (or the destructor) releases
-    t_head.release();
-    t_head.dev = dev;
-    HIP_TRY(hipStreamCreateWithFlags(&t_head.s, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&t_head.fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&t_head.join, hipEventDisableTiming));
-  }
-  *out = &t_head;
-  return DSGE_SUCCESS;
-}
+thread_local ThreadStream t_head;
 // hand-off records of the fast kernel for kalman_tail_kernel: one buffer per (device, stream), grown on demand
 StreamArenaPool g_tail_pool;
 int tail_reserve(size_t bytes, hipStream_t st, void** out) { return g_tail_pool.reserve(bytes, st, out); }
@@ -279,15 +246,13 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
               // The HEAD runs on the caller's stream, where it starts the moment the solver ends; the BULK goes to the library's
               // second stream (fork / join by events).  The other way round the bulk, in stream order right behind the solver, fills
               // every CU's LDS before the cross-stream dependency of the head resolves, and the slow draws start LAST (measured).
-              HeadStream* hs = nullptr;
+              ThreadStream* hs = nullptr;
               hipStream_t bulk_st = st;
+              ForkGuard head_guard{nullptr, st};  // (a return between fork and join still joins)
               if (head > 0 && head < batch) {
-                if ((rc = head_stream(&hs))) return;
-                if (hipEventRecord(hs->fork, st) != hipSuccess || hipStreamWaitEvent(hs->s, hs->fork, 0) != hipSuccess) {
-                  rc = fail(DSGE_ERR_HIP, "kalman head launch: fork failed");
-                  return;
-                }
-                bulk_st = hs->s;
+                hs = head_guard.side = &t_head;
+                if ((rc = hs->fork(st))) return;
+                bulk_st = hs->stream();
               }
               if constexpr (BS <= 4) {
                 if (head > 0) {
@@ -309,11 +274,9 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                                      g_kalman_timeline, rerun, g_kalman_steady_at, order ? order + head : nullptr, fold ? Rsel : nullptr,
                                      qdiag, q_batched, k_shocks, colmask, TAILV ? tail_rec : nullptr, tail_flag, tail_from);
               }
-              if (hs && TAILV && rc == DSGE_SUCCESS) rc = launch_tail(hs->s);  // the bulk's tails next to the head, not behind it
-              if (hs) {  // join: everything later on the caller's stream waits for the bulk
-                if (hipEventRecord(hs->join, hs->s) != hipSuccess || hipStreamWaitEvent(st, hs->join, 0) != hipSuccess)
-                  rc = fail(DSGE_ERR_HIP, "kalman head launch: join failed");
-              }
+              if (hs && TAILV && rc == DSGE_SUCCESS) rc = launch_tail(hs->stream());  // the bulk's tails next to the head, not behind it
+              // join: everything later on the caller's stream waits for the bulk (after an error: by the guard, which keeps it)
+              if (hs && rc == DSGE_SUCCESS) rc = hs->join(st);
             };
             // (the 32-wide tile only: on the 24-wide one the 20-column instance measured 1.4 % SLOWER on the headline step --
             //  1.588 against 1.566 ms per 4096 draws --, its rows are only four columns shorter.  Not an `if constexpr`: this

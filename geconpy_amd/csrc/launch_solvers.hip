@@ -68,8 +68,6 @@ int g_static_hint[DSGE_MAX_N + 2];  // per model size n: lower bound of the numb
 unsigned g_static_calls[DSGE_MAX_N + 2];
 bool g_static_hint_init = false;    // (stored as h + 1)
 StreamArenaPool g_defl_pool;
-int defl_reserve(size_t bytes, hipStream_t st, void** out) { return g_defl_pool.reserve(bytes, st, out); }
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 void cr_deflation_reset() {
@@ -115,11 +113,11 @@ int launch_cr_fused(const double* A, const double* B, const double* C, const dou
                             : ((bsf == 6 && bsd == 5) || (bsf == 7 && (bsd == 5 || bsd == 6)) || (bsf == 8 && bsd == 6));
   if (!have) return DSGE_SUCCESS;
   int rc;
-  void* base = nullptr;
-  const size_t tops = (size_t)batch * dsge::crd_top_doubles(n, k, h), rhss = (size_t)batch * dsge::crf_rhs_doubles(nd, 8 * bsd);
-  if ((rc = defl_reserve(al256(tops * 8) + al256(rhss * 8) + 4096, st, &base))) return rc;
-  double* top = (double*)base;
-  double* rhs = (double*)((char*)base + al256(tops * 8));
+  double *top = nullptr, *rhs = nullptr;
+  ScratchLayout lay;
+  lay.add(&top, (size_t)batch * dsge::crd_top_doubles(n, k, h));
+  lay.add(&rhs, (size_t)batch * dsge::crf_rhs_doubles(nd, 8 * bsd));
+  if ((rc = lay.reserve(g_defl_pool, st))) return rc;
 #define FUSED_CASE(F, D_, N_)                                                                                          \
   if (bsf == F && bsd == D_ && nc == N_)                                                                               \
     rc = launch_cr_fused_inst<F, D_, N_>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, st, \
@@ -184,7 +182,7 @@ int launch_cr_deflated(const double* A, const double* B, const double* C, const 
     if (capturing && g_static_hint[n] == 0) return DSGE_SUCCESS;
     const bool remeasure = !capturing && g_static_hint[n] != 0 && (++g_static_calls[n] & 255) == 0;
     if (g_static_hint[n] == 0 || remeasure) {
-      if ((rc = defl_reserve(256, st, &base))) return rc;
+      if ((rc = g_defl_pool.reserve(256, st, &base))) return rc;
       int32_t hmin = n;
       HIP_TRY(hipMemcpyAsync(base, &hmin, sizeof(hmin), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(dsge::cr_static_scan_kernel, dim3(batch < 4096 ? batch : 4096), dim3(64), 0, st, A, C, batch, n,
@@ -215,18 +213,14 @@ int launch_cr_deflated(const double* A, const double* B, const double* C, const 
   }
   const size_t lds1 = dsge::crd_deflate_smem(8 * tile_bs(n)), lds2 = dsge::crd_inflate_smem(8 * tile_bs(nd));
   const size_t ndd = (size_t)batch * nd * nd, ndk = (size_t)batch * nd * k, tops = (size_t)batch * dsge::crd_top_doubles(n, k, h);
-  if ((rc = defl_reserve(4 * al256(ndd * 8) + 2 * al256(ndk * 8) + al256(tops * 8) + al256((size_t)batch * 4) + 4096, st,
-                         &base)))
-    return rc;
-  char* p = (char*)base;
-  double* Ared = (double*)p; p += al256(ndd * 8);
-  double* Bred = (double*)p; p += al256(ndd * 8);
-  double* Cred = (double*)p; p += al256(ndd * 8);
-  double* Tdy = (double*)p; p += al256(ndd * 8);
-  double* Dred = (double*)p; p += al256(ndk * 8);
-  double* Rdy = (double*)p; p += al256(ndk * 8);
-  double* top = (double*)p; p += al256(tops * 8);
-  int32_t* flag = (int32_t*)p;
+  double *Ared = nullptr, *Bred = nullptr, *Cred = nullptr, *Tdy = nullptr, *Dred = nullptr, *Rdy = nullptr, *top = nullptr;
+  int32_t* flag = nullptr;
+  ScratchLayout lay;
+  for (double** m : {&Ared, &Bred, &Cred, &Tdy}) lay.add(m, ndd);
+  for (double** m : {&Dred, &Rdy}) lay.add(m, ndk);
+  lay.add(&top, tops);
+  lay.add(&flag, (size_t)batch);
+  if ((rc = lay.reserve(g_defl_pool, st))) return rc;
   rc = DSGE_ERR_INVALID;
   DISPATCH_BS(tile_bs(n), 8, {
     rc = DSGE_SUCCESS;

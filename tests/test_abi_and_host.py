@@ -148,7 +148,24 @@ def test_options_struct_defaults_and_scope():
     assert (o.kalman_order, o.kalman_tiny, o.kalman_block, o.kalman_mfma, o.pipeline_chunks, o.gensys_split) == (1, 1, 0, 2, 0, 1)
     assert o.n_static_hint == -1 and o.kalman_steady_tol == 1e-14
     assert (o.kalman_nt_products, o.cr_fused_deflation, o.cr_four_waves) == (1, 1, 1)
-    o2 = _lib.make_options({"kalman_steady_tol": 0.0}, n_static_hint=10)
+    # every field dsge_options_init fills, against a literal table (the library writes its defaults in one place:
+    # struct Options, csrc/dsge_host.hpp)
+    defaults = {
+        "struct_size": 136, "cr_compact": 1, "cr_fused_selection": 1, "cr_deflation": 1, "cr_two_waves": 1,
+        "n_static_hint": -1, "kalman_order": 1, "kalman_tiny": 1, "kalman_block": 0, "kalman_mfma": 2, "pipeline_chunks": 0,
+        "gensys_split": 1, "kalman_steady_tol": 1e-14, "kalman_nt_products": 1, "cr_fused_deflation": 1, "cr_four_waves": 1,
+        "gensys_real_stage": 1, "gensys_pairs": 1, "gensys_shape_cache": 1, "kalman_narrow": 1, "gensys_direct_blocks": 1,
+        "ll_constant": 0, "mask_d": 0, "joseph": 1, "kalman_head_draws": 0, "jitter_F": -1.0, "jitter_P": -1.0,
+        "gensys_doubling": 1, "kalman_grad_split": 2, "reserved_": [0, 0],
+    }
+    env = os.environ.get("DSGE_GENSYS_DOUBLING")  # (the one process-level override of a default, read when the library loads)
+    if env in ("0", "1", "2", "3"):
+        defaults["gensys_doubling"] = int(env)
+    assert [f[0] for f in _lib.Options._fields_] == list(defaults)
+    filled = {name: getattr(o, name) for name in defaults}
+    filled["reserved_"] = list(filled["reserved_"])
+    assert filled == defaults
+    o2 =_lib.make_options({"kalman_steady_tol": 0.0}, n_static_hint=10)
     assert o2.kalman_steady_tol == 0.0 and o2.n_static_hint == 10 and o2.cr_compact == 1
     with pytest.raises(ValueError):
         _lib.make_options(no_such_switch=1)
