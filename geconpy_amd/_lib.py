@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -28,6 +28,8 @@ ST_FILTER_NONFINITE = 8
 ST_GENSYS_QZ_FAIL = 16
 ST_GENSYS_TOO_BIG = 32
 ST_GRAD_UNSUPPORTED = 64
+ST_SECOND_ORDER_UNSUPPORTED = 128
+ST_SMOOTHER_SINGULAR = 256
 
 Q_DIAG_SHARED, Q_DIAG_BATCHED, Q_FULL_SHARED, Q_FULL_BATCHED = 0, 1, 2, 3
 SOLVER_CYCLE_REDUCTION, SOLVER_GENSYS, SOLVER_BACKWARD_DIRECT, SOLVER_SCAN_CYCLE_REDUCTION = 0, 1, 2, 3
@@ -69,6 +71,7 @@ class GensysForward(C.Structure):
 _dp = C.c_void_p  # double* / int32* / stream: passed as raw addresses (host or device)
 _i = C.c_int
 _f = C.c_double
+_z = C.c_size_t
 
 # name -> argtypes; every symbol include/dsge_hip.h declares must appear here
 PROTOTYPES = {
@@ -119,6 +122,10 @@ PROTOTYPES = {
                                            _dp, _dp, _dp, _i, _dp, _dp],
     "dsge_kalman_filter_outputs_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _dp,
                                                 _dp, _dp, _dp, _dp, _i, _dp],
+    "dsge_kalman_smoother_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _f, _z, _dp, _dp,
+                                     _dp, _dp, _i, _dp, _dp],
+    "dsge_kalman_smoother_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _f, _z, _dp,
+                                          _dp, _dp, _dp, _i, _dp],
     "dsge_solve_kalman_logp_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
     "dsge_solve_kalman_logp_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp],
     "dsge_solve_kalman_logp_augmented_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,

@@ -480,6 +480,63 @@ def kalman_filter_outputs_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None
     return out
 
 
+def _smoother_shapes(T, R, Q, Z, y, d, Hdiag, q_mode, rank_tol, scratch_limit_bytes):
+    """Argument checks of ``kalman_smoother_batched`` (ValueError before anything is staged)."""
+    T, R = _f64(T, 3), _f64(R, 3)
+    y = _f64(y, 2)
+    nb, m, m2 = T.shape
+    if m != m2 or R.shape[:2] != (nb, m):
+        raise ValueError(f"T must be (batch, m, m) and R (batch, m, k); got {T.shape}, {R.shape}")
+    if m > _lib.MAX_N:
+        raise ValueError(f"kalman_smoother_batched: m = {m}, the smoother takes at most {_lib.MAX_N} variables")
+    k = R.shape[2]
+    T_len, p = y.shape
+    Q, code = _resolve_q(Q, q_mode, nb, k)
+    Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, m)
+    rank_tol = 0.0 if rank_tol is None else float(rank_tol)
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    return T, R, Q, code, Z, zb, d, db, Hdiag, hb, y, nb, m, k, p, T_len, rank_tol, limit
+
+
+def smoother_scratch_bytes_per_draw(m, T_len):
+    """Bytes of library scratch the smoother's forward pass stores per draw (what ``scratch_limit_bytes`` counts):
+    ``2 T_len m^2 + 2 T_len m`` doubles."""
+    return 8 * (2 * T_len * m * m + 2 * T_len * m)
+
+
+def kalman_smoother_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, status=None, jitter=JITTER_DEFAULT,
+                            missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None, scratch_limit_bytes=None,
+                            options=None):
+    """Smoothed states, covariances and structural shocks for a batch of draws -- the "smoothed" output of
+    ``save_kalman_filter_outputs_in_idata=True`` (gEconpy/model/statespace.py:1145, 1151-1157; gEconpy/plotting.py:1791-1835):
+    the fixed-interval (Rauch-Tung-Striebel) recursion on the outputs of ``kalman_filter_outputs_batched`` with the
+    pseudo-inverse of the predicted covariance (include/dsge_hip.h, ``dsge_kalman_smoother_batched``).  Returns dict(ll (batch,
+    T_len), smoothed_states (batch, T_len, m), smoothed_covs: diagonals (batch, T_len, m) or, with ``full_covariances``,
+    (batch, T_len, m, m), smoothed_shocks (batch, T_len, k) with ``[:, 0] = NaN`` by definition, status).  ``options`` carries
+    the filter conventions (``_lib.filter_conventions``); ``rank_tol`` (default 1e-10) sets the rank of the range basis;
+    ``scratch_limit_bytes`` (default 2 GiB) bounds the stored forward pass (``smoother_scratch_bytes_per_draw`` per draw)."""
+    (T, R, Q, code, Z, zb, d, db, Hdiag, hb, y, nb, m, k, p, T_len, rank_tol, limit) = _smoother_shapes(
+        T, R, Q, Z, y, d, Hdiag, q_mode, rank_tol, scratch_limit_bytes)
+    st = np.zeros(nb, dtype=np.int32) if status is None else np.ascontiguousarray(status, dtype=np.int32).copy()
+    if st.shape != (nb,):
+        raise ValueError(f"status must be (batch,); got {st.shape}")
+    cshape = (nb, T_len, m, m) if full_covariances else (nb, T_len, m)
+    out = dict(ll=np.empty((nb, T_len)), smoothed_states=np.empty((nb, T_len, m)), smoothed_covs=np.empty(cshape),
+               smoothed_shocks=np.empty((nb, T_len, k)))
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        _lib.check(
+            _lib.load().dsge_kalman_smoother_batched_host(
+                _ptr(T), _ptr(R), _ptr(Q), code, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(y), nb, m, k, p, T_len, float(jitter),
+                float(missing_fill_value), rank_tol, limit, _ptr(out["ll"]), _ptr(out["smoothed_states"]),
+                _ptr(out["smoothed_covs"]), _ptr(out["smoothed_shocks"]), int(bool(full_covariances)), _ptr(st)
+            )
+        )
+    out["status"] = st
+    return out
+
+
 def solve_kalman_logp_batched(A, B, C, D, Q, Z, y, d=None, Hdiag=None, q_mode=None, solver="cycle_reduction",
                               tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL,
                               return_policy=False, n_state_hint=None, z_selector_hint=None, n_lead_hint=None,

@@ -545,6 +545,47 @@ int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, co
   return hc.finish();
 }
 
+int dsge_kalman_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
+                                      int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                      double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
+                                      double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m || p < 1 || p > DSGE_MAX_P || T_len < 0 || q_mode < 0 || q_mode > 3)
+    return fail(DSGE_ERR_INVALID, "size out of range");
+  if (!T || !R || !Q || !Z || !y || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!a_smooth_out && !p_smooth_out && !eps_smooth_out) return fail(DSGE_ERR_INVALID, "no smoothed output requested");
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
+               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, tm = (size_t)batch * T_len * m,
+               tc = full_cov ? tm * m : tm;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  double *dll, *das, *dps, *des;
+  int32_t* dS;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, mk);
+  hc.in(&dQ, Q, nq);
+  hc.in(&dZ, Z, nz);
+  hc.in(&dd, d, nd);
+  hc.in(&dH, Hdiag, nh);
+  hc.in(&dy, y, ny);
+  hc.io(&dS, status_io, batch);
+  hc.out(&dll, ll_out, (size_t)batch * T_len);
+  hc.out(&das, a_smooth_out, tm);
+  hc.out(&dps, p_smooth_out, tc);
+  hc.out(&des, eps_smooth_out, (size_t)batch * T_len * k);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_kalman_smoother_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k, p, T_len,
+                                         jitter, missing_fill, rank_tol, scratch_limit_bytes, dll, das, dps, des, full_cov, dS,
+                                         hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_policy_norms_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
                                    const double* R, const int32_t* state_mask, int batch, int n, int k,
                                    double* det_norm_out, double* stoch_norm_out) {

@@ -570,6 +570,69 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
                                missing_fill, ll_out, a_pred_out, a_filt_out, p_pred_out, p_filt_out, full_cov, status_io, st);
 }
 
+// Smoothed states, covariances and shocks (dsge_kalman_smooth.hpp): the forward pass is launch_kalman_outputs with full
+// covariances into library scratch, one contiguous chunk of draws after the other on the caller's stream.
+int dsge_kalman_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                 const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
+                                 int m, int k, int p, int T_len, double jitter, double missing_fill, double rank_tol,
+                                 size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out, double* p_smooth_out,
+                                 double* eps_smooth_out, int full_cov, int32_t* status_io, void* stream) {
+  int rc = check_common(batch, m, DSGE_MAX_N);
+  if (rc) return rc;
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
+  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!T || !R || !Q || !Z || !y || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!a_smooth_out && !p_smooth_out && !eps_smooth_out) return fail(DSGE_ERR_INVALID, "no smoothed output requested");
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  if (!(rank_tol > 0.0)) rank_tol = 1e-10;
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  // the per-step filter outputs of one draw (the limit counts these; the per-draw matrices next to them are a few m^2)
+  const size_t tm = (size_t)T_len * m, per_draw = (2 * tm * m + 2 * tm) * sizeof(double);
+  size_t fit = scratch_limit_bytes / per_draw;
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const size_t mm = (size_t)chunk * m * m, img = (size_t)chunk * smoother_image_doubles(m);
+  double *RQR = nullptr, *P0 = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr, *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
+  double* ll = nullptr;
+  int32_t* rank = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, mm);
+  lay.add(&P0, mm);
+  lay.add(&U, img);
+  lay.add(&UT, img);
+  lay.add(&UR, img);
+  lay.add(&ap, chunk * tm);
+  lay.add(&af, chunk * tm);
+  lay.add(&pp, chunk * tm * m);
+  lay.add(&pf, chunk * tm * m);
+  lay.add(&rank, (size_t)chunk);
+  if (!ll_out) lay.add(&ll, (size_t)chunk * T_len);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  const bool qb = q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED;
+  const size_t qs = qb ? q_elems(q_mode, 1, k) : 0, tc = full_cov ? tm * m : tm;
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const size_t o = (size_t)c0;
+    const double *Tc = T + o * m * m, *Rc = R + o * m * k, *Qc = Q + o * qs, *Zc = Z + (z_batched ? o * p * m : 0),
+                 *dc = d ? d + (d_batched ? o * p : 0) : nullptr, *Hc = Hdiag ? Hdiag + (h_batched ? o * p : 0) : nullptr;
+    int32_t* sc = status_io + o;
+    if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, Tc, Rc, Qc, q_mode, nb, m, k, nullptr, nullptr, RQR, P0, sc, 0, 1,
+                              st)))
+      return rc;
+    if ((rc = launch_kalman_outputs(Tc, RQR, P0, Zc, z_batched, dc, d_batched, Hc, h_batched, y, nb, m, p, T_len, jitter,
+                                    missing_fill, ll_out ? ll_out + o * T_len : ll, ap, af, pp, pf, 1, sc, st)))
+      return rc;
+    if ((rc = launch_kalman_smoother(Tc, Rc, Qc, q_mode, nb, m, k, T_len, rank_tol, U, UT, UR, rank, ap, af, pp, pf,
+                                     a_smooth_out ? a_smooth_out + o * tm : nullptr, p_smooth_out ? p_smooth_out + o * tc : nullptr,
+                                     eps_smooth_out ? eps_smooth_out + o * T_len * k : nullptr, full_cov, sc, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
 int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
                              int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
                              const double* y, int batch, int m, int k, int p, int T_len, double jitter,

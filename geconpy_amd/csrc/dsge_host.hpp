@@ -237,6 +237,13 @@ int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, 
                           int d_batched, const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
                           double jitter, double missing_fill, double* ll, double* a_pred, double* a_filt, double* p_pred,
                           double* p_filt, int full_cov, int32_t* status, hipStream_t st);
+// launch_smooth.hip (dsge_kalman_smooth.hpp): basis of range(P_pred) per draw (U, UT, UR: [batch] images of smoother_image_doubles(m)
+// doubles, rank: [batch]) and the backward pass over the stored outputs of launch_kalman_outputs (full covariances)
+size_t smoother_image_doubles(int m);
+int launch_kalman_smoother(const double* T, const double* R, const double* Q, int q_mode, int batch, int m, int k, int T_len,
+                           double rank_tol, double* U, double* UT, double* UR, int32_t* rank, const double* a_pred, const double* a_filt,
+                           const double* p_pred, const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov,
+                           int32_t* status, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q (Rsel, qdiag), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);

@@ -222,6 +222,38 @@ class LogpEngine:
         )
         return logp, status
 
+    def kalman_smoother(self, T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, jitter=JITTER_DEFAULT,
+                        missing_fill_value=MISSING_FILL, full_covariances=False, covariances=True, rank_tol=None,
+                        scratch_limit_bytes=None, status=None, options=None):
+        """Smoothed states, covariances and shocks of the whole batch (``dsge_kalman_smoother_batched``; see
+        ``batched.kalman_smoother_batched``) from device tensors T [batch][m][m], R [batch][m][k], on torch's current stream.
+        Returns a dict of device tensors: ll, smoothed_states, smoothed_covs (None with ``covariances=False``: the covariance
+        recursion is then skipped), smoothed_shocks, status (asynchronous: synchronize before reading on the host).  ``status``:
+        optional int32 tensor [batch] of incoming per-draw status words (updated in place)."""
+        torch = self.torch
+        nb, m, _ = T.shape
+        self._chk(T, (nb, m, m))
+        k = self._chk(R).shape[2]
+        # (the packing of solve_kalman_logp: T, R stand in for the model matrices)
+        _, _, _, p, T_len, qm, zb, db, hb = self._pack(T, T, T, R, Q, Z, y, d, Hdiag, q_mode)
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)  # noqa: E731
+        if status is None:
+            status = torch.zeros(nb, dtype=torch.int32, device=self.device)
+        out = dict(ll=mk(nb, T_len), smoothed_states=mk(nb, T_len, m),
+                   smoothed_covs=(mk(nb, T_len, m, m) if full_covariances else mk(nb, T_len, m)) if covariances else None,
+                   smoothed_shocks=mk(nb, T_len, k), status=status)
+        with _lib.options_scope(options):
+            _lib.check(
+                self.lib.dsge_kalman_smoother_batched(
+                    self._p(T), self._p(R), self._p(Q), qm, self._p(Z), zb, self._p(d), db, self._p(Hdiag), hb, self._p(y), nb, m,
+                    k, p, T_len, float(jitter), float(missing_fill_value), 0.0 if rank_tol is None else float(rank_tol),
+                    0 if scratch_limit_bytes is None else int(scratch_limit_bytes), self._p(out["ll"]),
+                    self._p(out["smoothed_states"]), self._p(out["smoothed_covs"]), self._p(out["smoothed_shocks"]),
+                    int(bool(full_covariances)), status.data_ptr(), self._stream(),
+                )
+            )
+        return out
+
     def solve_kalman_logp_grad(self, A, B, C, D, q, Z, y, d=None, Hdiag=None, solver="cycle_reduction", tol=1e-6, max_iter=50,
                                jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, n_filter_hint=0, n_lead_hint=0,
                                out=None, options=None, full_covariance=False, dense_z=False):

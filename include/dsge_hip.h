@@ -27,13 +27,14 @@
 #ifndef DSGE_HIP_H
 #define DSGE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 9
+#define DSGE_ABI_VERSION 10
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -44,6 +45,7 @@ extern "C" {
  * spectral division (gensys_doubling = 1) certifies a draw only if two scale guards hold that make the reference's absolute-tolerance
  * tests (coincident zeros, rank of Q2 Pi; gEconpy/solvers/gensys.py:243, 276-283) provably pass -- a draw with an equation scaled
  * by <= ~tol now gets the ordered QZ's verdict instead of eu = [1, 1, 0]. */
+/* ABI 10: dsge_kalman_smoother_batched (+ _host) and the status bit DSGE_ST_SMOOTHER_SINGULAR are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -75,6 +77,7 @@ extern "C" {
 #define DSGE_ST_GENSYS_TOO_BIG 32  /* n + #lead exceeds the on-chip capacity of the launch     */
 #define DSGE_ST_GRAD_UNSUPPORTED 64 /* gradient path: dense design matrix / reduced model exceeds the tile */
 #define DSGE_ST_SECOND_ORDER_UNSUPPORTED 128 /* second-order path: input violates the declared model structure */
+#define DSGE_ST_SMOOTHER_SINGULAR 256 /* smoother: sym(U' P_pred U) not positive definite at some step (jitter_P = 0 only) */
 
 /* covariance layouts for the Q argument */
 #define DSGE_Q_DIAG_SHARED 0    /* Q = diag(q), q: [k]            */
@@ -654,6 +657,44 @@ int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, co
                                             const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                                             double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
                                             double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io);
+
+/*
+ * Fixed-interval (Rauch-Tung-Striebel) SMOOTHER over the stored outputs of the filter above, batched over draws: the smoothed
+ * states and covariances that save_kalman_filter_outputs_in_idata=True keeps next to the filter's (statespace.py:1145,
+ * 1151-1157 -> pymc_extras' smoother; gEconpy/plotting.py:1791-1835 "smoothed"), and the smoothed structural shocks (an
+ * extension: upstream has none).  With n = T_len, 0-based t, the filter outputs under the call's filter conventions:
+ *     as[n-1] = a_filt[n-1], V[n-1] = P_filt[n-1];   for t = n-2 .. 0, with Pp = P_pred[t+1]:
+ *     w = Pp^+ (as[t+1] - a_pred[t+1]);  as[t] = a_filt[t] + P_filt[t] T' w;  eps[t+1] = Q R' w;
+ *     G = P_filt[t] T' Pp^+;  V[t] = P_filt[t] + sym(G (V[t+1] - Pp) G');      eps[0] = NaN BY DEFINITION (the period-0 innovation
+ *     is confounded with the unobserved pre-sample state).
+ * Pp^+ is the pseudo-inverse (upstream: pinv(Pp, hermitian=True); Pp is singular for every DSGE model), computed from the range
+ * of Pp, which is fixed per draw: range(Pp) = range(T) + range(R_J), J = {j : Q_jj > 0}.  TWO ASSUMPTIONS: P_filt positive
+ * definite (jitter_P > 0 guarantees it) and Q_JJ positive definite.  U = orthonormal basis of [T | R_J] (pivoted Gram-Schmidt,
+ * rank by |R_jj| > rank_tol |R_00|), M = sym(U' Pp U) = L L', Pp^+ x = U M^-1 U' x.  Arguments T .. missing_fill as
+ * dsge_kalman_filter_outputs_batched, plus
+ *   rank_tol            : <= 0: 1e-10
+ *   scratch_limit_bytes : the forward pass stores 2 T_len m^2 + 2 T_len m doubles per draw in library scratch; the batch is
+ *                         processed in contiguous chunks of draws, on the caller's stream and without host synchronisation, sized so
+ *                         that this store stays within the limit (0: 2 GiB; at least one draw per chunk)
+ *   ll_out         : [batch][T_len] ll_t as above, may be NULL
+ *   a_smooth_out   : [batch][T_len][m]      p_smooth_out : [batch][T_len][m] diagonals, or [..][m][m] with full_cov != 0
+ *   eps_smooth_out : [batch][T_len][k]      each of the three may be NULL, at least one must be given; without p_smooth_out the
+ *                                           covariance recursion is skipped
+ *   status_io      : [batch] in/out; a draw with a non-zero incoming status, or whose filter goes non-finite
+ *                    (DSGE_ST_FILTER_NONFINITE), has NaN in every smoothed output; a non-positive pivot of M sets
+ *                    DSGE_ST_SMOOTHER_SINGULAR and gives NaN for that step and all earlier ones (the later steps stay)
+ * batch == 0 or T_len == 0: success, nothing touched.  T_len == 1: smoothed = filtered, shocks NaN.  m <= DSGE_MAX_N.
+ */
+int dsge_kalman_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                 const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
+                                 int m, int k, int p, int T_len, double jitter, double missing_fill, double rank_tol,
+                                 size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out, double* p_smooth_out,
+                                 double* eps_smooth_out, int full_cov, int32_t* status_io, void* stream);
+int dsge_kalman_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
+                                      int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                      double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
+                                      double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw
