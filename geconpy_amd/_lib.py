@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -126,6 +126,14 @@ PROTOTYPES = {
                                      _dp, _dp, _i, _dp, _dp],
     "dsge_kalman_smoother_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _f, _z, _dp,
                                           _dp, _dp, _dp, _i, _dp],
+    "dsge_simulate_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _dp, _dp],
+    "dsge_simulate_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _dp],
+    "dsge_irf_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _dp, _dp, _dp],
+    "dsge_irf_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _dp, _dp],
+    "dsge_forecast_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _i, _i, _i, _i, _i, _dp, _dp, _i, _dp,
+                              _dp, _dp],
+    "dsge_forecast_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _i, _i, _i, _i, _i, _dp, _dp, _i, _dp,
+                                   _dp],
     "dsge_solve_kalman_logp_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
     "dsge_solve_kalman_logp_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp],
     "dsge_solve_kalman_logp_augmented_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,

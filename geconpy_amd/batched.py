@@ -537,6 +537,139 @@ def kalman_smoother_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, stat
     return out
 
 
+def _dyn_TR(T, R, name):
+    T, R = _f64(T, 3), _f64(R, 3)
+    nb, m, m2 = T.shape
+    if m != m2 or R.shape[:2] != (nb, m) or R.shape[2] < 1:
+        raise ValueError(f"T must be (batch, m, m) and R (batch, m, k); got {T.shape}, {R.shape}")
+    if m > _lib.MAX_N_BIG:
+        raise ValueError(f"{name}: m = {m}, at most {_lib.MAX_N_BIG} variables")
+    return T, R, nb, m, R.shape[2]
+
+
+def _dyn_shared_or_batched(x, nb, tail, name):
+    """``x`` of shape ``tail`` (shared) or ``(batch,) + tail`` -> (array, batched flag)."""
+    x = _f64(x)
+    if x.shape == tuple(tail):
+        return x, 0
+    if x.shape == (nb, *tail):
+        return x, 1
+    raise ValueError(f"{name} must be {tuple(tail)} or {(nb, *tail)}; got {x.shape}")
+
+
+def _dyn_status(status, nb):
+    if status is None:
+        return None
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    if st.shape != (nb,):
+        raise ValueError(f"status must be (batch,); got {st.shape}")
+    return st
+
+
+def simulate_batched(T, R, eps, n_steps=None, x0=None, status=None):
+    """Simulated paths ``x[b, s, t] = T_b x[b, s, t-1] + R_b eps[b, s, t]`` for a batch of draws -- the loop of
+    ``_simulate_linear_system`` (gEconpy/model/simulate.py:171-182) that ``simulate`` (:320-430) runs once per trajectory, for
+    every draw and path at once (include/dsge_hip.h, ``dsge_simulate_batched``).  ``eps``: (n_paths, n_shock_steps, k) shared by
+    all draws or (batch, n_paths, n_shock_steps, k) -- the caller draws the shocks, as ``simulate`` does from its
+    ``random_seed``; ``n_steps`` (default n_shock_steps) may exceed n_shock_steps: the later steps have no shock.  ``x0``:
+    (n_paths, m) or (batch, n_paths, m), default zero (the reference's start).  ``status``: optional (batch,) int32, a draw
+    with a non-zero word gets NaN.  Returns dict(paths (batch, n_paths, n_steps, m))."""
+    T, R, nb, m, k = _dyn_TR(T, R, "simulate_batched")
+    eps = _f64(eps)
+    if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+        raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {eps.shape}")
+    n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+    eps, eb = _dyn_shared_or_batched(eps, nb, (n_paths, n_shock, k), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    if n_steps < n_shock:
+        raise ValueError(f"n_steps = {n_steps} is less than the {n_shock} shock steps of eps")
+    xb = 0
+    if x0 is not None:
+        x0, xb = _dyn_shared_or_batched(x0, nb, (n_paths, m), "x0")
+    st = _dyn_status(status, nb)
+    out = np.empty((nb, n_paths, n_steps, m))
+    _lib.check(_lib.load().dsge_simulate_batched_host(_ptr(T), _ptr(R), _ptr(eps), eb, _ptr(x0), xb, _ptr(st), nb, m, k, n_paths,
+                                                      n_steps, n_shock, _ptr(out)))
+    return dict(paths=out)
+
+
+def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None):
+    """Impulse responses ``irf[b, j, h] = T_b^h R_b S[:, j]`` for a batch of draws -- ``impulse_response_function``
+    (gEconpy/model/simulate.py:201-317; its loop over shocks :300-311 calls ``_simulate_linear_system`` :171-182 once per
+    shock) for every draw and impulse at once (include/dsge_hip.h, ``dsge_irf_batched``).  ``S``: (k, c) or (batch, k, c),
+    impulse j is its column j; default ``I_k`` (unit impulses to every shock).  The reference's modes: ``shock_size`` ->
+    ``S = diag(s)``; ``return_individual_shocks=False`` -> ``S = s[:, None]``; orthogonalised ``shock_cov`` ->
+    ``S = cholesky(Q)``.  ``fevd=True`` adds the forecast-error variance decomposition with respect to these impulses
+    (``weights``: (c,) or (batch, c), default ones; an extension, the reference has none); ``irf=False`` skips the responses.
+    Returns dict(irf (batch, c, n_steps, m) or None, fevd (batch, n_steps, m, c) or None)."""
+    T, R, nb, m, k = _dyn_TR(T, R, "impulse_response_batched")
+    sb, c = 0, k
+    if S is not None:
+        S = _f64(S)
+        if S.ndim not in (2, 3) or S.shape[-2] != k:
+            raise ValueError(f"S must be ({k}, c) or (batch, {k}, c); got {S.shape}")
+        c = S.shape[-1]
+        S, sb = _dyn_shared_or_batched(S, nb, (k, c), "S")
+    wb = 0
+    if weights is not None:
+        weights, wb = _dyn_shared_or_batched(weights, nb, (c,), "weights")
+    if not (irf or fevd):
+        raise ValueError("nothing requested: irf and fevd are both off")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError("n_steps must be >= 0")
+    st = _dyn_status(status, nb)
+    out = dict(irf=np.empty((nb, c, n_steps, m)) if irf else None, fevd=np.empty((nb, n_steps, m, c)) if fevd else None)
+    _lib.check(_lib.load().dsge_irf_batched_host(_ptr(T), _ptr(R), _ptr(S), sb, _ptr(weights), wb, _ptr(st), nb, m, k, c, n_steps,
+                                                 _ptr(out["irf"]), _ptr(out["fevd"])))
+    return out
+
+
+def forecast_batched(T, R, Q, a0, P0=None, n_steps=10, Z=None, d=None, Hdiag=None, q_mode=None, covariances="diag",
+                     status=None):
+    """Out-of-sample forecast moments for a batch of draws -- the ``forecast`` of the pymc_extras state-space model that
+    ``DSGEStateSpace`` extends (gEconpy/model/statespace.py:51), which iterates ``x = T x + R eps`` from the last filtered
+    state per draw: ``a_h = T a_{h-1}``, ``P_h = sym(T P_{h-1} T') + sym(R Q R')``, ``y_h = Z a_h + d``,
+    ``F_h = sym(Z P_h Z') + diag(H)`` for h = 1..n_steps (include/dsge_hip.h, ``dsge_forecast_batched``).  ``a0``: (batch, m);
+    ``P0``: (batch, m, m) or None for zero; ``covariances``: ``"diag"``, ``"full"`` or ``None`` (the covariance recursion is
+    skipped).  With ``Z`` ((p, m) or (batch, p, m)) the observation moments are returned too.  Recipe from the filter:
+    ``kalman_filter_outputs_batched(..., full_covariances=True)`` -> ``a0 = filtered_states[:, -1]``,
+    ``P0 = filtered_covs[:, -1]``.  Returns dict(states (batch, n_steps, m), covs, observed (batch, n_steps, p) or None,
+    observed_covs (batch, n_steps, p, p) or None)."""
+    T, R, nb, m, k = _dyn_TR(T, R, "forecast_batched")
+    Q, code = _resolve_q(Q, q_mode, nb, k)
+    a0 = _f64(a0)
+    if a0.shape != (nb, m):
+        raise ValueError(f"a0 must be {(nb, m)}; got {a0.shape}")
+    if P0 is not None:
+        P0 = _f64(P0)
+        if P0.shape != (nb, m, m):
+            raise ValueError(f"P0 must be {(nb, m, m)}; got {P0.shape}")
+    if covariances not in ("diag", "full", None):
+        raise ValueError('covariances must be "diag", "full" or None')
+    p, zb, db, hb = 0, 0, 0, 0
+    if Z is not None:
+        Z = _f64(Z)
+        p = Z.shape[-2] if Z.ndim >= 2 else 0
+        Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, m)
+    elif d is not None or Hdiag is not None:
+        raise ValueError("d and Hdiag need Z")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError("n_steps must be >= 0")
+    st = _dyn_status(status, nb)
+    cov = covariances is not None
+    full = covariances == "full"
+    out = dict(states=np.empty((nb, n_steps, m)),
+               covs=np.empty((nb, n_steps, m, m) if full else (nb, n_steps, m)) if cov else None,
+               observed=np.empty((nb, n_steps, p)) if p else None,
+               observed_covs=np.empty((nb, n_steps, p, p)) if p and cov else None)
+    _lib.check(_lib.load().dsge_forecast_batched_host(
+        _ptr(T), _ptr(R), _ptr(Q), code, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(a0), _ptr(P0), _ptr(st), nb, m, k, p,
+        n_steps, _ptr(out["states"]), _ptr(out["covs"]), int(full), _ptr(out["observed"]), _ptr(out["observed_covs"])))
+    return out
+
+
 def solve_kalman_logp_batched(A, B, C, D, Q, Z, y, d=None, Hdiag=None, q_mode=None, solver="cycle_reduction",
                               tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL,
                               return_policy=False, n_state_hint=None, z_selector_hint=None, n_lead_hint=None,

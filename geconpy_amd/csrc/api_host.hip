@@ -586,6 +586,86 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
   return hc.finish();
 }
 
+int dsge_simulate_batched_host(const double* T, const double* R, const double* eps, int eps_batched, const double* x0,
+                               int x0_batched, const int32_t* status, int batch, int m, int k, int n_paths, int n_steps,
+                               int n_shock_steps, double* x_out) {
+  int rc = check_simulate(T, R, eps, batch, m, k, n_paths, n_steps, n_shock_steps, x_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const double *dT, *dR, *de, *dx0;
+  const int32_t* dS;
+  double* dx;
+  hc.in(&dT, T, (size_t)batch * m * m);
+  hc.in(&dR, R, (size_t)batch * m * k);
+  hc.in(&de, eps, (size_t)(eps_batched ? batch : 1) * n_paths * n_shock_steps * k);
+  hc.in(&dx0, x0, (size_t)(x0_batched ? batch : 1) * n_paths * m);
+  hc.in(&dS, status, (size_t)batch);
+  hc.out(&dx, x_out, (size_t)batch * n_paths * n_steps * m);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_simulate_batched(dT, dR, de, eps_batched, dx0, x0_batched, dS, batch, m, k, n_paths, n_steps, n_shock_steps, dx,
+                                  hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_irf_batched_host(const double* T, const double* R, const double* S, int s_batched, const double* weights, int w_batched,
+                          const int32_t* status, int batch, int m, int k, int c, int n_steps, double* irf_out, double* fevd_out) {
+  int rc = check_irf(T, R, S, batch, m, k, c, n_steps, irf_out, fevd_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || c == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const double *dT, *dR, *dSm, *dw;
+  const int32_t* dS;
+  double *di, *df;
+  const size_t no = (size_t)batch * c * n_steps * m;
+  hc.in(&dT, T, (size_t)batch * m * m);
+  hc.in(&dR, R, (size_t)batch * m * k);
+  hc.in(&dSm, S, (size_t)(s_batched ? batch : 1) * k * c);
+  hc.in(&dw, weights, (size_t)(w_batched ? batch : 1) * c);
+  hc.in(&dS, status, (size_t)batch);
+  hc.out(&di, irf_out, no);
+  hc.out(&df, fevd_out, no);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_irf_batched(dT, dR, dSm, s_batched, dw, w_batched, dS, batch, m, k, c, n_steps, di, df, hc.stream()))) return rc;
+  return hc.finish();
+}
+
+int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                               const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                               const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,
+                               double* p_out, int full_cov, double* y_out, double* f_out) {
+  int rc = check_forecast(T, R, Q, q_mode, Z, a0, batch, m, k, p, n_steps, a_out, p_out, y_out, f_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0;
+  const int32_t* dS;
+  double *da, *dp, *dy, *df;
+  const size_t mm = (size_t)batch * m * m, tm = (size_t)batch * n_steps * m;
+  hc.in(&dT, T, mm);
+  hc.in(&dR, R, (size_t)batch * m * k);
+  hc.in(&dQ, Q, q_elems(q_mode, batch, k));
+  hc.in(&dZ, Z, (size_t)(z_batched ? batch : 1) * p * m);
+  hc.in(&dd, d, (size_t)(d_batched ? batch : 1) * p);
+  hc.in(&dH, Hdiag, (size_t)(h_batched ? batch : 1) * p);
+  hc.in(&da0, a0, (size_t)batch * m);
+  hc.in(&dP0, P0, mm);
+  hc.in(&dS, status, (size_t)batch);
+  hc.out(&da, a_out, tm);
+  hc.out(&dp, p_out, full_cov ? tm * m : tm);
+  hc.out(&dy, y_out, (size_t)batch * n_steps * p);
+  hc.out(&df, f_out, (size_t)batch * n_steps * p * p);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_forecast_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dS, batch, m, k, p,
+                                  n_steps, da, dp, full_cov, dy, df, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_policy_norms_batched_host(const double* A, const double* B, const double* C, const double* D, const double* T,
                                    const double* R, const int32_t* state_mask, int batch, int n, int k,
                                    double* det_norm_out, double* stoch_norm_out) {

@@ -633,6 +633,94 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   return DSGE_SUCCESS;
 }
 
+// ---- post-solve dynamics (dsge_dynamics.hpp): simulate, impulse responses + FEVD, forecast -----------------------------------
+}  // extern "C"
+namespace dsge_host {
+int check_simulate(const double* T, const double* R, const double* eps, int batch, int m, int k, int n_paths, int n_steps,
+                   int n_shock_steps, const double* x_out) {
+  if (batch < 0 || m < 1 || n_paths < 0 || n_steps < 0 || n_shock_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (n_shock_steps > n_steps) return fail(DSGE_ERR_INVALID, "n_shock_steps > n_steps");
+  if (!T || !R || !x_out || (!eps && n_shock_steps > 0)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "simulate: m exceeds DSGE_MAX_N_BIG");
+  return DSGE_SUCCESS;
+}
+int check_irf(const double* T, const double* R, const double* S, int batch, int m, int k, int c, int n_steps, const double* irf_out,
+              const double* fevd_out) {
+  if (batch < 0 || m < 1 || c < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (!S && c != k) return fail(DSGE_ERR_INVALID, "S == NULL means S = I: c must equal k");
+  if (!T || !R) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!irf_out && !fevd_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "impulse responses: m exceeds DSGE_MAX_N_BIG");
+  return DSGE_SUCCESS;
+}
+int check_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, const double* a0, int batch,
+                   int m, int k, int p, int n_steps, const double* a_out, const double* p_out, const double* y_out,
+                   const double* f_out) {
+  if (batch < 0 || m < 1 || p < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!a_out && !p_out && !y_out && !f_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (!T || !R || !a0 || ((p_out || f_out) && !Q) || (p > 0 && !Z)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if ((y_out || f_out) && p == 0) return fail(DSGE_ERR_INVALID, "observation outputs requested with p == 0");
+  if (m > DSGE_MAX_N || p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "forecast: m exceeds DSGE_MAX_N or p exceeds DSGE_MAX_P");
+  return DSGE_SUCCESS;
+}
+}  // namespace dsge_host
+extern "C" {
+
+int dsge_simulate_batched(const double* T, const double* R, const double* eps, int eps_batched, const double* x0, int x0_batched,
+                          const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps,
+                          double* x_out, void* stream) {
+  int rc = check_simulate(T, R, eps, batch, m, k, n_paths, n_steps, n_shock_steps, x_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const long long per_path = (long long)n_shock_steps * k;
+  return launch_propagate(T, R, eps, eps_batched ? n_paths * per_path : 0, per_path, k, 1, 0, x0,
+                          x0_batched ? (long long)n_paths * m : 0, nullptr, 0, status, batch, m, k, n_paths, n_steps, n_shock_steps,
+                          x_out, nullptr, (hipStream_t)stream);
+}
+
+// Impulse j is column j of S: the propagation kernel entered with e_0 = S[:, j] and no shock afterwards.  Up to 16 impulses the FEVD
+// is accumulated on chip by the same launch; beyond, a second pass reads the stored responses (library scratch when the caller
+// wants the FEVD alone).
+int dsge_irf_batched(const double* T, const double* R, const double* S, int s_batched, const double* weights, int w_batched,
+                     const int32_t* status, int batch, int m, int k, int c, int n_steps, double* irf_out, double* fevd_out,
+                     void* stream) {
+  int rc = check_irf(T, R, S, batch, m, k, c, n_steps, irf_out, fevd_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || c == 0 || n_steps == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  const bool second_pass = fevd_out && c > 16;
+  double* irf = irf_out;
+  if (second_pass && !irf) {
+    ScratchLayout lay;
+    lay.add(&irf, (size_t)batch * c * n_steps * m);
+    if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  }
+  const long long w_draw = w_batched ? c : 0;
+  if ((rc = launch_propagate(T, R, S, s_batched ? (long long)k * c : 0, 1, 0, c, S ? 0 : 1, nullptr, 0, weights, w_draw, status, batch, m,
+                             k, c, n_steps, 1, irf, second_pass ? nullptr : fevd_out, st)))
+    return rc;
+  if (second_pass) return launch_fevd(irf, weights, w_draw, status, batch, m, c, n_steps, fevd_out, st);
+  return DSGE_SUCCESS;
+}
+
+int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
+                          const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,
+                          int full_cov, double* y_out, double* f_out, void* stream) {
+  int rc = check_forecast(T, R, Q, q_mode, Z, a0, batch, m, k, p, n_steps, a_out, p_out, y_out, f_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_steps == 0) return DSGE_SUCCESS;
+  return launch_forecast(T, R, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, a0, P0, status, batch, m, k, p, n_steps, a_out,
+                         p_out, full_cov, y_out, f_out, (hipStream_t)stream);
+}
+
 int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
                              int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
                              const double* y, int batch, int m, int k, int p, int T_len, double jitter,

@@ -120,6 +120,14 @@ int twin_streams(hipStream_t* s0, hipStream_t* s1);
 int ensure_device();                          // lazy check for a gfx950 device: nothing touches HIP before the first call
 int check_common(int batch, int n, int n_max);
 size_t q_elems(int q_mode, int batch, int k);  // elements of a shock covariance in layout DSGE_Q_*
+// argument checks of the dynamics entries (dsge_api.hip), shared with their host twins
+int check_simulate(const double* T, const double* R, const double* eps, int batch, int m, int k, int n_paths, int n_steps,
+                   int n_shock_steps, const double* x_out);
+int check_irf(const double* T, const double* R, const double* S, int batch, int m, int k, int c, int n_steps, const double* irf_out,
+              const double* fevd_out);
+int check_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, const double* a0, int batch,
+                   int m, int k, int p, int n_steps, const double* a_out, const double* p_out, const double* y_out,
+                   const double* f_out);
 // The fused solve + filter pipeline of ONE batch on ONE stream: what dsge_solve_kalman_logp_batched runs when it does not
 // split the batch (dsge_options.pipeline_chunks), with the stage timing of dsge_profile_pipeline (reps, ms_out) and an
 // optional slice of a scratch arena the caller reserved (chunks in flight on several streams).  Arguments as the public entry.
@@ -244,6 +252,19 @@ int launch_kalman_smoother(const double* T, const double* R, const double* Q, in
                            double rank_tol, double* U, double* UT, double* UR, int32_t* rank, const double* a_pred, const double* a_filt,
                            const double* p_pred, const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov,
                            int32_t* status, hipStream_t st);
+// launch_dynamics.hip (dsge_dynamics.hpp): x_t = T x_{t-1} + R e_t for groups of 16 paths per draw (shock element (draw, path,
+// step, component) at the four strides; identity: unit impulses, nothing read), optionally the FEVD of <= 16 paths; the FEVD of
+// more as a second pass over stored responses; the forecast moment recursion
+int launch_propagate(const double* T, const double* R, const double* shocks, long long sh_draw, long long sh_path, long long sh_step,
+                     long long sh_comp, int identity, const double* x0, long long x0_draw, const double* weights, long long w_draw,
+                     const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps, double* x_out,
+                     double* fevd_out, hipStream_t st);
+int launch_fevd(const double* irf, const double* weights, long long w_draw, const int32_t* status, int batch, int m, int c,
+                int n_steps, double* fevd_out, hipStream_t st);
+int launch_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
+                    int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0, const int32_t* status,
+                    int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out, int full_cov, double* y_out,
+                    double* f_out, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q (Rsel, qdiag), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);

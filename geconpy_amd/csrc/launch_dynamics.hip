@@ -1,0 +1,60 @@
+// Launchers of the post-solve dynamics kernels (dsge_dynamics.hpp): propagation (simulate, impulse responses, FEVD) and the
+// forecast moment recursion.
+#include "dsge_host.hpp"
+#include "dsge_dynamics.hpp"
+
+namespace dsge_host {
+
+int launch_propagate(const double* T, const double* R, const double* shocks, long long sh_draw, long long sh_path, long long sh_step,
+                     long long sh_comp, int identity, const double* x0, long long x0_draw, const double* weights, long long w_draw,
+                     const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps, double* x_out,
+                     double* fevd_out, hipStream_t st) {
+  dsge::DynArgs a{};
+  a.T = T; a.R = R; a.shocks = shocks; a.sh_draw = sh_draw; a.sh_path = sh_path; a.sh_step = sh_step; a.sh_comp = sh_comp;
+  a.identity = identity; a.x0 = x0; a.x0_draw = x0_draw; a.weights = weights; a.w_draw = w_draw; a.status = status; a.x_out = x_out;
+  a.fevd = fevd_out; a.batch = batch; a.m = m; a.k = k; a.n_paths = n_paths; a.n_steps = n_steps; a.n_shock_steps = n_shock_steps;
+  a.groups = (n_paths + dsge::DY_COLS - 1) / dsge::DY_COLS;
+  if (fevd_out && a.groups != 1) return fail(DSGE_ERR_INVALID, "propagate: on-chip FEVD takes one column group");
+  const size_t lds = dsge::dy_lds_doubles(m, k) * sizeof(double);
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "dynamics: [T | R] does not fit the LDS (m = 96 takes k <= 32)");
+  const long long grid = (long long)batch * a.groups;
+  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "dynamics: batch x path groups exceeds the grid");
+  int rc;
+  if ((rc = set_lds(dsge::dynamics_propagate_kernel, lds))) return rc;
+  hipLaunchKernelGGL(dsge::dynamics_propagate_kernel, dim3((unsigned)grid), dim3(dsge::DY_THREADS), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return DSGE_SUCCESS;
+}
+
+int launch_fevd(const double* irf, const double* weights, long long w_draw, const int32_t* status, int batch, int m, int c,
+                int n_steps, double* fevd_out, hipStream_t st) {
+  dsge::FevdArgs a{};
+  a.irf = irf; a.weights = weights; a.w_draw = w_draw; a.status = status; a.fevd = fevd_out; a.batch = batch; a.m = m; a.c = c;
+  a.n_steps = n_steps;
+  const size_t lds = dsge::dy_fevd_lds_doubles(m, c) * sizeof(double);
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "dynamics: the FEVD sums of this many impulses do not fit the LDS");
+  int rc;
+  if ((rc = set_lds(dsge::dynamics_fevd_kernel, lds))) return rc;
+  hipLaunchKernelGGL(dsge::dynamics_fevd_kernel, dim3(batch), dim3(dsge::DY_THREADS), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return DSGE_SUCCESS;
+}
+
+int launch_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
+                    int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0, const int32_t* status,
+                    int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out, int full_cov, double* y_out,
+                    double* f_out, hipStream_t st) {
+  dsge::FcArgs a{};
+  a.T = T; a.R = R; a.Q = Q; a.Z = Z; a.d = d; a.Hdiag = Hdiag; a.a0 = a0; a.P0 = P0; a.status = status; a.a_out = a_out;
+  a.p_out = p_out; a.y_out = y_out; a.f_out = f_out; a.batch = batch; a.m = m; a.k = k; a.p = p; a.n_steps = n_steps;
+  a.q_mode = q_mode; a.z_batched = z_batched; a.d_batched = d_batched; a.h_batched = h_batched; a.full_cov = full_cov;
+  const size_t lds = dsge::fc_lds_doubles(m, p) * sizeof(double);
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "forecast: LDS budget exceeded");
+  int rc;
+  if ((rc = set_lds(dsge::dynamics_forecast_kernel, lds))) return rc;
+  hipLaunchKernelGGL(dsge::dynamics_forecast_kernel, dim3(batch), dim3(dsge::FC_THREADS), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return DSGE_SUCCESS;
+}
+
+}  // namespace dsge_host

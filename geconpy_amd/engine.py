@@ -59,14 +59,7 @@ class LogpEngine:
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
 
-    def _pack(self, A, B, C, D, Q, Z, y, d, Hdiag, q_mode):
-        nb, n, _ = A.shape
-        k = D.shape[2]
-        T_len, p = y.shape
-        for t in (A, B, C):
-            self._chk(t, (nb, n, n))
-        self._chk(D, (nb, n, k))
-        self._chk(y, (T_len, p))
+    def _q_layout(self, Q, q_mode, nb, k):
         self._chk(Q)
         if q_mode is None:
             q_mode = {(k,): 0, (nb, k, k): 3}.get(tuple(Q.shape))
@@ -77,6 +70,17 @@ class LogpEngine:
                     q_mode = 2
                 else:
                     raise ValueError("ambiguous Q layout; pass q_mode")
+        return int(q_mode)
+
+    def _pack(self, A, B, C, D, Q, Z, y, d, Hdiag, q_mode):
+        nb, n, _ = A.shape
+        k = D.shape[2]
+        T_len, p = y.shape
+        for t in (A, B, C):
+            self._chk(t, (nb, n, n))
+        self._chk(D, (nb, n, k))
+        self._chk(y, (T_len, p))
+        q_mode = self._q_layout(Q, q_mode, nb, k)
         zb = int(self._chk(Z).dim() == 3)
         db = int(d is not None and self._chk(d).dim() == 2)
         hb = int(Hdiag is not None and self._chk(Hdiag).dim() == 2)
@@ -253,6 +257,108 @@ class LogpEngine:
                 )
             )
         return out
+
+    # -- post-solve dynamics (csrc/dsge_dynamics.hpp) -----------------------------------------
+    def _dyn_TR(self, T, R):
+        nb, m, _ = T.shape
+        self._chk(T, (nb, m, m))
+        k = self._chk(R).shape[-1]
+        self._chk(R, (nb, m, k))
+        return nb, m, k
+
+    def _dyn_flag(self, t, nb, tail, name):
+        """0 for shape ``tail`` (shared), 1 for ``(batch,) + tail``."""
+        shape = tuple(self._chk(t).shape)
+        if shape == tuple(tail):
+            return 0
+        if shape == (nb, *tail):
+            return 1
+        raise ValueError(f"{name} must be {tuple(tail)} or {(nb, *tail)}; got {shape}")
+
+    def _dyn_status(self, status, nb):
+        if status is not None and not (status.is_cuda and status.dtype == self.torch.int32 and status.is_contiguous()
+                                       and tuple(status.shape) == (nb,)):
+            raise ValueError("status must be a contiguous int32 CUDA tensor (batch,)")
+        return None if status is None else status.data_ptr()
+
+    def _dyn_out(self, out, shape):
+        if out is None:
+            return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
+        return self._chk(out, shape)
+
+    def simulate(self, T, R, eps, n_steps=None, x0=None, status=None, out=None):
+        """Simulated paths of the whole batch from device tensors (``dsge_simulate_batched``; see
+        ``batched.simulate_batched``), enqueued on torch's current stream.  ``eps``: (n_paths, n_shock_steps, k) or
+        (batch, n_paths, n_shock_steps, k) -- draw it with torch on the device.  Returns the paths
+        (batch, n_paths, n_steps, m) (``out`` if given); asynchronous."""
+        nb, m, k = self._dyn_TR(T, R)
+        if self._chk(eps).dim() not in (3, 4) or eps.shape[-1] != k:
+            raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k})")
+        n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+        eb = self._dyn_flag(eps, nb, (n_paths, n_shock, k), "eps")
+        n_steps = n_shock if n_steps is None else int(n_steps)
+        xb = 0 if x0 is None else self._dyn_flag(x0, nb, (n_paths, m), "x0")
+        out = self._dyn_out(out, (nb, n_paths, n_steps, m))
+        _lib.check(self.lib.dsge_simulate_batched(self._p(T), self._p(R), self._p(eps), eb, self._p(x0), xb,
+                                                  self._dyn_status(status, nb), nb, m, k, n_paths, n_steps, n_shock,
+                                                  self._p(out), self._stream()))
+        return out
+
+    def impulse_response(self, T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None, out=None):
+        """Impulse responses (and, with ``fevd=True``, their variance decomposition) of the whole batch from device tensors
+        (``dsge_irf_batched``; see ``batched.impulse_response_batched``), on torch's current stream.  ``out``: optional dict
+        with preallocated ``irf`` / ``fevd`` tensors.  Returns dict(irf (batch, c, n_steps, m) or None,
+        fevd (batch, n_steps, m, c) or None); asynchronous."""
+        nb, m, k = self._dyn_TR(T, R)
+        sb, c = 0, k
+        if S is not None:
+            if self._chk(S).dim() not in (2, 3) or S.shape[-2] != k:
+                raise ValueError(f"S must be ({k}, c) or (batch, {k}, c)")
+            c = S.shape[-1]
+            sb = self._dyn_flag(S, nb, (k, c), "S")
+        wb = 0 if weights is None else self._dyn_flag(weights, nb, (c,), "weights")
+        if not (irf or fevd):
+            raise ValueError("nothing requested: irf and fevd are both off")
+        n_steps = int(n_steps)
+        out = out or {}
+        res = dict(irf=self._dyn_out(out.get("irf"), (nb, c, n_steps, m)) if irf else None,
+                   fevd=self._dyn_out(out.get("fevd"), (nb, n_steps, m, c)) if fevd else None)
+        _lib.check(self.lib.dsge_irf_batched(self._p(T), self._p(R), self._p(S), sb, self._p(weights), wb,
+                                             self._dyn_status(status, nb), nb, m, k, c, n_steps, self._p(res["irf"]),
+                                             self._p(res["fevd"]), self._stream()))
+        return res
+
+    def forecast(self, T, R, Q, a0, P0=None, n_steps=10, Z=None, d=None, Hdiag=None, q_mode=None, covariances="diag",
+                 status=None, out=None):
+        """Forecast moments of the whole batch from device tensors (``dsge_forecast_batched``; see
+        ``batched.forecast_batched``), on torch's current stream.  ``out``: optional dict with preallocated ``states`` / ``covs``
+        / ``observed`` / ``observed_covs``.  Returns that dict (entries not requested are None); asynchronous."""
+        nb, m, k = self._dyn_TR(T, R)
+        self._chk(a0, (nb, m))
+        self._chk(P0, (nb, m, m) if P0 is not None else None)
+        if covariances not in ("diag", "full", None):
+            raise ValueError('covariances must be "diag", "full" or None')
+        qm = self._q_layout(Q, q_mode, nb, k)
+        p, zb, db, hb = 0, 0, 0, 0
+        if Z is not None:
+            p = self._chk(Z).shape[-2]
+            zb = self._dyn_flag(Z, nb, (p, m), "Z")
+            db = 0 if d is None else self._dyn_flag(d, nb, (p,), "d")
+            hb = 0 if Hdiag is None else self._dyn_flag(Hdiag, nb, (p,), "Hdiag")
+        elif d is not None or Hdiag is not None:
+            raise ValueError("d and Hdiag need Z")
+        n_steps = int(n_steps)
+        cov, full = covariances is not None, covariances == "full"
+        out = out or {}
+        res = dict(states=self._dyn_out(out.get("states"), (nb, n_steps, m)),
+                   covs=self._dyn_out(out.get("covs"), (nb, n_steps, m, m) if full else (nb, n_steps, m)) if cov else None,
+                   observed=self._dyn_out(out.get("observed"), (nb, n_steps, p)) if p else None,
+                   observed_covs=self._dyn_out(out.get("observed_covs"), (nb, n_steps, p, p)) if p and cov else None)
+        _lib.check(self.lib.dsge_forecast_batched(
+            self._p(T), self._p(R), self._p(Q), qm, self._p(Z), zb, self._p(d), db, self._p(Hdiag), hb, self._p(a0), self._p(P0),
+            self._dyn_status(status, nb), nb, m, k, p, n_steps, self._p(res["states"]), self._p(res["covs"]), int(full),
+            self._p(res["observed"]), self._p(res["observed_covs"]), self._stream()))
+        return res
 
     def solve_kalman_logp_grad(self, A, B, C, D, q, Z, y, d=None, Hdiag=None, solver="cycle_reduction", tol=1e-6, max_iter=50,
                                jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, n_filter_hint=0, n_lead_hint=0,

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 10
+#define DSGE_ABI_VERSION 11
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -46,6 +46,7 @@ extern "C" {
  * tests (coincident zeros, rank of Q2 Pi; gEconpy/solvers/gensys.py:243, 276-283) provably pass -- a draw with an equation scaled
  * by <= ~tol now gets the ordered QZ's verdict instead of eu = [1, 1, 0]. */
 /* ABI 10: dsge_kalman_smoother_batched (+ _host) and the status bit DSGE_ST_SMOOTHER_SINGULAR are new; nothing else changed. */
+/* ABI 11: dsge_simulate_batched, dsge_irf_batched, dsge_forecast_batched (+ _host) are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -695,6 +696,65 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
                                       int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
                                       double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
                                       double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io);
+
+/*
+ * POST-SOLVE DYNAMICS per draw (ABI 11; csrc/dsge_dynamics.hpp, docs/design/dynamics.md): what the reference runs on every retained
+ * draw after the solve, all of it the recursion x_t = T x_{t-1} + R e_t (gEconpy/model/simulate.py: _simulate_linear_system,
+ * simulate, impulse_response_function; the `forecast` of the pymc_extras state-space model that DSGEStateSpace extends).  T:
+ * [batch][m][m], R: [batch][m][k] as the solver entries return them; a *_batched flag of 0 means one shared array for all draws.
+ *   status : [batch], INPUT, may be NULL; a draw with a non-zero status gets NaN in all its outputs and does not affect the others
+ *
+ * dsge_simulate_batched:  x[b,s,t,:] = T_b x[b,s,t-1,:] + R_b eps[b,s,t,:],  t = 0 .. n_steps-1,  x[b,s,-1,:] = x0
+ *   eps   : [batch|1][n_paths][n_shock_steps][k], n_shock_steps <= n_steps (steps at or beyond it have e_t = 0); the caller draws
+ *           the shocks -- there is no device RNG, a seed stays the caller's business; may be NULL with n_shock_steps == 0
+ *   x0    : [batch|1][n_paths][m] or NULL for zero (then x[.,.,0,:] = R e_0, the reference's convention)
+ *   x_out : [batch][n_paths][n_steps][m], the reference's (simulation | shock, time, variable) order
+ * m <= DSGE_MAX_N_BIG (96), else DSGE_ERR_TOO_LARGE; [T | R] must fit the LDS (m = 96: k <= 32), else DSGE_ERR_TOO_LARGE.
+ * batch == 0, n_paths == 0 or n_steps == 0: success, nothing touched.
+ *
+ * dsge_irf_batched:  irf_out[b,j,h,:] = T_b^h R_b S[:, j],  h = 0 .. n_steps-1 -- the same kernel entered with one-period impulses
+ *   S        : [batch|1][k][c], impulse j is its column j; NULL: S = I_k, c must equal k, nothing is read.  Every deterministic
+ *              mode of impulse_response_function: shock_size (scalar, array, dict) S = diag(s); return_individual_shocks=False
+ *              c = 1, S = s; orthogonalised shock_cov S = chol(Q); a randomly drawn impulse is the caller's S
+ *   irf_out  : [batch][c][n_steps][m], may be NULL when only fevd_out is wanted
+ *   fevd_out : [batch][n_steps][m][c] or NULL (at least one of the two), the forecast-error variance decomposition with respect
+ *              to these impulses (an extension: the reference has none),
+ *                  fevd[b,h,i,j] = w_j sum_{s<=h} irf[b,j,s,i]^2 / sum_j' w_j' sum_{s<=h} irf[b,j',s,i]^2;
+ *              a zero denominator gives NaN in that (h, i, :) row.  c <= 16: accumulated on chip by the same launch; c > 16: a
+ *              second pass over the stored responses (library scratch of batch c n_steps m doubles when irf_out is NULL)
+ *   weights  : [batch|1][c] or NULL for ones (structural shocks with diagonal Q: S = I, w = q)
+ * Sizes as dsge_simulate_batched; c == 0: success, nothing touched.
+ *
+ * dsge_forecast_batched:  the moment recursion from a starting distribution, h = 1 .. n_steps (output index h-1),
+ *       a_h = T a_{h-1};   P_h = sym(T P_{h-1} T') + sym(R Q R');   y_h = Z a_h + d;   F_h = sym(Z P_h Z') + diag(H)
+ *   -- the filter's own prediction step: one step from (a_filt[t], P_filt[t]) of dsge_kalman_filter_outputs_batched reproduces
+ *   (a_pred[t+1], P_pred[t+1]).  T .. h_batched as there (Z may be NULL with p == 0; Q may be NULL when neither p_out nor f_out
+ *   is requested), plus
+ *   a0 : [batch][m]      P0 : [batch][m][m] or NULL for zero (a forecast conditional on a known state)
+ *   a_out : [batch][n_steps][m]      p_out : [batch][n_steps][m] diagonals, or [..][m][m] with full_cov != 0
+ *   y_out : [batch][n_steps][p]      f_out : [batch][n_steps][p][p]
+ *   each output may be NULL, at least one must be given; without p_out and f_out the covariance recursion is skipped
+ * m <= DSGE_MAX_N (64) and p <= DSGE_MAX_P, else DSGE_ERR_TOO_LARGE.  batch == 0 or n_steps == 0: success, nothing touched.
+ */
+int dsge_simulate_batched(const double* T, const double* R, const double* eps, int eps_batched, const double* x0, int x0_batched,
+                          const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps,
+                          double* x_out, void* stream);
+int dsge_simulate_batched_host(const double* T, const double* R, const double* eps, int eps_batched, const double* x0,
+                               int x0_batched, const int32_t* status, int batch, int m, int k, int n_paths, int n_steps,
+                               int n_shock_steps, double* x_out);
+int dsge_irf_batched(const double* T, const double* R, const double* S, int s_batched, const double* weights, int w_batched,
+                     const int32_t* status, int batch, int m, int k, int c, int n_steps, double* irf_out, double* fevd_out,
+                     void* stream);
+int dsge_irf_batched_host(const double* T, const double* R, const double* S, int s_batched, const double* weights, int w_batched,
+                          const int32_t* status, int batch, int m, int k, int c, int n_steps, double* irf_out, double* fevd_out);
+int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
+                          const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,
+                          int full_cov, double* y_out, double* f_out, void* stream);
+int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                               const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                               const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,
+                               double* p_out, int full_cov, double* y_out, double* f_out);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw

@@ -1,0 +1,105 @@
+"""GPU box: wall time (device events) of the post-solve dynamics entries on the SW-shaped workload (m = 40, k = 7, 40 steps).
+
+    python tools/dynamics_time.py [draws ...]          (default: 256 4096)
+
+Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
+  * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
+    plain device fill (torch's fill_) of an array the size of its output, timed in the same run -- the yardstick: the kernel
+    writes each output byte once and reads almost nothing; the implied write rate is printed next to both;
+  * the impulse responses with the on-chip FEVD;
+  * LogpEngine.forecast with full covariances (p = 0) against dsge_kalman_filter_outputs_batched with full covariances at
+    T_len = 40 on the same draws -- per step the forecast does that kernel's two covariance products and none of its update;
+  * the same two jobs as a host numpy loop over the draws (tests' restatement), for the CPU comparison.
+Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import oracle
+from geconpy_amd import _lib, workloads as wl
+from geconpy_amd.engine import LogpEngine
+from tests import dynamics_reference as dr
+
+N_STEPS = 40
+
+
+def timed(fn, min_seconds=1.0):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    reps, total = 0, 0.0
+    while total < min_seconds:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(4):
+            fn()
+        e1.record()
+        e1.synchronize()
+        total += e0.elapsed_time(e1) * 1e-3
+        reps += 4
+    return total / reps * 1e3  # ms per call
+
+
+def main():
+    sizes = [int(a) for a in sys.argv[1:]] or [256, 4096]
+    eng = LogpEngine(0)
+    lib = _lib.load()
+    b = wl.sw_shaped_batch(64)
+    om = wl.sw_shaped_observation_model()
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p = 40, 7, om["y"].shape[1]
+    Z, y, H = eng.to_device(om["Z"]), eng.to_device(om["y"][:N_STEPS]), eng.to_device(om["Hdiag"])
+    rng = np.random.default_rng(0)
+    print(f"SW shape m={m} k={k}, {N_STEPS} steps")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        Th, Rh, qh = np.tile(b["T_star"], (rep, 1, 1))[:nb], np.tile(R64, (rep, 1, 1))[:nb], np.tile(b["sigma"] ** 2, (rep, 1))[:nb]
+        T, R, q = eng.to_device(Th), eng.to_device(Rh), eng.to_device(qh)
+        mk = lambda *s: torch.empty(s, dtype=torch.float64, device=eng.device)  # noqa: E731
+        irf, fevd, paths = mk(nb, k, N_STEPS, m), mk(nb, N_STEPS, m, k), mk(nb, 16, N_STEPS, m)
+        eps = eng.to_device(rng.standard_normal((nb, 16, N_STEPS, k)))
+        a0, P0 = eng.to_device(rng.normal(0, 0.01, (nb, m))), eng.to_device(np.tile(1e-4 * np.eye(m), (nb, 1, 1)))
+        fc = dict(states=mk(nb, N_STEPS, m), covs=mk(nb, N_STEPS, m, m))
+        ll, ap, af, pp, pf = mk(nb, N_STEPS), mk(nb, N_STEPS, m), mk(nb, N_STEPS, m), mk(nb, N_STEPS, m, m), mk(nb, N_STEPS, m, m)
+        st = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+
+        def filter_outputs():
+            _lib.check(lib.dsge_kalman_filter_outputs_batched(
+                T.data_ptr(), R.data_ptr(), q.data_ptr(), 1, Z.data_ptr(), 0, None, 0, H.data_ptr(), 0, y.data_ptr(), nb, m, k, p,
+                N_STEPS, 1e-8, -9999.0, ll.data_ptr(), ap.data_ptr(), af.data_ptr(), pp.data_ptr(), pf.data_ptr(), 1, st.data_ptr(),
+                eng._stream()))
+
+        t_irf = timed(lambda: eng.impulse_response(T, R, n_steps=N_STEPS, out=dict(irf=irf)))
+        t_irf_fill = timed(lambda: irf.fill_(1.0))
+        t_fevd = timed(lambda: eng.impulse_response(T, R, n_steps=N_STEPS, weights=q, fevd=True, out=dict(irf=irf, fevd=fevd)))
+        t_sim = timed(lambda: eng.simulate(T, R, eps, out=paths))
+        t_sim_fill = timed(lambda: paths.fill_(1.0))
+        t_fc = timed(lambda: eng.forecast(T, R, q, a0, P0, n_steps=N_STEPS, covariances="full", q_mode=1, out=fc))
+        t_ko = timed(filter_outputs)
+        assert int(st.abs().max().item()) == 0
+        for name, t, tf, out in (("impulse responses", t_irf, t_irf_fill, irf), ("simulate, 16 paths", t_sim, t_sim_fill, paths)):
+            gb = out.numel() * 8e-9
+            print(f"draws={nb:5d} {name:20s}: {t:8.3f} ms = {gb / t:6.2f} TB/s written | fill {tf:8.3f} ms = {gb / tf:6.2f} TB/s | "
+                  f"ratio {t / tf:5.2f}")
+        print(f"draws={nb:5d} impulse responses + FEVD: {t_fevd:8.3f} ms")
+        print(f"draws={nb:5d} forecast, full covs : {t_fc:8.3f} ms | filter outputs, full covs, T_len={N_STEPS}: {t_ko:8.3f} ms | "
+              f"ratio {t_fc / t_ko:5.2f}")
+        nc = min(nb, 256)  # host numpy loop over (a sample of) the draws, scaled to the batch
+        t0 = time.perf_counter()
+        for i in range(nc):
+            dr.impulse_responses(Th[i], Rh[i], N_STEPS)
+        t_cpu_irf = (time.perf_counter() - t0) / nc * nb * 1e3
+        t0 = time.perf_counter()
+        for i in range(nc):
+            dr.forecast(Th[i], Rh[i], qh[i], np.zeros(m), 1e-4 * np.eye(m), N_STEPS)
+        t_cpu_fc = (time.perf_counter() - t0) / nc * nb * 1e3
+        print(f"draws={nb:5d} host numpy loop ({nc} draws timed, scaled): impulse responses {t_cpu_irf:9.1f} ms ({t_cpu_irf / t_irf:7.0f}x), "
+              f"forecast {t_cpu_fc:9.1f} ms ({t_cpu_fc / t_fc:7.0f}x)")
+
+
+if __name__ == "__main__":
+    main()
