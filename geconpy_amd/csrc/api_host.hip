@@ -82,6 +82,22 @@ class HostCall {
     declare(dev, dev, nullptr, nullptr, count * sizeof(T));
   }
 
+  // The observation model / the shock covariance of a filter call on `batch` draws of a model with m variables / k shocks: the host
+  // arrays of `host` as inputs, *dev the same description with the device addresses after stage().  upload = false: a per-draw
+  // member gets its space only (the caller uploads it chunk by chunk).
+  void in(ObsModel* dev, const ObsModel& host, int batch, int m, bool upload = true) {
+    *dev = host;
+    const size_t b = (size_t)batch, p = (size_t)host.p;
+    member(&dev->Z, host.Z, (host.z_batched ? b : 1) * p * m, upload || !host.z_batched);
+    member(&dev->d, host.d, (host.d_batched ? b : 1) * p, upload || !host.d_batched);
+    member(&dev->Hdiag, host.Hdiag, (host.h_batched ? b : 1) * p, upload || !host.h_batched);
+    in(&dev->y, host.y, (size_t)host.T_len * p);
+  }
+  void in(ShockCov* dev, const ShockCov& host, int batch, int k, bool upload = true) {
+    *dev = host;
+    member(&dev->Q, host.Q, host.elems(batch, k), upload || !host.batched());
+  }
+
   // Ends the declarations: leases an arena that holds every declared buffer (each rounded up to 256 bytes), assigns the
   // addresses in declaration order and enqueues the uploads on stream 0.
   int stage() {
@@ -127,6 +143,9 @@ class HostCall {
   static constexpr size_t TAIL_PAD = 16384;
   static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+  void member(const double** dev, const double* host, size_t count, bool upload) {
+    declare(dev, host, upload ? host : nullptr, nullptr, count * sizeof(double));
+  }
   template <typename P>
   void declare(P** dev, const void* present, const void* up, void* down, size_t bytes) {
     *dev = nullptr;
@@ -202,52 +221,45 @@ int grad_host(const double* A, const double* B, const double* C, const double* D
               double missing_fill, int n_filter_hint, int n_lead_hint, double* logp_out, int32_t* status_out, double* A_bar,
               double* B_bar, double* C_bar, double* D_bar, double* q_bar, double* d_bar, double* h_bar, bool dense_z,
               double* Z_bar) {
-  int rc = check_common(batch, n, 56);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov qc{q, q_batched};
+  int rc = check_grad(batch, n, k, obs, qc, solver, dense_z,
+                      A && B && C && D && logp_out && status_out && A_bar && B_bar && C_bar && D_bar && q_bar);
   if (rc) return rc;
-  if (dense_z && n + p > 56)
-    return fail(DSGE_ERR_INVALID, "gradient path with a dense design matrix: n + p must not exceed 56");
-  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0) return fail(DSGE_ERR_INVALID, "bad sizes");
-  if (!A || !B || !C || !D || !q || !Z || !y || !logp_out || !status_out || !A_bar || !B_bar || !C_bar || !D_bar || !q_bar)
-    return fail(DSGE_ERR_INVALID, "null pointer");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  if (q_batched < 0 || q_batched > 3) return fail(DSGE_ERR_INVALID, "gradient path: q_batched is a DSGE_Q_* mode (0..3)");
-  const size_t qstride = (q_batched >= 2) ? (size_t)k * k : (size_t)k;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = (size_t)((q_batched & 1) ? batch : 1) * qstride;
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, bp = (size_t)batch * p;
-  const double *dA, *dB, *dC, *dD, *dq, *dZ, *dd, *dH, *dy;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, bp = (size_t)batch * p;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dA, *dB, *dC, *dD;
   double *dL, *gA, *gB, *gC, *gD, *gq, *gd, *gh, *gZ;
   int32_t* dS;
   hc.in(&dA, A, nn);
   hc.in(&dB, B, nn);
   hc.in(&dC, C, nn);
   hc.in(&dD, D, nk);
-  hc.in(&dq, q, nq);
-  hc.in(&dZ, Z, nz);
-  hc.in(&dd, d, nd);
-  hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, qc, batch, k);
+  hc.in(&dobs, obs, batch, n);
   hc.out(&dL, logp_out, batch);
   hc.out(&dS, status_out, batch);
   hc.out(&gA, A_bar, nn);
   hc.out(&gB, B_bar, nn);
   hc.out(&gC, C_bar, nn);
   hc.out(&gD, D_bar, nk);
-  hc.out(&gq, q_bar, (size_t)batch * qstride);
+  hc.out(&gq, q_bar, (size_t)batch * qc.elems(1, k));
   hc.out(&gd, d_bar, bp);
   hc.out(&gh, h_bar, bp);
   hc.out(&gZ, dense_z ? Z_bar : nullptr, (size_t)batch * p * n);
   if ((rc = hc.stage())) return rc;
-  rc = dense_z ? dsge_solve_kalman_logp_grad_dense_z_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH,
-                                                             h_batched, dy, batch, n, k, p, T_len, solver, tol, max_iter,
-                                                             jitter, missing_fill, n_filter_hint, n_lead_hint, dL, dS, gA, gB,
+  rc = dense_z ? dsge_solve_kalman_logp_grad_dense_z_batched(dA, dB, dC, dD, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d,
+                                                             dobs.d_batched, dobs.Hdiag, dobs.h_batched, dobs.y, batch, n, k, p, T_len, solver, tol,
+                                                             max_iter, jitter, missing_fill, n_filter_hint, n_lead_hint, dL, dS, gA, gB,
                                                              gC, gD, gq, gd, gh, gZ, hc.stream())
-               : dsge_solve_kalman_logp_grad_batched(dA, dB, dC, dD, dq, q_batched, dZ, z_batched, dd, d_batched, dH, h_batched,
-                                                     dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
-                                                     n_filter_hint, n_lead_hint, dL, dS, gA, gB, gC, gD, gq, gd, gh,
-                                                     hc.stream());
+               : dsge_solve_kalman_logp_grad_batched(dA, dB, dC, dD, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched,
+                                                     dobs.Hdiag, dobs.h_batched, dobs.y, batch, n, k, p, T_len, solver, tol,
+                                                     max_iter, jitter, missing_fill, n_filter_hint, n_lead_hint, dL, dS, gA, gB, gC, gD, gq,
+                                                     gd, gh, hc.stream());
   if (rc) return rc;
   return hc.finish();
 }
@@ -455,26 +467,18 @@ int dsge_second_order_logp_batched_host(const double* A, const double* B, const 
                                         const int32_t* lead_idx, int n_lead, const int32_t* ret_idx, int n_ret,
                                         double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* gyy_out,
                                         double* gyu_out, double* guu_out, double* gss_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N_CR);
+  const ObsModel obs{Z, 0, d, 0, Hdiag, 0, y, p, T_len, jitter, missing_fill};
+  const ShockCov qc{q, q_batched ? DSGE_Q_DIAG_BATCHED : DSGE_Q_DIAG_SHARED};
+  int rc = check_second_order(batch, n, k, obs, qc, solver, nnz, state_idx, n_state, lead_idx, n_lead, ret_idx, n_ret,
+                              A && B && C && D && (nnz == 0 || (hess_idx && hess_val)) && logp_out && status_out);
   if (rc) return rc;
-  if (k < 1 || k > n || p < 1 || p > 8 || T_len < 0 || nnz < 0 || n_state < 1 || n_state > 24)
-    return fail(DSGE_ERR_INVALID, "second order: size out of range");
-  if (!A || !B || !C || !D || (nnz > 0 && (!hess_idx || !hess_val)) || !q || !Z || !y || !logp_out || !status_out ||
-      !state_idx || !ret_idx || (n_lead > 0 && !lead_idx))
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  // the structure arguments are host arrays here as in the device entry point: validated BEFORE anything is staged
-  if (n_lead < 0 || n_lead > n || n_ret < n_state || n_ret > n) return fail(DSGE_ERR_INVALID, "second order: n_lead / n_ret out of range");
-  for (int i = 0; i < n_state; ++i)
-    if (state_idx[i] < 0 || state_idx[i] >= n) return fail(DSGE_ERR_INVALID, "state_idx out of range");
-  for (int i = 0; i < n_lead; ++i)
-    if (lead_idx[i] < 0 || lead_idx[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
-  for (int i = 0; i < n_ret; ++i)
-    if (ret_idx[i] < 0 || ret_idx[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nv = (size_t)batch * nnz, ss = (size_t)n_state * n_state;
-  const double *dA, *dB, *dC, *dD, *dHv, *dq, *dZ, *dd, *dH, *dy;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dA, *dB, *dC, *dD, *dHv;
   const int32_t* dHi;
   double *dlp, *dT, *dR, *dgyy, *dgyu, *dguu, *dgss;
   int32_t* dst;
@@ -484,11 +488,8 @@ int dsge_second_order_logp_batched_host(const double* A, const double* B, const 
   hc.in(&dD, D, nk);
   hc.in(&dHi, hess_idx, (size_t)nnz * 3);
   hc.in(&dHv, hess_val, nv);
-  hc.in(&dq, q, q_batched ? (size_t)batch * k : (size_t)k);
-  hc.in(&dZ, Z, (size_t)p * n);
-  hc.in(&dd, d, p);
-  hc.in(&dH, Hdiag, p);
-  hc.in(&dy, y, (size_t)T_len * p);
+  hc.in(&dq, qc, batch, k);
+  hc.in(&dobs, obs, batch, n);
   hc.out(&dlp, logp_out, batch);
   hc.out(&dst, status_out, batch);
   hc.out(&dT, T_out, nn);
@@ -498,7 +499,7 @@ int dsge_second_order_logp_batched_host(const double* A, const double* B, const 
   hc.out(&dguu, guu_out, (size_t)batch * n * k * k);
   hc.out(&dgss, gss_out, (size_t)batch * n);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_second_order_logp_batched(dA, dB, dC, dD, dHi, nnz, dHv, dq, q_batched, dZ, dd, dH, dy, batch, n, k, p, T_len,
+  if ((rc = dsge_second_order_logp_batched(dA, dB, dC, dD, dHi, nnz, dHv, dq.Q, q_batched, dobs.Z, dobs.d, dobs.Hdiag, dobs.y, batch, n, k, p, T_len,
                                            solver, tol, max_iter, jitter, missing_fill, state_idx, n_state, lead_idx, n_lead,
                                            ret_idx, n_ret, dlp, dst, dT, dR, dgyy, dgyu, dguu, dgss, nullptr, hc.stream())))
     return rc;
@@ -510,28 +511,23 @@ int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, co
                                             const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                                             double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
                                             double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman(batch, m, k, obs, q, T && R && ll_out && status_io);
   if (rc) return rc;
-  if (k < 1 || k > m || p < 1 || p > DSGE_MAX_P || T_len < 0 || q_mode < 0 || q_mode > 3)
-    return fail(DSGE_ERR_INVALID, "size out of range");
-  if (!T || !R || !Q || !Z || !y || !ll_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, tm = (size_t)batch * T_len * m,
-               tc = full_cov ? tm * m : tm;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, tm = (size_t)batch * T_len * m, tc = full_cov ? tm * m : tm;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dT, *dR;
   double *dll, *dap, *daf, *dpp, *dpf;
   int32_t* dS;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, mk);
-  hc.in(&dQ, Q, nq);
-  hc.in(&dZ, Z, nz);
-  hc.in(&dd, d, nd);
-  hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
   hc.io(&dS, status_io, batch);
   hc.out(&dll, ll_out, (size_t)batch * T_len);
   hc.out(&dap, a_pred_out, tm);
@@ -539,8 +535,9 @@ int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, co
   hc.out(&dpp, p_pred_out, tc);
   hc.out(&dpf, p_filt_out, tc);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_filter_outputs_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k, p,
-                                               T_len, jitter, missing_fill, dll, dap, daf, dpp, dpf, full_cov, dS, hc.stream())))
+  if ((rc = dsge_kalman_filter_outputs_batched(dT, dR, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched, dobs.Hdiag,
+                                               dobs.h_batched, dobs.y, batch, m, k, p, T_len, jitter, missing_fill, dll, dap,
+                                               daf, dpp, dpf, full_cov, dS, hc.stream())))
     return rc;
   return hc.finish();
 }
@@ -550,36 +547,31 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
                                       int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
                                       double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
                                       double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_smoother(batch, m, k, obs, q, T && R && status_io, a_smooth_out || p_smooth_out || eps_smooth_out);
   if (rc) return rc;
-  if (k < 1 || k > m || p < 1 || p > DSGE_MAX_P || T_len < 0 || q_mode < 0 || q_mode > 3)
-    return fail(DSGE_ERR_INVALID, "size out of range");
-  if (!T || !R || !Q || !Z || !y || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (!a_smooth_out && !p_smooth_out && !eps_smooth_out) return fail(DSGE_ERR_INVALID, "no smoothed output requested");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p, tm = (size_t)batch * T_len * m,
-               tc = full_cov ? tm * m : tm;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, tm = (size_t)batch * T_len * m, tc = full_cov ? tm * m : tm;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dT, *dR;
   double *dll, *das, *dps, *des;
   int32_t* dS;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, mk);
-  hc.in(&dQ, Q, nq);
-  hc.in(&dZ, Z, nz);
-  hc.in(&dd, d, nd);
-  hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
   hc.io(&dS, status_io, batch);
   hc.out(&dll, ll_out, (size_t)batch * T_len);
   hc.out(&das, a_smooth_out, tm);
   hc.out(&dps, p_smooth_out, tc);
   hc.out(&des, eps_smooth_out, (size_t)batch * T_len * k);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_smoother_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k, p, T_len,
+  if ((rc = dsge_kalman_smoother_batched(dT, dR, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched, dobs.Hdiag,
+                                         dobs.h_batched, dobs.y, batch, m, k, p, T_len,
                                          jitter, missing_fill, rank_tol, scratch_limit_bytes, dll, das, dps, des, full_cov, dS,
                                          hc.stream())))
     return rc;
@@ -637,21 +629,23 @@ int dsge_forecast_batched_host(const double* T, const double* R, const double* Q
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,
                                double* p_out, int full_cov, double* y_out, double* f_out) {
-  int rc = check_forecast(T, R, Q, q_mode, Z, a0, batch, m, k, p, n_steps, a_out, p_out, y_out, f_out);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, nullptr, p, 0, 0.0, 0.0};  // (no panel: the moments only)
+  const ShockCov q{Q, q_mode};
+  int rc = check_forecast(T, R, q, obs, a0, batch, m, k, n_steps, a_out, p_out, y_out, f_out);
   if (rc) return rc;
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0 || n_steps == 0) return DSGE_SUCCESS;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dT, *dR, *da0, *dP0;
   const int32_t* dS;
   double *da, *dp, *dy, *df;
   const size_t mm = (size_t)batch * m * m, tm = (size_t)batch * n_steps * m;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, (size_t)batch * m * k);
-  hc.in(&dQ, Q, q_elems(q_mode, batch, k));
-  hc.in(&dZ, Z, (size_t)(z_batched ? batch : 1) * p * m);
-  hc.in(&dd, d, (size_t)(d_batched ? batch : 1) * p);
-  hc.in(&dH, Hdiag, (size_t)(h_batched ? batch : 1) * p);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
   hc.in(&da0, a0, (size_t)batch * m);
   hc.in(&dP0, P0, mm);
   hc.in(&dS, status, (size_t)batch);
@@ -660,8 +654,9 @@ int dsge_forecast_batched_host(const double* T, const double* R, const double* Q
   hc.out(&dy, y_out, (size_t)batch * n_steps * p);
   hc.out(&df, f_out, (size_t)batch * n_steps * p * p);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_forecast_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dS, batch, m, k, p,
-                                  n_steps, da, dp, full_cov, dy, df, hc.stream())))
+  if ((rc = dsge_forecast_batched(dT, dR, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched, dobs.Hdiag,
+                                  dobs.h_batched, da0, dP0,
+                                  dS, batch, m, k, p, n_steps, da, dp, full_cov, dy, df, hc.stream())))
     return rc;
   return hc.finish();
 }
@@ -727,18 +722,19 @@ int dsge_lyapunov_batched_host(const double* T, const double* R, const double* Q
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const double *dT, *dR, *dQ;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
+  ShockCov dq;
+  const double *dT, *dR;
   double *dP, *dX;
   int32_t* dS;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, mk);
-  hc.in(&dQ, Q, nq);
+  hc.in(&dq, ShockCov{Q, q_mode}, batch, k);
   hc.out(&dP, P0_out, mm);
   hc.out(&dX, RQR_out, mm);
   hc.out(&dS, status, batch);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_lyapunov_batched(dT, dR, dQ, q_mode, batch, m, k, dP, dX, dS, hc.stream()))) return rc;
+  if ((rc = dsge_lyapunov_batched(dT, dR, dq.Q, dq.mode, batch, m, k, dP, dX, dS, hc.stream()))) return rc;
   return hc.finish();
 }
 
@@ -751,20 +747,18 @@ int dsge_solve_kalman_logp_augmented_batched_host(const double* A, const double*
                                                   const int32_t* link_cols, int n_state_hint, int z_selector_hint,
                                                   int n_lead_hint, double* logp_out, int32_t* status_out,
                                                   double* T_aug_out, double* R_aug_out, double* resid_out) {
-  int rc = check_common(batch, n, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_augmented(batch, n, k, obs, q, solver, m, n_links,
+                           A && B && C && D && logp_out && status_out && (n_links == 0 || (link_rows && link_cols)));
   if (rc) return rc;
-  if (m < n || m > DSGE_MAX_N_BIG || k < 1 || k > n || p < 1 || p > DSGE_MAX_P || T_len < 0 || n_links < 0)
-    return fail(DSGE_ERR_INVALID, "bad sizes");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
-  const double *dA, *dB, *dC, *dD, *dQ, *dZ, *dd, *dH, *dy;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dA, *dB, *dC, *dD;
   const int32_t *dinv, *dlr, *dlc;
   double *dL, *dTa, *dRa, *dRes;
   int32_t* dS;
@@ -772,11 +766,8 @@ int dsge_solve_kalman_logp_augmented_batched_host(const double* A, const double*
   hc.in(&dB, B, nn);
   hc.in(&dC, C, nn);
   hc.in(&dD, D, nk);
-  hc.in(&dQ, Q, nq);
-  hc.in(&dZ, Z, nz);
-  hc.in(&dd, d, nd);
-  hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
   hc.in(&dinv, inv_var_order, n);
   hc.in(&dlr, link_rows, n_links);
   hc.in(&dlc, link_cols, n_links);
@@ -786,8 +777,8 @@ int dsge_solve_kalman_logp_augmented_batched_host(const double* A, const double*
   hc.out(&dRa, R_aug_out, mk);
   hc.out(&dRes, resid_out, batch);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_solve_kalman_logp_augmented_batched(dA, dB, dC, dD, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched,
-                                                     dy, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
+  if ((rc = dsge_solve_kalman_logp_augmented_batched(dA, dB, dC, dD, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched,
+                                                     dobs.Hdiag, dobs.h_batched, dobs.y, batch, n, k, p, T_len, solver, tol, max_iter, jitter, missing_fill,
                                                      m, dinv, n_links, dlr, dlc, n_state_hint, z_selector_hint, n_lead_hint,
                                                      dL, dS, dTa, dRa, dRes, hc.stream())))
     return rc;
@@ -835,14 +826,15 @@ int dsge_autocorrelation_batched_host(const double* T, const double* R, const do
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   const int dim = Z ? p : m;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
   const size_t no = (size_t)batch * (n_lags + 1) * dim * dim;
-  const double *dT, *dR, *dQ, *dZ, *dH;
+  ShockCov dq;
+  const double *dT, *dR, *dZ, *dH;
   double *dSig, *dO;
   int32_t* dS;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, mk);
-  hc.in(&dQ, Q, nq);
+  hc.in(&dq, ShockCov{Q, q_mode}, batch, k);
   hc.in(&dZ, Z, (size_t)p * m);
   hc.in(&dH, Hdiag, p);
   if (Sigma_out)  // (the device entry always writes the state covariance)
@@ -852,7 +844,7 @@ int dsge_autocorrelation_batched_host(const double* T, const double* R, const do
   hc.out(&dO, acf_out, no);
   hc.out(&dS, status, batch);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_autocorrelation_batched(dT, dR, dQ, q_mode, dZ, dH, batch, m, k, p, n_lags, lag_step, correlation, dO,
+  if ((rc = dsge_autocorrelation_batched(dT, dR, dq.Q, dq.mode, dZ, dH, batch, m, k, p, n_lags, lag_step, correlation, dO,
                                          dSig, dS, hc.stream())))
     return rc;
   return hc.finish();
@@ -863,34 +855,28 @@ int dsge_kalman_logp_batched_host(const double* T, const double* R, const double
                                   const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                                   double missing_fill, int n_state_hint, int z_selector_hint, double* logp_out,
                                   int32_t* status_io) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman(batch, m, k, obs, q, T && R && logp_out && status_io);
   if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !Z || !y || !logp_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * m, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *dy;
+  const size_t mm = (size_t)batch * m * m, mk = (size_t)batch * m * k;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dT, *dR;
   double* dL;
   int32_t* dS;
   hc.in(&dT, T, mm);
   hc.in(&dR, R, mk);
-  hc.in(&dQ, Q, nq);
-  hc.in(&dZ, Z, nz);
-  hc.in(&dd, d, nd);
-  hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
   hc.io(&dS, status_io, batch);
   hc.out(&dL, logp_out, batch);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_logp_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, dy, batch, m, k,
-                                     p, T_len, jitter, missing_fill, n_state_hint, z_selector_hint, dL, dS, hc.stream())))
+  if ((rc = dsge_kalman_logp_batched(dT, dR, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched, dobs.Hdiag,
+                                     dobs.h_batched, dobs.y, batch, m, k, p, T_len, jitter, missing_fill, n_state_hint, z_selector_hint, dL, dS, hc.stream())))
     return rc;
   return hc.finish();
 }
@@ -902,41 +888,29 @@ int dsge_solve_kalman_logp_batched_host(const double* A, const double* B, const 
                                         double jitter, double missing_fill, int n_state_hint, int z_selector_hint,
                                         int n_lead_hint, double* logp_out, int32_t* status_out, double* T_out,
                                         double* R_out, double* resid_out, int32_t* n_iter_out) {
-  const int solver_code = solver & ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
-  int rc = check_common(batch, n, (solver_code == DSGE_SOLVER_CYCLE_REDUCTION || solver_code == DSGE_SOLVER_SCAN_CYCLE_REDUCTION ||
-                                   (solver_code == DSGE_SOLVER_GENSYS && opt().gensys_doubling != 0))
-                                      ? DSGE_MAX_N_BIG
-                                      : DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_pipeline(batch, n, k, obs, q, solver, A && B && C && D && logp_out && status_out);
   if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
-  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k, nq = q_elems(q_mode, batch, k);
-  const size_t nz = (size_t)(z_batched ? batch : 1) * p * n, nd = (size_t)(d_batched ? batch : 1) * p,
-               nh = (size_t)(h_batched ? batch : 1) * p, ny = (size_t)T_len * p;
+  const size_t nn = (size_t)batch * n * n, nk = (size_t)batch * n * k;
   // Shared inputs first (stream 0, by stage()), then the batch in chunks on two streams: while the kernels of chunk c run,
   // the host stages chunk c+1 (pageable memory: hipMemcpyAsync returns once the runtime has staged the buffer), so
   // the PCIe transfer of the Jacobians overlaps the compute.  Outputs come back in one go at the end.
-  const bool q_b = (q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED);
-  const bool d_b = d && d_batched, h_b = Hdiag && h_batched;
   // (per draw: space only, uploaded chunk by chunk below -- as are Q, Z, d, Hdiag when they are batched)
-  const double *dA, *dB, *dC, *dD, *dQ, *dZ, *dd, *dH, *dy;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dA, *dB, *dC, *dD;
   double *dL, *dT, *dR, *dRes;
   int32_t *dS, *dI;
   hc.space(&dA, nn);
   hc.space(&dB, nn);
   hc.space(&dC, nn);
   hc.space(&dD, nk);
-  q_b ? hc.space(&dQ, nq) : hc.in(&dQ, Q, nq);
-  z_batched ? hc.space(&dZ, nz) : hc.in(&dZ, Z, nz);
-  d_b ? hc.space(&dd, nd) : hc.in(&dd, d, nd);
-  h_b ? hc.space(&dH, nh) : hc.in(&dH, Hdiag, nh);
-  hc.in(&dy, y, ny);
+  hc.in(&dq, q, batch, k, false);
+  hc.in(&dobs, obs, batch, n, false);
   hc.out(&dL, logp_out, batch);
   hc.out(&dS, status_out, batch);
   hc.out(&dT, T_out, nn);
@@ -947,13 +921,14 @@ int dsge_solve_kalman_logp_batched_host(const double* A, const double* B, const 
   HIP_TRY(hipStreamSynchronize(hc.stream(0)));
   const int n_chunks = (batch >= 2048) ? 4 : (batch >= 512 ? 2 : 1);
   const int per = (batch + n_chunks - 1) / n_chunks;
-  const size_t qk = (q_mode == DSGE_Q_FULL_BATCHED) ? (size_t)k * k : (size_t)k;
   for (int c = 0; c < n_chunks; ++c) {
     const int c0 = c * per;
     const int nb = (batch - c0 < per) ? batch - c0 : per;
     if (nb <= 0) break;
     hipStream_t st = hc.stream(c & 1);
-    const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k, oq = c0 * qk, oz = (size_t)c0 * p * n, op = (size_t)c0 * p;
+    const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k;
+    const ObsModel ho = obs.at(c0, n), dc = dobs.at(c0, n);  // the chunk's slice, on the host and on the device
+    const ShockCov hq = q.at(c0, k), dqc = dq.at(c0, k);
     auto up = [st](const double* dev, const double* host, size_t count) {  // a slice of a space-only buffer
       return hipMemcpyAsync(const_cast<double*>(dev), host, count * sizeof(double), hipMemcpyHostToDevice, st);
     };
@@ -961,15 +936,13 @@ int dsge_solve_kalman_logp_batched_host(const double* A, const double* B, const 
     HIP_TRY(up(dB + o2, B + o2, (size_t)nb * n * n));
     HIP_TRY(up(dC + o2, C + o2, (size_t)nb * n * n));
     HIP_TRY(up(dD + ok, D + ok, (size_t)nb * n * k));
-    if (q_b) HIP_TRY(up(dQ + oq, Q + oq, (size_t)nb * qk));
-    if (z_batched) HIP_TRY(up(dZ + oz, Z + oz, (size_t)nb * p * n));
-    if (d_b) HIP_TRY(up(dd + op, d + op, (size_t)nb * p));
-    if (h_b) HIP_TRY(up(dH + op, Hdiag + op, (size_t)nb * p));
+    if (q.batched()) HIP_TRY(up(dqc.Q, hq.Q, q.elems(nb, k)));
+    if (z_batched) HIP_TRY(up(dc.Z, ho.Z, (size_t)nb * p * n));
+    if (d && d_batched) HIP_TRY(up(dc.d, ho.d, (size_t)nb * p));
+    if (Hdiag && h_batched) HIP_TRY(up(dc.Hdiag, ho.Hdiag, (size_t)nb * p));
     // (pipeline_unchunked, not the public entry: that one would chunk again under dsge_options.pipeline_chunks)
-    if ((rc = pipeline_unchunked(dA + o2, dB + o2, dC + o2, dD + ok, q_b ? dQ + oq : dQ, q_mode, z_batched ? dZ + oz : dZ,
-                                 z_batched, d_b ? dd + op : dd, d_batched, h_b ? dH + op : dH, h_batched, dy, nb, n, k, p,
-                                 T_len, solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
-                                 dL + c0, dS + c0, dT ? dT + o2 : nullptr, dR ? dR + ok : nullptr,
+    if ((rc = pipeline_unchunked(dA + o2, dB + o2, dC + o2, dD + ok, dqc, dc, nb, n, k, solver, tol, max_iter, n_state_hint,
+                                 z_selector_hint, n_lead_hint, dL + c0, dS + c0, dT ? dT + o2 : nullptr, dR ? dR + ok : nullptr,
                                  dRes ? dRes + c0 : nullptr, dI ? dI + c0 : nullptr, st, 1, nullptr)))
       return rc;
   }

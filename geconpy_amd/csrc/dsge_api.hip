@@ -272,24 +272,6 @@ StreamArenaPool g_scratch_pool;
 StreamArenaPool g_aug_big_pool;  // the gathered model of the augmented route beyond 64 states
 }  // namespace
 
-namespace dsge_host {
-int check_common(int batch, int n, int n_max) {
-  if (batch < 0) return fail(DSGE_ERR_INVALID, "batch < 0");
-  if (n < 1 || n > n_max) return fail(DSGE_ERR_INVALID, "n out of range (1.." + std::to_string(n_max) + ")");
-  return DSGE_SUCCESS;
-}
-
-size_t q_elems(int q_mode, int batch, int k) {
-  switch (q_mode) {
-    case DSGE_Q_DIAG_SHARED: return (size_t)k;
-    case DSGE_Q_DIAG_BATCHED: return (size_t)batch * k;
-    case DSGE_Q_FULL_SHARED: return (size_t)k * k;
-    case DSGE_Q_FULL_BATCHED: return (size_t)batch * k * k;
-    default: return 0;
-  }
-}
-}  // namespace dsge_host
-
 extern "C" {
 
 int dsge_abi_version(void) { return DSGE_ABI_VERSION; }
@@ -400,8 +382,7 @@ int dsge_gensys_batched(const double* A, const double* B, const double* C, const
                           R_out ? D : nullptr, k, R_out)))
     return rc;
   if (R_out)  // gensys_pt: R = -(C T + B)^-1 D  (gensys.py:681); computed for every draw, as the graph does
-    return launch_assemble(nullptr, B, C, D, T_out, nullptr, nullptr, 0, batch, n, k, R_out, nullptr, nullptr, nullptr,
-                           nullptr, 1, 0, (hipStream_t)stream);
+    return assemble_selection(nullptr, B, C, D, T_out, batch, n, k, R_out, nullptr, nullptr, (hipStream_t)stream);
   return DSGE_SUCCESS;
 }
 
@@ -451,8 +432,7 @@ int dsge_selection_batched(const double* A, const double* B, const double* C, co
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   if (big_size(n)) return launch_selection_big(A, B, C, D, T, batch, n, k, R_out, resid_out, nullptr, (hipStream_t)stream);
-  return launch_assemble(A, B, C, D, T, nullptr, nullptr, 0, batch, n, k, R_out, resid_out, nullptr, nullptr, nullptr,
-                         1, 0, (hipStream_t)stream);
+  return assemble_selection(A, B, C, D, T, batch, n, k, R_out, resid_out, nullptr, (hipStream_t)stream);
 }
 
 int dsge_policy_adjoints_batched(const double* B, const double* C, const double* T, const double* T_bar, int batch,
@@ -512,8 +492,7 @@ int dsge_lyapunov_batched(const double* T, const double* R, const double* Q, int
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
-  return launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, RQR_out,
-                         P0_out, status, 0, 1, (hipStream_t)stream);
+  return assemble_rqr_p0(T, R, ShockCov{Q, q_mode}, batch, m, k, RQR_out, P0_out, status, (hipStream_t)stream);
 }
 
 int dsge_autocorrelation_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
@@ -536,9 +515,7 @@ int dsge_autocorrelation_batched(const double* T, const double* R, const double*
     if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   }
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * batch, st));
-  if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, nullptr,
-                            Sigma, status, 0, 1, st)))
-    return rc;
+  if ((rc = assemble_rqr_p0(T, R, ShockCov{Q, q_mode}, batch, m, k, nullptr, Sigma, status, st))) return rc;
   return launch_acf(T, Sigma, Z, Hdiag, batch, m, p, n_lags, lag_step, correlation, acf_out, status, st);
 }
 
@@ -547,13 +524,10 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
                                        const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                                        double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
                                        double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io, void* stream) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman(batch, m, k, obs, q, T && R && ll_out && status_io);
   if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !Z || !y || !ll_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
@@ -563,11 +537,9 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
   lay.add(&RQR, mm);
   lay.add(&P0, mm);
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, RQR, P0,
-                            status_io, 0, 1, st)))
-    return rc;
-  return launch_kalman_outputs(T, RQR, P0, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, jitter,
-                               missing_fill, ll_out, a_pred_out, a_filt_out, p_pred_out, p_filt_out, full_cov, status_io, st);
+  if ((rc = assemble_rqr_p0(T, R, q, batch, m, k, RQR, P0, status_io, st))) return rc;
+  return launch_kalman_outputs(T, RQR, P0, obs, batch, m, ll_out, a_pred_out, a_filt_out, p_pred_out, p_filt_out, full_cov,
+                               status_io, st);
 }
 
 // Smoothed states, covariances and shocks (dsge_kalman_smooth.hpp): the forward pass is launch_kalman_outputs with full
@@ -577,14 +549,10 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
                                  int m, int k, int p, int T_len, double jitter, double missing_fill, double rank_tol,
                                  size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out, double* p_smooth_out,
                                  double* eps_smooth_out, int full_cov, int32_t* status_io, void* stream) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_smoother(batch, m, k, obs, q, T && R && status_io, a_smooth_out || p_smooth_out || eps_smooth_out);
   if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !Z || !y || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (!a_smooth_out && !p_smooth_out && !eps_smooth_out) return fail(DSGE_ERR_INVALID, "no smoothed output requested");
   if ((rc = ensure_device())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
@@ -611,21 +579,17 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   lay.add(&rank, (size_t)chunk);
   if (!ll_out) lay.add(&ll, (size_t)chunk * T_len);
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  const bool qb = q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED;
-  const size_t qs = qb ? q_elems(q_mode, 1, k) : 0, tc = full_cov ? tm * m : tm;
+  const size_t tc = full_cov ? tm * m : tm;
   for (int c0 = 0; c0 < batch; c0 += chunk) {
     const int nb = batch - c0 < chunk ? batch - c0 : chunk;
     const size_t o = (size_t)c0;
-    const double *Tc = T + o * m * m, *Rc = R + o * m * k, *Qc = Q + o * qs, *Zc = Z + (z_batched ? o * p * m : 0),
-                 *dc = d ? d + (d_batched ? o * p : 0) : nullptr, *Hc = Hdiag ? Hdiag + (h_batched ? o * p : 0) : nullptr;
+    const double *Tc = T + o * m * m, *Rc = R + o * m * k;
+    const ShockCov qc = q.at(o, k);
     int32_t* sc = status_io + o;
-    if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, Tc, Rc, Qc, q_mode, nb, m, k, nullptr, nullptr, RQR, P0, sc, 0, 1,
-                              st)))
+    if ((rc = assemble_rqr_p0(Tc, Rc, qc, nb, m, k, RQR, P0, sc, st))) return rc;
+    if ((rc = launch_kalman_outputs(Tc, RQR, P0, obs.at(o, m), nb, m, ll_out ? ll_out + o * T_len : ll, ap, af, pp, pf, 1, sc, st)))
       return rc;
-    if ((rc = launch_kalman_outputs(Tc, RQR, P0, Zc, z_batched, dc, d_batched, Hc, h_batched, y, nb, m, p, T_len, jitter,
-                                    missing_fill, ll_out ? ll_out + o * T_len : ll, ap, af, pp, pf, 1, sc, st)))
-      return rc;
-    if ((rc = launch_kalman_smoother(Tc, Rc, Qc, q_mode, nb, m, k, T_len, rank_tol, U, UT, UR, rank, ap, af, pp, pf,
+    if ((rc = launch_kalman_smoother(Tc, Rc, qc, nb, m, k, T_len, rank_tol, U, UT, UR, rank, ap, af, pp, pf,
                                      a_smooth_out ? a_smooth_out + o * tm : nullptr, p_smooth_out ? p_smooth_out + o * tc : nullptr,
                                      eps_smooth_out ? eps_smooth_out + o * T_len * k : nullptr, full_cov, sc, st)))
       return rc;
@@ -634,42 +598,6 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
 }
 
 // ---- post-solve dynamics (dsge_dynamics.hpp): simulate, impulse responses + FEVD, forecast -----------------------------------
-}  // extern "C"
-namespace dsge_host {
-int check_simulate(const double* T, const double* R, const double* eps, int batch, int m, int k, int n_paths, int n_steps,
-                   int n_shock_steps, const double* x_out) {
-  if (batch < 0 || m < 1 || n_paths < 0 || n_steps < 0 || n_shock_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (n_shock_steps > n_steps) return fail(DSGE_ERR_INVALID, "n_shock_steps > n_steps");
-  if (!T || !R || !x_out || (!eps && n_shock_steps > 0)) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "simulate: m exceeds DSGE_MAX_N_BIG");
-  return DSGE_SUCCESS;
-}
-int check_irf(const double* T, const double* R, const double* S, int batch, int m, int k, int c, int n_steps, const double* irf_out,
-              const double* fevd_out) {
-  if (batch < 0 || m < 1 || c < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (!S && c != k) return fail(DSGE_ERR_INVALID, "S == NULL means S = I: c must equal k");
-  if (!T || !R) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (!irf_out && !fevd_out) return fail(DSGE_ERR_INVALID, "no output requested");
-  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "impulse responses: m exceeds DSGE_MAX_N_BIG");
-  return DSGE_SUCCESS;
-}
-int check_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, const double* a0, int batch,
-                   int m, int k, int p, int n_steps, const double* a_out, const double* p_out, const double* y_out,
-                   const double* f_out) {
-  if (batch < 0 || m < 1 || p < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!a_out && !p_out && !y_out && !f_out) return fail(DSGE_ERR_INVALID, "no output requested");
-  if (!T || !R || !a0 || ((p_out || f_out) && !Q) || (p > 0 && !Z)) return fail(DSGE_ERR_INVALID, "null pointer");
-  if ((y_out || f_out) && p == 0) return fail(DSGE_ERR_INVALID, "observation outputs requested with p == 0");
-  if (m > DSGE_MAX_N || p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "forecast: m exceeds DSGE_MAX_N or p exceeds DSGE_MAX_P");
-  return DSGE_SUCCESS;
-}
-}  // namespace dsge_host
-extern "C" {
-
 int dsge_simulate_batched(const double* T, const double* R, const double* eps, int eps_batched, const double* x0, int x0_batched,
                           const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps,
                           double* x_out, void* stream) {
@@ -713,12 +641,14 @@ int dsge_forecast_batched(const double* T, const double* R, const double* Q, int
                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
                           const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,
                           int full_cov, double* y_out, double* f_out, void* stream) {
-  int rc = check_forecast(T, R, Q, q_mode, Z, a0, batch, m, k, p, n_steps, a_out, p_out, y_out, f_out);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, nullptr, p, 0, 0.0, 0.0};  // (no panel: the moments only)
+  const ShockCov q{Q, q_mode};
+  int rc = check_forecast(T, R, q, obs, a0, batch, m, k, n_steps, a_out, p_out, y_out, f_out);
   if (rc) return rc;
   if ((rc = ensure_device())) return rc;
   if (batch == 0 || n_steps == 0) return DSGE_SUCCESS;
-  return launch_forecast(T, R, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, a0, P0, status, batch, m, k, p, n_steps, a_out,
-                         p_out, full_cov, y_out, f_out, (hipStream_t)stream);
+  return launch_forecast(T, R, q, obs, a0, P0, status, batch, m, k, n_steps, a_out, p_out, full_cov, y_out, f_out,
+                         (hipStream_t)stream);
 }
 
 int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
@@ -726,13 +656,10 @@ int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, 
                              const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                              double missing_fill, int n_state_hint, int z_selector_hint, double* logp_out,
                              int32_t* status_io, void* stream) {
-  int rc = check_common(batch, m, DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman(batch, m, k, obs, q, T && R && logp_out && status_io);
   if (rc) return rc;
-  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!T || !R || !Q || !Z || !y || !logp_out || !status_io) return fail(DSGE_ERR_INVALID, "null pointer");
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
@@ -742,11 +669,8 @@ int dsge_kalman_logp_batched(const double* T, const double* R, const double* Q, 
   lay.add(&RQR, mm);
   lay.add(&P0, mm);
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, Q, q_mode, batch, m, k, nullptr, nullptr, RQR, P0,
-                            status_io, 0, 2, st)))
-    return rc;
-  return launch_kalman(T, RQR, P0, 0, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, jitter,
-                       missing_fill, n_state_hint, z_selector_hint, logp_out, status_io, st);
+  if ((rc = assemble_rqr(R, q, batch, m, k, RQR, status_io, st))) return rc;
+  return launch_kalman(T, RQR, P0, 0, obs, batch, m, n_state_hint, z_selector_hint, logp_out, status_io, st);
 }
 
 // The scratch of the fused pipeline for one batch, declared once for both of its routes: pipeline_unchunked and pipeline_big
@@ -790,16 +714,15 @@ static void pipeline_declare(ScratchLayout& lay, PipelineScratch& s, int batch, 
 // model restricted to F = {state variables} u {observed variables}: x_t[F] = T[F, F] x_{t-1}[F] + R[F, :] eps_t is exact because
 // every column of T outside the state variables is zero (T = -(B + C T)^-1 A inherits the zero columns of A), and y_t reads
 // x_t[F] only.  |F| <= 64 or DSGE_ERR_TOO_LARGE.  Measuring F synchronises the stream once per call.
-static int pipeline_big(const double* A, const double* B, const double* C, const double* D, const double* Q, int q_mode,
-                        const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                        const double* y, int batch, int n, int k, int p, int T_len, int solver, bool park_failures, double tol,
-                        int max_iter, double jitter, double missing_fill, int z_selector_hint, double* logp_out,
-                        int32_t* status_out, double* T_out, double* R_out, double* resid_out, int32_t* n_iter_out, hipStream_t st,
-                        int reps, float* ms_out, void* scratch_slice) {
+static int pipeline_big(const double* A, const double* B, const double* C, const double* D, const ShockCov& q, const ObsModel& o,
+                        int batch, int n, int k, int solver, bool park_failures, double tol, int max_iter, int z_selector_hint,
+                        double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* resid_out, int32_t* n_iter_out,
+                        hipStream_t st, int reps, float* ms_out, void* scratch_slice) {
+  const int p = o.p;
   int rc;
   ScratchLayout lay;
   PipelineScratch s;
-  pipeline_declare(lay, s, batch, n, k, z_batched, T_out, R_out, n_iter_out);
+  pipeline_declare(lay, s, batch, n, k, o.z_batched, T_out, R_out, n_iter_out);
   if ((rc = lay.reserve(g_scratch_pool, st, scratch_slice))) return rc;
   double *Tw = s.Tw, *Rw = s.Rw, *T_r = s.T_r, *R_r = s.R_r, *Z_r = s.Z_r, *RQR = s.RQR, *P0 = s.P0;
   int32_t *it_w = s.it_w, *park_w = s.park_w, *eu_w = s.eu_w;
@@ -808,7 +731,7 @@ static int pipeline_big(const double* A, const double* B, const double* C, const
   // before any output of this call is touched (DSGE_ERR_TOO_LARGE: "nothing computed", include/dsge_hip.h)
   unsigned char idx[64];
   int u = 0, ns = 0;
-  if ((rc = big_filtered_variables(A, Z, z_batched, batch, n, p, st, idx, &u, &ns))) return rc;
+  if ((rc = big_filtered_variables(A, o.Z, o.z_batched, batch, n, p, st, idx, &u, &ns))) return rc;
   if (u > 64)
     return fail(DSGE_ERR_TOO_LARGE, "solve + Kalman with n > 64: " + std::to_string(u) +
                                         " state and observed variables, the filter kernels take at most 64");
@@ -839,23 +762,22 @@ static int pipeline_big(const double* A, const double* B, const double* C, const
     if (!fuse_R && (rc = launch_selection_big(A, B, C, D, Tw, batch, n, k, Rw, resid_out, status_out, st))) return rc;
     }
     if (ms_out) HIP_TRY(hipEventRecord(ev[1], st));
-    if ((rc = launch_big_compress(Tw, Rw, Z, z_batched, batch, n, k, p, idx, u, T_r, R_r, Z_r, st))) return rc;
+    if ((rc = launch_big_compress(Tw, Rw, o.Z, o.z_batched, batch, n, k, p, idx, u, T_r, R_r, Z_r, st))) return rc;
     const int ns_hint = (ns > 0 && ns < u) ? ns : 0;
-    const bool q_diag = q_mode == DSGE_Q_DIAG_SHARED || q_mode == DSGE_Q_DIAG_BATCHED;
-    const bool fold_rqr = !park_failures && q_diag && kalman_folds_rqr(u, p, k, ns_hint, z_selector_hint);
+    const bool fold_rqr = !park_failures && q.diag() && kalman_folds_rqr(u, p, k, ns_hint, z_selector_hint);
     if (fold_rqr)
       rc = DSGE_SUCCESS;
-    else if (q_diag && k <= 16)
-      rc = launch_rqr(R_r, Q, q_mode == DSGE_Q_DIAG_BATCHED, batch, u, k, status_out, RQR, st);
+    else if (q.diag() && k <= 16)
+      rc = launch_rqr(R_r, q.Q, q.batched(), batch, u, k, status_out, RQR, st);
     else
-      rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T_r, R_r, Q, q_mode, batch, u, k, nullptr, nullptr, RQR, P0,
-                           status_out, 0, 2, st);
+      rc = assemble_rqr(R_r, q, batch, u, k, RQR, status_out, st);
     if (rc) return rc;
     if (ms_out) HIP_TRY(hipEventRecord(ev[2], st));
     const int32_t* okey = (opt().kalman_order == 1) ? it_w : nullptr;
-    if ((rc = launch_kalman(T_r, RQR, P0, 0, Z_r, z_batched, d, d_batched, Hdiag, h_batched, y, batch, u, p, T_len, jitter,
-                            missing_fill, ns_hint, z_selector_hint, logp_out, status_out, st, okey, fold_rqr ? R_r : nullptr,
-                            fold_rqr ? Q : nullptr, q_mode == DSGE_Q_DIAG_BATCHED, k, nullptr)))
+    ObsModel o_r = o;  // the observation model on the gathered variables
+    o_r.Z = Z_r;
+    if ((rc = launch_kalman(T_r, RQR, P0, 0, o_r, batch, u, ns_hint, z_selector_hint, logp_out, status_out, st, okey,
+                            fold_rqr ? R_r : nullptr, q, k)))
       return rc;
     if (park_failures && (rc = launch_status_park(status_out, park_w, batch, 1, st))) return rc;
     if (ms_out) {
@@ -876,39 +798,26 @@ static int pipeline_big(const double* A, const double* B, const double* C, const
 }  // extern "C"
 
 // (declared in dsge_host.hpp: the fused host twin calls it chunk by chunk)
-int dsge_host::pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const double* Q,
-                                  int q_mode, const double* Z, int z_batched, const double* d, int d_batched,
-                                  const double* Hdiag, int h_batched, const double* y, int batch, int n, int k, int p,
-                                  int T_len, int solver, double tol, int max_iter, double jitter, double missing_fill,
-                                  int n_state_hint, int z_selector_hint, int n_lead_hint, double* logp_out,
-                                  int32_t* status_out, double* T_out, double* R_out, double* resid_out, int32_t* n_iter_out,
-                                  hipStream_t st, int reps, float* ms_out, void* scratch_slice) {
+int dsge_host::pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const ShockCov& q,
+                                  const ObsModel& o, int batch, int n, int k, int solver, double tol, int max_iter, int n_state_hint,
+                                  int z_selector_hint, int n_lead_hint, double* logp_out, int32_t* status_out, double* T_out,
+                                  double* R_out, double* resid_out, int32_t* n_iter_out, hipStream_t st, int reps, float* ms_out,
+                                  void* scratch_slice) {
   const bool zero_T_on_failure = (solver & DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE) != 0;
   solver &= ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
   const bool is_cr = solver == DSGE_SOLVER_CYCLE_REDUCTION || solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION;
   const bool park_failures = zero_T_on_failure && is_cr;
-  // (gensys beyond 64 variables exists by spectral division only: dsge_options.gensys_doubling != 0)
-  const bool big_ok = is_cr || (solver == DSGE_SOLVER_GENSYS && opt().gensys_doubling != 0);
-  int rc = check_common(batch, n, big_ok ? DSGE_MAX_N_BIG : DSGE_MAX_N);
-  if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out) return fail(DSGE_ERR_INVALID, "null pointer");
-  if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_BACKWARD_DIRECT && solver != DSGE_SOLVER_GENSYS &&
-      solver != DSGE_SOLVER_SCAN_CYCLE_REDUCTION)
-    return fail(DSGE_ERR_INVALID, "unknown solver code");
+  const int p = o.p;
+  int rc;
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   if (big_size(n))
-    return pipeline_big(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                        park_failures, tol, max_iter, jitter, missing_fill, z_selector_hint, logp_out, status_out, T_out, R_out,
-                        resid_out, n_iter_out, st, reps, ms_out, scratch_slice);
+    return pipeline_big(A, B, C, D, q, o, batch, n, k, solver, park_failures, tol, max_iter, z_selector_hint, logp_out, status_out,
+                        T_out, R_out, resid_out, n_iter_out, st, reps, ms_out, scratch_slice);
 
   ScratchLayout lay;
   PipelineScratch s;
-  pipeline_declare(lay, s, batch, n, k, z_batched, T_out, R_out, n_iter_out);
+  pipeline_declare(lay, s, batch, n, k, o.z_batched, T_out, R_out, n_iter_out);
   // (scratch_slice: a slice of an arena the caller reserved -- chunks in flight on several streams)
   if ((rc = lay.reserve(g_scratch_pool, st, scratch_slice))) return rc;
   double *Tw = s.Tw, *Rw = s.Rw, *RQR = s.RQR, *P0 = s.P0;
@@ -952,9 +861,8 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
       // gensys_doubling = 3 keeps the verdict on the caller's stream.
       hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
       const bool capturing = (hipStreamIsCapturing(st, &cap) == hipSuccess) && cap != hipStreamCaptureStatusNone;
-      const bool q_diag_ = q_mode == DSGE_Q_DIAG_SHARED || q_mode == DSGE_Q_DIAG_BATCHED;
       const bool want_overlap = opt().gensys_doubling == 1 && !ms_out && !resid_out && !park_failures && !capturing && batch >= 256 &&
-                                q_diag_ && n <= 64 && kalman_folds_rqr(n, p, k, n_state_hint, z_selector_hint);
+                                q.diag() && n <= 64 && kalman_folds_rqr(n, p, k, n_state_hint, z_selector_hint);
       if (want_overlap) {
         gov.side = verdict_guard.side = &t_verdict;
         gov.status = vst_w;
@@ -974,25 +882,22 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
     if (ms_out) HIP_TRY(hipEventRecord(ev[1], st));
     // backward_direct already produced R; the assemble kernel recomputes it from the same
     // formula (C T + B = B when C == 0), which keeps a single code path for resid/RQR/P0.
-    const bool q_diag = q_mode == DSGE_Q_DIAG_SHARED || q_mode == DSGE_Q_DIAG_BATCHED;
     // sym(R Q R') inside the filter kernel (its retained block only) when the fast selector kernel takes the draws
     // (round 4: also behind the explicit selection of gensys / backward-direct / a requested residual -- the assemble launch then
     // forms R (and the residual) only: no 40 x 40 product, no 51 MB of R Q R' through HBM per 4096 draws)
-    const bool fold_rqr = !park_failures && q_diag && n <= 64 && kalman_folds_rqr(n, p, k, n_state_hint, z_selector_hint);
+    const bool fold_rqr = !park_failures && q.diag() && n <= 64 && kalman_folds_rqr(n, p, k, n_state_hint, z_selector_hint);
     if (fold_rqr && fuse_R)
       rc = DSGE_SUCCESS;
     else if (fold_rqr && gov.used)
       rc = DSGE_SUCCESS;  // (R of the draws the verdict re-solves: behind the join, below)
     else if (fold_rqr)
-      rc = launch_assemble(A, B, C, D, Tw, nullptr, Q, q_mode, batch, n, k, Rw, resid_out, nullptr, nullptr, status_out, 1, 0, st,
-                           resid_out ? nullptr : gensys_qz_marks);
-    else if (fuse_R && q_diag && k <= 16 && n <= 64)
-      rc = launch_rqr(Rw, Q, q_mode == DSGE_Q_DIAG_BATCHED, batch, n, k, status_out, RQR, st);  // (RQR_KMAX = 16)
+      rc = assemble_selection(A, B, C, D, Tw, batch, n, k, Rw, resid_out, status_out, st, resid_out ? nullptr : gensys_qz_marks);
+    else if (fuse_R && q.diag() && k <= 16 && n <= 64)
+      rc = launch_rqr(Rw, q.Q, q.batched(), batch, n, k, status_out, RQR, st);  // (RQR_KMAX = 16)
     else if (fuse_R)
-      rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, Tw, Rw, Q, q_mode, batch, n, k, nullptr, nullptr, RQR, P0,
-                           status_out, 0, 2, st);
+      rc = assemble_rqr(Rw, q, batch, n, k, RQR, status_out, st);
     else
-      rc = launch_assemble(A, B, C, D, Tw, nullptr, Q, q_mode, batch, n, k, Rw, resid_out, RQR, P0, status_out, 1, 2, st);
+      rc = assemble_selection_rqr(A, B, C, D, Tw, q, batch, n, k, Rw, resid_out, RQR, status_out, st);
     if (rc) return rc;
     if (ms_out) HIP_TRY(hipEventRecord(ev[2], st));
     const int32_t* okey = nullptr;
@@ -1005,22 +910,17 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
       if (!gensys_key && (rc = launch_persistence_key(Tw, status_out, batch, n, key_w, st))) return rc;
       okey = key_w;
     }
-    if ((rc = launch_kalman(Tw, RQR, P0, 0, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, p, T_len, jitter,
-                            missing_fill, n_state_hint, z_selector_hint, logp_out, status_out, st, okey,
-                            fold_rqr ? Rw : nullptr, fold_rqr ? Q : nullptr, q_mode == DSGE_Q_DIAG_BATCHED, k,
-                            have_colmask ? cm_w : nullptr)))
+    if ((rc = launch_kalman(Tw, RQR, P0, 0, o, batch, n, n_state_hint, z_selector_hint, logp_out, status_out, st, okey,
+                            fold_rqr ? Rw : nullptr, q, k, have_colmask ? cm_w : nullptr)))
       return rc;
     if (gov.used) {
       // join the verdict; R of the draws the ordered QZ solved (explicit selection, marked draws only, by the verdict's status);
       // their status words; their filter (every launch a second pass)
       if ((rc = gov.side->join(st))) return rc;
-      if ((rc = launch_assemble(A, B, C, D, Tw, nullptr, Q, q_mode, batch, n, k, Rw, nullptr, nullptr, nullptr, gov.status, 1, 0, st,
-                                gov.marks)))
-        return rc;
+      if ((rc = assemble_selection(A, B, C, D, Tw, batch, n, k, Rw, nullptr, gov.status, st, gov.marks))) return rc;
       if ((rc = dsge_host::launch_gensys_overlap_merge(batch, gov.marks, gov.status, status_out, logp_out, st))) return rc;
-      if ((rc = launch_kalman(Tw, RQR, P0, 0, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, p, T_len, jitter,
-                              missing_fill, n_state_hint, z_selector_hint, logp_out, status_out, st, nullptr, fold_rqr ? Rw : nullptr,
-                              fold_rqr ? Q : nullptr, q_mode == DSGE_Q_DIAG_BATCHED, k, nullptr, 1)))
+      if ((rc = launch_kalman(Tw, RQR, P0, 0, o, batch, n, n_state_hint, z_selector_hint, logp_out, status_out, st, nullptr,
+                              fold_rqr ? Rw : nullptr, q, k, nullptr, 1)))
         return rc;
     }
     if (park_failures) {
@@ -1054,12 +954,14 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
   // stream): a draw whose covariance recursion converges late -- or never, within the sample -- keeps ONE wavefront of the
   // Kalman launch busy for up to 200 full steps (1.5 ms) while the rest of the GPU has long finished; with two chunk
   // pipelines in flight that tail overlaps the cycle-reduction launch of the next chunk instead of being idle time.
-  if (opt().pipeline_chunks < 2 || batch < 1024 || batch / opt().pipeline_chunks < 256)
-    return pipeline_unchunked(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len,
-                              solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
-                              logp_out, status_out, T_out, R_out, resid_out, n_iter_out, (hipStream_t)stream, 1, nullptr);
-  int rc = ensure_device();
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_pipeline(batch, n, k, obs, q, solver, A && B && C && D && logp_out && status_out);
   if (rc) return rc;
+  if (opt().pipeline_chunks < 2 || batch < 1024 || batch / opt().pipeline_chunks < 256)
+    return pipeline_unchunked(A, B, C, D, q, obs, batch, n, k, solver, tol, max_iter, n_state_hint, z_selector_hint, n_lead_hint,
+                              logp_out, status_out, T_out, R_out, resid_out, n_iter_out, (hipStream_t)stream, 1, nullptr);
+  if ((rc = ensure_device())) return rc;
   hipStream_t caller = (hipStream_t)stream;
   const int n_chunks = opt().pipeline_chunks;
   const int n_str = n_chunks < MAX_CHUNK_STREAMS ? n_chunks : MAX_CHUNK_STREAMS;
@@ -1079,18 +981,13 @@ int dsge_solve_kalman_logp_batched(const double* A, const double* B, const doubl
     open[i].into = caller;
     if ((rc = t_chunk[i].fork(caller))) return rc;
   }
-  const bool q_b = (q_mode == DSGE_Q_DIAG_BATCHED || q_mode == DSGE_Q_FULL_BATCHED);
-  const size_t qk = (q_mode == DSGE_Q_FULL_BATCHED) ? (size_t)k * k : (size_t)k;
   for (int c = 0; c * per < batch; ++c) {
     const int c0 = c * per;
     const int nb = (batch - c0 < per) ? batch - c0 : per;
     const size_t o2 = (size_t)c0 * n * n, ok = (size_t)c0 * n * k;
-    rc = pipeline_unchunked(A + o2, B + o2, C + o2, D + ok, q_b ? Q + c0 * qk : Q, q_mode,
-                            z_batched ? Z + (size_t)c0 * p * n : Z, z_batched, (d && d_batched) ? d + (size_t)c0 * p : d,
-                            d_batched, (Hdiag && h_batched) ? Hdiag + (size_t)c0 * p : Hdiag, h_batched, y, nb, n, k, p, T_len,
-                            solver, tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint,
-                            logp_out + c0, status_out + c0, T_out ? T_out + o2 : nullptr, R_out ? R_out + ok : nullptr,
-                            resid_out ? resid_out + c0 : nullptr, n_iter_out ? n_iter_out + c0 : nullptr,
+    rc = pipeline_unchunked(A + o2, B + o2, C + o2, D + ok, q.at(c0, k), obs.at(c0, n), nb, n, k, solver, tol, max_iter, n_state_hint,
+                            z_selector_hint, n_lead_hint, logp_out + c0, status_out + c0, T_out ? T_out + o2 : nullptr,
+                            R_out ? R_out + ok : nullptr, resid_out ? resid_out + c0 : nullptr, n_iter_out ? n_iter_out + c0 : nullptr,
                             t_chunk[c % n_str].stream(), 1, nullptr, (char*)base + slice * c);
     if (rc) return rc;
   }
@@ -1107,22 +1004,11 @@ int dsge_second_order_logp_batched(const double* A, const double* B, const doubl
                                    int n_lead, const int32_t* ret_idx, int n_ret, double* logp_out, int32_t* status_out,
                                    double* T_out, double* R_out, double* gyy_out, double* gyu_out, double* guu_out,
                                    double* gss_out, float* stage_ms, void* stream) {
-  int rc = check_common(batch, n, DSGE_MAX_N_CR);
+  const ObsModel obs{Z, 0, d, 0, Hdiag, 0, y, p, T_len, jitter, missing_fill};
+  const ShockCov qc{q, q_batched ? DSGE_Q_DIAG_BATCHED : DSGE_Q_DIAG_SHARED};
+  int rc = check_second_order(batch, n, k, obs, qc, solver, nnz, state_idx, n_state, lead_idx, n_lead, ret_idx, n_ret,
+                              A && B && C && D && (nnz == 0 || (hess_idx && hess_val)) && logp_out && status_out);
   if (rc) return rc;
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > 8) return fail(DSGE_ERR_INVALID, "second order: p out of range (1..8)");
-  if (T_len < 0 || nnz < 0) return fail(DSGE_ERR_INVALID, "T_len < 0 or nnz < 0");
-  if (!A || !B || !C || !D || (nnz > 0 && (!hess_idx || !hess_val)) || !q || !Z || !y || !logp_out || !status_out ||
-      !state_idx || !ret_idx || (n_lead > 0 && !lead_idx))
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_GENSYS)
-    return fail(DSGE_ERR_INVALID, "second order: solver must be cycle reduction or gensys");
-  for (int i = 0; i < n_state; ++i)
-    if (state_idx[i] < 0 || state_idx[i] >= n) return fail(DSGE_ERR_INVALID, "state_idx out of range");
-  for (int i = 0; i < n_lead; ++i)
-    if (lead_idx[i] < 0 || lead_idx[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
-  for (int i = 0; i < n_ret; ++i)
-    if (ret_idx[i] < 0 || ret_idx[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
@@ -1147,9 +1033,7 @@ int dsge_second_order_logp_batched(const double* A, const double* B, const doubl
     if (!deflated && (rc = launch_cr(A, B, C, batch, n, max_iter, tol, Tw, status_out, it_w, st, 0, D, k, Rw))) return rc;
   } else {
     if ((rc = launch_gensys(A, B, C, batch, n, tol, n_lead, Tw, eu_w, status_out, st))) return rc;
-    if ((rc = launch_assemble(A, B, C, D, Tw, nullptr, q, q_batched ? DSGE_Q_DIAG_BATCHED : DSGE_Q_DIAG_SHARED, batch, n, k,
-                              Rw, nullptr, nullptr, nullptr, status_out, 1, 0, st)))
-      return rc;
+    if ((rc = assemble_selection(A, B, C, D, Tw, batch, n, k, Rw, nullptr, status_out, st))) return rc;
   }
   if (stage_ms) HIP_TRY(hipEventRecord(e1, st));
   rc = launch_second_order(B, C, Tw, Rw, hess_idx, nnz, hess_val, q, q_batched, Z, d, Hdiag, y, batch, n, k, p, T_len, jitter,
@@ -1174,17 +1058,11 @@ int dsge_solve_kalman_logp_augmented_batched(const double* A, const double* B, c
                                              int n_lead_hint, double* logp_out, int32_t* status_out, double* T_aug_out,
                                              double* R_aug_out, double* resid_out, void* stream) {
   const bool is_cr = solver == DSGE_SOLVER_CYCLE_REDUCTION || solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION;
-  int rc = check_common(batch, n, is_cr ? DSGE_MAX_N_CR : DSGE_MAX_N);
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_augmented(batch, n, k, obs, q, solver, m, n_links,
+                           A && B && C && D && logp_out && status_out && (n_links == 0 || (link_rows && link_cols)));
   if (rc) return rc;
-  if (m < n || m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_INVALID, "augmented state dimension m out of range (n..DSGE_MAX_N_BIG)");
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > DSGE_MAX_P) return fail(DSGE_ERR_INVALID, "p out of range (1..DSGE_MAX_P)");
-  if (T_len < 0 || n_links < 0) return fail(DSGE_ERR_INVALID, "T_len < 0 or n_links < 0");
-  if (q_mode < 0 || q_mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
-  if (!A || !B || !C || !D || !Q || !Z || !y || !logp_out || !status_out || (n_links > 0 && (!link_rows || !link_cols)))
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if (!is_cr && solver != DSGE_SOLVER_BACKWARD_DIRECT && solver != DSGE_SOLVER_GENSYS)
-    return fail(DSGE_ERR_INVALID, "unknown solver code");
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
@@ -1210,9 +1088,7 @@ int dsge_solve_kalman_logp_augmented_batched(const double* A, const double* B, c
   }
   if (rc) return rc;
   // R and the policy residual in SOLVER order (statespace.py:213), then un-permute + augment
-  if ((rc = launch_assemble(A, B, C, D, Tw, nullptr, Q, q_mode, batch, n, k, Rw, resid_out, nullptr, nullptr, status_out, 1,
-                            0, st)))
-    return rc;
+  if ((rc = assemble_selection(A, B, C, D, Tw, batch, n, k, Rw, resid_out, status_out, st))) return rc;
   if ((rc = launch_augment(Tw, Rw, batch, n, k, m, inv_var_order, n_links, link_rows, link_cols, Ta, Ra, st))) return rc;
   if (m > DSGE_MAX_N) {
     // Round 6: 65 .. 96 augmented states (cumulator and observation-lag chains on a 40-variable model, statespace.py:598-723).
@@ -1238,46 +1114,33 @@ int dsge_solve_kalman_logp_augmented_batched(const double* A, const double* B, c
     gathered.add(&Z_r, z_batched ? (size_t)batch * p * 64 : (size_t)p * 64);
     if ((rc = gathered.reserve(g_aug_big_pool, st))) return rc;
     if ((rc = launch_big_compress(Ta, Ra, Z, z_batched, batch, m, k, p, idx, u, T_r, R_r, Z_r, st))) return rc;
-    if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T_r, R_r, Q, q_mode, batch, u, k, nullptr, nullptr, RQR_r, P0_r,
-                              status_out, 0, 2, st)))
-      return rc;
+    if ((rc = assemble_rqr(R_r, q, batch, u, k, RQR_r, status_out, st))) return rc;
     const int ns_hint = (ns > 0 && ns < u) ? ns : 0;
-    return launch_kalman(T_r, RQR_r, P0_r, 0, Z_r, z_batched, d, d_batched, Hdiag, h_batched, y, batch, u, p, T_len, jitter,
-                         missing_fill, ns_hint, z_selector_hint, logp_out, status_out, st);
+    ObsModel o_r = obs;  // the observation model on the gathered variables
+    o_r.Z = Z_r;
+    return launch_kalman(T_r, RQR_r, P0_r, 0, o_r, batch, u, ns_hint, z_selector_hint, logp_out, status_out, st);
   }
-  if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, Ta, Ra, Q, q_mode, batch, m, k, nullptr, nullptr, RQR, P0,
-                            status_out, 0, 2, st)))
-    return rc;
-  return launch_kalman(Ta, RQR, P0, 0, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, jitter,
-                       missing_fill, n_state_hint, z_selector_hint, logp_out, status_out, st);
+  if ((rc = assemble_rqr(Ra, q, batch, m, k, RQR, status_out, st))) return rc;
+  return launch_kalman(Ta, RQR, P0, 0, obs, batch, m, n_state_hint, z_selector_hint, logp_out, status_out, st);
 }
 
 // dense_z = 0: the selector path.  dense_z = 1: any design matrix, by carrying the observed combinations as p extra variables
 // (dsge_augment.hpp: dense_z_augment_kernel): the reverse sweep runs on the augmented model of n + p variables, the assembly
 // reverse and the policy adjoints on the original n; n_filter_hint then counts the STATE variables (non-zero columns of A).
-static int grad_pipeline(const double* A, const double* B, const double* C, const double* D, const double* q, int q_batched,
-                         const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                         const double* y, int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
-                         double jitter, double missing_fill, int n_filter_hint, int n_lead_hint, double* logp_out,
-                         int32_t* status_out, double* A_bar, double* B_bar, double* C_bar, double* D_bar, double* q_bar,
-                         double* d_bar, double* h_bar, int dense_z, double* Z_bar, void* stream) {
-  int rc = check_common(batch, n, 56);
+static int grad_pipeline(const double* A, const double* B, const double* C, const double* D, const ShockCov& q, const ObsModel& o,
+                         int batch, int n, int k, int solver, double tol, int max_iter, int n_filter_hint, int n_lead_hint,
+                         double* logp_out, int32_t* status_out, double* A_bar, double* B_bar, double* C_bar, double* D_bar,
+                         double* q_bar, double* d_bar, double* h_bar, int dense_z, double* Z_bar, void* stream) {
+  const int p = o.p, T_len = o.T_len;
+  int rc = check_grad(batch, n, k, o, q, solver, dense_z != 0,
+                      A && B && C && D && logp_out && status_out && A_bar && B_bar && C_bar && D_bar && q_bar);
   if (rc) return rc;
-  if (dense_z && n + p > 56) return fail(DSGE_ERR_INVALID, "gradient path with a dense design matrix: n + p must not exceed 56");
-  if (k < 1 || k > n) return fail(DSGE_ERR_INVALID, "k out of range (1..n)");
-  if (p < 1 || p > 8) return fail(DSGE_ERR_INVALID, "gradient path: p out of range (1..8)");
-  if (T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
-  if (!A || !B || !C || !D || !q || !Z || !y || !logp_out || !status_out || !A_bar || !B_bar || !C_bar || !D_bar || !q_bar)
-    return fail(DSGE_ERR_INVALID, "null pointer");
-  if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_GENSYS && solver != DSGE_SOLVER_SCAN_CYCLE_REDUCTION)
-    return fail(DSGE_ERR_INVALID, "gradient path: solver must be cycle_reduction, scan_cycle_reduction or gensys");
-  if (q_batched < 0 || q_batched > 3) return fail(DSGE_ERR_INVALID, "gradient path: q_batched is a DSGE_Q_* mode (0..3)");
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   const int m = dense_z ? n + p : n;                                   // size of the model the reverse sweep runs on
   const int u_hint = dense_z ? (n_filter_hint > 0 ? n_filter_hint + p : 0) : n_filter_hint;
-  const bool qfull = q_batched >= 2;                       // DSGE_Q_FULL_*: Q and q_bar are k x k
+  const bool qfull = !q.diag();                            // DSGE_Q_FULL_*: Q and q_bar are k x k
   const size_t qstride = qfull ? (size_t)k * k : (size_t)k;
   // the reverse sweep re-reads the stored (a_t, P_t): chunk the batch so that the store stays <= 16 GiB of the 288 GB
   const size_t per_draw = kalman_grad_store_doubles_per_draw(u_hint, m, T_len) * sizeof(double);
@@ -1311,10 +1174,8 @@ static int grad_pipeline(const double* A, const double* B, const double* C, cons
   for (size_t c0 = 0; c0 < (size_t)batch; c0 += chunk) {
     const int nb = (int)(((size_t)batch - c0 < chunk) ? (size_t)batch - c0 : chunk);
     const double *Ac = A + c0 * n * n, *Bc = B + c0 * n * n, *Cc = C + c0 * n * n, *Dc = D + c0 * n * k;
-    const double* qc = q + ((q_batched & 1) ? c0 * qstride : 0);
-    const double* Zc = Z + (z_batched ? c0 * p * n : 0);
-    const double* dc = d ? d + (d_batched ? c0 * p : 0) : nullptr;
-    const double* hc = Hdiag ? Hdiag + (h_batched ? c0 * p : 0) : nullptr;
+    const ShockCov qc = q.at(c0, k);
+    const ObsModel oc = o.at(c0, n);
     int32_t* stc = status_out + c0;
     if (solver == DSGE_SOLVER_GENSYS)
       rc = launch_gensys(Ac, Bc, Cc, nb, n, tol, n_lead_hint, Tw, eu_w, stc, st);
@@ -1334,15 +1195,12 @@ static int grad_pipeline(const double* A, const double* B, const double* C, cons
     }
     if (rc) return rc;
     if (have_R && k <= 16 && n <= 64 && !qfull) {
-      if (!dense_z && (rc = launch_rqr(Rw, qc, q_batched, nb, n, k, stc, RQR, st))) return rc;
-    } else if ((rc = launch_assemble(Ac, Bc, Cc, Dc, Tw, nullptr, qc, q_batched, nb, n, k, Rw, nullptr, RQR, nullptr, stc, 1, 2,
-                                     st)))
+      if (!dense_z && (rc = launch_rqr(Rw, qc.Q, qc.mode, nb, n, k, stc, RQR, st))) return rc;
+    } else if ((rc = assemble_selection_rqr(Ac, Bc, Cc, Dc, Tw, qc, nb, n, k, Rw, nullptr, RQR, stc, st)))
       return rc;
     if (dense_z) {  // the augmented model and its sym(R Q R')
-      if ((rc = launch_dense_z_augment(Tw, Rw, Zc, z_batched, nb, n, k, p, Ta, Ra, Zaug, st))) return rc;
-      if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, Ta, Ra, qc, q_batched, nb, m, k, nullptr, nullptr, RQRa, nullptr,
-                                stc, 0, 2, st)))
-        return rc;
+      if ((rc = launch_dense_z_augment(Tw, Rw, oc.Z, oc.z_batched, nb, n, k, p, Ta, Ra, Zaug, st))) return rc;
+      if ((rc = assemble_rqr(Ra, qc, nb, m, k, RQRa, stc, st))) return rc;
     }
     int32_t* gkey = (solver == DSGE_SOLVER_GENSYS) ? nullptr : it_w;  // (the gradient's forward sweep overwrites it with its step counts)
     if (opt().kalman_order == 0) {
@@ -1351,27 +1209,29 @@ static int grad_pipeline(const double* A, const double* B, const double* C, cons
       if ((rc = launch_persistence_key(Tw, stc, nb, n, it_w, st))) return rc;  // (the iteration counts are not needed again)
       gkey = it_w;
     }
+    double *dbc = d_bar ? d_bar + c0 * p : nullptr, *hbc = h_bar ? h_bar + c0 * p : nullptr;
     if (dense_z) {
-      if ((rc = launch_kalman_grad(Ta, RQRa, Zaug, 0, dc, d_batched, hc, h_batched, y, nb, m, p, T_len, jitter, missing_fill,
-                                   u_hint, store, logp_out + c0, stc, Tbar_a, Gbar_a, d_bar ? d_bar + c0 * p : nullptr,
-                                   h_bar ? h_bar + c0 * p : nullptr, st, gkey, ord_w)))
+      ObsModel oa = oc;  // the observed combinations are variables of the augmented model: one shared selector
+      oa.Z = Zaug;
+      oa.z_batched = 0;
+      if ((rc = launch_kalman_grad(Ta, RQRa, oa, nb, m, u_hint, store, logp_out + c0, stc, Tbar_a, Gbar_a, dbc, hbc, st, gkey,
+                                   ord_w)))
         return rc;
-      if ((rc = launch_dense_z_deaugment(Tbar_a, Gbar_a, Tw, RQRa, Zc, z_batched, stc, nb, n, p, Tbar, Gbar,
+      if ((rc = launch_dense_z_deaugment(Tbar_a, Gbar_a, Tw, RQRa, oc.Z, oc.z_batched, stc, nb, n, p, Tbar, Gbar,
                                          Z_bar ? Z_bar + c0 * p * n : nullptr, st)))
         return rc;
-    } else if ((rc = launch_kalman_grad(Tw, RQR, Zc, z_batched, dc, d_batched, hc, h_batched, y, nb, n, p, T_len, jitter,
-                                        missing_fill, u_hint, store, logp_out + c0, stc, Tbar, Gbar,
-                                        d_bar ? d_bar + c0 * p : nullptr, h_bar ? h_bar + c0 * p : nullptr, st, gkey, ord_w)))
+    } else if ((rc = launch_kalman_grad(Tw, RQR, oc, nb, n, u_hint, store, logp_out + c0, stc, Tbar, Gbar, dbc, hbc, st, gkey,
+                                        ord_w)))
       return rc;
     // Round 6: diagonal Q, k <= 16, up to 40 variables: one launch for the reverse of the assembly AND the policy adjoints (they
     // share the elimination of B + C T; adjoint_kernel<BS, false, true>), the two-kernel path behind it for what it flags
     if (!qfull && k <= 16 && n <= 40 && opt().grad_fused_adjoint) {
-      if ((rc = launch_adjoint_fused(Bc, Cc, Tw, Rw, qc, q_batched, Gbar, Tbar, nb, n, k, A_bar + c0 * n * n, B_bar + c0 * n * n,
+      if ((rc = launch_adjoint_fused(Bc, Cc, Tw, Rw, qc.Q, qc.mode, Gbar, Tbar, nb, n, k, A_bar + c0 * n * n, B_bar + c0 * n * n,
                                      C_bar + c0 * n * n, D_bar + c0 * n * k, q_bar + c0 * qstride, stc, st)))
         return rc;
       continue;
     }
-    if ((rc = launch_grad_assemble(Bc, Cc, Tw, Rw, qc, q_batched, Gbar, nb, n, k, stc, Tbar, B_bar + c0 * n * n,
+    if ((rc = launch_grad_assemble(Bc, Cc, Tw, Rw, qc.Q, qc.mode, Gbar, nb, n, k, stc, Tbar, B_bar + c0 * n * n,
                                    C_bar + c0 * n * n, D_bar + c0 * n * k, q_bar + c0 * qstride, st)))
       return rc;
     if ((rc = launch_adjoint(Bc, Cc, Tw, Tbar, nb, n, A_bar + c0 * n * n, B_bar + c0 * n * n, C_bar + c0 * n * n, stc, st,
@@ -1388,9 +1248,10 @@ int dsge_solve_kalman_logp_grad_batched(const double* A, const double* B, const 
                                         double missing_fill, int n_filter_hint, int n_lead_hint, double* logp_out,
                                         int32_t* status_out, double* A_bar, double* B_bar, double* C_bar, double* D_bar,
                                         double* q_bar, double* d_bar, double* h_bar, void* stream) {
-  return grad_pipeline(A, B, C, D, q, q_batched, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                       tol, max_iter, jitter, missing_fill, n_filter_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar,
-                       D_bar, q_bar, d_bar, h_bar, 0, nullptr, stream);
+  return grad_pipeline(A, B, C, D, ShockCov{q, q_batched},
+                       ObsModel{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill}, batch, n, k, solver, tol,
+                       max_iter, n_filter_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar, D_bar, q_bar, d_bar, h_bar, 0, nullptr,
+                       stream);
 }
 
 int dsge_solve_kalman_logp_grad_dense_z_batched(const double* A, const double* B, const double* C, const double* D,
@@ -1401,9 +1262,10 @@ int dsge_solve_kalman_logp_grad_dense_z_batched(const double* A, const double* B
                                                 double* logp_out, int32_t* status_out, double* A_bar, double* B_bar,
                                                 double* C_bar, double* D_bar, double* q_bar, double* d_bar, double* h_bar,
                                                 double* Z_bar, void* stream) {
-  return grad_pipeline(A, B, C, D, q, q_batched, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                       tol, max_iter, jitter, missing_fill, n_state_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar,
-                       D_bar, q_bar, d_bar, h_bar, 1, Z_bar, stream);
+  return grad_pipeline(A, B, C, D, ShockCov{q, q_batched},
+                       ObsModel{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill}, batch, n, k, solver, tol,
+                       max_iter, n_state_hint, n_lead_hint, logp_out, status_out, A_bar, B_bar, C_bar, D_bar, q_bar, d_bar, h_bar, 1, Z_bar,
+                       stream);
 }
 
 int dsge_profile_pipeline(const double* A, const double* B, const double* C, const double* D, const double* Q,
@@ -1413,8 +1275,12 @@ int dsge_profile_pipeline(const double* A, const double* B, const double* C, con
                           int n_state_hint, int z_selector_hint, int n_lead_hint, double* logp_out,
                           int32_t* status_out, int reps, float* ms_out, void* stream) {
   if (!ms_out || reps < 1) return fail(DSGE_ERR_INVALID, "ms_out null or reps < 1");
-  return pipeline_unchunked(A, B, C, D, Q, q_mode, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, n, k, p, T_len, solver,
-                            tol, max_iter, jitter, missing_fill, n_state_hint, z_selector_hint, n_lead_hint, logp_out,
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_pipeline(batch, n, k, obs, q, solver, A && B && C && D && logp_out && status_out);
+  if (rc) return rc;
+  return pipeline_unchunked(A, B, C, D, q, obs, batch, n, k, solver, tol, max_iter, n_state_hint, z_selector_hint, n_lead_hint,
+                            logp_out,
                             status_out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, reps, ms_out);
 }
 

@@ -116,26 +116,41 @@ struct ForkGuard {
 // The two streams the host twins of the calling thread run on
 int twin_streams(hipStream_t* s0, hipStream_t* s1);
 
-// Shared by the device entry points (dsge_api.hip) and their host twins (api_host.hip)
-int ensure_device();                          // lazy check for a gfx950 device: nothing touches HIP before the first call
-int check_common(int batch, int n, int n_max);
-size_t q_elems(int q_mode, int batch, int k);  // elements of a shock covariance in layout DSGE_Q_*
-// argument checks of the dynamics entries (dsge_api.hip), shared with their host twins
-int check_simulate(const double* T, const double* R, const double* eps, int batch, int m, int k, int n_paths, int n_steps,
-                   int n_shock_steps, const double* x_out);
-int check_irf(const double* T, const double* R, const double* S, int batch, int m, int k, int c, int n_steps, const double* irf_out,
-              const double* fevd_out);
-int check_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, const double* a0, int batch,
-                   int m, int k, int p, int n_steps, const double* a_out, const double* p_out, const double* y_out,
-                   const double* f_out);
+// The observation side of a filter problem -- y_t = Z x_t + d + e_t, e_t ~ N(0, diag(Hdiag)), the data panel and how it is read --
+// as every entry of the filter family receives it
+struct ObsModel {
+  const double* Z; int z_batched;      // [p][m] or [batch][p][m]
+  const double* d; int d_batched;      // [p] or [batch][p]; may be null
+  const double* Hdiag; int h_batched;  // likewise
+  const double* y;                     // [T_len][p]
+  int p, T_len;
+  double jitter, missing_fill;
+  // the same description for the draws from c0 on, of a model with m variables: only the per-draw members move
+  ObsModel at(size_t c0, int m) const {
+    ObsModel o = *this;
+    if (z_batched) o.Z += c0 * p * m;
+    if (d && d_batched) o.d += c0 * p;
+    if (Hdiag && h_batched) o.Hdiag += c0 * p;
+    return o;
+  }
+};
+// The shock covariance in one of the layouts DSGE_Q_*: [k], [batch][k], [k][k] or [batch][k][k]
+struct ShockCov {
+  const double* Q = nullptr; int mode = DSGE_Q_DIAG_SHARED;
+  bool diag() const { return mode == DSGE_Q_DIAG_SHARED || mode == DSGE_Q_DIAG_BATCHED; }
+  bool batched() const { return mode == DSGE_Q_DIAG_BATCHED || mode == DSGE_Q_FULL_BATCHED; }
+  size_t elems(int batch, int k) const { return (size_t)(batched() ? batch : 1) * k * (diag() ? 1 : k); }
+  ShockCov at(size_t c0, int k) const { return ShockCov{batched() ? Q + c0 * elems(1, k) : Q, mode}; }
+};
+
+int ensure_device();  // lazy check for a gfx950 device: nothing touches HIP before the first call
 // The fused solve + filter pipeline of ONE batch on ONE stream: what dsge_solve_kalman_logp_batched runs when it does not
 // split the batch (dsge_options.pipeline_chunks), with the stage timing of dsge_profile_pipeline (reps, ms_out) and an
-// optional slice of a scratch arena the caller reserved (chunks in flight on several streams).  Arguments as the public entry.
-int pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const double* Q, int q_mode,
-                       const double* Z, int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
-                       const double* y, int batch, int n, int k, int p, int T_len, int solver, double tol, int max_iter,
-                       double jitter, double missing_fill, int n_state_hint, int z_selector_hint, int n_lead_hint,
-                       double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* resid_out,
+// optional slice of a scratch arena the caller reserved (chunks in flight on several streams).  Arguments as the public entry,
+// which has checked them (check_pipeline, below).
+int pipeline_unchunked(const double* A, const double* B, const double* C, const double* D, const ShockCov& q, const ObsModel& o,
+                       int batch, int n, int k, int solver, double tol, int max_iter, int n_state_hint, int z_selector_hint,
+                       int n_lead_hint, double* logp_out, int32_t* status_out, double* T_out, double* R_out, double* resid_out,
                        int32_t* n_iter_out, hipStream_t st, int reps, float* ms_out, void* scratch_slice = nullptr);
 
 // hipEvent_t that destroys itself: stage-timing events must not leak on the early returns of HIP_TRY
@@ -206,10 +221,21 @@ int launch_bdirect(const double* A, const double* B, const double* D, int batch,
 int launch_rqr(const double* R, const double* q, int q_batched, int batch, int n, int k, const int32_t* status,
                double* RQR_out, hipStream_t st, int rerun_only = 0);  // sym(R diag(q) R') alone, k <= RQR_KMAX (dsge_kernels.hpp);
                                                                       // rerun_only: draws flagged DSGE_ST_INTERNAL_RERUN
-int launch_assemble(const double* A, const double* B, const double* C, const double* D, const double* T,
-                    const double* R_in, const double* Q, int q_mode, int batch, int n, int k, double* R_out,
-                    double* resid_out, double* RQR_out, double* P0_out, int32_t* status, int do_sel, int do_lyap,
-                    hipStream_t st, const int32_t* only_marked = nullptr);  // only_marked: draws with a non-zero mark (selection only)
+// launch_assemble.hip: the operations of assemble_kernel (dsge_kernels.hpp), each with the arguments it reads.  status (may be null):
+// a draw with a non-zero word gets zero-filled outputs (resid = inf)
+// selection R = -(C T + B)^-1 D, optionally the policy residual |A + (B + C T) T|_F^2 (reads A); only_marked: draws with a non-zero mark
+int assemble_selection(const double* A, const double* B, const double* C, const double* D, const double* T, int batch, int n, int k,
+                       double* R_out, double* resid_out, int32_t* status, hipStream_t st, const int32_t* only_marked = nullptr);
+// sym(R Q R') alone; the selection and sym(R Q R') in one launch
+int assemble_rqr(const double* R, const ShockCov& q, int batch, int n, int k, double* RQR_out, int32_t* status, hipStream_t st);
+int assemble_selection_rqr(const double* A, const double* B, const double* C, const double* D, const double* T, const ShockCov& q,
+                           int batch, int n, int k, double* R_out, double* resid_out, double* RQR_out, int32_t* status, hipStream_t st);
+// sym(R Q R') (RQR_out may be null) and P0 = solve_discrete_lyapunov(T, R Q R'); a draw that does not converge: DSGE_ST_LYAP_FAIL
+int assemble_rqr_p0(const double* T, const double* R, const ShockCov& q, int batch, int n, int k, double* RQR_out, double* P0_out,
+                    int32_t* status, hipStream_t st);
+// P0 from a stored sym(R Q R'): for every healthy draw, or for the draws flagged DSGE_ST_INTERNAL_RERUN only
+int assemble_p0_from_rqr(const double* T, double* RQR, int batch, int n, double* P0_out, int32_t* status, bool flagged_only,
+                         hipStream_t st);
 int launch_dense_z_augment(const double* T, const double* R, const double* Z, int z_batched, int batch, int n, int k, int p,
                            double* T_aug, double* R_aug, double* Z_aug, hipStream_t st);
 int launch_dense_z_deaugment(const double* Tbar_a, const double* Gbar_a, const double* T, const double* G_aug, const double* Z,
@@ -228,27 +254,21 @@ int launch_augment(const double* T, const double* R, int batch, int n, int k, in
                    hipStream_t st);
 int launch_acf(const double* T, const double* Sigma, const double* Z, const double* Hdiag, int batch, int m, int p,
                int n_lags, int lag_step, int correlation, double* out, const int32_t* status, hipStream_t st);
-int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const double* Z, int z_batched,
-                  const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
-                  int m, int p, int T_len, double jitter, double missing_fill, int n_state_hint, int z_selector_hint,
-                  double* logp, int32_t* status, hipStream_t st, const int32_t* order_key = nullptr,
-                  const double* Rsel = nullptr, const double* qdiag = nullptr, int q_batched = 0, int k_shocks = 0,
+int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const ObsModel& o, int batch, int m, int n_state_hint,
+                  int z_selector_hint, double* logp, int32_t* status, hipStream_t st, const int32_t* order_key = nullptr,
+                  const double* Rsel = nullptr, const ShockCov& q = ShockCov{}, int k_shocks = 0,  // R folded into the filter, see below
                   const unsigned long long* colmask = nullptr,
                   int rerun_all = 0);  // 1: every launch is a second pass -- only the draws flagged DSGE_ST_INTERNAL_RERUN are filtered
 // launch_kalman_mf.hip: the tile-layout filter kernel (dsge_kalman_mf.hpp) in front of launch_kalman's cascade
-int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const double* Z, int z_batched, const double* d,
-                     int d_batched, const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                     dsge::FilterConv cv, double missing_fill, int n_state_hint, double* logp, int32_t* status, hipStream_t st,
-                     const int32_t* order, const double* Rsel, const double* qdiag, int q_batched, int k_shocks,
+int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, dsge::FilterConv cv,
+                     int n_state_hint, double* logp, int32_t* status, hipStream_t st, const int32_t* order, const double* Rsel, const ShockCov& q, int k_shocks,
                      const unsigned long long* colmask, int rerun_first, int* launched, bool* covers);
-int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const double* Z, int z_batched, const double* d,
-                          int d_batched, const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                          double jitter, double missing_fill, double* ll, double* a_pred, double* a_filt, double* p_pred,
-                          double* p_filt, int full_cov, int32_t* status, hipStream_t st);
+int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, double* ll,
+                          double* a_pred, double* a_filt, double* p_pred, double* p_filt, int full_cov, int32_t* status, hipStream_t st);
 // launch_smooth.hip (dsge_kalman_smooth.hpp): basis of range(P_pred) per draw (U, UT, UR: [batch] images of smoother_image_doubles(m)
 // doubles, rank: [batch]) and the backward pass over the stored outputs of launch_kalman_outputs (full covariances)
 size_t smoother_image_doubles(int m);
-int launch_kalman_smoother(const double* T, const double* R, const double* Q, int q_mode, int batch, int m, int k, int T_len,
+int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, int T_len,
                            double rank_tol, double* U, double* UT, double* UR, int32_t* rank, const double* a_pred, const double* a_filt,
                            const double* p_pred, const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov,
                            int32_t* status, hipStream_t st);
@@ -261,19 +281,16 @@ int launch_propagate(const double* T, const double* R, const double* shocks, lon
                      double* fevd_out, hipStream_t st);
 int launch_fevd(const double* irf, const double* weights, long long w_draw, const int32_t* status, int batch, int m, int c,
                 int n_steps, double* fevd_out, hipStream_t st);
-int launch_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
-                    int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0, const int32_t* status,
-                    int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out, int full_cov, double* y_out,
-                    double* f_out, hipStream_t st);
-// true if launch_kalman, given the selection matrix R and a diagonal Q (Rsel, qdiag), forms sym(R Q R')[U,U] inside the
+int launch_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, const double* P0,
+                    const int32_t* status, int batch, int m, int k, int n_steps, double* a_out, double* p_out, int full_cov,
+                    double* y_out, double* f_out, hipStream_t st);  // (of o: Z, d, Hdiag, p)
+// true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
 // launch_grad.hip: reverse sweep of the Kalman filter + reverse of the assembly (dsge_kalman_grad.hpp)
 int launch_persistence_key(const double* T, const int32_t* status, int batch, int n, int32_t* key, hipStream_t st);
-int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int z_batched, const double* d, int d_batched,
-                       const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                       double jitter, double missing_fill, int u_hint, double* store, double* logp, int32_t* status,
-                       double* Tbar, double* Gbar, double* dbar, double* hbar, hipStream_t st,
+int launch_kalman_grad(const double* T, const double* RQR, const ObsModel& o, int batch, int m, int u_hint, double* store,
+                       double* logp, int32_t* status, double* Tbar, double* Gbar, double* dbar, double* hbar, hipStream_t st,
                        int32_t* order_key = nullptr, int32_t* order_buf = nullptr);
 size_t kalman_grad_store_doubles_per_draw(int u_hint, int m, int T_len);
 int launch_grad_assemble(const double* B, const double* C, const double* T, const double* R, const double* q,
@@ -381,6 +398,116 @@ inline dsge::FilterConv filter_conv(double jitter) {
   cv.ll_mode = o.ll_constant;
   cv.mask_d = o.mask_d ? 1 : 0;
   return cv;
+}
+
+// ---- Argument checks, each written ONCE for a device entry (dsge_api.hip) and its host twin (api_host.hip): both run them before
+// their first HIP call and so report the same code and message.  `others`: no required pointer outside the two aggregates is null.
+inline int check_common(int batch, int n, int n_max) {
+  if (batch < 0) return fail(DSGE_ERR_INVALID, "batch < 0");
+  if (n < 1 || n > n_max) return fail(DSGE_ERR_INVALID, "n out of range (1.." + std::to_string(n_max) + ")");
+  return DSGE_SUCCESS;
+}
+// a filter call on a model of m <= m_max variables (`dim`: 'm' or 'n' in the messages) with 1 <= p <= p_max; `family` prefixes the
+// messages of an entry with caps of its own
+inline int check_filter(const char* family, int batch, int m, int m_max, char dim, int k, const ObsModel& o, int p_max,
+                        const ShockCov& q, bool others) {
+  const std::string pre = family;
+  int rc = check_common(batch, m, m_max);
+  if (rc) return rc;
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, std::string("k out of range (1..") + dim + ")");
+  if (o.p < 1 || o.p > p_max)
+    return fail(DSGE_ERR_INVALID, pre + "p out of range (1.." + (p_max == DSGE_MAX_P ? "DSGE_MAX_P" : std::to_string(p_max)) + ")");
+  if (o.T_len < 0) return fail(DSGE_ERR_INVALID, "T_len < 0");
+  if (q.mode < 0 || q.mode > 3) return fail(DSGE_ERR_INVALID, pre.empty() ? "bad q_mode" : pre + "q_batched is a DSGE_Q_* mode (0..3)");
+  if (!others || !q.Q || !o.Z || !o.y) return fail(DSGE_ERR_INVALID, "null pointer");
+  return DSGE_SUCCESS;
+}
+inline int check_kalman(int batch, int m, int k, const ObsModel& o, const ShockCov& q, bool others) {
+  return check_filter("", batch, m, DSGE_MAX_N, 'm', k, o, DSGE_MAX_P, q, others);
+}
+inline int check_smoother(int batch, int m, int k, const ObsModel& o, const ShockCov& q, bool others, bool any_output) {
+  int rc = check_kalman(batch, m, k, o, q, others);
+  if (rc) return rc;
+  return any_output ? DSGE_SUCCESS : fail(DSGE_ERR_INVALID, "no smoothed output requested");
+}
+inline int check_pipeline(int batch, int n, int k, const ObsModel& o, const ShockCov& q, int solver, bool others) {
+  solver &= ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;
+  const bool is_cr = solver == DSGE_SOLVER_CYCLE_REDUCTION || solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION;
+  // (gensys beyond 64 variables exists by spectral division only: dsge_options.gensys_doubling != 0)
+  const bool big_ok = is_cr || (solver == DSGE_SOLVER_GENSYS && opt().gensys_doubling != 0);
+  int rc = check_filter("", batch, n, big_ok ? DSGE_MAX_N_BIG : DSGE_MAX_N, 'n', k, o, DSGE_MAX_P, q, others);
+  if (rc) return rc;
+  if (!is_cr && solver != DSGE_SOLVER_BACKWARD_DIRECT && solver != DSGE_SOLVER_GENSYS) return fail(DSGE_ERR_INVALID, "unknown solver code");
+  return DSGE_SUCCESS;
+}
+inline int check_augmented(int batch, int n, int k, const ObsModel& o, const ShockCov& q, int solver, int m, int n_links, bool others) {
+  const bool is_cr = solver == DSGE_SOLVER_CYCLE_REDUCTION || solver == DSGE_SOLVER_SCAN_CYCLE_REDUCTION;
+  int rc = check_common(batch, n, is_cr ? DSGE_MAX_N_CR : DSGE_MAX_N);
+  if (rc) return rc;
+  if (m < n || m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_INVALID, "augmented state dimension m out of range (n..DSGE_MAX_N_BIG)");
+  if (n_links < 0) return fail(DSGE_ERR_INVALID, "n_links < 0");
+  if ((rc = check_filter("", batch, n, DSGE_MAX_N, 'n', k, o, DSGE_MAX_P, q, others))) return rc;
+  if (!is_cr && solver != DSGE_SOLVER_BACKWARD_DIRECT && solver != DSGE_SOLVER_GENSYS) return fail(DSGE_ERR_INVALID, "unknown solver code");
+  return DSGE_SUCCESS;
+}
+inline int check_grad(int batch, int n, int k, const ObsModel& o, const ShockCov& q, int solver, bool dense_z, bool others) {
+  int rc = check_common(batch, n, 56);
+  if (rc) return rc;
+  if (dense_z && n + o.p > 56) return fail(DSGE_ERR_INVALID, "gradient path with a dense design matrix: n + p must not exceed 56");
+  if ((rc = check_filter("gradient path: ", batch, n, 56, 'n', k, o, 8, q, others))) return rc;
+  if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_GENSYS && solver != DSGE_SOLVER_SCAN_CYCLE_REDUCTION)
+    return fail(DSGE_ERR_INVALID, "gradient path: solver must be cycle_reduction, scan_cycle_reduction or gensys");
+  return DSGE_SUCCESS;
+}
+// (S, L, U: the state / lead / retained index lists, host arrays in the entry and in its twin)
+inline int check_second_order(int batch, int n, int k, const ObsModel& o, const ShockCov& q, int solver, int nnz, const int32_t* S, int s,
+                              const int32_t* L, int l, const int32_t* U, int u, bool others) {
+  if (nnz < 0) return fail(DSGE_ERR_INVALID, "nnz < 0");
+  int rc = check_filter("second order: ", batch, n, DSGE_MAX_N_CR, 'n', k, o, 8, q, others && S && U && (l <= 0 || L));
+  if (rc) return rc;
+  if (s < 1 || s > 24) return fail(DSGE_ERR_INVALID, "second order: n_state out of range (1..24)");
+  if (l < 0 || l > n || u < s || u > n) return fail(DSGE_ERR_INVALID, "second order: n_lead / n_ret out of range");
+  if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_GENSYS)
+    return fail(DSGE_ERR_INVALID, "second order: solver must be cycle reduction or gensys");
+  for (int i = 0; i < s; ++i)
+    if (S[i] < 0 || S[i] >= n) return fail(DSGE_ERR_INVALID, "state_idx out of range");
+  for (int i = 0; i < l; ++i)
+    if (L[i] < 0 || L[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
+  for (int i = 0; i < u; ++i)
+    if (U[i] < 0 || U[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
+  return DSGE_SUCCESS;
+}
+// the dynamics entries (DSGE_ERR_TOO_LARGE: a well-formed call beyond a capacity)
+inline int check_simulate(const double* T, const double* R, const double* eps, int batch, int m, int k, int n_paths, int n_steps,
+                          int n_shock_steps, const double* x_out) {
+  if (batch < 0 || m < 1 || n_paths < 0 || n_steps < 0 || n_shock_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (n_shock_steps > n_steps) return fail(DSGE_ERR_INVALID, "n_shock_steps > n_steps");
+  if (!T || !R || !x_out || (!eps && n_shock_steps > 0)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "simulate: m exceeds DSGE_MAX_N_BIG");
+  return DSGE_SUCCESS;
+}
+inline int check_irf(const double* T, const double* R, const double* S, int batch, int m, int k, int c, int n_steps,
+                     const double* irf_out, const double* fevd_out) {
+  if (batch < 0 || m < 1 || c < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (!S && c != k) return fail(DSGE_ERR_INVALID, "S == NULL means S = I: c must equal k");
+  if (!T || !R) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!irf_out && !fevd_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "impulse responses: m exceeds DSGE_MAX_N_BIG");
+  return DSGE_SUCCESS;
+}
+inline int check_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, int batch, int m,
+                          int k, int n_steps, const double* a_out, const double* p_out, const double* y_out, const double* f_out) {
+  const int p = o.p;
+  if (batch < 0 || m < 1 || p < 0 || n_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (q.mode < 0 || q.mode > 3) return fail(DSGE_ERR_INVALID, "bad q_mode");
+  if (!a_out && !p_out && !y_out && !f_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (!T || !R || !a0 || ((p_out || f_out) && !q.Q) || (p > 0 && !o.Z)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if ((y_out || f_out) && p == 0) return fail(DSGE_ERR_INVALID, "observation outputs requested with p == 0");
+  if (m > DSGE_MAX_N || p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "forecast: m exceeds DSGE_MAX_N or p exceeds DSGE_MAX_P");
+  return DSGE_SUCCESS;
 }
 
 }  // namespace dsge_host

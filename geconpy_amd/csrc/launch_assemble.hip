@@ -7,26 +7,55 @@
 
 namespace dsge_host {
 
+namespace {
+// what assemble_kernel understands: do_selection = 0 | 1 and one of these (the comment at its head, dsge_kernels.hpp)
+enum AsmLyapunov { LYAP_NONE = 0, LYAP_RQR_P0 = 1, LYAP_RQR = 2, LYAP_P0_FLAGGED = 3, LYAP_P0_ALL = 4 };
+
 int launch_assemble(const double* A, const double* B, const double* C, const double* D, const double* T,
-                    const double* R_in, const double* Q, int q_mode, int batch, int n, int k, double* R_out,
-                    double* resid_out, double* RQR_out, double* P0_out, int32_t* status, int do_sel, int do_lyap,
-                    hipStream_t st, const int32_t* only_marked) {
+                    const double* R_in, const ShockCov& q, int batch, int n, int k, double* R_out, double* resid_out,
+                    double* RQR_out, double* P0_out, int32_t* status, int do_sel, AsmLyapunov do_lyap, hipStream_t st,
+                    const int32_t* only_marked = nullptr) {
   const int bs = tile_bs(n);
   int rc = DSGE_ERR_INVALID;
   DISPATCH_BS(bs, 8, {
     rc = set_lds(dsge::assemble_kernel<BS>, dsge::AsmSmem<BS>::bytes);
     // sym(R Q R') alone needs the two column groups of W only (see the kernel)
     // ... and the selection without a doubling iteration M1 + W (the Gauss-Jordan scratch moves into M1)
-    const size_t lds = (!do_sel && do_lyap == 2) ? sizeof(double) * dsge::AsmSmem<BS>::NP * dsge::AsmSmem<BS>::LDW
-                       : (do_sel && (do_lyap == 0 || do_lyap == 2))
+    const size_t lds = (!do_sel && do_lyap == LYAP_RQR) ? sizeof(double) * dsge::AsmSmem<BS>::NP * dsge::AsmSmem<BS>::LDW
+                       : (do_sel && (do_lyap == LYAP_NONE || do_lyap == LYAP_RQR))
                            ? sizeof(double) * dsge::AsmSmem<BS>::NP * (dsge::AsmSmem<BS>::LD + dsge::AsmSmem<BS>::LDW)
                            : dsge::AsmSmem<BS>::bytes;
     if (rc == DSGE_SUCCESS) {
-      hipLaunchKernelGGL(dsge::assemble_kernel<BS>, dim3(do_lyap == 3 ? rerun_grid(batch) : batch), dim3(64), lds, st, A, B, C, D, T, R_in, Q, q_mode, batch, n, k, R_out, resid_out, RQR_out, P0_out, status, do_sel, do_lyap, only_marked);
+      hipLaunchKernelGGL(dsge::assemble_kernel<BS>, dim3(do_lyap == LYAP_P0_FLAGGED ? rerun_grid(batch) : batch), dim3(64), lds, st, A, B, C, D, T, R_in, q.Q, q.mode, batch, n, k, R_out, resid_out, RQR_out, P0_out, status, do_sel, (int)do_lyap, only_marked);
       HIP_TRY(hipGetLastError());
     }
   });
   return rc;
+}
+}  // namespace
+
+int assemble_selection(const double* A, const double* B, const double* C, const double* D, const double* T, int batch, int n, int k,
+                       double* R_out, double* resid_out, int32_t* status, hipStream_t st, const int32_t* only_marked) {
+  return launch_assemble(A, B, C, D, T, nullptr, ShockCov{}, batch, n, k, R_out, resid_out, nullptr, nullptr, status, 1, LYAP_NONE,
+                         st, only_marked);
+}
+int assemble_rqr(const double* R, const ShockCov& q, int batch, int n, int k, double* RQR_out, int32_t* status, hipStream_t st) {
+  return launch_assemble(nullptr, nullptr, nullptr, nullptr, nullptr, R, q, batch, n, k, nullptr, nullptr, RQR_out, nullptr, status,
+                         0, LYAP_RQR, st);
+}
+int assemble_rqr_p0(const double* T, const double* R, const ShockCov& q, int batch, int n, int k, double* RQR_out, double* P0_out,
+                    int32_t* status, hipStream_t st) {
+  return launch_assemble(nullptr, nullptr, nullptr, nullptr, T, R, q, batch, n, k, nullptr, nullptr, RQR_out, P0_out, status, 0,
+                         LYAP_RQR_P0, st);
+}
+int assemble_selection_rqr(const double* A, const double* B, const double* C, const double* D, const double* T, const ShockCov& q,
+                           int batch, int n, int k, double* R_out, double* resid_out, double* RQR_out, int32_t* status, hipStream_t st) {
+  return launch_assemble(A, B, C, D, T, nullptr, q, batch, n, k, R_out, resid_out, RQR_out, nullptr, status, 1, LYAP_RQR, st);
+}
+int assemble_p0_from_rqr(const double* T, double* RQR, int batch, int n, double* P0_out, int32_t* status, bool flagged_only,
+                         hipStream_t st) {
+  return launch_assemble(nullptr, nullptr, nullptr, nullptr, T, nullptr, ShockCov{}, batch, n, 1, nullptr, nullptr, RQR, P0_out,
+                         status, 0, flagged_only ? LYAP_P0_FLAGGED : LYAP_P0_ALL, st);
 }
 
 int launch_rqr(const double* R, const double* q, int q_batched, int batch, int n, int k, const int32_t* status,

@@ -40,15 +40,14 @@ int launch_fevd(const double* irf, const double* weights, long long w_draw, cons
   return DSGE_SUCCESS;
 }
 
-int launch_forecast(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched, const double* d,
-                    int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0, const int32_t* status,
-                    int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out, int full_cov, double* y_out,
-                    double* f_out, hipStream_t st) {
+int launch_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, const double* P0,
+                    const int32_t* status, int batch, int m, int k, int n_steps, double* a_out, double* p_out, int full_cov,
+                    double* y_out, double* f_out, hipStream_t st) {
   dsge::FcArgs a{};
-  a.T = T; a.R = R; a.Q = Q; a.Z = Z; a.d = d; a.Hdiag = Hdiag; a.a0 = a0; a.P0 = P0; a.status = status; a.a_out = a_out;
-  a.p_out = p_out; a.y_out = y_out; a.f_out = f_out; a.batch = batch; a.m = m; a.k = k; a.p = p; a.n_steps = n_steps;
-  a.q_mode = q_mode; a.z_batched = z_batched; a.d_batched = d_batched; a.h_batched = h_batched; a.full_cov = full_cov;
-  const size_t lds = dsge::fc_lds_doubles(m, p) * sizeof(double);
+  a.T = T; a.R = R; a.Q = q.Q; a.Z = o.Z; a.d = o.d; a.Hdiag = o.Hdiag; a.a0 = a0; a.P0 = P0; a.status = status; a.a_out = a_out;
+  a.p_out = p_out; a.y_out = y_out; a.f_out = f_out; a.batch = batch; a.m = m; a.k = k; a.p = o.p; a.n_steps = n_steps;
+  a.q_mode = q.mode; a.z_batched = o.z_batched; a.d_batched = o.d_batched; a.h_batched = o.h_batched; a.full_cov = full_cov;
+  const size_t lds = dsge::fc_lds_doubles(m, o.p) * sizeof(double);
   if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "forecast: LDS budget exceeded");
   int rc;
   if ((rc = set_lds(dsge::dynamics_forecast_kernel, lds))) return rc;

@@ -21,11 +21,9 @@ static_assert(dsge::KgRec<3>::per_draw(200) == (size_t)200 * (24 * 24 + 24 * 8 +
                   dsge::KgRec<7>::per_draw(5) == (size_t)5 * (56 * 56 + 56 * 8 + 128 + 56 + 2) + 56 * 56 + (16 + 56 + 8 + 64 * 57),
               "kalman_grad_store_doubles_per_draw and KgRec describe the same record");
 
-int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int z_batched, const double* d, int d_batched,
-                       const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                       double jitter, double missing_fill, int u_hint, double* store, double* logp, int32_t* status,
-                       double* Tbar, double* Gbar, double* dbar, double* hbar, hipStream_t st, int32_t* order_key,
-                       int32_t* order_buf) {
+int launch_kalman_grad(const double* T, const double* RQR, const ObsModel& o, int batch, int m, int u_hint, double* store,
+                       double* logp, int32_t* status, double* Tbar, double* Gbar, double* dbar, double* hbar, hipStream_t st,
+                       int32_t* order_key, int32_t* order_buf) {
   const int bs = grad_tile(u_hint, m);
   int rc = DSGE_ERR_INVALID;
   const int32_t* order = nullptr;
@@ -34,7 +32,7 @@ int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int 
     HIP_TRY(hipGetLastError());
     order = order_buf;
   }
-  const dsge::FilterConv cv = filter_conv(jitter);
+  const dsge::FilterConv cv = filter_conv(o.jitter);
   const double stol = opt().kalman_steady_tol;
   DISPATCH_BS(bs, 8, {
     const size_t lds = dsge::KgSmem<BS>::bytes;
@@ -47,7 +45,7 @@ int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int 
     // (under the phase-stamp hook the split path runs too when DSGE_DBG_SPLIT_PHASES is set: the reverse sweep's stamps of draw 0 then
     //  come from kalman_grad_kernel<BS, true>; tools/grad_phases.py reads the one-kernel path's stamps otherwise)
     static const bool dbg_split = std::getenv("DSGE_DBG_SPLIT_PHASES") != nullptr;
-    const bool split = opt().kalman_grad_split != 0 && (!g_kalman_dbg || dbg_split) && p <= 8 && lds_f <= LDS_LIMIT;
+    const bool split = opt().kalman_grad_split != 0 && (!g_kalman_dbg || dbg_split) && o.p <= 8 && lds_f <= LDS_LIMIT;
     if (split) {
       rc = set_lds(dsge::kalman_nt_kernel<BS, false, 8 * BS, false, true>, lds_f);
       if (rc == DSGE_SUCCESS) rc = set_lds(dsge::kalman_grad_kernel<BS, true>, lds);
@@ -66,8 +64,8 @@ int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int 
           rc = set_lds(dsge::kalman_mf_kernel<5, 5, false, true, 3>, SMF::bytes);
           if (rc == DSGE_SUCCESS) {
             hipLaunchKernelGGL((dsge::kalman_mf_kernel<5, 5, false, true, 3>), dim3(batch), dim3(64), SMF::bytes, st, T, RQR,
-                               (const double*)nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, cv,
-                               missing_fill, stol, logp, status, (long long*)nullptr, 0, steps_key, order,
+                               (const double*)nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv,
+                               o.missing_fill, stol, logp, status, (long long*)nullptr, 0, steps_key, order,
                                (const double*)nullptr, (const double*)nullptr, 0, 0, (const unsigned long long*)nullptr, store);
             nt_rerun = 1;
           }
@@ -75,33 +73,36 @@ int launch_kalman_grad(const double* T, const double* RQR, const double* Z, int 
       }
       if (rc == DSGE_SUCCESS) {
         hipLaunchKernelGGL((dsge::kalman_nt_kernel<BS, false, 8 * BS, false, true>), dim3(batch), dim3(64), lds_f, st, T, RQR,
-                           (const double*)nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, 8 * BS, cv,
-                           missing_fill, stol, logp, status, (long long*)nullptr, nt_rerun, steps_key, order,
+                           (const double*)nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, 8 * BS, cv,
+                           o.missing_fill, stol, logp, status, (long long*)nullptr, nt_rerun, steps_key, order,
                            (const double*)nullptr, (const double*)nullptr, 0, 0, (const unsigned long long*)nullptr,
                            (double*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr, store);
         // the reverse mean side of every draw's LAST steady segment at two wavefronts per SIMD (kalman_grad_tail_kernel); the
         // reverse sweep then starts at that segment's source step (kalman_grad_split = 2; the default is 1: without it)
         if (steps_key) {
           hipLaunchKernelGGL(dsge::kalman_order_kernel<1024>, dim3(1), dim3(1024), 0, st, (const int32_t*)steps_key, batch, order_buf,
-                             T_len);
+                             o.T_len);
         }
         const int with_tail = opt().kalman_grad_split >= 2;
         if (with_tail)
-          hipLaunchKernelGGL((dsge::kalman_grad_tail_kernel<BS>), dim3(batch), dim3(64), 0, st, T, Z, z_batched, d, d_batched, y,
-                             batch, m, p, T_len, cv, missing_fill, store, (const int32_t*)status, order);
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, true>), dim3(batch), dim3(64), lds, st, T, RQR, Z, z_batched, d, d_batched,
-                           Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
+          hipLaunchKernelGGL((dsge::kalman_grad_tail_kernel<BS>), dim3(batch), dim3(64), 0, st, T, o.Z, o.z_batched, o.d,
+                             o.d_batched, o.y,
+                             batch, m, o.p, o.T_len, cv, o.missing_fill, store, (const int32_t*)status, order);
+        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, true>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
+                           o.d_batched,
+                           o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
                            hbar, g_kalman_dbg, order, 0, with_tail);
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, Z, z_batched, d,
-                           d_batched, Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, stol, store, logp, status, Tbar, Gbar,
+        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
+                           o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar,
                            dbar, hbar, (long long*)nullptr, (const int32_t*)nullptr, 1, 0);
         HIP_TRY(hipGetLastError());
       }
     } else {
       rc = set_lds(dsge::kalman_grad_kernel<BS, false>, lds);
       if (rc == DSGE_SUCCESS) {
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, Z, z_batched, d, d_batched,
-                           Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
+        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
+                           o.d_batched,
+                           o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
                            hbar, g_kalman_dbg, order, 0, 0);
         HIP_TRY(hipGetLastError());
       }

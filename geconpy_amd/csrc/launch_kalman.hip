@@ -52,14 +52,12 @@ bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint
   return (size_t)m * kp <= (size_t)np * (np + 2);
 }
 
-int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const double* Z, int z_batched,
-                  const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
-                  int m, int p, int T_len, double jitter, double missing_fill, int n_state_hint, int z_selector_hint,
-                  double* logp, int32_t* status, hipStream_t st, const int32_t* order_key, const double* Rsel,
-                  const double* qdiag, int q_batched, int k_shocks, const unsigned long long* colmask, int rerun_all) {
+int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const ObsModel& o, int batch, int m, int n_state_hint,
+                  int z_selector_hint, double* logp, int32_t* status, hipStream_t st, const int32_t* order_key, const double* Rsel,
+                  const ShockCov& q, int k_shocks, const unsigned long long* colmask, int rerun_all) {
   const int bs = tile_bs(m);
-  const dsge::FilterConv cv = filter_conv(jitter);  // the call's jitter + the conventions of dsge_options
-  const bool fold = Rsel && qdiag && kalman_folds_rqr(m, p, k_shocks, n_state_hint, z_selector_hint);
+  const dsge::FilterConv cv = filter_conv(o.jitter);  // the call's jitter + the conventions of dsge_options
+  const bool fold = Rsel && q.Q && kalman_folds_rqr(m, o.p, k_shocks, n_state_hint, z_selector_hint);
   if (Rsel && !fold) return fail(DSGE_ERR_INVALID, "launch_kalman: R given but the filter kernel cannot form R Q R' itself");
   int rc = DSGE_ERR_INVALID;
   // Fast path: selector Z, p <= 8, compact state block of at most s_cap columns.  Draws that
@@ -67,19 +65,21 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
   // Fast path (p <= 8): compact state block of at most s_cap columns; selector Z (gathers) or dense
   // Z (one extra product per step).  Draws that violate a hint come back flagged and are re-run by
   // the general kernel below.
-  const bool fast = p <= 8;
+  const bool fast = o.p <= 8;
   bool launched_fast = rerun_all != 0;  // (rerun_all: every launch below is a second pass on the flagged draws)
   // Small models (reduced filter of at most 6 variables, p <= 3, selector Z): one thread per draw, all in
   // registers.  Draws that do not fit are flagged and fall through to the wave-per-draw cascade below.
-  if (opt().kalman_tiny && z_selector_hint && p <= 3 && n_state_hint > 0 && n_state_hint + p <= 6 && !rerun_all) {
+  if (opt().kalman_tiny && z_selector_hint && o.p <= 3 && n_state_hint > 0 && n_state_hint + o.p <= 6 && !rerun_all) {
     const int blocks = (batch + 63) / 64;
-    if (n_state_hint + p <= 4) {
-      hipLaunchKernelGGL((dsge::kalman_tiny_kernel<4, 3>), dim3(blocks), dim3(64), 0, st, T, RQR, Z, z_batched, d, d_batched,
-                         Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, opt().kalman_steady_tol, logp, status,
+    if (n_state_hint + o.p <= 4) {
+      hipLaunchKernelGGL((dsge::kalman_tiny_kernel<4, 3>), dim3(blocks), dim3(64), 0, st, T, RQR, o.Z, o.z_batched, o.d,
+                         o.d_batched,
+                         o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, opt().kalman_steady_tol, logp, status,
                          g_kalman_steady_at);
     } else {
-      hipLaunchKernelGGL((dsge::kalman_tiny_kernel<6, 3>), dim3(blocks), dim3(64), 0, st, T, RQR, Z, z_batched, d, d_batched,
-                         Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, opt().kalman_steady_tol, logp, status,
+      hipLaunchKernelGGL((dsge::kalman_tiny_kernel<6, 3>), dim3(blocks), dim3(64), 0, st, T, RQR, o.Z, o.z_batched, o.d,
+                         o.d_batched,
+                         o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, opt().kalman_steady_tol, logp, status,
                          g_kalman_steady_at);
     }
     HIP_TRY(hipGetLastError());
@@ -91,7 +91,7 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
   int32_t* tail_flag = nullptr;
   int32_t* tail_from = nullptr;
   int32_t* order = nullptr;
-  const bool want_tail = fast && z_selector_hint && opt().kalman_block && T_len >= 8;
+  const bool want_tail = fast && z_selector_hint && opt().kalman_block && o.T_len >= 8;
   const bool want_order = fast && order_key && opt().kalman_order && batch >= 512;
   if (want_tail || want_order) {
     void* base = nullptr;
@@ -104,7 +104,7 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
       tail_from = ints + batch;
       tail_rec = (double*)((char*)base + int_bytes);
       HIP_TRY(hipMemsetAsync(tail_flag, 0, ((size_t)batch + 1) * sizeof(int32_t), st));
-      hipLaunchKernelGGL(dsge::kalman_mask_scan_kernel, dim3(1), dim3(64), 0, st, y, p, T_len, missing_fill, tail_from);
+      hipLaunchKernelGGL(dsge::kalman_mask_scan_kernel, dim3(1), dim3(64), 0, st, o.y, o.p, o.T_len, o.missing_fill, tail_from);
     }
     if (want_order) {
       order = ints + batch + 1;
@@ -118,13 +118,13 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
     // kalman_block = 2: the two-step kernel of round 2 (kept for comparison)
     if (opt().kalman_block == 2) {
       hipLaunchKernelGGL(dsge::kalman_tail_kernel, dim3(batch), dim3(64), 0, ts, (const double*)tail_rec,
-                         (int32_t*)tail_flag, y, batch, p, T_len, missing_fill, logp, status, g_kalman_steady_at, cv);
+                         (int32_t*)tail_flag, o.y, batch, o.p, o.T_len, o.missing_fill, logp, status, g_kalman_steady_at, cv);
     } else {
       const int bs_lo = tile_bs((z_selector_hint && n_state_hint > 0 && n_state_hint < m) ? n_state_hint : m);
-      const int bs_hi = tile_bs((z_selector_hint && n_state_hint > 0 && n_state_hint + p < m) ? n_state_hint + p : m);
+      const int bs_hi = tile_bs((z_selector_hint && n_state_hint > 0 && n_state_hint + o.p < m) ? n_state_hint + o.p : m);
 #define LAUNCH_TAIL4(MCV)                                                                                                     \
   hipLaunchKernelGGL((dsge::kalman_tail4_kernel<MCV>), dim3(batch), dim3(64), 0, ts, (const double*)tail_rec,                 \
-                     (int32_t*)tail_flag, y, batch, p, T_len, missing_fill, logp, status, g_kalman_steady_at, cv, m_lo)
+                     (int32_t*)tail_flag, o.y, batch, o.p, o.T_len, o.missing_fill, logp, status, g_kalman_steady_at, cv, m_lo)
       for (int b = bs_lo; b <= bs_hi && b <= 4; ++b) {
         const int m_lo = (b == bs_lo) ? 0 : 8 * (b - 1);  // (the narrowest instance also takes the draws that are smaller than its tile)
         if (b <= 1)
@@ -146,9 +146,8 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
   if (fast && z_selector_hint && opt().kalman_mfma == 2 && opt().kalman_nt_products && !want_tail && opt().kalman_head_draws == 0 &&
       n_state_hint >= 9 && n_state_hint <= 20 && (!launched_fast || rerun_all)) {
     int launched = 0;
-    if ((rc = launch_kalman_mf(T, RQR, p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, cv,
-                               missing_fill, n_state_hint, logp, status, st, order, fold ? Rsel : nullptr, qdiag, q_batched, k_shocks,
-                               colmask, rerun_all, &launched, &mf_covers)))
+    if ((rc = launch_kalman_mf(T, RQR, p0_valid ? P0 : nullptr, o, batch, m, cv, n_state_hint, logp, status, st, order,
+                               fold ? Rsel : nullptr, q, k_shocks, colmask, rerun_all, &launched, &mf_covers)))
       return rc;
     launched_fast = launched_fast || launched > 0;
   }
@@ -162,7 +161,7 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
     int n_tiles = 0;
     if (z_selector_hint && n_state_hint > 0 && n_state_hint < m) {
       tiles[n_tiles++] = tile_bs(n_state_hint);
-      const int hi = tile_bs(n_state_hint + p < m ? n_state_hint + p : m);
+      const int hi = tile_bs(n_state_hint + o.p < m ? n_state_hint + o.p : m);
       if (hi != tiles[0]) tiles[n_tiles++] = hi;
     } else {
       tiles[n_tiles++] = tile_bs(m);
@@ -183,8 +182,8 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
               rc = set_lds(dsge::kalman_sel_kernel<BS, true, true>, lds);
               if (rc == DSGE_SUCCESS) {
                 hipLaunchKernelGGL((dsge::kalman_sel_kernel<BS, true, true>), dim3(rerun ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR,
-                                   p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p,
-                                   T_len, s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
+                                   p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p,
+                                   o.T_len, s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
                                    g_kalman_steady_at, nullptr, nullptr, nullptr, order);
                 HIP_TRY(hipGetLastError());
                 launched_fast = true;
@@ -196,8 +195,8 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
             rc = set_lds(dsge::kalman_sel_kernel<BS, true, false, true>, lds);
             if (rc == DSGE_SUCCESS) {
               hipLaunchKernelGGL((dsge::kalman_sel_kernel<BS, true, false, true>), dim3(rerun ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR,
-                                 p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len,
-                                 s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
+                                 p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len,
+                                 s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
                                  g_kalman_steady_at, tail_rec, tail_flag, tail_from, order);
               HIP_TRY(hipGetLastError());
               launched_fast = true;
@@ -218,9 +217,9 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                   rc = set_lds(dsge::kalman_nt2_kernel<BS, SKV, true>, lds2);
                   if (rc == DSGE_SUCCESS)
                     hipLaunchKernelGGL((dsge::kalman_nt2_kernel<BS, SKV, true>), dim3(batch), dim3(128), lds2, st, T, RQR,
-                                       p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len,
-                                       s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, rerun, g_kalman_steady_at,
-                                       order, fold ? Rsel : nullptr, qdiag, q_batched, k_shocks, colmask, g_kalman_dbg);
+                                       p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len,
+                                       s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, rerun, g_kalman_steady_at,
+                                       order, fold ? Rsel : nullptr, q.Q, q.batched(), k_shocks, colmask, g_kalman_dbg);
                   return;
                 }
               }
@@ -228,9 +227,9 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                 rc = set_lds(dsge::kalman_nt_kernel<BS, true, SKV>, lds_q);
                 if (rc == DSGE_SUCCESS)
                   hipLaunchKernelGGL((dsge::kalman_nt_kernel<BS, true, SKV>), dim3(batch), dim3(64), lds_q,
-                                     st, T, RQR, p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m,
-                                     p, T_len, s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg,
-                                     rerun, g_kalman_steady_at, order, fold ? Rsel : nullptr, qdiag, q_batched, k_shocks, colmask);
+                                     st, T, RQR, p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m,
+                                     o.p, o.T_len, s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg,
+                                     rerun, g_kalman_steady_at, order, fold ? Rsel : nullptr, q.Q, q.batched(), k_shocks, colmask);
                 return;
               }
               // Head of the dispatch order on the two-wavefront kernel (dsge_kalman_nt2.hpp), on a second stream next to the bulk:
@@ -259,9 +258,9 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                   const size_t lds2 = dsge::Knt2Smem<BS, SKV>::bytes(s_cap);
                   if ((rc = set_lds(dsge::kalman_nt2_kernel<BS, SKV>, lds2))) return;
                   hipLaunchKernelGGL((dsge::kalman_nt2_kernel<BS, SKV>), dim3(head), dim3(128), lds2, st, T, RQR,
-                                     p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, head, m, p, T_len,
-                                     s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, rerun, g_kalman_steady_at,
-                                     order, fold ? Rsel : nullptr, qdiag, q_batched, k_shocks, colmask, nullptr);
+                                     p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, head, m, o.p, o.T_len,
+                                     s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, rerun, g_kalman_steady_at,
+                                     order, fold ? Rsel : nullptr, q.Q, q.batched(), k_shocks, colmask, nullptr);
                 }
               }
               rc = DSGE_SUCCESS;
@@ -269,10 +268,10 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                 rc = set_lds(dsge::kalman_nt_kernel<BS, false, SKV, TAILV>, lds_q);
                 if (rc == DSGE_SUCCESS)
                   hipLaunchKernelGGL((dsge::kalman_nt_kernel<BS, false, SKV, TAILV>), dim3(batch - head), dim3(64), lds_q,
-                                     bulk_st, T, RQR, p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y,
-                                     batch - head, m, p, T_len, s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status,
+                                     bulk_st, T, RQR, p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y,
+                                     batch - head, m, o.p, o.T_len, s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status,
                                      g_kalman_timeline, rerun, g_kalman_steady_at, order ? order + head : nullptr, fold ? Rsel : nullptr,
-                                     qdiag, q_batched, k_shocks, colmask, TAILV ? tail_rec : nullptr, tail_flag, tail_from);
+                                     q.Q, q.batched(), k_shocks, colmask, TAILV ? tail_rec : nullptr, tail_flag, tail_from);
               }
               if (hs && TAILV && rc == DSGE_SUCCESS) rc = launch_tail(hs->stream());  // the bulk's tails next to the head, not behind it
               // join: everything later on the caller's stream waits for the bulk (after an error: by the guard, which keeps it)
@@ -304,8 +303,8 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
             rc = set_lds(dsge::kalman_sel_kernel<BS, true>, lds);
             if (rc == DSGE_SUCCESS) {
               hipLaunchKernelGGL((dsge::kalman_sel_kernel<BS, true>), dim3(rerun ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR,
-                                 p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len,
-                                 s_cap, cv, missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
+                                 p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len,
+                                 s_cap, cv, o.missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
                                  g_kalman_steady_at, nullptr, nullptr, nullptr, order);
               HIP_TRY(hipGetLastError());
               launched_fast = true;
@@ -319,8 +318,8 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
             rc = set_lds(dsge::kalman_sel_kernel<BS, false>, lds);
             if (rc == DSGE_SUCCESS) {
               hipLaunchKernelGGL((dsge::kalman_sel_kernel<BS, false>), dim3(rerun ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR,
-                                 p0_valid ? P0 : nullptr, Z, z_batched, d, d_batched, Hdiag, h_batched, y, batch, m, p, T_len, s_cap,
-                                 cv, missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
+                                 p0_valid ? P0 : nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, s_cap,
+                                 cv, o.missing_fill, opt().kalman_steady_tol, logp, status, g_kalman_dbg, rerun,
                                  g_kalman_steady_at, nullptr, nullptr, nullptr, order);
               HIP_TRY(hipGetLastError());
               launched_fast = true;
@@ -335,22 +334,21 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
     if ((rc = launch_tail(st))) return rc;
   }
   if (fold) {  // the general kernel's inputs for the draws the fast kernel handed on: their sym(R Q R') after all
-    if ((rc = launch_rqr(Rsel, qdiag, q_batched, batch, m, k_shocks, status, RQR, st, 1))) return rc;
+    if ((rc = launch_rqr(Rsel, q.Q, q.batched(), batch, m, k_shocks, status, RQR, st, 1))) return rc;
   }
   if (!p0_valid) {
     // full-size P0 for the general kernel: flagged draws only when a fast kernel ran, else every draw
-    if ((rc = launch_assemble(nullptr, nullptr, nullptr, nullptr, T, nullptr, nullptr, 0, batch, m, 1, nullptr, nullptr,
-                              RQR, P0, status, 0, launched_fast ? 3 : 4, st)))
-      return rc;
+    if ((rc = assemble_p0_from_rqr(T, RQR, batch, m, P0, status, launched_fast, st))) return rc;
   }
   rc = DSGE_ERR_INVALID;
   DISPATCH_BS(bs, 8, {
-    const size_t lds = dsge::KfSmem<BS>::bytes(p);
+    const size_t lds = dsge::KfSmem<BS>::bytes(o.p);
     rc = set_lds(dsge::kalman_kernel<BS>, lds);
     if (rc == DSGE_SUCCESS) {
-      hipLaunchKernelGGL(dsge::kalman_kernel<BS>, dim3(launched_fast ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR, P0, Z,
-                         z_batched, d,
-                         d_batched, Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, logp, status,
+      hipLaunchKernelGGL(dsge::kalman_kernel<BS>, dim3(launched_fast ? rerun_grid(batch) : batch), dim3(64), lds, st, T, RQR, P0,
+                         o.Z,
+                         o.z_batched, o.d,
+                         o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, logp, status,
                          launched_fast ? 1 : 0);
       HIP_TRY(hipGetLastError());
     }
@@ -359,16 +357,15 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
 }
 
 // per-step filter outputs (dsge_kalman_out.hpp)
-int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const double* Z, int z_batched, const double* d,
-                          int d_batched, const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                          double jitter, double missing_fill, double* ll, double* a_pred, double* a_filt, double* p_pred,
-                          double* p_filt, int full_cov, int32_t* status, hipStream_t st) {
+int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, double* ll,
+                          double* a_pred, double* a_filt, double* p_pred, double* p_filt, int full_cov, int32_t* status,
+                          hipStream_t st) {
   dsge::KoArgs a{};
-  a.T = T; a.RQR = RQR; a.P0 = P0; a.Z = Z; a.d = d; a.Hdiag = Hdiag; a.y = y; a.ll = ll; a.a_pred = a_pred; a.a_filt = a_filt;
-  a.p_pred = p_pred; a.p_filt = p_filt; a.status = status; a.batch = batch; a.m = m; a.p = p; a.T_len = T_len;
-  a.z_batched = z_batched; a.d_batched = d_batched; a.h_batched = h_batched; a.full_cov = full_cov; a.cv = filter_conv(jitter);
-  a.missing_fill = missing_fill;
-  const size_t lds = dsge::ko_lds_doubles(m, p) * sizeof(double);
+  a.T = T; a.RQR = RQR; a.P0 = P0; a.Z = o.Z; a.d = o.d; a.Hdiag = o.Hdiag; a.y = o.y; a.ll = ll; a.a_pred = a_pred; a.a_filt = a_filt;
+  a.p_pred = p_pred; a.p_filt = p_filt; a.status = status; a.batch = batch; a.m = m; a.p = o.p; a.T_len = o.T_len;
+  a.z_batched = o.z_batched; a.d_batched = o.d_batched; a.h_batched = o.h_batched; a.full_cov = full_cov; a.cv = filter_conv(o.jitter);
+  a.missing_fill = o.missing_fill;
+  const size_t lds = dsge::ko_lds_doubles(m, o.p) * sizeof(double);
   int rc;
   if ((rc = set_lds(dsge::kalman_outputs_kernel, lds))) return rc;
   hipLaunchKernelGGL(dsge::kalman_outputs_kernel, dim3(batch), dim3(dsge::KO_THREADS), lds, st, a);

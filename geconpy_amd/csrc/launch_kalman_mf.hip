@@ -17,10 +17,8 @@ namespace dsge_host {
 //   variables than the hint, a design matrix that is no selector -- the VALU fast kernels refuse too (their state-block capacity
 //   comes from the same hint, and with s <= 20, p <= 8 no draw has more than 28 retained variables): the caller then skips that
 //   cascade's empty second passes (~5 us each) and a refused draw goes straight to the general kernel.
-int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const double* Z, int z_batched, const double* d,
-                     int d_batched, const double* Hdiag, int h_batched, const double* y, int batch, int m, int p, int T_len,
-                     dsge::FilterConv cv, double missing_fill, int n_state_hint, double* logp, int32_t* status, hipStream_t st,
-                     const int32_t* order, const double* Rsel, const double* qdiag, int q_batched, int k_shocks,
+int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, dsge::FilterConv cv,
+                     int n_state_hint, double* logp, int32_t* status, hipStream_t st, const int32_t* order, const double* Rsel, const ShockCov& q, int k_shocks,
                      const unsigned long long* colmask, int rerun_first, int* launched, bool* covers) {
   *launched = 0;
   *covers = false;
@@ -33,17 +31,18 @@ int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const
     if (r_doubles > (size_t)SMF::WT) return DSGE_SUCCESS;  // the staged selection matrix does not fit this instance's W' buffer
     int rc2;
     if ((rc2 = set_lds(dsge::kalman_mf_kernel<KTV, TMV, DBGV>, SMF::bytes))) return rc2;
-    hipLaunchKernelGGL((dsge::kalman_mf_kernel<KTV, TMV, DBGV>), dim3(batch), dim3(64), SMF::bytes, st, T, RQR, P0, Z, z_batched, d,
-                       d_batched, Hdiag, h_batched, y, batch, m, p, T_len, cv, missing_fill, opt().kalman_steady_tol, logp, status,
-                       DBGV ? g_kalman_dbg : (long long*)nullptr, (n_mf > 0 || rerun_first) ? 1 : 0, g_kalman_steady_at, order, Rsel, qdiag, q_batched,
-                       k_shocks, colmask);
+    hipLaunchKernelGGL((dsge::kalman_mf_kernel<KTV, TMV, DBGV>), dim3(batch), dim3(64), SMF::bytes, st, T, RQR, P0, o.Z,
+                       o.z_batched,
+                       o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, opt().kalman_steady_tol, logp,
+                       status, DBGV ? g_kalman_dbg : (long long*)nullptr, (n_mf > 0 || rerun_first) ? 1 : 0, g_kalman_steady_at, order,
+                       Rsel, q.Q, q.batched(), k_shocks, colmask);
     HIP_TRY(hipGetLastError());
     ++n_mf;
     return DSGE_SUCCESS;
   };
   using std::integral_constant;
   const int kt = (n_state_hint + 3) / 4;
-  const bool wide = n_state_hint + p > 4 * kt && n_state_hint < m;  // observed non-states may exceed the KT x KT instance
+  const bool wide = n_state_hint + o.p > 4 * kt && n_state_hint < m;  // observed non-states may exceed the KT x KT instance
   int rc = DSGE_SUCCESS;
   if (g_kalman_dbg) {  // (tools/kalman_phases.py: the stamped instance of the SW-shaped size)
     if (kt == 5) rc = launch_mf(integral_constant<int, 5>{}, integral_constant<int, 5>{}, std::true_type{});

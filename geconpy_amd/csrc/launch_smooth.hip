@@ -6,14 +6,14 @@ namespace dsge_host {
 
 size_t smoother_image_doubles(int m) { return dsge::ks_mat(m); }
 
-int launch_kalman_smoother(const double* T, const double* R, const double* Q, int q_mode, int batch, int m, int k, int T_len,
+int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, int T_len,
                            double rank_tol, double* U, double* UT, double* UR, int32_t* rank, const double* a_pred, const double* a_filt,
                            const double* p_pred, const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov,
                            int32_t* status, hipStream_t st) {
   dsge::KsArgs a{};
-  a.T = T; a.R = R; a.Q = Q; a.U = U; a.UT = UT; a.UR = UR; a.rank = rank; a.a_pred = a_pred; a.a_filt = a_filt; a.p_pred = p_pred;
+  a.T = T; a.R = R; a.Q = q.Q; a.U = U; a.UT = UT; a.UR = UR; a.rank = rank; a.a_pred = a_pred; a.a_filt = a_filt; a.p_pred = p_pred;
   a.p_filt = p_filt; a.a_s = a_s; a.p_s = p_s; a.e_s = e_s; a.status = status; a.batch = batch; a.m = m; a.k = k;
-  a.T_len = T_len; a.q_mode = q_mode; a.full_cov = full_cov; a.rank_tol = rank_tol;
+  a.T_len = T_len; a.q_mode = q.mode; a.full_cov = full_cov; a.rank_tol = rank_tol;
   int rc;
   const size_t lds_b = dsge::ksb_lds_doubles(m, k) * sizeof(double), lds = dsge::ks_lds_doubles(m) * sizeof(double);
   if (lds_b > LDS_LIMIT || lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "smoother: LDS budget exceeded");

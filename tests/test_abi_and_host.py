@@ -192,3 +192,51 @@ def test_options_struct_defaults_and_scope():
     bad.ll_constant = 3
     assert lib.dsge_options_push(ctypes.addressof(bad)) != 0
     assert lib.dsge_forget_measured_shapes() == 0  # (host-side records only: no GPU needed)
+
+
+# ---- argument checks of the filter family: one table of calls, each malformed in exactly one argument ------------------------
+_PTR = np.zeros(8)  # a valid address for every pointer argument: nothing is dereferenced, the checks come first
+_OBS = "Z z_batched d d_batched Hdiag h_batched"
+_FILTER_FAMILY = {
+    # entry -> its argument names in order, without the device entry's trailing stream (the forecast's n_steps goes as T_len)
+    "dsge_kalman_logp_batched": (f"T R Q q_mode {_OBS} y batch m k p T_len jitter missing_fill n_state_hint z_selector_hint "
+                                 "logp_out status_io"),
+    "dsge_kalman_filter_outputs_batched": (f"T R Q q_mode {_OBS} y batch m k p T_len jitter missing_fill ll_out a_pred_out "
+                                           "a_filt_out p_pred_out p_filt_out full_cov status_io"),
+    "dsge_kalman_smoother_batched": (f"T R Q q_mode {_OBS} y batch m k p T_len jitter missing_fill rank_tol scratch_limit_bytes "
+                                     "ll_out a_smooth_out p_smooth_out eps_smooth_out full_cov status_io"),
+    "dsge_solve_kalman_logp_batched": (f"A B C D Q q_mode {_OBS} y batch m k p T_len solver tol max_iter jitter missing_fill "
+                                       "n_state_hint z_selector_hint n_lead_hint logp_out status_out T_out R_out resid_out n_iter_out"),
+    "dsge_solve_kalman_logp_grad_batched": (f"A B C D Q q_mode {_OBS} y batch m k p T_len solver tol max_iter jitter missing_fill "
+                                            "n_filter_hint n_lead_hint logp_out status_out A_bar B_bar C_bar D_bar q_bar d_bar h_bar"),
+    "dsge_forecast_batched": f"T R Q q_mode {_OBS} a0 P0 status batch m k p T_len a_out p_out full_cov y_out f_out",
+}
+_SCALARS = dict(q_mode=_lib.Q_DIAG_SHARED, z_batched=0, d_batched=0, h_batched=0, batch=2, m=6, k=2, p=3, T_len=5, jitter=1e-8,
+                missing_fill=-9999.0, n_state_hint=0, z_selector_hint=0, n_lead_hint=0, n_filter_hint=0, full_cov=0, rank_tol=0.0,
+                scratch_limit_bytes=0, solver=_lib.SOLVER_CODES["cycle_reduction"], tol=1e-8, max_iter=10)
+
+
+def _malformed_cases():
+    for entry, names in _FILTER_FAMILY.items():
+        p_cap = 8 if "grad" in entry else _lib.MAX_P
+        too_large = _lib.ERR_TOO_LARGE if "forecast" in entry else _lib.ERR_INVALID  # (check_forecast: a size beyond a cap)
+        for what, change, code in (("k = 0", dict(k=0), _lib.ERR_INVALID), ("k = m + 1", dict(k=7), _lib.ERR_INVALID),
+                                   ("p = 0", dict(p=0), _lib.ERR_INVALID), ("p = cap + 1", dict(p=p_cap + 1), too_large),
+                                   ("steps = -1", dict(T_len=-1), _lib.ERR_INVALID), ("q_mode = 4", dict(q_mode=4), _lib.ERR_INVALID),
+                                   ("Z null", dict(Z=None), _lib.ERR_INVALID)):
+            yield pytest.param(entry, names.split(), change, code, id=f"{entry}-{what}")
+
+
+@pytest.mark.parametrize("entry,names,change,code", list(_malformed_cases()))
+def test_filter_family_argument_checks(entry, names, change, code):
+    """Every entry of the filter family and its host twin refuse a call that is malformed in one argument with the documented
+    code and the same message, before anything touches the device (so this needs no GPU)."""
+    lib = _lib.load()
+    values = {name: _SCALARS.get(name, _PTR.ctypes.data) for name in names}
+    values.update(change)
+    args = [values[name] for name in names]
+    assert getattr(lib, entry)(*args, None) == code
+    message = lib.dsge_last_error()
+    assert message
+    assert getattr(lib, entry + "_host")(*args) == code
+    assert lib.dsge_last_error() == message

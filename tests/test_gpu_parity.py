@@ -1515,6 +1515,46 @@ def test_dispatch_order_and_chunks_do_not_change_results():
         _set_option("pipeline_chunks", 0)
 
 
+def test_chunks_with_every_per_draw_member_batched():
+    """`pipeline_chunks` with Z, d, Hdiag and a full Q given per draw, all different from draw to draw (1024 draws in four chunks
+    of 256: the smallest batch the entry splits): logp / status bit-identical to the unsplit call, and the first and last draw
+    of the batch and the two draws at a chunk boundary bit-identical to one-draw calls on their own slices -- which an offset
+    that is wrong in both runs would not be."""
+    import torch
+
+    from geconpy_amd.engine import LogpEngine
+
+    nb, sh = 1024, dict(n=17, n_state=7, n_lead=5, k=3)
+    b = wl.sw_shaped_batch(nb, **sh)
+    om = wl.sw_shaped_observation_model(p=4, **sh)
+    scale = 1.0 + np.arange(nb) / 16.0
+    s = b["sigma"]
+    diag = np.eye(3, dtype=bool)
+    Q = np.einsum("bi,bj->bij", s, s) * np.where(diag, 1.0, (0.1 + 0.3 * np.arange(nb) / nb)[:, None, None])
+    assert np.linalg.eigvalsh(Q).min() > 0
+    host = dict(A=b["A"], B=b["B"], C=b["C"], D=b["D"], Q=Q, Z=om["Z"][None] * scale[:, None, None],
+                d=np.random.default_rng(9).normal(0, 0.01, (nb, 4)), H=om["Hdiag"][None] * scale[:, None])
+    eng = LogpEngine(torch.device("cuda", 0))
+    dev = {key: eng.to_device(x) for key, x in host.items()}
+    dy = eng.to_device(om["y"][:12])
+    hints = eng.structure_hints(dev["A"], dev["Z"])
+
+    def run(t, chunks):
+        lp, st = eng.solve_kalman_logp(t["A"], t["B"], t["C"], t["D"], t["Q"], t["Z"], dy, d=t["d"], Hdiag=t["H"], tol=1e-8,
+                                       max_iter=1000, n_state_hint=hints[0], z_selector_hint=hints[1],
+                                       options={"pipeline_chunks": chunks})
+        torch.cuda.synchronize()
+        return lp.cpu().numpy(), st.cpu().numpy()
+
+    ref_lp, ref_st = run(dev, 0)
+    lp, st = run(dev, 4)
+    assert (ref_st == 0).all() and np.isfinite(ref_lp).all()
+    assert np.array_equal(st, ref_st) and np.array_equal(lp, ref_lp)
+    for i in (0, 255, 256, 1023):
+        lp1, st1 = run({key: x[i:i + 1].contiguous() for key, x in dev.items()}, 0)
+        assert st1[0] == 0 and lp1[0] == lp[i], (i, lp1[0], lp[i])
+
+
 def test_fused_calls_on_two_streams_do_not_share_scratch():
     """The library is re-entrant per stream: fused evaluations enqueued back to back on two torch streams --
     different batches, cycle reduction on one and gensys on the other -- keep their intermediates (T, R, RQR, P0, the gensys

@@ -200,6 +200,37 @@ def test_chunked_equals_unchunked():
         assert_array_equal(one[key], tiny[key], err_msg=key)
 
 
+def test_chunked_equals_unchunked_every_member_batched():
+    """The same chunks (3, 3, 2) with Z, d, Hdiag and a full Q given per draw, all different from draw to draw: bit-identical to
+    one chunk, and draws 2, 3, 5, 7 (last of a chunk, first of the next, mid-chunk, last of the batch) bit-identical to the
+    one-draw call on their own slices -- which an offset that is wrong in both runs would not be."""
+    sh = dict(n=17, n_state=7, n_lead=5, k=3)
+    b = wl.sw_shaped_batch(8, **sh)
+    T = b["T_star"]
+    R = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], T[i]) for i in range(8)])
+    c = _case("sw17")
+    scale = 1.0 + np.arange(8) / 16.0
+    Z = c["Z"][None] * scale[:, None, None]
+    d = np.random.default_rng(8).normal(0, 0.01, (8, 4))
+    H = c["H"][None] * scale[:, None] ** 2
+    s = b["sigma"]
+    Q = np.stack([np.diag(s[i] ** 2) + 0.1 * scale[i] * (np.outer(s[i], s[i]) - np.diag(s[i] ** 2)) for i in range(8)])
+    assert all(np.linalg.eigvalsh(Q[i]).min() > 0 for i in range(8))
+    y = c["y"][:12]
+    kw = dict(full_covariances=True)
+    keys = ("ll", "smoothed_states", "smoothed_covs", "smoothed_shocks", "status")
+    one = batched.kalman_smoother_batched(T, R, Q, Z, y, d=d, Hdiag=H, **kw)
+    three = batched.kalman_smoother_batched(T, R, Q, Z, y, d=d, Hdiag=H, **kw,
+                                            scratch_limit_bytes=3 * batched.smoother_scratch_bytes_per_draw(17, 12))
+    assert (one["status"] == 0).all() and np.isfinite(one["smoothed_covs"]).all()
+    for key in keys:
+        assert_array_equal(one[key], three[key], err_msg=key)
+    for i in (2, 3, 5, 7):
+        own = batched.kalman_smoother_batched(T[i:i + 1], R[i:i + 1], Q[i:i + 1], Z[i:i + 1], y, d=d[i:i + 1], Hdiag=H[i:i + 1], **kw)
+        for key in keys:
+            assert_array_equal(three[key][i], own[key][0], err_msg=f"{key}, draw {i}")
+
+
 def test_edges():
     c = _case("sw")
     kw = dict(Hdiag=c["H"], full_covariances=True)
