@@ -1,0 +1,332 @@
+"""The front-end of the entry points that exist for host arrays (``batched.*_batched``) AND for device tensors (``LogpEngine``),
+written once: shapes and layouts are read off ``.shape`` (numpy array or torch tensor alike), outputs are allocated or reused,
+the arguments are named once and handed to ``_lib.call``.
+
+A backend ``b`` is what differs between the two: ``b.inp(x, dtype)`` coerces (host) or checks (device) an input, ``b.empty(shape,
+dtype)`` allocates an output, ``b.ptr(x)`` takes its address, ``b.host`` / ``b.stream`` pick the host twin or the stream, and
+``b.status_io(status, nb)`` is the in/out status word of a filter (fresh zeros by default).  ``HOST`` is the numpy one; the torch one
+lives in engine.py (this module never imports torch).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+Q_MODES = {"diag": _lib.Q_DIAG_SHARED, "diag_batched": _lib.Q_DIAG_BATCHED, "full": _lib.Q_FULL_SHARED,
+           "full_batched": _lib.Q_FULL_BATCHED}
+
+
+class HostBackend:
+    host, stream = True, None
+
+    @staticmethod
+    def inp(x, dtype="float64"):
+        return None if x is None else np.ascontiguousarray(x, dtype=dtype)
+
+    @staticmethod
+    def empty(shape, dtype="float64"):
+        return np.empty(shape, dtype=dtype)
+
+    @staticmethod
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    @staticmethod
+    def status_io(status, nb):
+        return np.zeros(nb, dtype=np.int32) if status is None else np.ascontiguousarray(status, dtype=np.int32).copy()
+
+
+HOST = HostBackend()
+
+
+# ---- shapes and layouts ----------------------------------------------------------------------------------------------------------
+def q_layout(shape, q_mode, nb, k):
+    """The layout code of a shock covariance of this shape: named by ``q_mode`` (a key of ``Q_MODES`` or the code itself) and
+    checked, or inferred (ambiguous only when batch == k)."""
+    shape = tuple(shape)
+    want = {_lib.Q_DIAG_SHARED: (k,), _lib.Q_DIAG_BATCHED: (nb, k), _lib.Q_FULL_SHARED: (k, k), _lib.Q_FULL_BATCHED: (nb, k, k)}
+    if q_mode is None:
+        codes = [code for code, s in want.items() if s == shape]
+        if len(codes) != 1:
+            raise ValueError(f"cannot infer the layout of Q with shape {shape} (batch={nb}, k={k}); pass q_mode")
+        return codes[0]
+    code = Q_MODES[q_mode] if isinstance(q_mode, str) else int(q_mode)
+    if shape != want[code]:
+        raise ValueError(f"Q has shape {shape}, q_mode needs {want[code]}")
+    return code
+
+
+def grad_q_layout(shape, full, nb, k):
+    """The gradient and second-order entries are told whether the covariance is full; the shape says whether it is batched."""
+    shape = tuple(shape)
+    if full:
+        if shape not in ((k, k), (nb, k, k)):
+            raise ValueError("Q must be (k, k) or (batch, k, k)")
+        return _lib.Q_FULL_SHARED + (len(shape) == 3)
+    if shape not in ((k,), (nb, k)):
+        raise ValueError("q must be (k,) or (batch, k) (diagonal shock covariance)")
+    return int(len(shape) == 2)
+
+
+def shared_or_batched(x, nb, tail, name, says=None):
+    """0 for ``x`` of shape ``tail`` (shared by all draws), 1 for ``(batch,) + tail``."""
+    shape, tail = tuple(x.shape), tuple(tail)
+    if shape == tail:
+        return 0
+    if shape == (nb, *tail):
+        return 1
+    raise ValueError(f"{name} must be {says or f'{tail} or {(nb, *tail)}'}; got {shape}")
+
+
+def obs_flags(Z, d, Hdiag, nb, p, m):
+    """(z_batched, d_batched, h_batched) of the observation model ``y = Z x + d + N(0, diag(Hdiag))``; d, Hdiag may be None."""
+    return (shared_or_batched(Z, nb, (p, m), "Z", "(p, m) or (batch, p, m)"),
+            *(0 if x is None else shared_or_batched(x, nb, (p,), name, "(p,) or (batch, p)") for x, name in ((d, "d"), (Hdiag, "Hdiag"))))
+
+
+def check_status(st, nb):
+    if st is not None and tuple(st.shape) != (nb,):
+        raise ValueError(f"status must be (batch,); got {tuple(st.shape)}")
+    return st
+
+
+def cov_flags(covariances):
+    """``covariances`` = "diag" / "full" / None -> (covariances wanted, full matrices)."""
+    if covariances not in ("diag", "full", None):
+        raise ValueError('covariances must be "diag", "full" or None')
+    return covariances is not None, covariances == "full"
+
+
+def _nd(x, ndim):
+    if x.ndim != ndim:
+        raise ValueError(f"expected a {ndim}-d array, got shape {tuple(x.shape)}")
+    return x
+
+
+def _is(x, shape, name, says=None):
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {says or tuple(shape)}; got {tuple(x.shape)}")
+    return x
+
+
+def check_abc(b, A, B, C):
+    A, B, C = (_nd(b.inp(x), 3) for x in (A, B, C))
+    if not (A.shape == B.shape == C.shape and A.shape[1] == A.shape[2]):
+        raise ValueError(f"A, B, C must be (batch, n, n); got {tuple(A.shape)}, {tuple(B.shape)}, {tuple(C.shape)}")
+    return A, B, C
+
+
+def model_args(b, A, B, C, D, y):
+    """The inputs every fused entry takes first -> the named arguments they make."""
+    A, B, C = check_abc(b, A, B, C)
+    D, y = _nd(b.inp(D), 3), _nd(b.inp(y), 2)
+    nb, n, _ = A.shape
+    _is(D, (nb, n, D.shape[2]), "D", "(batch, n, k)")
+    return dict(A=A, B=B, C=C, D=D, y=y, batch=nb, n=n, k=D.shape[2], p=y.shape[1], T_len=y.shape[0])
+
+
+def obs_args(b, Z, d, Hdiag, nb, p, m):
+    Z, d, Hdiag = b.inp(Z), b.inp(d), b.inp(Hdiag)
+    zb, db, hb = obs_flags(Z, d, Hdiag, nb, p, m)
+    return dict(Z=Z, z_batched=zb, d=d, d_batched=db, Hdiag=Hdiag, h_batched=hb)
+
+
+def _TR(b, T, R, name, smoother=False):
+    T, R = _nd(b.inp(T), 3), _nd(b.inp(R), 3)
+    nb, m, m2 = T.shape
+    if m != m2 or tuple(R.shape[:2]) != (nb, m) or (R.shape[2] < 1 and not smoother):
+        raise ValueError(f"T must be (batch, m, m) and R (batch, m, k); got {tuple(T.shape)}, {tuple(R.shape)}")
+    cap = _lib.MAX_N if smoother else _lib.MAX_N_BIG
+    if m > cap:
+        raise ValueError(f"{name}: m = {m}, {'the smoother takes ' if smoother else ''}at most {cap} variables")
+    return T, R, nb, m, R.shape[2]
+
+
+def _out(b, given, shape, dtype="float64"):
+    """An output buffer: ``given`` (checked) or a fresh one."""
+    return b.empty(shape, dtype) if given is None else _is(b.inp(given, dtype), shape, "an output buffer")
+
+
+def call(b, entry, **named):
+    """``_lib.call`` for backend ``b``: a POINTER argument (by the table, not by the look of the value) that is not an address
+    already (None or an int) is a buffer of the backend."""
+    pointers = {name for name, kind in _lib.SIGNATURES[entry] if kind is ctypes.c_void_p}
+    _lib.call(entry, host=b.host, stream=b.stream,
+              **{key: b.ptr(v) if key in pointers and not (v is None or isinstance(v, int)) else v for key, v in named.items()})
+
+
+# ---- the entry points --------------------------------------------------------------------------------------------------------------
+def solve_kalman_logp(b, A, B, C, D, Q, Z, y, *, d, Hdiag, q_mode, solver, tol, max_iter, jitter, missing_fill, hints, options,
+                      solver_flags=0, return_policy=False, out=None):
+    """``hints(a)``: the named hint arguments, from the validated arguments ``a``.  ``out``: buffers to reuse (logp, status, T, R)."""
+    a = model_args(b, A, B, C, D, y)
+    nb, n, k = a["batch"], a["n"], a["k"]
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    a.update(obs_args(b, Z, d, Hdiag, nb, a["p"], n))
+    out = out or {}
+    res = dict(logp=_out(b, out.get("logp"), (nb,)), status=_out(b, out.get("status"), (nb,), "int32"))
+    for key, shape, dtype in (("T", (nb, n, n), "float64"), ("R", (nb, n, k), "float64"), ("resid", (nb,), "float64"),
+                              ("n_iter", (nb,), "int32")):
+        res[key] = _out(b, out.get(key), shape, dtype) if return_policy or out.get(key) is not None else None
+    op, _keep = _lib.opt_ptr(options)
+    call(b, "dsge_solve_kalman_logp_batched_opt", opt=op, **a, Q=Q, q_mode=code, solver=_lib.SOLVER_CODES[solver] | solver_flags,
+         tol=tol, max_iter=max_iter, jitter=jitter, missing_fill=missing_fill, **hints(a), logp_out=res["logp"],
+         status_out=res["status"], T_out=res["T"], R_out=res["R"], resid_out=res["resid"], n_iter_out=res["n_iter"])
+    return res
+
+
+def solve_kalman_logp_grad(b, A, B, C, D, q, Z, y, *, full, d, Hdiag, solver, tol, max_iter, jitter, missing_fill, route, options,
+                           out=None):
+    """``full``: ``q`` is a full covariance.  ``route(a)`` -> dict(dense_z, Z_bar (wanted), n_hint, n_lead_hint).  ``out``: the dict
+    of an earlier call, completed in place."""
+    a = model_args(b, A, B, C, D, y)
+    nb, n, k, p = a["batch"], a["n"], a["k"], a["p"]
+    q = b.inp(q)
+    qb = grad_q_layout(q.shape, full, nb, k)
+    a.update(obs_args(b, Z, d, Hdiag, nb, p, n))
+    r = route(a)
+    res = {} if out is None else out
+    for key, shape, wanted in (("logp", (nb,), True), ("status", (nb,), True), ("A_bar", (nb, n, n), True), ("B_bar", (nb, n, n), True),
+                               ("C_bar", (nb, n, n), True), ("D_bar", (nb, n, k), True), ("q_bar", (nb, k, k) if full else (nb, k), True),
+                               ("d_bar", (nb, p), d is not None), ("h_bar", (nb, p), Hdiag is not None), ("Z_bar", (nb, p, n), r["Z_bar"])):
+        if wanted or res.get(key) is not None:
+            res[key] = _out(b, res.get(key), shape, "int32" if key == "status" else "float64")
+    named = dict(a, q=q, q_batched=qb, solver=_lib.SOLVER_CODES[solver], tol=tol, max_iter=max_iter, jitter=jitter,
+                 missing_fill=missing_fill, n_lead_hint=r["n_lead_hint"], logp_out=res["logp"], status_out=res["status"],
+                 d_bar=res.get("d_bar"), h_bar=res.get("h_bar"), **{key: res[key] for key in ("A_bar", "B_bar", "C_bar", "D_bar", "q_bar")})
+    if r["dense_z"]:
+        with _lib.options_scope(options):
+            call(b, "dsge_solve_kalman_logp_grad_dense_z_batched", **named, n_state_hint=r["n_hint"], Z_bar=res.get("Z_bar"))
+    else:
+        op, _keep = _lib.opt_ptr(options)
+        call(b, "dsge_solve_kalman_logp_grad_batched_opt", opt=op, **named, n_filter_hint=r["n_hint"])
+    return res
+
+
+def second_order_logp(b, A, B, C, D, hess_idx, hess_val, q, Z, y, *, d, Hdiag, solver, tol, max_iter, jitter, missing_fill, structure,
+                      options, return_solution=False, out=None, stage_ms=None):
+    """``structure``: (S, L, U) index lists, or the function of the validated (A, C, Z) that makes them.  Returns the outputs and S."""
+    a = model_args(b, A, B, C, D, y)
+    nb, n, k, p = a["batch"], a["n"], a["k"], a["p"]
+    hess_idx = _nd(b.inp(hess_idx, "int32"), 2)
+    nnz = hess_idx.shape[0]
+    _is(hess_idx, (nnz, 3), "hess_idx", "(nnz, 3)")
+    hess_val = _is(_nd(b.inp(hess_val), 2), (nb, nnz), "hess_val", "(batch, nnz)")
+    q = b.inp(q)
+    qb = grad_q_layout(q.shape, False, nb, k)
+    Z = _is(_nd(b.inp(Z), 2), (p, n), "Z", "(p, n)")
+    d, Hdiag = (None if x is None else _is(_nd(b.inp(x), 1), (p,), name, "(p,)") for x, name in ((d, "d"), (Hdiag, "Hdiag")))
+    S, Lc, U = (np.ascontiguousarray(x, dtype=np.int32) for x in (structure(a["A"], a["C"], Z) if callable(structure) else structure))
+    s = len(S)
+    out = out or {}
+    res = dict(logp=_out(b, out.get("logp"), (nb,)), status=_out(b, out.get("status"), (nb,), "int32"))
+    for key, shape in (("T", (nb, n, n)), ("R", (nb, n, k)), ("g_yy", (nb, n, s, s)), ("g_yu", (nb, n, s, k)), ("g_uu", (nb, n, k, k)),
+                       ("g_ss", (nb, n))):
+        res[key] = b.empty(shape) if return_solution else None
+    with _lib.options_scope(options):
+        call(b, "dsge_second_order_logp_batched", **a, hess_idx=hess_idx, nnz=nnz, hess_val=hess_val, q=q, q_batched=qb, Z=Z, d=d,
+             Hdiag=Hdiag, solver=_lib.SOLVER_CODES[solver], tol=tol, max_iter=max_iter, jitter=jitter, missing_fill=missing_fill,
+             state_idx=S.ctypes.data, n_state=s, lead_idx=Lc.ctypes.data, n_lead=len(Lc), ret_idx=U.ctypes.data, n_ret=len(U),
+             logp_out=res["logp"], status_out=res["status"], T_out=res["T"], R_out=res["R"], gyy_out=res["g_yy"], gyu_out=res["g_yu"],
+             guu_out=res["g_uu"], gss_out=res["g_ss"], stage_ms=stage_ms)
+    return res, S
+
+
+def kalman_smoother(b, name, T, R, Q, Z, y, *, d, Hdiag, q_mode, status, jitter, missing_fill, cov, full, rank_tol, scratch_limit_bytes,
+                    options):
+    """``cov`` / ``full``: covariances wanted / as full matrices."""
+    T, R, nb, m, k = _TR(b, T, R, name, smoother=True)
+    y = _nd(b.inp(y), 2)
+    T_len, p = y.shape
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    obs = obs_args(b, Z, d, Hdiag, nb, p, m)
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    st = check_status(b.status_io(status, nb), nb)
+    res = dict(ll=b.empty((nb, T_len)), smoothed_states=b.empty((nb, T_len, m)),
+               smoothed_covs=b.empty((nb, T_len, m, m) if full else (nb, T_len, m)) if cov else None,
+               smoothed_shocks=b.empty((nb, T_len, k)), status=st)
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        call(b, "dsge_kalman_smoother_batched", T=T, R=R, Q=Q, q_mode=code, **obs, y=y, batch=nb, m=m, k=k, p=p, T_len=T_len,
+             jitter=jitter, missing_fill=missing_fill, rank_tol=0.0 if rank_tol is None else rank_tol, scratch_limit_bytes=limit,
+             ll_out=res["ll"], a_smooth_out=res["smoothed_states"], p_smooth_out=res["smoothed_covs"],
+             eps_smooth_out=res["smoothed_shocks"], full_cov=bool(full), status_io=st)
+    return res
+
+
+def simulate(b, name, T, R, eps, *, n_steps, x0, status, out=None):
+    T, R, nb, m, k = _TR(b, T, R, name)
+    eps = b.inp(eps)
+    if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+        raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {tuple(eps.shape)}")
+    n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+    eb = shared_or_batched(eps, nb, (n_paths, n_shock, k), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    if n_steps < n_shock:
+        raise ValueError(f"n_steps = {n_steps} is less than the {n_shock} shock steps of eps")
+    x0 = b.inp(x0)
+    xb = 0 if x0 is None else shared_or_batched(x0, nb, (n_paths, m), "x0")
+    st = check_status(b.inp(status, "int32"), nb)
+    paths = _out(b, out, (nb, n_paths, n_steps, m))
+    call(b, "dsge_simulate_batched", T=T, R=R, eps=eps, eps_batched=eb, x0=x0, x0_batched=xb, status=st, batch=nb, m=m, k=k,
+         n_paths=n_paths, n_steps=n_steps, n_shock_steps=n_shock, x_out=paths)
+    return paths
+
+
+def impulse_response(b, name, T, R, *, n_steps, S, weights, fevd, irf, status, out=None):
+    T, R, nb, m, k = _TR(b, T, R, name)
+    sb, c = 0, k
+    if S is not None:
+        S = b.inp(S)
+        if S.ndim not in (2, 3) or S.shape[-2] != k:
+            raise ValueError(f"S must be ({k}, c) or (batch, {k}, c); got {tuple(S.shape)}")
+        c = S.shape[-1]
+        sb = shared_or_batched(S, nb, (k, c), "S")
+    weights = b.inp(weights)
+    wb = 0 if weights is None else shared_or_batched(weights, nb, (c,), "weights")
+    if not (irf or fevd):
+        raise ValueError("nothing requested: irf and fevd are both off")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError("n_steps must be >= 0")
+    st = check_status(b.inp(status, "int32"), nb)
+    out = out or {}
+    res = dict(irf=_out(b, out.get("irf"), (nb, c, n_steps, m)) if irf else None,
+               fevd=_out(b, out.get("fevd"), (nb, n_steps, m, c)) if fevd else None)
+    call(b, "dsge_irf_batched", T=T, R=R, S=S, s_batched=sb, weights=weights, w_batched=wb, status=st, batch=nb, m=m, k=k, c=c,
+         n_steps=n_steps, irf_out=res["irf"], fevd_out=res["fevd"])
+    return res
+
+
+def forecast(b, name, T, R, Q, a0, *, P0, n_steps, Z, d, Hdiag, q_mode, covariances, status, out=None):
+    T, R, nb, m, k = _TR(b, T, R, name)
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    a0 = _is(b.inp(a0), (nb, m), "a0")
+    P0 = None if P0 is None else _is(b.inp(P0), (nb, m, m), "P0")
+    cov, full = cov_flags(covariances)
+    p, obs = 0, dict(Z=None, z_batched=0, d=None, d_batched=0, Hdiag=None, h_batched=0)
+    if Z is not None:
+        Z = b.inp(Z)
+        p = Z.shape[-2] if Z.ndim >= 2 else 0
+        obs = obs_args(b, Z, d, Hdiag, nb, p, m)
+    elif d is not None or Hdiag is not None:
+        raise ValueError("d and Hdiag need Z")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError("n_steps must be >= 0")
+    st = check_status(b.inp(status, "int32"), nb)
+    out = out or {}
+    res = dict(states=_out(b, out.get("states"), (nb, n_steps, m)),
+               covs=_out(b, out.get("covs"), (nb, n_steps, m, m) if full else (nb, n_steps, m)) if cov else None,
+               observed=_out(b, out.get("observed"), (nb, n_steps, p)) if p else None,
+               observed_covs=_out(b, out.get("observed_covs"), (nb, n_steps, p, p)) if p and cov else None)
+    call(b, "dsge_forecast_batched", T=T, R=R, Q=Q, q_mode=code, **obs, a0=a0, P0=P0, status=st, batch=nb, m=m, k=k, p=p,
+         n_steps=n_steps, a_out=res["states"], p_out=res["covs"], full_cov=full, y_out=res["observed"], f_out=res["observed_covs"])
+    return res

@@ -68,107 +68,89 @@ class GensysForward(C.Structure):
                 ("n_unstable", C.c_void_p), ("pi_raw", C.c_int32)]
 
 
-_dp = C.c_void_p  # double* / int32* / stream: passed as raw addresses (host or device)
-_i = C.c_int
-_f = C.c_double
-_z = C.c_size_t
-
-# name -> argtypes; every symbol include/dsge_hip.h declares must appear here
-PROTOTYPES = {
-    "dsge_abi_version": [],
-    "dsge_last_error": [],
-    "dsge_device_count": [],
-    "dsge_set_device": [_i],
-    "dsge_stream_synchronize": [_dp],
-    "dsge_cycle_reduction_batched": [_dp, _dp, _dp, _i, _i, _i, _f, _dp, _dp, _dp, _dp],
-    "dsge_cycle_reduction_batched_host": [_dp, _dp, _dp, _i, _i, _i, _f, _dp, _dp, _dp],
-    "dsge_scan_cycle_reduction_batched": [_dp, _dp, _dp, _i, _i, _i, _f, _dp, _dp, _dp, _dp],
-    "dsge_scan_cycle_reduction_batched_host": [_dp, _dp, _dp, _i, _i, _i, _f, _dp, _dp, _dp],
-    "dsge_gensys_batched": [_dp, _dp, _dp, _dp, _i, _i, _i, _f, _i, _dp, _dp, _dp, _dp, _dp],
-    "dsge_gensys_batched_host": [_dp, _dp, _dp, _dp, _i, _i, _i, _f, _i, _dp, _dp, _dp, _dp],
-    "dsge_gensys_pencil_batched": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_gensys_pencil_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_gensys_pencil_full_batched": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_gensys_pencil_full_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_bk_eigenvalues_batched": [_dp, _dp, _dp, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_bk_eigenvalues_batched_host": [_dp, _dp, _dp, _i, _i, _f, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_debug_cr_phases": [_i, _dp],
-    "dsge_debug_kalman_steady_steps": [_dp],
-    "dsge_debug_kalman_timeline": [_dp],
-    "dsge_debug_kalman_phases": [_i, _dp],
-    "dsge_debug_big_phases": [_i, _dp],
-    "dsge_debug_gensys_window_phases": [_i, _dp],
-    "dsge_debug_gensys_phases": [_dp, _dp, _dp, _i, _i, _f, _i, _dp, _dp, _dp, _dp],
-    "dsge_debug_gensys_stage_ms": [_i, _dp],
-    "dsge_selection_batched": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_selection_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp],
-    "dsge_policy_adjoints_batched": [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _dp, _dp],
-    "dsge_policy_adjoints_batched_host": [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _dp],
-    "dsge_debug_adjoint_refine": [_i],
-    "dsge_debug_second_order_phases": [_i, _dp],
-    "dsge_selection_adjoints_batched": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp, _dp, _dp, _dp],
-    "dsge_selection_adjoints_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp, _dp, _dp],
-    "dsge_policy_norms_batched": [_dp, _dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_policy_norms_batched_host": [_dp, _dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp],
-    "dsge_backward_direct_batched": [_dp, _dp, _dp, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_backward_direct_batched_host": [_dp, _dp, _dp, _i, _i, _i, _dp, _dp],
-    "dsge_lyapunov_batched": [_dp, _dp, _dp, _i, _i, _i, _i, _dp, _dp, _dp, _dp],
-    "dsge_lyapunov_batched_host": [_dp, _dp, _dp, _i, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_autocorrelation_batched": [_dp, _dp, _dp, _i, _dp, _dp, _i, _i, _i, _i, _i, _i, _i, _dp, _dp, _dp, _dp],
-    "dsge_autocorrelation_batched_host": [_dp, _dp, _dp, _i, _dp, _dp, _i, _i, _i, _i, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_kalman_logp_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _dp, _dp, _dp],
-    "dsge_kalman_logp_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _dp, _dp],
-    "dsge_kalman_filter_outputs_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _dp, _dp,
-                                           _dp, _dp, _dp, _i, _dp, _dp],
-    "dsge_kalman_filter_outputs_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _dp,
-                                                _dp, _dp, _dp, _dp, _i, _dp],
-    "dsge_kalman_smoother_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _f, _z, _dp, _dp,
-                                     _dp, _dp, _i, _dp, _dp],
-    "dsge_kalman_smoother_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _f, _f, _f, _z, _dp,
-                                          _dp, _dp, _dp, _i, _dp],
-    "dsge_simulate_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _dp, _dp],
-    "dsge_simulate_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _dp],
-    "dsge_irf_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _dp, _dp, _dp],
-    "dsge_irf_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _dp, _dp],
-    "dsge_forecast_batched": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _i, _i, _i, _i, _i, _dp, _dp, _i, _dp,
-                              _dp, _dp],
-    "dsge_forecast_batched_host": [_dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _i, _i, _i, _i, _i, _dp, _dp, _i, _dp,
-                                   _dp],
-    "dsge_solve_kalman_logp_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_augmented_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,
-                                                 _i, _f, _i, _f, _f, _i, _dp, _i, _dp, _dp, _i, _i, _i, _dp, _dp, _dp, _dp,
-                                                 _dp, _dp],
-    "dsge_solve_kalman_logp_augmented_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i,
-                                                      _i, _i, _i, _f, _i, _f, _f, _i, _dp, _i, _dp, _dp, _i, _i, _i, _dp,
-                                                      _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_grad_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i,
-                                            _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_grad_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,
-                                                 _i, _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_grad_dense_z_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,
-                                                    _i, _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                                    _dp],
-    "dsge_solve_kalman_logp_grad_dense_z_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i,
-                                                         _i, _i, _i, _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                                         _dp, _dp, _dp],
-    "dsge_options_init": [_dp],
-    "dsge_options_push": [_dp],
-    "dsge_options_pop": [],
-    "dsge_forget_measured_shapes": [],
-    "dsge_solve_kalman_logp_batched_opt": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_batched_host_opt": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_grad_batched_opt": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i,
-                                                _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_solve_kalman_logp_grad_batched_host_opt": [_dp, _dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i,
-                                                     _i, _f, _i, _f, _f, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_second_order_logp_batched": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i, _f,
-                                       _i, _f, _f, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_second_order_logp_batched_host": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i,
-                                            _f, _i, _f, _f, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
-    "dsge_profile_pipeline": [_dp, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _dp, _dp, _i, _dp, _dp],
+# ---- the C ABI, by name ------------------------------------------------------------------------------------------------------
+# entry -> its argument names in the order of include/dsge_hip.h (tests/test_abi_and_host.py compares both, names and kinds).  A
+# name is an int, a double or a size_t when it is listed below, a pointer (double* / int32_t* / struct* / stream, passed as a raw
+# host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
+_INTS = ("N T_len batch c correlation d_batched device enable eps_batched full_cov h_batched k lag_step m max_iter mode n n_eta "
+         "n_filter_hint n_lags n_lead n_lead_hint n_links n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p q_batched "
+         "q_mode reps s_batched solver w_batched x0_batched z_batched z_selector_hint")
+_KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
+          "scratch_limit_bytes": C.c_size_t}
+_OBS = "Z z_batched d d_batched Hdiag h_batched"
+_FILTER = f"T R Q q_mode {_OBS} y batch m k p T_len jitter missing_fill"
+_FUSED = f"A B C D Q q_mode {_OBS} y batch n k p T_len solver tol max_iter jitter missing_fill"
+_LOGP = f"{_FUSED} n_state_hint z_selector_hint n_lead_hint logp_out status_out"
+_GRAD = f"A B C D q q_batched {_OBS} y batch n k p T_len solver tol max_iter jitter missing_fill"
+_BARS = "logp_out status_out A_bar B_bar C_bar D_bar q_bar d_bar h_bar"
+_PENCIL = "g0 g1 *c psi pi batch N k n_eta tol G1_out C_out impact_out gev_out eu_out status"
+_DEVICE_ENTRIES = {
+    "dsge_abi_version": "",
+    "dsge_last_error": "",
+    "dsge_device_count": "",
+    "dsge_set_device": "device",
+    "dsge_stream_synchronize": "stream",
+    "dsge_options_init": "opt",
+    "dsge_options_push": "opt",
+    "dsge_options_pop": "",
+    "dsge_forget_measured_shapes": "",
+    "dsge_debug_cr_phases": "enable cycles_out",
+    "dsge_debug_kalman_steady_steps": "steady_at_device",
+    "dsge_debug_kalman_timeline": "timeline_device",
+    "dsge_debug_kalman_phases": "enable cycles_out",
+    "dsge_debug_big_phases": "enable cycles_out",
+    "dsge_debug_gensys_phases": "A B C batch n tol n_lead_hint T_out eu_out status cycles_out",
+    "dsge_debug_gensys_window_phases": "enable cycles_out",
+    "dsge_debug_gensys_stage_ms": "enable ms_out",
+    "dsge_debug_adjoint_refine": "mode",
+    "dsge_debug_second_order_phases": "enable cycles_out",
+    "dsge_profile_pipeline": f"{_LOGP} reps ms_out stream",
+    # every entry below has a host twin (``host_twin``)
+    "dsge_cycle_reduction_batched": "A B C batch n max_iter tol T_out status n_iter stream",
+    "dsge_scan_cycle_reduction_batched": "A B C batch n max_iter tol T_out status *n_steps stream",
+    "dsge_gensys_batched": "A B C D batch n k tol n_lead_hint T_out R_out eu_out status stream",
+    "dsge_gensys_pencil_batched": f"{_PENCIL} stream",
+    "dsge_gensys_pencil_full_batched": f"{_PENCIL} forward stream",
+    "dsge_bk_eigenvalues_batched": "A B C batch n tol eig_re eig_im n_eig n_forward n_unstable status stream",
+    "dsge_selection_batched": "A B C D T batch n k R_out resid_out stream",
+    "dsge_policy_adjoints_batched": "B C T T_bar batch n A_bar B_bar C_bar status stream",
+    "dsge_selection_adjoints_batched": "B C T R R_bar batch n k B_bar C_bar D_bar T_bar stream",
+    "dsge_policy_norms_batched": "A B C D T R state_mask batch n k det_norm_out stoch_norm_out stream",
+    "dsge_backward_direct_batched": "A B D batch n k T_out R_out stream",
+    "dsge_lyapunov_batched": "T R Q q_mode batch m k P0_out RQR_out status stream",
+    "dsge_autocorrelation_batched": "T R Q q_mode Z Hdiag batch m k p n_lags lag_step correlation acf_out Sigma_out status stream",
+    "dsge_kalman_logp_batched": f"{_FILTER} n_state_hint z_selector_hint logp_out status_io stream",
+    "dsge_kalman_filter_outputs_batched": f"{_FILTER} ll_out a_pred_out a_filt_out p_pred_out p_filt_out full_cov status_io stream",
+    "dsge_kalman_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes ll_out a_smooth_out p_smooth_out eps_smooth_out "
+                                     "full_cov status_io stream"),
+    "dsge_simulate_batched": "T R eps eps_batched x0 x0_batched status batch m k n_paths n_steps n_shock_steps x_out stream",
+    "dsge_irf_batched": "T R S s_batched weights w_batched status batch m k c n_steps irf_out fevd_out stream",
+    "dsge_forecast_batched": f"T R Q q_mode {_OBS} a0 P0 status batch m k p n_steps a_out p_out full_cov y_out f_out stream",
+    "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
+    "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
+    "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "
+                                                 "n_lead_hint logp_out status_out T_aug_out R_aug_out resid_out stream"),
+    "dsge_solve_kalman_logp_grad_batched": f"{_GRAD} n_filter_hint n_lead_hint {_BARS} stream",
+    "dsge_solve_kalman_logp_grad_batched_opt": f"opt {_GRAD} n_filter_hint n_lead_hint {_BARS} stream",
+    "dsge_solve_kalman_logp_grad_dense_z_batched": f"{_GRAD} n_state_hint n_lead_hint {_BARS} Z_bar stream",
+    "dsge_second_order_logp_batched": ("A B C D hess_idx nnz hess_val q q_batched Z d Hdiag y batch n k p T_len solver tol max_iter "
+                                       "jitter missing_fill state_idx n_state lead_idx n_lead ret_idx n_ret logp_out status_out "
+                                       "T_out R_out gyy_out gyu_out guu_out gss_out stage_ms stream"),
 }
+_HOST_DROPS = {"dsge_second_order_logp_batched": 2}  # trailing arguments a host twin does not take: ``stream``; here ``stage_ms`` too
 
+
+def host_twin(entry):
+    """Name of the twin of a device entry that takes host pointers and stages through device memory."""
+    return entry[:-4] + "_host_opt" if entry.endswith("_opt") else entry + "_host"
+
+
+# name -> ((argument name, ctypes type), ...); every symbol include/dsge_hip.h declares must appear here
+SIGNATURES = {name: tuple((w[1:], C.c_void_p) if w[0] == "*" else (w, _KINDS.get(w, C.c_void_p)) for w in sig.split())
+              for name, sig in _DEVICE_ENTRIES.items()}
+SIGNATURES.update({host_twin(name): SIGNATURES[name][:-_HOST_DROPS.get(name, 1)]
+                   for name in _DEVICE_ENTRIES if "_batched" in name})
+PROTOTYPES = {name: [kind for _, kind in sig] for name, sig in SIGNATURES.items()}  # name -> argtypes
 
 
 class Options(C.Structure):
@@ -308,6 +290,26 @@ def check(rc):
         err = cls(f"libdsge_hip call failed (code {rc}): {msg.decode() if msg else '?'}")
         err.code = rc
         raise err
+
+
+_TO_C = {C.c_int: int, C.c_size_t: int, C.c_double: float}
+
+
+def call(entry, *, host, stream=None, **named):
+    """Call the device entry ``entry`` (``host=False``: ``stream`` is appended) or its host twin with the arguments given BY NAME,
+    ordered by ``SIGNATURES``; a missing or an unknown name is a ``TypeError``, a non-zero return code raises (``check``).  What
+    a host twin does not take (``stream``; second order: ``stage_ms``) may be passed to it as None only."""
+    name = host_twin(entry) if host else entry
+    sig = SIGNATURES[name]
+    named["stream"] = stream
+    if host:
+        for dropped, _ in SIGNATURES[entry][len(sig):]:
+            if named.pop(dropped, None) is not None:
+                raise TypeError(f"{name} takes no {dropped}")
+    names = {arg for arg, _ in sig}
+    if named.keys() != names:
+        raise TypeError(f"{name}: missing {sorted(names - named.keys())}, unknown {sorted(named.keys() - names)}")
+    check(getattr(load(), name)(*[named[arg] if kind is C.c_void_p else _TO_C[kind](named[arg]) for arg, kind in sig]))
 
 
 def device_count():

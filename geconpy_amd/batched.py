@@ -11,7 +11,9 @@ import ctypes
 
 import numpy as np
 
+from . import _frontend as F
 from . import _lib
+from ._frontend import HOST
 from ._lib import DsgeHipError  # noqa: F401
 
 JITTER_DEFAULT = 1e-8  # float64 cov_jitter default (gEconpy/model/statespace.py:22,1144)
@@ -42,15 +44,11 @@ def _f64(x, ndim=None):
     return a
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
+_ptr = HOST.ptr
 
 
 def _check_abc(A, B, C):
-    A, B, C = _f64(A, 3), _f64(B, 3), _f64(C, 3)
-    if not (A.shape == B.shape == C.shape and A.shape[1] == A.shape[2]):
-        raise ValueError(f"A, B, C must be (batch, n, n); got {A.shape}, {B.shape}, {C.shape}")
-    return A, B, C
+    return F.check_abc(HOST, A, B, C)
 
 
 def cycle_reduction_batched(A, B, C, max_iter=1000, tol=1e-9, options=None):
@@ -267,30 +265,12 @@ def backward_direct_batched(A, B, D):
 
 def _q_mode(Q, nb, k):
     """Infer the covariance layout from the shape (ambiguous only when batch == k)."""
-    Q = _f64(Q)
-    if Q.shape == (k,):
-        return Q, _lib.Q_DIAG_SHARED
-    if Q.shape == (nb, k, k):
-        return Q, _lib.Q_FULL_BATCHED
-    if Q.ndim == 2 and nb != k:
-        if Q.shape == (nb, k):
-            return Q, _lib.Q_DIAG_BATCHED
-        if Q.shape == (k, k):
-            return Q, _lib.Q_FULL_SHARED
-    raise ValueError(f"cannot infer the layout of Q with shape {Q.shape} (batch={nb}, k={k}); pass q_mode")
+    return _resolve_q(Q, None, nb, k)
 
 
 def _resolve_q(Q, q_mode, nb, k):
-    if q_mode is None:
-        return _q_mode(Q, nb, k)
-    modes = {"diag": _lib.Q_DIAG_SHARED, "diag_batched": _lib.Q_DIAG_BATCHED, "full": _lib.Q_FULL_SHARED,
-             "full_batched": _lib.Q_FULL_BATCHED}
-    code = modes[q_mode] if isinstance(q_mode, str) else int(q_mode)
     Q = _f64(Q)
-    want = {0: (k,), 1: (nb, k), 2: (k, k), 3: (nb, k, k)}[code]
-    if Q.shape != want:
-        raise ValueError(f"Q has shape {Q.shape}, q_mode needs {want}")
-    return Q, code
+    return Q, F.q_layout(Q.shape, q_mode, nb, k)
 
 
 def lyapunov_batched(T, R, Q, q_mode=None):
@@ -338,26 +318,8 @@ def autocorrelation_matrices_batched(T, R, Q, n_lags=10, lag_step=1, Z=None, Hdi
 
 
 def _obs_args(Z, d, Hdiag, nb, p, m):
-    Z = _f64(Z)
-    if Z.shape == (p, m):
-        zb = 0
-    elif Z.shape == (nb, p, m):
-        zb = 1
-    else:
-        raise ValueError(f"Z must be (p, m) or (batch, p, m); got {Z.shape}")
-
-    def vec(x, name):
-        if x is None:
-            return None, 0
-        x = _f64(x)
-        if x.shape == (p,):
-            return x, 0
-        if x.shape == (nb, p):
-            return x, 1
-        raise ValueError(f"{name} must be (p,) or (batch, p); got {x.shape}")
-
-    d, db = vec(d, "d")
-    Hdiag, hb = vec(Hdiag, "Hdiag")
+    Z, d, Hdiag = _f64(Z), HOST.inp(d), HOST.inp(Hdiag)
+    zb, db, hb = F.obs_flags(Z, d, Hdiag, nb, p, m)
     return Z, zb, d, db, Hdiag, hb
 
 
@@ -480,26 +442,6 @@ def kalman_filter_outputs_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None
     return out
 
 
-def _smoother_shapes(T, R, Q, Z, y, d, Hdiag, q_mode, rank_tol, scratch_limit_bytes):
-    """Argument checks of ``kalman_smoother_batched`` (ValueError before anything is staged)."""
-    T, R = _f64(T, 3), _f64(R, 3)
-    y = _f64(y, 2)
-    nb, m, m2 = T.shape
-    if m != m2 or R.shape[:2] != (nb, m):
-        raise ValueError(f"T must be (batch, m, m) and R (batch, m, k); got {T.shape}, {R.shape}")
-    if m > _lib.MAX_N:
-        raise ValueError(f"kalman_smoother_batched: m = {m}, the smoother takes at most {_lib.MAX_N} variables")
-    k = R.shape[2]
-    T_len, p = y.shape
-    Q, code = _resolve_q(Q, q_mode, nb, k)
-    Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, m)
-    rank_tol = 0.0 if rank_tol is None else float(rank_tol)
-    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
-    if limit < 0:
-        raise ValueError("scratch_limit_bytes must be >= 0")
-    return T, R, Q, code, Z, zb, d, db, Hdiag, hb, y, nb, m, k, p, T_len, rank_tol, limit
-
-
 def smoother_scratch_bytes_per_draw(m, T_len):
     """Bytes of library scratch the smoother's forward pass stores per draw (what ``scratch_limit_bytes`` counts):
     ``2 T_len m^2 + 2 T_len m`` doubles."""
@@ -517,53 +459,9 @@ def kalman_smoother_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, stat
     (batch, T_len, m, m), smoothed_shocks (batch, T_len, k) with ``[:, 0] = NaN`` by definition, status).  ``options`` carries
     the filter conventions (``_lib.filter_conventions``); ``rank_tol`` (default 1e-10) sets the rank of the range basis;
     ``scratch_limit_bytes`` (default 2 GiB) bounds the stored forward pass (``smoother_scratch_bytes_per_draw`` per draw)."""
-    (T, R, Q, code, Z, zb, d, db, Hdiag, hb, y, nb, m, k, p, T_len, rank_tol, limit) = _smoother_shapes(
-        T, R, Q, Z, y, d, Hdiag, q_mode, rank_tol, scratch_limit_bytes)
-    st = np.zeros(nb, dtype=np.int32) if status is None else np.ascontiguousarray(status, dtype=np.int32).copy()
-    if st.shape != (nb,):
-        raise ValueError(f"status must be (batch,); got {st.shape}")
-    cshape = (nb, T_len, m, m) if full_covariances else (nb, T_len, m)
-    out = dict(ll=np.empty((nb, T_len)), smoothed_states=np.empty((nb, T_len, m)), smoothed_covs=np.empty(cshape),
-               smoothed_shocks=np.empty((nb, T_len, k)))
-    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
-        _lib.check(
-            _lib.load().dsge_kalman_smoother_batched_host(
-                _ptr(T), _ptr(R), _ptr(Q), code, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(y), nb, m, k, p, T_len, float(jitter),
-                float(missing_fill_value), rank_tol, limit, _ptr(out["ll"]), _ptr(out["smoothed_states"]),
-                _ptr(out["smoothed_covs"]), _ptr(out["smoothed_shocks"]), int(bool(full_covariances)), _ptr(st)
-            )
-        )
-    out["status"] = st
-    return out
-
-
-def _dyn_TR(T, R, name):
-    T, R = _f64(T, 3), _f64(R, 3)
-    nb, m, m2 = T.shape
-    if m != m2 or R.shape[:2] != (nb, m) or R.shape[2] < 1:
-        raise ValueError(f"T must be (batch, m, m) and R (batch, m, k); got {T.shape}, {R.shape}")
-    if m > _lib.MAX_N_BIG:
-        raise ValueError(f"{name}: m = {m}, at most {_lib.MAX_N_BIG} variables")
-    return T, R, nb, m, R.shape[2]
-
-
-def _dyn_shared_or_batched(x, nb, tail, name):
-    """``x`` of shape ``tail`` (shared) or ``(batch,) + tail`` -> (array, batched flag)."""
-    x = _f64(x)
-    if x.shape == tuple(tail):
-        return x, 0
-    if x.shape == (nb, *tail):
-        return x, 1
-    raise ValueError(f"{name} must be {tuple(tail)} or {(nb, *tail)}; got {x.shape}")
-
-
-def _dyn_status(status, nb):
-    if status is None:
-        return None
-    st = np.ascontiguousarray(status, dtype=np.int32)
-    if st.shape != (nb,):
-        raise ValueError(f"status must be (batch,); got {st.shape}")
-    return st
+    return F.kalman_smoother(HOST, "kalman_smoother_batched", T, R, Q, Z, y, d=d, Hdiag=Hdiag, q_mode=q_mode, status=status,
+                             jitter=jitter, missing_fill=missing_fill_value, cov=True, full=full_covariances, rank_tol=rank_tol,
+                             scratch_limit_bytes=scratch_limit_bytes, options=options)
 
 
 def simulate_batched(T, R, eps, n_steps=None, x0=None, status=None):
@@ -574,23 +472,7 @@ def simulate_batched(T, R, eps, n_steps=None, x0=None, status=None):
     ``random_seed``; ``n_steps`` (default n_shock_steps) may exceed n_shock_steps: the later steps have no shock.  ``x0``:
     (n_paths, m) or (batch, n_paths, m), default zero (the reference's start).  ``status``: optional (batch,) int32, a draw
     with a non-zero word gets NaN.  Returns dict(paths (batch, n_paths, n_steps, m))."""
-    T, R, nb, m, k = _dyn_TR(T, R, "simulate_batched")
-    eps = _f64(eps)
-    if eps.ndim not in (3, 4) or eps.shape[-1] != k:
-        raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {eps.shape}")
-    n_paths, n_shock = eps.shape[-3], eps.shape[-2]
-    eps, eb = _dyn_shared_or_batched(eps, nb, (n_paths, n_shock, k), "eps")
-    n_steps = n_shock if n_steps is None else int(n_steps)
-    if n_steps < n_shock:
-        raise ValueError(f"n_steps = {n_steps} is less than the {n_shock} shock steps of eps")
-    xb = 0
-    if x0 is not None:
-        x0, xb = _dyn_shared_or_batched(x0, nb, (n_paths, m), "x0")
-    st = _dyn_status(status, nb)
-    out = np.empty((nb, n_paths, n_steps, m))
-    _lib.check(_lib.load().dsge_simulate_batched_host(_ptr(T), _ptr(R), _ptr(eps), eb, _ptr(x0), xb, _ptr(st), nb, m, k, n_paths,
-                                                      n_steps, n_shock, _ptr(out)))
-    return dict(paths=out)
+    return dict(paths=F.simulate(HOST, "simulate_batched", T, R, eps, n_steps=n_steps, x0=x0, status=status))
 
 
 def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None):
@@ -602,27 +484,8 @@ def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False,
     ``S = cholesky(Q)``.  ``fevd=True`` adds the forecast-error variance decomposition with respect to these impulses
     (``weights``: (c,) or (batch, c), default ones; an extension, the reference has none); ``irf=False`` skips the responses.
     Returns dict(irf (batch, c, n_steps, m) or None, fevd (batch, n_steps, m, c) or None)."""
-    T, R, nb, m, k = _dyn_TR(T, R, "impulse_response_batched")
-    sb, c = 0, k
-    if S is not None:
-        S = _f64(S)
-        if S.ndim not in (2, 3) or S.shape[-2] != k:
-            raise ValueError(f"S must be ({k}, c) or (batch, {k}, c); got {S.shape}")
-        c = S.shape[-1]
-        S, sb = _dyn_shared_or_batched(S, nb, (k, c), "S")
-    wb = 0
-    if weights is not None:
-        weights, wb = _dyn_shared_or_batched(weights, nb, (c,), "weights")
-    if not (irf or fevd):
-        raise ValueError("nothing requested: irf and fevd are both off")
-    n_steps = int(n_steps)
-    if n_steps < 0:
-        raise ValueError("n_steps must be >= 0")
-    st = _dyn_status(status, nb)
-    out = dict(irf=np.empty((nb, c, n_steps, m)) if irf else None, fevd=np.empty((nb, n_steps, m, c)) if fevd else None)
-    _lib.check(_lib.load().dsge_irf_batched_host(_ptr(T), _ptr(R), _ptr(S), sb, _ptr(weights), wb, _ptr(st), nb, m, k, c, n_steps,
-                                                 _ptr(out["irf"]), _ptr(out["fevd"])))
-    return out
+    return F.impulse_response(HOST, "impulse_response_batched", T, R, n_steps=n_steps, S=S, weights=weights, fevd=fevd, irf=irf,
+                              status=status)
 
 
 def forecast_batched(T, R, Q, a0, P0=None, n_steps=10, Z=None, d=None, Hdiag=None, q_mode=None, covariances="diag",
@@ -636,38 +499,8 @@ def forecast_batched(T, R, Q, a0, P0=None, n_steps=10, Z=None, d=None, Hdiag=Non
     ``kalman_filter_outputs_batched(..., full_covariances=True)`` -> ``a0 = filtered_states[:, -1]``,
     ``P0 = filtered_covs[:, -1]``.  Returns dict(states (batch, n_steps, m), covs, observed (batch, n_steps, p) or None,
     observed_covs (batch, n_steps, p, p) or None)."""
-    T, R, nb, m, k = _dyn_TR(T, R, "forecast_batched")
-    Q, code = _resolve_q(Q, q_mode, nb, k)
-    a0 = _f64(a0)
-    if a0.shape != (nb, m):
-        raise ValueError(f"a0 must be {(nb, m)}; got {a0.shape}")
-    if P0 is not None:
-        P0 = _f64(P0)
-        if P0.shape != (nb, m, m):
-            raise ValueError(f"P0 must be {(nb, m, m)}; got {P0.shape}")
-    if covariances not in ("diag", "full", None):
-        raise ValueError('covariances must be "diag", "full" or None')
-    p, zb, db, hb = 0, 0, 0, 0
-    if Z is not None:
-        Z = _f64(Z)
-        p = Z.shape[-2] if Z.ndim >= 2 else 0
-        Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, m)
-    elif d is not None or Hdiag is not None:
-        raise ValueError("d and Hdiag need Z")
-    n_steps = int(n_steps)
-    if n_steps < 0:
-        raise ValueError("n_steps must be >= 0")
-    st = _dyn_status(status, nb)
-    cov = covariances is not None
-    full = covariances == "full"
-    out = dict(states=np.empty((nb, n_steps, m)),
-               covs=np.empty((nb, n_steps, m, m) if full else (nb, n_steps, m)) if cov else None,
-               observed=np.empty((nb, n_steps, p)) if p else None,
-               observed_covs=np.empty((nb, n_steps, p, p)) if p and cov else None)
-    _lib.check(_lib.load().dsge_forecast_batched_host(
-        _ptr(T), _ptr(R), _ptr(Q), code, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(a0), _ptr(P0), _ptr(st), nb, m, k, p,
-        n_steps, _ptr(out["states"]), _ptr(out["covs"]), int(full), _ptr(out["observed"]), _ptr(out["observed_covs"])))
-    return out
+    return F.forecast(HOST, "forecast_batched", T, R, Q, a0, P0=P0, n_steps=n_steps, Z=Z, d=d, Hdiag=Hdiag, q_mode=q_mode,
+                      covariances=covariances, status=status)
 
 
 def solve_kalman_logp_batched(A, B, C, D, Q, Z, y, d=None, Hdiag=None, q_mode=None, solver="cycle_reduction",
@@ -683,38 +516,17 @@ def solve_kalman_logp_batched(A, B, C, D, Q, Z, y, d=None, Hdiag=None, q_mode=No
     ``options``: per-call kernel-variant switches (dict of ``dsge_options`` fields or ``_lib.Options``).
     Returns dict(logp, status[, T, R, resid, n_iter])."""
     check_filter_type(filter_type)
-    A, B, C = _check_abc(A, B, C)
-    D = _f64(D, 3)
-    y = _f64(y, 2)
-    nb, n, _ = A.shape
-    k = D.shape[2]
-    T_len, p = y.shape
-    Q, code = _resolve_q(Q, q_mode, nb, k)
-    Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, n)
-    logp = np.empty(nb)
-    status = np.empty(nb, dtype=np.int32)
-    T = R = resid = n_iter = None
-    if return_policy:
-        T = np.empty_like(A)
-        R = np.empty((nb, n, k))
-        resid = np.empty(nb)
-        n_iter = np.empty(nb, dtype=np.int32)
-    ns = state_hint(A) if n_state_hint is None else int(n_state_hint)
-    zs = selector_hint(Z) if z_selector_hint is None else int(z_selector_hint)
-    nl = (lead_hint(C, tol) if solver == "gensys" else 0) if n_lead_hint is None else int(n_lead_hint)
-    op, _keep = _lib.opt_ptr(options)
-    _lib.check(
-        _lib.load().dsge_solve_kalman_logp_batched_host_opt(
-            op, _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(Q), code, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(y), nb,
-            n, k, p, T_len, _lib.SOLVER_CODES[solver] | (0 if add_solver_success_check else _lib.SOLVER_FLAG_ZERO_T_ON_FAILURE),
-            float(tol), int(max_iter), float(jitter),
-            float(missing_fill_value), ns, zs, nl, _ptr(logp), _ptr(status), _ptr(T), _ptr(R), _ptr(resid), _ptr(n_iter)
-        )
-    )
-    out = dict(logp=logp, status=status)
-    if return_policy:
-        out.update(T=T, R=R, resid=resid, n_iter=n_iter)
-    return out
+
+    def hints(a):
+        return dict(n_state_hint=state_hint(a["A"]) if n_state_hint is None else n_state_hint,
+                    z_selector_hint=selector_hint(a["Z"]) if z_selector_hint is None else z_selector_hint,
+                    n_lead_hint=(lead_hint(a["C"], tol) if solver == "gensys" else 0) if n_lead_hint is None else n_lead_hint)
+
+    out = F.solve_kalman_logp(HOST, A, B, C, D, Q, Z, y, d=d, Hdiag=Hdiag, q_mode=q_mode, solver=solver, tol=tol, max_iter=max_iter,
+                              jitter=jitter, missing_fill=missing_fill_value, hints=hints, options=options,
+                              solver_flags=0 if add_solver_success_check else _lib.SOLVER_FLAG_ZERO_T_ON_FAILURE,
+                              return_policy=return_policy)
+    return out if return_policy else dict(logp=out["logp"], status=out["status"])
 
 
 def solve_kalman_logp_grad_batched(A, B, C, D, q, Z, y, d=None, Hdiag=None, solver="cycle_reduction", tol=1e-6, max_iter=50,
@@ -729,63 +541,25 @@ def solve_kalman_logp_grad_batched(A, B, C, D, q, Z, y, d=None, Hdiag=None, solv
     A design matrix that is not a selector (observation equations, statespace.py:298-332) takes the dense-Z entry point
     (``dsge_solve_kalman_logp_grad_dense_z_batched``: the observed combinations become p extra variables, n + p <= 56) --
     automatically, or forced with ``dense_z=True``; ``return_Z_bar=True`` adds ``Z_bar`` (batch, p, n), the cotangent of Z."""
-    A, B, C = _check_abc(A, B, C)
-    D = _f64(D, 3)
-    y = _f64(y, 2)
-    nb, n, _ = A.shape
-    k = D.shape[2]
-    T_len, p = y.shape
+    if Q is not None and q is not None:
+        raise ValueError("pass either q (diagonal variances) or Q (full covariance)")
+
+    def route(a):
+        A, Z, n = a["A"], a["Z"], a["n"]
+        dense = (bool(return_Z_bar) or not selector_hint(Z)) if dense_z is None else dense_z
+        if n_filter_hint is not None:
+            ns = n_filter_hint
+        elif dense:  # the dense entry point wants the number of STATE variables (non-zero columns of A in any draw)
+            ns = np.count_nonzero(np.any(A.reshape(-1, n) != 0, axis=0))
+        else:  # |S u O|: non-zero columns of A (in any draw) or of Z
+            ns = np.count_nonzero(np.any(A.reshape(-1, n) != 0, axis=0) | np.any(Z.reshape(-1, n) != 0, axis=0))
+        nl = (lead_hint(a["C"], tol) if solver == "gensys" else 0) if n_lead_hint is None else n_lead_hint
+        return dict(dense_z=dense, Z_bar=dense and return_Z_bar, n_hint=ns, n_lead_hint=nl)
+
+    out = F.solve_kalman_logp_grad(HOST, A, B, C, D, q if Q is None else Q, Z, y, full=Q is not None, d=d, Hdiag=Hdiag, solver=solver,
+                                   tol=tol, max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value, route=route,
+                                   options=options)
     if Q is not None:
-        if q is not None:
-            raise ValueError("pass either q (diagonal variances) or Q (full covariance)")
-        q = _f64(Q)
-        if q.shape not in ((k, k), (nb, k, k)):
-            raise ValueError("Q must be (k, k) or (batch, k, k)")
-        qb = 2 + int(q.ndim == 3)
-    else:
-        q = _f64(q)
-        if q.shape not in ((k,), (nb, k)):
-            raise ValueError("q must be (k,) or (batch, k) (diagonal shock covariance)")
-        qb = int(q.ndim == 2)
-    Z, zb, d, db, Hdiag, hb = _obs_args(Z, d, Hdiag, nb, p, n)
-    if dense_z is None:
-        dense_z = bool(return_Z_bar) or not selector_hint(Z)
-    if n_filter_hint is not None:
-        ns = int(n_filter_hint)
-    elif dense_z:  # the dense entry point wants the number of STATE variables (non-zero columns of A in any draw)
-        ns = int(np.count_nonzero(np.any(A.reshape(-1, n) != 0, axis=0)))
-    else:  # |S u O|: non-zero columns of A (in any draw) or of Z
-        ns = int(np.count_nonzero(np.any(A.reshape(-1, n) != 0, axis=0) | np.any(Z.reshape(-1, n) != 0, axis=0)))
-    nl = (lead_hint(C, tol) if solver == "gensys" else 0) if n_lead_hint is None else int(n_lead_hint)
-    out = dict(logp=np.empty(nb), status=np.empty(nb, dtype=np.int32), A_bar=np.empty_like(A), B_bar=np.empty_like(A),
-               C_bar=np.empty_like(A), D_bar=np.empty_like(D), q_bar=np.empty((nb, k, k) if qb >= 2 else (nb, k)))
-    if d is not None:
-        out["d_bar"] = np.empty((nb, p))
-    if Hdiag is not None:
-        out["h_bar"] = np.empty((nb, p))
-    if dense_z:
-        if return_Z_bar:
-            out["Z_bar"] = np.empty((nb, p, n))
-        with _lib.options_scope(options):
-            _lib.check(
-                _lib.load().dsge_solve_kalman_logp_grad_dense_z_batched_host(
-                    _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(q), qb, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(y), nb, n, k,
-                    p, T_len, _lib.SOLVER_CODES[solver], float(tol), int(max_iter), float(jitter), float(missing_fill_value), ns,
-                    nl, _ptr(out["logp"]), _ptr(out["status"]), _ptr(out["A_bar"]), _ptr(out["B_bar"]), _ptr(out["C_bar"]),
-                    _ptr(out["D_bar"]), _ptr(out["q_bar"]), _ptr(out.get("d_bar")), _ptr(out.get("h_bar")), _ptr(out.get("Z_bar"))
-                )
-            )
-    else:
-        op, _keep = _lib.opt_ptr(options)
-        _lib.check(
-            _lib.load().dsge_solve_kalman_logp_grad_batched_host_opt(
-                op, _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(q), qb, _ptr(Z), zb, _ptr(d), db, _ptr(Hdiag), hb, _ptr(y), nb, n, k,
-                p, T_len, _lib.SOLVER_CODES[solver], float(tol), int(max_iter), float(jitter), float(missing_fill_value), ns, nl,
-                _ptr(out["logp"]), _ptr(out["status"]), _ptr(out["A_bar"]), _ptr(out["B_bar"]), _ptr(out["C_bar"]),
-                _ptr(out["D_bar"]), _ptr(out["q_bar"]), _ptr(out.get("d_bar")), _ptr(out.get("h_bar"))
-            )
-        )
-    if qb >= 2:
         out["Q_bar"] = out.pop("q_bar")
     return out
 
@@ -813,41 +587,10 @@ def second_order_logp_batched(A, B, C, D, hess_idx, hess_val, q, Z, y, d=None, H
     ``hess_idx``: (nnz, 3) int32 (equation, z_a <= z_b) sorted by equation, z = [y-; y; y+; u]; ``hess_val``: (batch, nnz);
     ``q``: (k,) or (batch, k) shock variances; ``Z``: (p, n), p <= 8.
     Returns dict(logp, status[, T, R, g_yy (batch, n, s, s), g_yu (batch, n, s, k), g_uu (batch, n, k, k), g_ss (batch, n), S])."""
-    A, B, C = _check_abc(A, B, C)
-    D = _f64(D, 3)
-    y = _f64(y, 2)
-    nb, n, _ = A.shape
-    k = D.shape[2]
-    T_len, p = y.shape
-    hess_idx = np.ascontiguousarray(hess_idx, dtype=np.int32).reshape(-1, 3)
-    nnz = hess_idx.shape[0]
-    hess_val = _f64(hess_val, 2)
-    if hess_val.shape != (nb, nnz):
-        raise ValueError("hess_val must be (batch, nnz)")
-    q = _f64(q)
-    if q.shape not in ((k,), (nb, k)):
-        raise ValueError("q must be (k,) or (batch, k) (diagonal shock covariance)")
-    Z = _f64(Z, 2)
-    if Z.shape != (p, n):
-        raise ValueError("Z must be (p, n)")
-    d = None if d is None else _f64(d, 1)
-    Hdiag = None if Hdiag is None else _f64(Hdiag, 1)
-    S, Lc, U = second_order_structure(A, C, Z) if structure is None else (np.ascontiguousarray(x, dtype=np.int32) for x in structure)
-    s = len(S)
-    out = dict(logp=np.empty(nb), status=np.empty(nb, dtype=np.int32))
-    T = R = gyy = gyu = guu = gss = None
-    if return_solution:
-        T, R = np.empty_like(A), np.empty((nb, n, k))
-        gyy, gyu, guu, gss = np.empty((nb, n, s, s)), np.empty((nb, n, s, k)), np.empty((nb, n, k, k)), np.empty((nb, n))
-    with _lib.options_scope(options):
-        _lib.check(
-            _lib.load().dsge_second_order_logp_batched_host(
-                _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(hess_idx), nnz, _ptr(hess_val), _ptr(q), int(q.ndim == 2), _ptr(Z),
-                _ptr(d), _ptr(Hdiag), _ptr(y), nb, n, k, p, T_len, _lib.SOLVER_CODES[solver], float(tol), int(max_iter),
-                float(jitter), float(missing_fill_value), _ptr(S), s, _ptr(Lc), len(Lc), _ptr(U), len(U), _ptr(out["logp"]),
-                _ptr(out["status"]), _ptr(T), _ptr(R), _ptr(gyy), _ptr(gyu), _ptr(guu), _ptr(gss)
-            )
-        )
-    if return_solution:
-        out.update(T=T, R=R, g_yy=gyy, g_yu=gyu, g_uu=guu, g_ss=gss, S=S)
-    return out
+    out, S = F.second_order_logp(HOST, A, B, C, D, np.asarray(hess_idx).reshape(-1, 3), hess_val, q, Z, y, d=d, Hdiag=Hdiag,
+                                 solver=solver, tol=tol, max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value,
+                                 structure=second_order_structure if structure is None else structure, options=options,
+                                 return_solution=return_solution)
+    if not return_solution:
+        return dict(logp=out["logp"], status=out["status"])
+    return dict(out, S=S)

@@ -5,8 +5,11 @@ every FLOP of the path runs in the hand-written kernels behind the C ABI.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
+from . import _frontend as F
 from . import _lib
 from .batched import JITTER_DEFAULT, MISSING_FILL
 from .workloads import shard_bounds
@@ -16,6 +19,35 @@ def _torch():
     import torch
 
     return torch
+
+
+class DeviceBackend:
+    """The torch side of ``_frontend``: float64 / int32 CUDA tensors on one device, work enqueued on torch's current stream."""
+
+    host = False
+
+    def __init__(self, torch, device):
+        self.torch, self.device = torch, device
+
+    @property
+    def stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def inp(self, t, dtype="float64"):
+        if t is not None and not (isinstance(t, self.torch.Tensor) and t.is_cuda and t.dtype == getattr(self.torch, dtype)
+                                  and t.is_contiguous()):
+            raise ValueError(f"expected a contiguous {dtype} CUDA tensor")
+        return t
+
+    def empty(self, shape, dtype="float64"):
+        return self.torch.empty(shape, dtype=getattr(self.torch, dtype), device=self.device)
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def status_io(self, status, nb):
+        return self.torch.zeros(nb, dtype=self.torch.int32, device=self.device) if status is None else self.inp(status, "int32")
 
 
 class LogpEngine:
@@ -32,6 +64,7 @@ class LogpEngine:
         self.torch = torch
         self.device = torch.device("cuda", device) if not isinstance(device, torch.device) else device
         self.lib = _lib.load()
+        self.backend = DeviceBackend(torch, self.device)
         torch.cuda.set_device(self.device)
         _lib.check(self.lib.dsge_set_device(self.device.index or 0))
 
@@ -42,49 +75,13 @@ class LogpEngine:
             return x.to(self.device, dtype or torch.float64).contiguous()
         return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype or torch.float64, device=self.device)
 
-    def _chk(self, t, shape=None):
-        torch = self.torch
-        if t is None:
-            return None
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("expected a contiguous float64 CUDA tensor")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError(f"expected shape {shape}, got {tuple(t.shape)}")
-        return t
+    def _chk(self, t):
+        return self.backend.inp(t)
 
-    @staticmethod
-    def _p(t):
-        return None if t is None else t.data_ptr()
+    _p = staticmethod(DeviceBackend.ptr)
 
     def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def _q_layout(self, Q, q_mode, nb, k):
-        self._chk(Q)
-        if q_mode is None:
-            q_mode = {(k,): 0, (nb, k, k): 3}.get(tuple(Q.shape))
-            if q_mode is None:
-                if tuple(Q.shape) == (nb, k) and nb != k:
-                    q_mode = 1
-                elif tuple(Q.shape) == (k, k) and nb != k:
-                    q_mode = 2
-                else:
-                    raise ValueError("ambiguous Q layout; pass q_mode")
-        return int(q_mode)
-
-    def _pack(self, A, B, C, D, Q, Z, y, d, Hdiag, q_mode):
-        nb, n, _ = A.shape
-        k = D.shape[2]
-        T_len, p = y.shape
-        for t in (A, B, C):
-            self._chk(t, (nb, n, n))
-        self._chk(D, (nb, n, k))
-        self._chk(y, (T_len, p))
-        q_mode = self._q_layout(Q, q_mode, nb, k)
-        zb = int(self._chk(Z).dim() == 3)
-        db = int(d is not None and self._chk(d).dim() == 2)
-        hb = int(Hdiag is not None and self._chk(Hdiag).dim() == 2)
-        return nb, n, k, p, T_len, int(q_mode), zb, db, hb
+        return self.backend.stream
 
     def structure_hints(self, A, Z):
         """(n_state_hint, z_selector_hint) from device tensors: one small reduction + host sync;
@@ -107,9 +104,7 @@ class LogpEngine:
     def record_steady_steps(self, buf):
         """Debug: ``buf`` (int32 CUDA tensor [batch]) receives, from the fast-path Kalman launches that
         follow, the first time step each draw ran in steady-state mode (-1 = never); ``None`` stops."""
-        if buf is not None and not (buf.is_cuda and buf.dtype == self.torch.int32 and buf.is_contiguous()):
-            raise ValueError("expected a contiguous int32 CUDA tensor")
-        _lib.check(self.lib.dsge_debug_kalman_steady_steps(None if buf is None else buf.data_ptr()))
+        _lib.check(self.lib.dsge_debug_kalman_steady_steps(self._p(self.backend.inp(buf, "int32"))))
 
     # -- on-device Jacobians (SURVEY 8 f1) ---------------------------------------------------
     def jacobians_from_theta(self, program, theta, out=None):
@@ -208,23 +203,11 @@ class LogpEngine:
         """Enqueue one fused evaluation of the whole batch; returns (logp, status) tensors
         (asynchronous: synchronize the stream before reading them on the host).  ``T_out`` [batch][n][n] /
         ``R_out`` [batch][n][k]: optional float64 CUDA tensors that receive the policy matrices."""
-        torch = self.torch
-        nb, n, k, p, T_len, qm, zb, db, hb = self._pack(A, B, C, D, Q, Z, y, d, Hdiag, q_mode)
-        if logp is None:
-            logp = torch.empty(nb, dtype=torch.float64, device=self.device)
-        if status is None:
-            status = torch.empty(nb, dtype=torch.int32, device=self.device)
-        op, _keep = _lib.opt_ptr(options)
-        _lib.check(
-            self.lib.dsge_solve_kalman_logp_batched_opt(
-                op, self._p(A), self._p(B), self._p(C), self._p(D), self._p(Q), qm, self._p(Z), zb, self._p(d), db,
-                self._p(Hdiag), hb, self._p(y), nb, n, k, p, T_len, _lib.SOLVER_CODES[solver], float(tol),
-                int(max_iter), float(jitter), float(missing_fill_value), int(n_state_hint), int(z_selector_hint),
-                int(n_lead_hint), self._p(logp), status.data_ptr(), self._p(T_out), self._p(R_out), None, None,
-                self._stream(),
-            )
-        )
-        return logp, status
+        hints = dict(n_state_hint=n_state_hint, z_selector_hint=z_selector_hint, n_lead_hint=n_lead_hint)
+        out = F.solve_kalman_logp(self.backend, A, B, C, D, Q, Z, y, d=d, Hdiag=Hdiag, q_mode=q_mode, solver=solver, tol=tol,
+                                  max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value, hints=lambda a: hints,
+                                  options=options, out=dict(logp=logp, status=status, T=T_out, R=R_out))
+        return out["logp"], out["status"]
 
     def kalman_smoother(self, T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, jitter=JITTER_DEFAULT,
                         missing_fill_value=MISSING_FILL, full_covariances=False, covariances=True, rank_tol=None,
@@ -234,131 +217,33 @@ class LogpEngine:
         Returns a dict of device tensors: ll, smoothed_states, smoothed_covs (None with ``covariances=False``: the covariance
         recursion is then skipped), smoothed_shocks, status (asynchronous: synchronize before reading on the host).  ``status``:
         optional int32 tensor [batch] of incoming per-draw status words (updated in place)."""
-        torch = self.torch
-        nb, m, _ = T.shape
-        self._chk(T, (nb, m, m))
-        k = self._chk(R).shape[2]
-        # (the packing of solve_kalman_logp: T, R stand in for the model matrices)
-        _, _, _, p, T_len, qm, zb, db, hb = self._pack(T, T, T, R, Q, Z, y, d, Hdiag, q_mode)
-        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)  # noqa: E731
-        if status is None:
-            status = torch.zeros(nb, dtype=torch.int32, device=self.device)
-        out = dict(ll=mk(nb, T_len), smoothed_states=mk(nb, T_len, m),
-                   smoothed_covs=(mk(nb, T_len, m, m) if full_covariances else mk(nb, T_len, m)) if covariances else None,
-                   smoothed_shocks=mk(nb, T_len, k), status=status)
-        with _lib.options_scope(options):
-            _lib.check(
-                self.lib.dsge_kalman_smoother_batched(
-                    self._p(T), self._p(R), self._p(Q), qm, self._p(Z), zb, self._p(d), db, self._p(Hdiag), hb, self._p(y), nb, m,
-                    k, p, T_len, float(jitter), float(missing_fill_value), 0.0 if rank_tol is None else float(rank_tol),
-                    0 if scratch_limit_bytes is None else int(scratch_limit_bytes), self._p(out["ll"]),
-                    self._p(out["smoothed_states"]), self._p(out["smoothed_covs"]), self._p(out["smoothed_shocks"]),
-                    int(bool(full_covariances)), status.data_ptr(), self._stream(),
-                )
-            )
-        return out
+        return F.kalman_smoother(self.backend, "kalman_smoother", T, R, Q, Z, y, d=d, Hdiag=Hdiag, q_mode=q_mode, status=status,
+                                 jitter=jitter, missing_fill=missing_fill_value, cov=covariances, full=full_covariances,
+                                 rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes, options=options)
 
     # -- post-solve dynamics (csrc/dsge_dynamics.hpp) -----------------------------------------
-    def _dyn_TR(self, T, R):
-        nb, m, _ = T.shape
-        self._chk(T, (nb, m, m))
-        k = self._chk(R).shape[-1]
-        self._chk(R, (nb, m, k))
-        return nb, m, k
-
-    def _dyn_flag(self, t, nb, tail, name):
-        """0 for shape ``tail`` (shared), 1 for ``(batch,) + tail``."""
-        shape = tuple(self._chk(t).shape)
-        if shape == tuple(tail):
-            return 0
-        if shape == (nb, *tail):
-            return 1
-        raise ValueError(f"{name} must be {tuple(tail)} or {(nb, *tail)}; got {shape}")
-
-    def _dyn_status(self, status, nb):
-        if status is not None and not (status.is_cuda and status.dtype == self.torch.int32 and status.is_contiguous()
-                                       and tuple(status.shape) == (nb,)):
-            raise ValueError("status must be a contiguous int32 CUDA tensor (batch,)")
-        return None if status is None else status.data_ptr()
-
-    def _dyn_out(self, out, shape):
-        if out is None:
-            return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
-        return self._chk(out, shape)
-
     def simulate(self, T, R, eps, n_steps=None, x0=None, status=None, out=None):
         """Simulated paths of the whole batch from device tensors (``dsge_simulate_batched``; see
         ``batched.simulate_batched``), enqueued on torch's current stream.  ``eps``: (n_paths, n_shock_steps, k) or
         (batch, n_paths, n_shock_steps, k) -- draw it with torch on the device.  Returns the paths
         (batch, n_paths, n_steps, m) (``out`` if given); asynchronous."""
-        nb, m, k = self._dyn_TR(T, R)
-        if self._chk(eps).dim() not in (3, 4) or eps.shape[-1] != k:
-            raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k})")
-        n_paths, n_shock = eps.shape[-3], eps.shape[-2]
-        eb = self._dyn_flag(eps, nb, (n_paths, n_shock, k), "eps")
-        n_steps = n_shock if n_steps is None else int(n_steps)
-        xb = 0 if x0 is None else self._dyn_flag(x0, nb, (n_paths, m), "x0")
-        out = self._dyn_out(out, (nb, n_paths, n_steps, m))
-        _lib.check(self.lib.dsge_simulate_batched(self._p(T), self._p(R), self._p(eps), eb, self._p(x0), xb,
-                                                  self._dyn_status(status, nb), nb, m, k, n_paths, n_steps, n_shock,
-                                                  self._p(out), self._stream()))
-        return out
+        return F.simulate(self.backend, "simulate", T, R, eps, n_steps=n_steps, x0=x0, status=status, out=out)
 
     def impulse_response(self, T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None, out=None):
         """Impulse responses (and, with ``fevd=True``, their variance decomposition) of the whole batch from device tensors
         (``dsge_irf_batched``; see ``batched.impulse_response_batched``), on torch's current stream.  ``out``: optional dict
         with preallocated ``irf`` / ``fevd`` tensors.  Returns dict(irf (batch, c, n_steps, m) or None,
         fevd (batch, n_steps, m, c) or None); asynchronous."""
-        nb, m, k = self._dyn_TR(T, R)
-        sb, c = 0, k
-        if S is not None:
-            if self._chk(S).dim() not in (2, 3) or S.shape[-2] != k:
-                raise ValueError(f"S must be ({k}, c) or (batch, {k}, c)")
-            c = S.shape[-1]
-            sb = self._dyn_flag(S, nb, (k, c), "S")
-        wb = 0 if weights is None else self._dyn_flag(weights, nb, (c,), "weights")
-        if not (irf or fevd):
-            raise ValueError("nothing requested: irf and fevd are both off")
-        n_steps = int(n_steps)
-        out = out or {}
-        res = dict(irf=self._dyn_out(out.get("irf"), (nb, c, n_steps, m)) if irf else None,
-                   fevd=self._dyn_out(out.get("fevd"), (nb, n_steps, m, c)) if fevd else None)
-        _lib.check(self.lib.dsge_irf_batched(self._p(T), self._p(R), self._p(S), sb, self._p(weights), wb,
-                                             self._dyn_status(status, nb), nb, m, k, c, n_steps, self._p(res["irf"]),
-                                             self._p(res["fevd"]), self._stream()))
-        return res
+        return F.impulse_response(self.backend, "impulse_response", T, R, n_steps=n_steps, S=S, weights=weights, fevd=fevd, irf=irf,
+                                  status=status, out=out)
 
     def forecast(self, T, R, Q, a0, P0=None, n_steps=10, Z=None, d=None, Hdiag=None, q_mode=None, covariances="diag",
                  status=None, out=None):
         """Forecast moments of the whole batch from device tensors (``dsge_forecast_batched``; see
         ``batched.forecast_batched``), on torch's current stream.  ``out``: optional dict with preallocated ``states`` / ``covs``
         / ``observed`` / ``observed_covs``.  Returns that dict (entries not requested are None); asynchronous."""
-        nb, m, k = self._dyn_TR(T, R)
-        self._chk(a0, (nb, m))
-        self._chk(P0, (nb, m, m) if P0 is not None else None)
-        if covariances not in ("diag", "full", None):
-            raise ValueError('covariances must be "diag", "full" or None')
-        qm = self._q_layout(Q, q_mode, nb, k)
-        p, zb, db, hb = 0, 0, 0, 0
-        if Z is not None:
-            p = self._chk(Z).shape[-2]
-            zb = self._dyn_flag(Z, nb, (p, m), "Z")
-            db = 0 if d is None else self._dyn_flag(d, nb, (p,), "d")
-            hb = 0 if Hdiag is None else self._dyn_flag(Hdiag, nb, (p,), "Hdiag")
-        elif d is not None or Hdiag is not None:
-            raise ValueError("d and Hdiag need Z")
-        n_steps = int(n_steps)
-        cov, full = covariances is not None, covariances == "full"
-        out = out or {}
-        res = dict(states=self._dyn_out(out.get("states"), (nb, n_steps, m)),
-                   covs=self._dyn_out(out.get("covs"), (nb, n_steps, m, m) if full else (nb, n_steps, m)) if cov else None,
-                   observed=self._dyn_out(out.get("observed"), (nb, n_steps, p)) if p else None,
-                   observed_covs=self._dyn_out(out.get("observed_covs"), (nb, n_steps, p, p)) if p and cov else None)
-        _lib.check(self.lib.dsge_forecast_batched(
-            self._p(T), self._p(R), self._p(Q), qm, self._p(Z), zb, self._p(d), db, self._p(Hdiag), hb, self._p(a0), self._p(P0),
-            self._dyn_status(status, nb), nb, m, k, p, n_steps, self._p(res["states"]), self._p(res["covs"]), int(full),
-            self._p(res["observed"]), self._p(res["observed_covs"]), self._stream()))
-        return res
+        return F.forecast(self.backend, "forecast", T, R, Q, a0, P0=P0, n_steps=n_steps, Z=Z, d=d, Hdiag=Hdiag, q_mode=q_mode,
+                          covariances=covariances, status=status, out=out)
 
     def solve_kalman_logp_grad(self, A, B, C, D, q, Z, y, d=None, Hdiag=None, solver="cycle_reduction", tol=1e-6, max_iter=50,
                                jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, n_filter_hint=0, n_lead_hint=0,
@@ -370,63 +255,10 @@ class LogpEngine:
         reuse the buffers.  ``dense_z=True``: any design matrix (observation equations), through
         ``dsge_solve_kalman_logp_grad_dense_z_batched`` (n + p <= 56); the dict then also holds ``Z_bar`` (batch, p, n) and
         ``n_filter_hint`` counts the state variables (non-zero columns of A)."""
-        torch = self.torch
-        nb, n, _ = A.shape
-        k = D.shape[2]
-        T_len, p = y.shape
-        for t in (A, B, C):
-            self._chk(t, (nb, n, n))
-        self._chk(D, (nb, n, k))
-        self._chk(y, (T_len, p))
-        self._chk(q)
-        if full_covariance:
-            if tuple(q.shape) not in ((k, k), (nb, k, k)):
-                raise ValueError("Q must be (k, k) or (batch, k, k)")
-            q_mode = 2 + int(q.dim() == 3)
-        else:
-            if tuple(q.shape) not in ((k,), (nb, k)):
-                raise ValueError("q must be (k,) or (batch, k)")
-            q_mode = int(q.dim() == 2)
-        zb = int(self._chk(Z).dim() == 3)
-        db = int(d is not None and self._chk(d).dim() == 2)
-        hb = int(Hdiag is not None and self._chk(Hdiag).dim() == 2)
-        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)  # noqa: E731
-        if out is None:
-            out = dict(logp=mk(nb), status=torch.empty(nb, dtype=torch.int32, device=self.device), A_bar=mk(nb, n, n),
-                       B_bar=mk(nb, n, n), C_bar=mk(nb, n, n), D_bar=mk(nb, n, k),
-                       q_bar=mk(nb, k, k) if full_covariance else mk(nb, k))
-        # buffers this call needs that a reused ``out`` (from a call with another observation model) does not carry yet
-        if d is not None and "d_bar" not in out:
-            out["d_bar"] = mk(nb, p)
-        if Hdiag is not None and "h_bar" not in out:
-            out["h_bar"] = mk(nb, p)
-        if dense_z and "Z_bar" not in out:
-            out["Z_bar"] = mk(nb, p, n)
-        if dense_z:
-            with _lib.options_scope(options):
-                _lib.check(
-                    self.lib.dsge_solve_kalman_logp_grad_dense_z_batched(
-                        self._p(A), self._p(B), self._p(C), self._p(D), self._p(q), q_mode, self._p(Z), zb, self._p(d), db,
-                        self._p(Hdiag), hb, self._p(y), nb, n, k, p, T_len, _lib.SOLVER_CODES[solver], float(tol), int(max_iter),
-                        float(jitter), float(missing_fill_value), int(n_filter_hint), int(n_lead_hint), self._p(out["logp"]),
-                        out["status"].data_ptr(), self._p(out["A_bar"]), self._p(out["B_bar"]), self._p(out["C_bar"]),
-                        self._p(out["D_bar"]), self._p(out["q_bar"]), self._p(out.get("d_bar")), self._p(out.get("h_bar")),
-                        self._p(out.get("Z_bar")), self._stream(),
-                    )
-                )
-            return out
-        op, _keep = _lib.opt_ptr(options)
-        _lib.check(
-            self.lib.dsge_solve_kalman_logp_grad_batched_opt(
-                op, self._p(A), self._p(B), self._p(C), self._p(D), self._p(q), q_mode, self._p(Z), zb, self._p(d), db,
-                self._p(Hdiag), hb, self._p(y), nb, n, k, p, T_len, _lib.SOLVER_CODES[solver], float(tol), int(max_iter),
-                float(jitter), float(missing_fill_value), int(n_filter_hint), int(n_lead_hint), self._p(out["logp"]),
-                out["status"].data_ptr(), self._p(out["A_bar"]), self._p(out["B_bar"]), self._p(out["C_bar"]),
-                self._p(out["D_bar"]), self._p(out["q_bar"]), self._p(out.get("d_bar")), self._p(out.get("h_bar")),
-                self._stream(),
-            )
-        )
-        return out
+        route = dict(dense_z=dense_z, Z_bar=dense_z, n_hint=n_filter_hint, n_lead_hint=n_lead_hint)
+        return F.solve_kalman_logp_grad(self.backend, A, B, C, D, q, Z, y, full=full_covariance, d=d, Hdiag=Hdiag, solver=solver, tol=tol,
+                                        max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value, route=lambda a: route,
+                                        options=options, out=out)
 
     def second_order_structure(self, A, C, Z):
         """(S, L, U) int32 numpy index lists of ``batched.second_order_structure`` from device tensors (a property of the
@@ -446,58 +278,27 @@ class LogpEngine:
         (include/dsge_hip.h: ``dsge_second_order_logp_batched``; BASELINE configs[4]).  ``hess_idx``: int32 CUDA tensor
         (nnz, 3); ``hess_val``: float64 (batch, nnz); ``q``: (k,) or (batch, k); ``structure`` = ``second_order_structure``.
         ``stage_ms``: a ctypes float[4] that receives the stage durations (synchronises).  Returns (logp, status)."""
-        torch = self.torch
-        nb, n, _ = A.shape
-        k = D.shape[2]
-        T_len, p = y.shape
-        for t in (A, B, C):
-            self._chk(t, (nb, n, n))
-        self._chk(D, (nb, n, k))
-        self._chk(y, (T_len, p))
-        self._chk(Z, (p, n))
-        self._chk(q)
-        if not (hess_idx.is_cuda and hess_idx.dtype == torch.int32 and hess_idx.is_contiguous() and hess_idx.shape[1] == 3):
-            raise ValueError("hess_idx must be a contiguous int32 CUDA tensor (nnz, 3)")
-        nnz = hess_idx.shape[0]
-        self._chk(hess_val, (nb, nnz))
-        S, Lc, U = (np.ascontiguousarray(x, dtype=np.int32) for x in structure)
-        if logp is None:
-            logp = torch.empty(nb, dtype=torch.float64, device=self.device)
-        if status is None:
-            status = torch.empty(nb, dtype=torch.int32, device=self.device)
-        with _lib.options_scope(options):
-            _lib.check(
-                self.lib.dsge_second_order_logp_batched(
-                    self._p(A), self._p(B), self._p(C), self._p(D), hess_idx.data_ptr(), nnz, self._p(hess_val), self._p(q),
-                    int(q.dim() == 2), self._p(Z), self._p(d), self._p(Hdiag), self._p(y), nb, n, k, p, T_len,
-                    _lib.SOLVER_CODES[solver], float(tol), int(max_iter), float(jitter), float(missing_fill_value),
-                    S.ctypes.data, len(S), Lc.ctypes.data, len(Lc), U.ctypes.data, len(U), self._p(logp), status.data_ptr(),
-                    None, None, None, None, None, None, None if stage_ms is None else __import__("ctypes").addressof(stage_ms),
-                    self._stream(),
-                )
-            )
-        return logp, status
+        out, _ = F.second_order_logp(self.backend, A, B, C, D, hess_idx, hess_val, q, Z, y, d=d, Hdiag=Hdiag, solver=solver, tol=tol,
+                                     max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value, structure=structure,
+                                     options=options, out=dict(logp=logp, status=status),
+                                     stage_ms=None if stage_ms is None else ctypes.addressof(stage_ms))
+        return out["logp"], out["status"]
 
     def profile_kernels(self, A, B, C, D, Q, Z, y, d=None, Hdiag=None, q_mode=None, solver="cycle_reduction",
                         tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, reps=5,
                         n_state_hint=0, z_selector_hint=0, n_lead_hint=0):
         """Average per-kernel durations (ms) measured with HIP events on the launch stream:
         dict(solver=, assemble=, kalman=)."""
-        import ctypes
-
-        torch = self.torch
-        nb, n, k, p, T_len, qm, zb, db, hb = self._pack(A, B, C, D, Q, Z, y, d, Hdiag, q_mode)
-        logp = torch.empty(nb, dtype=torch.float64, device=self.device)
-        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        b = self.backend
+        a = F.model_args(b, A, B, C, D, y)
+        nb, n, k = a["batch"], a["n"], a["k"]
+        a.update(F.obs_args(b, Z, d, Hdiag, nb, a["p"], n))
+        logp, status = b.empty((nb,)), b.empty((nb,), "int32")
         ms = (ctypes.c_float * 3)()
-        _lib.check(
-            self.lib.dsge_profile_pipeline(
-                self._p(A), self._p(B), self._p(C), self._p(D), self._p(Q), qm, self._p(Z), zb, self._p(d), db,
-                self._p(Hdiag), hb, self._p(y), nb, n, k, p, T_len, _lib.SOLVER_CODES[solver], float(tol),
-                int(max_iter), float(jitter), float(missing_fill_value), int(n_state_hint), int(z_selector_hint),
-                int(n_lead_hint), self._p(logp), status.data_ptr(), int(reps), ctypes.addressof(ms), self._stream(),
-            )
-        )
+        F.call(b, "dsge_profile_pipeline", **a, Q=b.inp(Q), q_mode=F.q_layout(Q.shape, q_mode, nb, k), solver=_lib.SOLVER_CODES[solver],
+               tol=tol, max_iter=max_iter, jitter=jitter, missing_fill=missing_fill_value, n_state_hint=n_state_hint,
+               z_selector_hint=z_selector_hint, n_lead_hint=n_lead_hint, logp_out=logp, status_out=status, reps=reps,
+               ms_out=ctypes.addressof(ms))
         return dict(solver=float(ms[0]), assemble=float(ms[1]), kalman=float(ms[2]))
 
 

@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/dsge_hip.h declares; host-side
 argument handling; the product path refuses to run without a GPU (no CPU fallback)."""
+import ctypes
 import os
 import re
 
@@ -12,10 +13,26 @@ from geconpy_amd import workloads as wl
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_symbols():
+def _header():
     text = open(os.path.join(ROOT, "include", "dsge_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dsge_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(dsge_[a-z0-9_]+)\s*\(", _header())))
+
+
+def _declared_signatures():
+    """name -> ((argument name, kind), ...) of every declaration: kind is the ctypes type of a pointer / int / double / size_t."""
+    kinds = {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+    out = {}
+    for name, args in re.findall(r"\b(dsge_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header()):
+        out[name] = []
+        for arg in (" ".join(a.split()) for a in args.split(",")):
+            if arg not in ("void", ""):
+                typ, arg_name = re.fullmatch(r"(.*?)(\w+)", arg).groups()
+                out[name].append((arg_name, ctypes.c_void_p if "*" in typ else kinds[typ.replace("const ", "").strip()]))
+    return out
 
 
 def test_library_exports_every_declared_symbol():
@@ -31,6 +48,22 @@ def test_library_exports_every_declared_symbol():
         assert name in _lib.PROTOTYPES, f"{name} has no ctypes prototype"
     assert sorted(_lib.PROTOTYPES) == declared
     assert lib.dsge_abi_version() == _lib.ABI_VERSION
+    # names, order and kind of every argument, against the header
+    signatures = _declared_signatures()
+    assert sorted(signatures) == declared
+    for name, sig in signatures.items():
+        assert list(_lib.SIGNATURES[name]) == sig, name
+        assert _lib.PROTOTYPES[name] == [kind for _, kind in sig], name
+        assert getattr(lib, name).argtypes == _lib.PROTOTYPES[name], name
+    # a host twin is its device entry minus the trailing stream (second order: minus stage_ms too), in the HEADER as in the table
+    twins = [name for name in declared if name.endswith(("_host", "_host_opt"))]
+    assert set(twins) == {_lib.host_twin(entry) for entry in _lib._DEVICE_ENTRIES if "_batched" in entry}
+    for twin in twins:
+        entry = twin.replace("_host", "")
+        assert _lib.host_twin(entry) == twin
+        dropped = signatures[entry][len(signatures[twin]):]
+        assert signatures[twin] == signatures[entry][:len(signatures[twin])], twin
+        assert [arg for arg, _ in dropped] == (["stage_ms", "stream"] if entry == "dsge_second_order_logp_batched" else ["stream"]), twin
 
 
 def test_header_constants_match_python():
