@@ -30,6 +30,39 @@ def rts_smoother(states, T, R, Q):
     return a_s, V, eps
 
 
+def range_smoother(states, T, R, Q, rank_tol=1e-10):
+    """The DEVICE's form of the same recursion (csrc/dsge_kalman_smooth.hpp), restated: the pseudo-inverse of P_pred from its
+    range, which is fixed per draw.  U (m x r) is an orthonormal basis of [T | R_J], J = {j : Q_jj > 0}, by column-pivoted QR with
+    the rank |R_jj| > rank_tol |R_00|; per step M = sym(U' P_pred U) and P_pred^+ x = U M^-1 U' x; everything else as in
+    ``rts_smoother``.  Returns (smoothed states, covariances, shocks, r, min over the steps of lambda_min(M) / lambda_max(M))."""
+    a_pred, P_pred, a_filt, P_filt = (states[x] for x in ("a_pred", "P_pred", "a_filt", "P_filt"))
+    n, m = a_filt.shape
+    k = R.shape[1]
+    J = np.diag(Q) > 0
+    Qf, Rf, _ = sla.qr(np.hstack([T, R[:, J]]), mode="economic", pivoting=True)
+    dg = np.abs(np.diag(Rf))
+    r = int(np.count_nonzero(dg > rank_tol * dg[0]))
+    U = Qf[:, :r]
+    a_s = np.empty((n, m))
+    V = np.empty((n, m, m))
+    eps = np.full((n, k), np.nan)
+    a_s[-1], V[-1] = a_filt[-1], P_filt[-1]
+    lam = np.inf
+    for t in range(n - 2, -1, -1):
+        Pp = P_pred[t + 1]
+        M = U.T @ Pp @ U
+        M = 0.5 * (M + M.T)
+        ev = np.linalg.eigvalsh(M)
+        lam = min(lam, ev[0] / ev[-1])
+        w = U @ np.linalg.solve(M, U.T @ (a_s[t + 1] - a_pred[t + 1]))
+        a_s[t] = a_filt[t] + P_filt[t] @ (T.T @ w)
+        eps[t + 1] = Q @ (R.T @ w)
+        G = (U @ np.linalg.solve(M, U.T @ T @ P_filt[t])).T  # P_filt T' U M^-1 U'  (P_filt, M symmetric)
+        S = G @ (V[t + 1] - Pp) @ G.T
+        V[t] = P_filt[t] + 0.5 * (S + S.T)
+    return a_s, V, eps, r, lam
+
+
 def brute_force_smoother(y, T, R, Q, Z, H, jitter_F, missing_fill_value=-9999.0):
     """E[x_t | y], Cov[x_t | y], E[eps_t | y] by conditioning u = [x_{-1}, eps_0 .. eps_{n-1}] ~ N(0, blockdiag(dlyap(T, R Q R'),
     Q, ..., Q)) on the observed entries of y_t = Z x_t + noise, noise ~ N(0, H + jitter_F I), with x_t = T x_{t-1} + R eps_t."""

@@ -14,6 +14,7 @@ import oracle
 from geconpy_amd import _lib, batched
 from geconpy_amd import workloads as wl
 
+from tests import smoother_cases as cases
 from tests.smoother_reference import rts_smoother
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,10 @@ def _missing(y):
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
-    """dict(T, R, q, Z, y, d, H): the inputs of one parity case (computed once, shared, never modified)."""
+    """dict(T, R, q, q_mode, Z, y, d, H): the inputs of one parity case (computed once, shared, never modified); the edge cases
+    come from tests/smoother_cases.py, which the CPU test of the two numpy forms reads too."""
+    if name in cases.ALL_CASES:
+        return cases.case(name)
     rng = np.random.default_rng(5)
     d = None
     if name == "rbc":
@@ -85,7 +89,7 @@ def _case(name):
     q = b["sigma"][: T.shape[0]] ** 2
     for a in (T, R, q, Z, y, H):
         a.setflags(write=False)
-    return dict(T=T, R=R, q=q, Z=Z, y=y, d=d, H=H)
+    return dict(T=T, R=R, q=q, q_mode="diag_batched", Z=Z, y=y, d=d, H=H)
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,16 +98,16 @@ def _reference(name, conv=None):
     cv = None if conv is None else oracle.FilterConventions(**dict(conv))
     out = []
     for i in range(c["T"].shape[0]):
-        Q = np.diag(c["q"][i])
-        _, ll, stt = oracle.kalman_filter_logp(c["y"], c["T"][i], c["R"][i], Q, c["Z"], H=np.diag(c["H"]), d=c["d"],
+        x = cases.draw(c, i)  # (the matrices of draw i: Q as (k, k), Z, d, H of the draw where they are given per draw)
+        _, ll, stt = oracle.kalman_filter_logp(c["y"], x["T"], x["R"], x["Q"], x["Z"], H=x["H"], d=x["d"],
                                                return_states=True, conventions=cv)
-        out.append((ll, stt) + rts_smoother(stt, c["T"][i], c["R"][i], Q))
+        out.append((ll, stt) + rts_smoother(stt, x["T"], x["R"], x["Q"]))
     return out
 
 
 def _run(name, **kw):
     c = _case(name)
-    return batched.kalman_smoother_batched(c["T"], c["R"], c["q"], c["Z"], c["y"], d=c["d"], Hdiag=c["H"], **kw)
+    return batched.kalman_smoother_batched(c["T"], c["R"], c["q"], c["Z"], c["y"], d=c["d"], Hdiag=c["H"], q_mode=c["q_mode"], **kw)
 
 
 def _check_parity(name, conv=None, options=None, guard=False):
@@ -115,7 +119,7 @@ def _check_parity(name, conv=None, options=None, guard=False):
     assert_array_equal(full["smoothed_states"], diag["smoothed_states"])
     assert_array_equal(np.diagonal(full["smoothed_covs"], axis1=2, axis2=3), diag["smoothed_covs"])
     for i, (ll, stt, a, V, e) in enumerate(_reference(name, conv)):
-        sc, pc, ec = max(1.0, np.abs(stt["a_filt"]).max()), np.abs(stt["P_pred"]).max(), np.sqrt(c["q"][i]).max()
+        sc, pc, ec = cases.scales(c, i, stt)  # max(1, |a_filt|max), |P_pred|max, max sqrt(Q_jj)
         errs = (np.abs(full["smoothed_states"][i] - a).max() / sc, np.abs(full["smoothed_covs"][i] - V).max() / pc,
                 np.abs(full["smoothed_shocks"][i, 1:] - e[1:]).max() / ec)
         print(name, i, "errors / scale (states, covs, shocks):", errs)
@@ -277,3 +281,105 @@ def test_engine_equals_host_twin():
         assert_array_equal(out[key].cpu().numpy(), ref[key], err_msg=key)
     assert_array_equal(nocov["smoothed_states"].cpu().numpy(), ref["smoothed_states"])
     assert_array_equal(nocov["smoothed_shocks"].cpu().numpy(), ref["smoothed_shocks"])
+
+
+# ---- the edges (tests/smoother_cases.py; the same inputs pass tests/test_smoother_reference.py::test_range_form_matches_pinv_form
+#      at 1e-10 x scale in numpy, so a miss here is the device's) ----------------------------------------------------------------
+@pytest.mark.parametrize("name", list(cases.ZERO_COLUMN))
+def test_parity_zero_columns_at_class_boundaries(name):
+    """m = 16, 32, 33, 48, 49 with r = 10, 19, 19, 29, 29: the last model of each LDS class and the first of the next (m = 48:
+    seven images in LDS; m = 49: U, U'T, U'R read from global memory)."""
+    _check_parity(name)
+
+
+@pytest.mark.parametrize("name", list(cases.DENSE))
+def test_parity_full_rank(name):
+    """r = m: a dense T with [T | R] of full rank (the plain Rauch-Tung-Striebel case; rt == mt, r4 == m4, an m x m elimination
+    with m right-hand sides; at m = 16, 32, 48, 64 the 16-wide tiles are full, no zero padding) -- m = 1 and 2, every class
+    boundary, p = 16, k = m = 20 and k = m = 64 (lanes 64 .. 64 + k, m + k = 128 column norms in the basis kernel)."""
+    _check_parity(name)
+
+
+@pytest.mark.parametrize("name", list(cases.SHOCK_FORMS))
+def test_parity_shock_covariance_forms(name):
+    """A full Q, shared and per draw (eps = Q (R'w), the diagonal pick Q[j, j] of the basis kernel), and J = {j : Q_jj > 0} a
+    proper subset, in a diagonal and in a full Q (the R column of the shock without variance leaves the basis: r = 9 instead of 10
+    at m = 17), each against the reference; the shock without variance is smoothed to exactly 0."""
+    c = _case(name)
+    out = _check_parity(name)
+    if c["zero_shock"] is not None:
+        assert (out["smoothed_shocks"][:, 1:, c["zero_shock"]] == 0.0).all()
+
+
+@pytest.mark.parametrize("name", ["obs_batched", "p1", "tlen2", "tlen3"])
+def test_parity_observation_forms_and_short_samples(name):
+    """Z, d, Hdiag and a full Q per draw against the reference, draw by draw; p = 1; T_len = 2 (one backward step, the prefetch of
+    step t - 1 never runs) and 3."""
+    _check_parity(name)
+
+
+def _own_call(c, i, **kw):
+    """Draw i of the case on its own."""
+    own = lambda x, shared_ndim: x if x is None or x.ndim == shared_ndim else x[i:i + 1]  # noqa: E731
+    q = c["q"][i:i + 1] if c["q_mode"].endswith("batched") else c["q"]
+    return batched.kalman_smoother_batched(c["T"][i:i + 1], c["R"][i:i + 1], q, own(c["Z"], 2), c["y"], d=own(c["d"], 1),
+                                           Hdiag=own(c["H"], 1), q_mode=c["q_mode"], **kw)
+
+
+KEYS = ("ll", "smoothed_states", "smoothed_covs", "smoothed_shocks")
+
+
+def test_singular_m_sets_the_status_and_returns():
+    """DSGE_ST_SMOOTHER_SINGULAR (256), deterministically: without the P jitter the second pivot of M is exactly 0 in draw 1 at the
+    first backward step (tests/smoother_cases.py).  The draw keeps its log-likelihood and its last step (= the filter's, bit for
+    bit), every earlier step and every shock row is NaN; draws 0 and 2 are bit-identical to their own one-draw calls and within
+    the bar of the reference.  Under the default conventions the same batch has status 0 and meets the bar in every draw."""
+    name = "singular_m_nojit"
+    c = _case(name)
+    kw = dict(full_covariances=True, options=_lib.filter_conventions(**c["conv"]))
+    out = _run(name, **kw)
+    assert out["status"].tolist() == [0, _lib.ST_SMOOTHER_SINGULAR, 0]
+    assert _lib.ST_SMOOTHER_SINGULAR == 256
+    filt = batched.kalman_filter_outputs_batched(c["T"], c["R"], c["q"], c["Z"], c["y"], Hdiag=c["H"], q_mode=c["q_mode"], **kw)
+    assert (filt["status"] == 0).all()
+    assert np.isfinite(out["ll"][1]).all()
+    assert_array_equal(out["ll"][1], filt["ll"][1])
+    assert_array_equal(out["smoothed_states"][1, -1], filt["filtered_states"][1, -1])
+    assert_array_equal(out["smoothed_covs"][1, -1], filt["filtered_covs"][1, -1])
+    assert np.isnan(out["smoothed_states"][1, :-1]).all() and np.isnan(out["smoothed_covs"][1, :-1]).all()
+    assert np.isnan(out["smoothed_shocks"][1]).all()
+    diag = _run(name, options=kw["options"])  # (the diagonal call takes the other extent of the NaN prefix)
+    assert diag["status"].tolist() == [0, _lib.ST_SMOOTHER_SINGULAR, 0]
+    assert_array_equal(diag["smoothed_covs"][1, -1], np.diagonal(filt["filtered_covs"][1, -1]))
+    assert np.isnan(diag["smoothed_covs"][1, :-1]).all() and np.isnan(diag["smoothed_states"][1, :-1]).all()
+    for i, (ll, stt, a, V, e) in cases.reference(name).items():
+        own = _own_call(c, i, **kw)
+        assert own["status"][0] == 0
+        for key in KEYS:
+            assert_array_equal(out[key][i], own[key][0], err_msg=f"{key}, draw {i}")
+        assert_array_equal(diag["smoothed_states"][i], out["smoothed_states"][i])
+        sc, pc, ec = cases.scales(c, i, stt)
+        assert_allclose(out["ll"][i], ll, rtol=1e-8, atol=1e-9)
+        assert_allclose(out["smoothed_states"][i], a, rtol=0, atol=BAR * sc)
+        assert_allclose(out["smoothed_covs"][i], V, rtol=0, atol=BAR * pc)
+        assert_allclose(out["smoothed_shocks"][i, 1:], e[1:], rtol=0, atol=BAR * ec)
+    _check_parity("singular_m")  # default conventions: M = diag(1.3, 2.5e-9) in draw 1
+
+
+def test_forward_pass_failing_on_one_draw():
+    """DSGE_ST_FILTER_NONFINITE (8) set by the outputs kernel INSIDE a smoother call and read by the two smoother kernels on the
+    same stream: without the F jitter, F[1, 1] is exactly 0 in draw 1 (a zero row of its Z, no measurement error).  Every smoothed
+    output of that draw is NaN; draws 0 and 2 have status 0 and are bit-identical to their own one-draw calls."""
+    c = _case("forward_fail")
+    kw = dict(full_covariances=True, options=_lib.filter_conventions(**c["conv"]))
+    out = _run("forward_fail", **kw)
+    assert _lib.ST_FILTER_NONFINITE == 8
+    assert out["status"][1] & _lib.ST_FILTER_NONFINITE
+    assert out["status"][0] == 0 and out["status"][2] == 0
+    for key in KEYS[1:]:
+        assert np.isnan(out[key][1]).all(), key
+    for i in (0, 2):
+        own = _own_call(c, i, **kw)
+        assert own["status"][0] == 0 and np.isfinite(own["smoothed_covs"]).all()
+        for key in KEYS:
+            assert_array_equal(out[key][i], own[key][0], err_msg=f"{key}, draw {i}")
