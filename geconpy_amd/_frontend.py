@@ -38,6 +38,23 @@ class HostBackend:
     def status_io(status, nb):
         return np.zeros(nb, dtype=np.int32) if status is None else np.ascontiguousarray(status, dtype=np.int32).copy()
 
+    # what the generated draws of ``simulation_smoother`` need: the array module, standard normals from ``rng`` (a seed or a
+    # ``np.random.Generator``), and the symmetric-eigen factor S S' = A of a stack of positive semi-definite matrices
+    xp = np
+
+    @staticmethod
+    def generator(rng):
+        return np.random.default_rng(rng)
+
+    @staticmethod
+    def randn(gen, shape):
+        return gen.standard_normal(shape)
+
+    @staticmethod
+    def sym_factor(A):
+        w, V = np.linalg.eigh(np.where(np.isfinite(A), A, 0.0))  # (a failed draw's matrix: its outputs are NaN by its status)
+        return np.ascontiguousarray(V * np.sqrt(np.clip(w, 0.0, None))[..., None, :])
+
 
 HOST = HostBackend()
 
@@ -257,6 +274,76 @@ def kalman_smoother(b, name, T, R, Q, Z, y, *, d, Hdiag, q_mode, status, jitter,
              jitter=jitter, missing_fill=missing_fill, rank_tol=0.0 if rank_tol is None else rank_tol, scratch_limit_bytes=limit,
              ll_out=res["ll"], a_smooth_out=res["smoothed_states"], p_smooth_out=res["smoothed_covs"],
              eps_smooth_out=res["smoothed_shocks"], full_cov=bool(full), status_io=st)
+    return res
+
+
+def simulation_smoother_scratch_bytes_per_draw(m, T_len, n_paths):
+    """``2 T_len m^2 + 2 T_len m`` doubles of the stored forward pass and ``3 n_paths T_len m`` of the paths (x+, a*_pred, a*_filt)."""
+    return 8 * (2 * T_len * m * m + 2 * T_len * m + 3 * n_paths * T_len * m)
+
+
+def stationary_factor(b, name, T, R, Q, *, q_mode):
+    """F (batch, m, m) with F F' = P0 = dlyap(T, R Q R') (``dsge_lyapunov_batched``), F = V sqrt(max(lambda, 0)) from a float64
+    symmetric eigendecomposition."""
+    T, R, nb, m, k = _TR(b, T, R, name, smoother=True)
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    P0, RQR, st = b.empty((nb, m, m)), b.empty((nb, m, m)), b.empty((nb,), "int32")
+    call(b, "dsge_lyapunov_batched", T=T, R=R, Q=Q, q_mode=code, batch=nb, m=m, k=k, P0_out=P0, RQR_out=RQR, status=st)
+    return b.sym_factor(0.5 * (P0 + b.xp.swapaxes(P0, -1, -2)))
+
+
+def _path_array(b, x, nb, tail, name):
+    """A draw array: None, ``tail`` (shared by all draws) or ``(batch,) + tail`` -> (array, batched flag)."""
+    x = b.inp(x)
+    return (None, 0) if x is None else (x, shared_or_batched(x, nb, tail, name))
+
+
+def simulation_smoother(b, name, T, R, Q, Z, y, *, n_paths, d, Hdiag, q_mode, x0, eps, eta, rng, return_draws, status, jitter,
+                        missing_fill, rank_tol, scratch_limit_bytes, options):
+    """``rng``: what ``b.generator`` takes (host: a seed or ``np.random.Generator``; device: a ``torch.Generator`` or None)."""
+    T, R, nb, m, k = _TR(b, T, R, name, smoother=True)
+    y = _nd(b.inp(y), 2)
+    T_len, p = y.shape
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    obs = obs_args(b, Z, d, Hdiag, nb, p, m)
+    n_paths = int(n_paths)
+    if n_paths < 1:
+        raise ValueError(f"n_paths must be >= 1; got {n_paths}")
+    if eta is not None and Hdiag is None:
+        raise ValueError("eta (a measurement-noise draw) needs Hdiag")
+    x0, xb = _path_array(b, x0, nb, (n_paths, m), "x0")
+    eps, eb = _path_array(b, eps, nb, (n_paths, T_len, k), "eps")
+    eta, hb = _path_array(b, eta, nb, (n_paths, T_len, p), "eta")
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    st = check_status(b.status_io(status, nb), nb)
+    # the draws nobody passed, from standard normals: eps = z sqrt(q) or z S' (S S' = Q), eta = z sqrt(H), x0 = z F' (F F' = P0)
+    xp = b.xp
+    gen = b.generator(rng) if (x0 is None or eps is None or (eta is None and Hdiag is not None)) else None
+    if x0 is None:
+        F = stationary_factor(b, name, T, R, Q, q_mode=code)
+        x0, xb = xp.matmul(b.randn(gen, (nb, n_paths, m)), xp.swapaxes(F, -1, -2)), 1
+    if eps is None:
+        z = b.randn(gen, (nb, n_paths, T_len, k))
+        if code in (_lib.Q_DIAG_SHARED, _lib.Q_DIAG_BATCHED):
+            eps = z * xp.sqrt(Q).reshape(-1, 1, 1, k)
+        else:
+            eps = xp.matmul(z, xp.swapaxes(b.sym_factor(Q), -1, -2).reshape(-1, 1, k, k))
+        eb = 1
+    if eta is None and Hdiag is not None:
+        eta, hb = b.randn(gen, (nb, n_paths, T_len, p)) * xp.sqrt(obs["Hdiag"]).reshape(-1, 1, 1, p), 1
+    x0, eps, eta = (None if v is None else b.inp(v if b.host else v.contiguous()) for v in (x0, eps, eta))
+    res = dict(states=b.empty((nb, n_paths, T_len, m)), shocks=b.empty((nb, n_paths, T_len, k)), ll=b.empty((nb, T_len)), status=st)
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        call(b, "dsge_simulation_smoother_batched", T=T, R=R, Q=Q, q_mode=code, **obs, y=y, batch=nb, m=m, k=k, p=p, T_len=T_len,
+             jitter=jitter, missing_fill=missing_fill, rank_tol=0.0 if rank_tol is None else rank_tol, scratch_limit_bytes=limit,
+             x0=x0, x0_batched=xb, eps=eps, eps_batched=eb, eta=eta, eta_batched=hb, n_paths=n_paths, ll_out=res["ll"],
+             x_out=res["states"], eps_out=res["shocks"], status_io=st)
+    if return_draws:
+        res.update(x0=x0, eps=eps, eta=eta)
     return res
 
 

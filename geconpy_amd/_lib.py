@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -72,7 +72,7 @@ class GensysForward(C.Structure):
 # entry -> its argument names in the order of include/dsge_hip.h (tests/test_abi_and_host.py compares both, names and kinds).  A
 # name is an int, a double or a size_t when it is listed below, a pointer (double* / int32_t* / struct* / stream, passed as a raw
 # host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
-_INTS = ("N T_len batch c correlation d_batched device enable eps_batched full_cov h_batched k lag_step m max_iter mode n n_eta "
+_INTS = ("N T_len batch c correlation d_batched device enable eps_batched eta_batched full_cov h_batched k lag_step m max_iter mode n n_eta "
          "n_filter_hint n_lags n_lead n_lead_hint n_links n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p q_batched "
          "q_mode reps s_batched solver w_batched x0_batched z_batched z_selector_hint")
 _KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
@@ -123,6 +123,8 @@ _DEVICE_ENTRIES = {
     "dsge_kalman_filter_outputs_batched": f"{_FILTER} ll_out a_pred_out a_filt_out p_pred_out p_filt_out full_cov status_io stream",
     "dsge_kalman_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes ll_out a_smooth_out p_smooth_out eps_smooth_out "
                                      "full_cov status_io stream"),
+    "dsge_simulation_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes x0 x0_batched eps eps_batched eta eta_batched "
+                                         "n_paths ll_out x_out eps_out status_io stream"),
     "dsge_simulate_batched": "T R eps eps_batched x0 x0_batched status batch m k n_paths n_steps n_shock_steps x_out stream",
     "dsge_irf_batched": "T R S s_batched weights w_batched status batch m k c n_steps irf_out fevd_out stream",
     "dsge_forecast_batched": f"T R Q q_mode {_OBS} a0 P0 status batch m k p n_steps a_out p_out full_cov y_out f_out stream",

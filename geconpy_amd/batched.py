@@ -464,6 +464,36 @@ def kalman_smoother_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, stat
                              scratch_limit_bytes=scratch_limit_bytes, options=options)
 
 
+simulation_smoother_scratch_bytes_per_draw = F.simulation_smoother_scratch_bytes_per_draw
+
+
+def stationary_factor(T, R, Q, q_mode=None):
+    """F (batch, m, m) with ``F F' = P0 = solve_discrete_lyapunov(T, R Q R')`` per draw: ``x0 = z F'`` with standard normal z
+    is a draw of the pre-sample state.  P0 from ``dsge_lyapunov_batched``, ``F = V sqrt(max(lambda, 0))`` from
+    ``numpy.linalg.eigh`` (P0 is singular for every DSGE model, so no Cholesky factor)."""
+    return F.stationary_factor(HOST, "stationary_factor", T, R, Q, q_mode=q_mode)
+
+
+def simulation_smoother_batched(T, R, Q, Z, y, n_paths=1, d=None, Hdiag=None, q_mode=None, x0=None, eps=None, eta=None, rng=None,
+                                return_draws=False, status=None, jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL,
+                                rank_tol=None, scratch_limit_bytes=None, options=None):
+    """``n_paths`` JOINT posterior draws of the whole state path and of the structural shocks per parameter draw, conditional
+    on the data -- what ``sample_conditional_posterior`` of the pymc_extras model behind ``DSGEStateSpace`` is used for (its
+    draws are per-step marginals, these are joint over time) and what Dynare's simulation smoother draws: Durbin and Koopman's
+    mean correction on ``kalman_smoother_batched`` (include/dsge_hip.h, ``dsge_simulation_smoother_batched``).  The draws the
+    correction starts from -- ``x0`` (n_paths, m) ~ N(0, P0), ``eps`` (n_paths, T_len, k) ~ N(0, Q), ``eta``
+    (n_paths, T_len, p) ~ N(0, diag Hdiag), each shared by all draws or with a leading batch axis -- are the caller's, or, where
+    None, made here from standard normals of ``rng`` (a seed or ``np.random.Generator``): ``eps = z sqrt(q)`` / ``z S'`` with the
+    symmetric-eigen factor ``S S' = Q``, ``eta = z sqrt(H)`` (none without ``Hdiag``), ``x0 = z F'`` with ``stationary_factor``.
+    All-zero draws give the smoothed means (pass zero arrays: a None is drawn).  Returns dict(states (batch, n_paths, T_len, m), shocks (batch, n_paths, T_len, k)
+    with ``[:, :, 0] = NaN`` by the smoother's definition, ll (batch, T_len), status[, x0, eps, eta with ``return_draws``]).
+    ``scratch_limit_bytes`` counts ``simulation_smoother_scratch_bytes_per_draw(m, T_len, n_paths)`` per draw."""
+    return F.simulation_smoother(HOST, "simulation_smoother_batched", T, R, Q, Z, y, n_paths=n_paths, d=d, Hdiag=Hdiag, q_mode=q_mode,
+                                 x0=x0, eps=eps, eta=eta, rng=rng, return_draws=return_draws, status=status, jitter=jitter,
+                                 missing_fill=missing_fill_value, rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes,
+                                 options=options)
+
+
 def simulate_batched(T, R, eps, n_steps=None, x0=None, status=None):
     """Simulated paths ``x[b, s, t] = T_b x[b, s, t-1] + R_b eps[b, s, t]`` for a batch of draws -- the loop of
     ``_simulate_linear_system`` (gEconpy/model/simulate.py:171-182) that ``simulate`` (:320-430) runs once per trajectory, for

@@ -578,6 +578,45 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
   return hc.finish();
 }
 
+int dsge_simulation_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
+                                          int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                          double rank_tol, size_t scratch_limit_bytes, const double* x0, int x0_batched,
+                                          const double* eps, int eps_batched, const double* eta, int eta_batched, int n_paths,
+                                          double* ll_out, double* x_out, double* eps_out, int32_t* status_io) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_simulation_smoother(batch, m, k, obs, q, T && R && status_io, n_paths, eps, eta, x_out || eps_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || T_len == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, tl = (size_t)T_len;
+  ObsModel dobs;
+  ShockCov dq;
+  const double *dT, *dR, *dx0, *deps, *deta;
+  double *dll, *dx, *de;
+  int32_t* dS;
+  hc.in(&dT, T, b * m * m);
+  hc.in(&dR, R, b * m * k);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dobs, obs, batch, m);
+  hc.in(&dx0, x0, (x0_batched ? b : 1) * np * m);
+  hc.in(&deps, eps, (eps_batched ? b : 1) * np * tl * k);
+  hc.in(&deta, eta, (eta_batched ? b : 1) * np * tl * p);
+  hc.io(&dS, status_io, b);
+  hc.out(&dll, ll_out, b * tl);
+  hc.out(&dx, x_out, b * np * tl * m);
+  hc.out(&de, eps_out, b * np * tl * k);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_simulation_smoother_batched(dT, dR, dq.Q, dq.mode, dobs.Z, dobs.z_batched, dobs.d, dobs.d_batched, dobs.Hdiag,
+                                             dobs.h_batched, dobs.y, batch, m, k, p, T_len, jitter, missing_fill, rank_tol,
+                                             scratch_limit_bytes, dx0, x0_batched, deps, eps_batched, deta, eta_batched, n_paths, dll,
+                                             dx, de, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_simulate_batched_host(const double* T, const double* R, const double* eps, int eps_batched, const double* x0,
                                int x0_batched, const int32_t* status, int batch, int m, int k, int n_paths, int n_steps,
                                int n_shock_steps, double* x_out) {

@@ -597,6 +597,72 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   return DSGE_SUCCESS;
 }
 
+// Joint posterior draws of the state path and the shocks (dsge_simsmooth.hpp): the smoother's forward pass and basis per chunk of
+// draws, x+ of every path through the propagation kernel, then the two path kernels -- all on the caller's stream.
+int dsge_simulation_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                     const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
+                                     int m, int k, int p, int T_len, double jitter, double missing_fill, double rank_tol,
+                                     size_t scratch_limit_bytes, const double* x0, int x0_batched, const double* eps,
+                                     int eps_batched, const double* eta, int eta_batched, int n_paths, double* ll_out,
+                                     double* x_out, double* eps_out, int32_t* status_io, void* stream) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_simulation_smoother(batch, m, k, obs, q, T && R && status_io, n_paths, eps, eta, x_out || eps_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || T_len == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  if (!(rank_tol > 0.0)) rank_tol = 1e-10;
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  // per draw: the per-step filter outputs of the smoother entry (an upper bound: the means of y are not stored here), and x+,
+  // a*_pred, a*_filt of every path
+  const size_t tm = (size_t)T_len * m, ptm = (size_t)n_paths * tm, per_draw = (2 * tm * m + 2 * tm + 3 * ptm) * sizeof(double);
+  size_t fit = scratch_limit_bytes / per_draw;
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const size_t mm = (size_t)chunk * m * m, img = (size_t)chunk * smoother_image_doubles(m);
+  double *RQR = nullptr, *P0 = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr, *pp = nullptr, *pf = nullptr;
+  double *xp = nullptr, *asp = nullptr, *asf = nullptr, *ll = nullptr;
+  int32_t *rank = nullptr, *snap = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, mm);
+  lay.add(&P0, mm);
+  lay.add(&U, img);
+  lay.add(&UT, img);
+  lay.add(&UR, img);
+  lay.add(&pp, chunk * tm * m);
+  lay.add(&pf, chunk * tm * m);
+  lay.add(&xp, chunk * ptm);
+  lay.add(&asp, chunk * ptm);
+  lay.add(&asf, chunk * ptm);
+  lay.add(&rank, (size_t)chunk);
+  lay.add(&snap, (size_t)chunk);
+  if (!ll_out) lay.add(&ll, (size_t)chunk * T_len);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  const long long eps_path = (long long)T_len * k, eps_draw = eps_batched ? n_paths * eps_path : 0;
+  const long long eta_draw = eta_batched ? (long long)n_paths * T_len * p : 0, x0_draw = x0_batched ? (long long)n_paths * m : 0;
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const size_t o = (size_t)c0;
+    const double *Tc = T + o * m * m, *Rc = R + o * m * k;
+    const ShockCov qc = q.at(o, k);
+    const ObsModel oc = obs.at(o, m);
+    int32_t* sc = status_io + o;
+    const double* epc = eps + o * eps_draw;
+    if ((rc = assemble_rqr_p0(Tc, Rc, qc, nb, m, k, RQR, P0, sc, st))) return rc;
+    if ((rc = launch_kalman_outputs(Tc, RQR, P0, oc, nb, m, ll_out ? ll_out + o * T_len : ll, nullptr, nullptr, pp, pf, 1, sc, st)))
+      return rc;  // (the means of y itself are not stored: the path kernels filter y*)
+    if ((rc = launch_smoother_basis(Tc, Rc, qc, nb, m, k, rank_tol, U, UT, UR, rank, sc, st))) return rc;
+    if ((rc = launch_propagate(Tc, Rc, epc, eps_draw, eps_path, k, 1, 0, x0 ? x0 + o * x0_draw : nullptr, x0_draw, nullptr, 0, nullptr, nb, m,
+                               k, n_paths, T_len, T_len, xp, nullptr, st)))
+      return rc;
+    if ((rc = launch_simulation_smoother(Tc, qc, oc, nb, m, k, n_paths, U, UT, UR, rank, pp, pf, xp, epc, eps_draw,
+                                         eta ? eta + o * eta_draw : nullptr, eta_draw, asp, asf, x_out ? x_out + o * ptm : nullptr,
+                                         eps_out ? eps_out + o * n_paths * eps_path : nullptr, sc, snap, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
 // ---- post-solve dynamics (dsge_dynamics.hpp): simulate, impulse responses + FEVD, forecast -----------------------------------
 int dsge_simulate_batched(const double* T, const double* R, const double* eps, int eps_batched, const double* x0, int x0_batched,
                           const int32_t* status, int batch, int m, int k, int n_paths, int n_steps, int n_shock_steps,

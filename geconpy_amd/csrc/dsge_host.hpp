@@ -272,6 +272,16 @@ int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, 
                            double rank_tol, double* U, double* UT, double* UR, int32_t* rank, const double* a_pred, const double* a_filt,
                            const double* p_pred, const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov,
                            int32_t* status, hipStream_t st);
+int launch_smoother_basis(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, double rank_tol, double* U,
+                          double* UT, double* UR, int32_t* rank, int32_t* status, hipStream_t st);  // the basis alone
+// launch_simsmooth.hip (dsge_simsmooth.hpp): the simulation smoother's forward (filter means of n_paths transformed data sets per
+// draw over the stored P_pred) and backward pass (smoother means, x+ / eps+ added) for groups of 16 paths per draw.  xp, a_pred,
+// a_filt: [batch][n_paths][T_len][m] (a_pred, a_filt: scratch); eps / eta: draw strides, 0 = shared; snap: [batch] scratch
+int launch_simulation_smoother(const double* T, const ShockCov& q, const ObsModel& o, int batch, int m, int k, int n_paths,
+                               const double* U, const double* UT, const double* UR, const int32_t* rank, const double* p_pred,
+                               const double* p_filt, const double* xp, const double* eps, long long eps_draw, const double* eta,
+                               long long eta_draw, double* a_pred, double* a_filt, double* x_out, double* e_out, int32_t* status,
+                               int32_t* snap, hipStream_t st);
 // launch_dynamics.hip (dsge_dynamics.hpp): x_t = T x_{t-1} + R e_t for groups of 16 paths per draw (shock element (draw, path,
 // step, component) at the four strides; identity: unit impulses, nothing read), optionally the FEVD of <= 16 paths; the FEVD of
 // more as a second pass over stored responses; the forecast moment recursion
@@ -429,6 +439,17 @@ inline int check_smoother(int batch, int m, int k, const ObsModel& o, const Shoc
   int rc = check_kalman(batch, m, k, o, q, others);
   if (rc) return rc;
   return any_output ? DSGE_SUCCESS : fail(DSGE_ERR_INVALID, "no smoothed output requested");
+}
+inline int check_simulation_smoother(int batch, int m, int k, const ObsModel& o, const ShockCov& q, bool others, int n_paths,
+                                     const double* eps, const double* eta, bool any_output) {
+  if (m > DSGE_MAX_N || o.p > DSGE_MAX_P)
+    return fail(DSGE_ERR_TOO_LARGE, "simulation smoother: m exceeds DSGE_MAX_N or p exceeds DSGE_MAX_P");
+  int rc = check_kalman(batch, m, k, o, q, others);
+  if (rc) return rc;
+  if (n_paths < 0) return fail(DSGE_ERR_INVALID, "n_paths < 0");
+  if (eta && !o.Hdiag) return fail(DSGE_ERR_INVALID, "eta given without Hdiag");
+  if (!eps && n_paths > 0 && o.T_len > 0) return fail(DSGE_ERR_INVALID, "null pointer");
+  return any_output ? DSGE_SUCCESS : fail(DSGE_ERR_INVALID, "no output requested");
 }
 inline int check_pipeline(int batch, int n, int k, const ObsModel& o, const ShockCov& q, int solver, bool others) {
   solver &= ~DSGE_SOLVER_FLAG_ZERO_T_ON_FAILURE;

@@ -49,6 +49,22 @@ class DeviceBackend:
     def status_io(self, status, nb):
         return self.torch.zeros(nb, dtype=self.torch.int32, device=self.device) if status is None else self.inp(status, "int32")
 
+    # the generated draws of ``_frontend.simulation_smoother``, with torch on the current stream
+    @property
+    def xp(self):
+        return self.torch
+
+    @staticmethod
+    def generator(gen):
+        return gen  # a torch.Generator of this device, or None for torch's default one
+
+    def randn(self, gen, shape):
+        return self.torch.randn(shape, generator=gen, dtype=self.torch.float64, device=self.device)
+
+    def sym_factor(self, A):
+        w, V = self.torch.linalg.eigh(self.torch.nan_to_num(A, nan=0.0, posinf=0.0, neginf=0.0))
+        return (V * self.torch.sqrt(self.torch.clamp(w, min=0.0))[..., None, :]).contiguous()
+
 
 class LogpEngine:
     """Fused ``A,B,C,D -> logp`` on one GPU with inputs and outputs resident in HBM.
@@ -220,6 +236,23 @@ class LogpEngine:
         return F.kalman_smoother(self.backend, "kalman_smoother", T, R, Q, Z, y, d=d, Hdiag=Hdiag, q_mode=q_mode, status=status,
                                  jitter=jitter, missing_fill=missing_fill_value, cov=covariances, full=full_covariances,
                                  rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes, options=options)
+
+    def stationary_factor(self, T, R, Q, q_mode=None):
+        """F [batch][m][m] with F F' = P0 per draw (``batched.stationary_factor``) from device tensors: ``dsge_lyapunov_batched``
+        and a batched ``torch.linalg.eigh``, on torch's current stream."""
+        return F.stationary_factor(self.backend, "stationary_factor", T, R, Q, q_mode=q_mode)
+
+    def simulation_smoother(self, T, R, Q, Z, y, n_paths=1, d=None, Hdiag=None, q_mode=None, x0=None, eps=None, eta=None,
+                            generator=None, return_draws=False, status=None, jitter=JITTER_DEFAULT,
+                            missing_fill_value=MISSING_FILL, rank_tol=None, scratch_limit_bytes=None, options=None):
+        """Joint posterior draws of the state paths and shocks of the whole batch (``dsge_simulation_smoother_batched``; see
+        ``batched.simulation_smoother_batched``) from device tensors, on torch's current stream.  Draw arrays that are None are
+        made on the device from ``generator`` (a ``torch.Generator`` of this device; None: torch's default).  Returns a dict of
+        device tensors: states, shocks, ll, status[, x0, eps, eta]; asynchronous."""
+        return F.simulation_smoother(self.backend, "simulation_smoother", T, R, Q, Z, y, n_paths=n_paths, d=d, Hdiag=Hdiag,
+                                     q_mode=q_mode, x0=x0, eps=eps, eta=eta, rng=generator, return_draws=return_draws, status=status,
+                                     jitter=jitter, missing_fill=missing_fill_value, rank_tol=rank_tol,
+                                     scratch_limit_bytes=scratch_limit_bytes, options=options)
 
     # -- post-solve dynamics (csrc/dsge_dynamics.hpp) -----------------------------------------
     def simulate(self, T, R, eps, n_steps=None, x0=None, status=None, out=None):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 11
+#define DSGE_ABI_VERSION 12
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -47,6 +47,7 @@ extern "C" {
  * by <= ~tol now gets the ordered QZ's verdict instead of eu = [1, 1, 0]. */
 /* ABI 10: dsge_kalman_smoother_batched (+ _host) and the status bit DSGE_ST_SMOOTHER_SINGULAR are new; nothing else changed. */
 /* ABI 11: dsge_simulate_batched, dsge_irf_batched, dsge_forecast_batched (+ _host) are new; nothing else changed. */
+/* ABI 12: dsge_simulation_smoother_batched (+ _host) is new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -696,6 +697,45 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
                                       int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
                                       double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
                                       double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io);
+
+/*
+ * SIMULATION SMOOTHER (ABI 12; csrc/dsge_simsmooth.hpp, docs/design/simulation_smoother.md): n_paths JOINT posterior draws of the
+ * whole state path and of the structural shocks per parameter draw, conditional on the data -- what sample_conditional_posterior
+ * of the pymc_extras model behind DSGEStateSpace is used for, and what Dynare's simulation smoother draws once per parameter draw.
+ * Durbin and Koopman's mean correction on the smoother above: smoothing is affine in the data and its gains depend on the
+ * covariances only, so with inputs the CALLER draws from the model's own distributions (no device RNG, as dsge_simulate_batched)
+ *     x0+[b,s] ~ N(0, P0), P0 = dlyap(T, R Q R');   eps+[b,s,t] ~ N(0, Q);   eta+[b,s,t] ~ N(0, diag Hdiag)
+ *     x+[-1] = x0+;  x+[t] = T x+[t-1] + R eps+[t];    y*[t] = y[t] - Z x+[t] - eta+[t]   (a missing entry of y stays missing)
+ *     (as*, es*) = the smoothed states and shocks of y* under the call's own d and filter conventions
+ *     x~[t] = x+[t] + as*[t];    eps~[t] = eps+[t] + es*[t] for t >= 1,   eps~[0] = NaN by the smoother's definition
+ * (x~, eps~[1:]) is an exact joint draw from the posterior of the stored filter's model; zero inputs give the outputs of
+ * dsge_kalman_smoother_batched.  The filter models the observation noise as Hdiag + jitter_F I, eta+ has variance Hdiag: the
+ * gap of 1e-8 is documented, not corrected.  Arguments T .. scratch_limit_bytes as dsge_kalman_smoother_batched, plus
+ *   x0  : [batch|1][n_paths][m], NULL = zero                       (x0_batched: 0 = one array shared by all draws)
+ *   eps : [batch|1][n_paths][T_len][k]                             (eps_batched)
+ *   eta : [batch|1][n_paths][T_len][p], NULL = no measurement-noise draw; needs Hdiag    (eta_batched)
+ *   n_paths : >= 0, any value; the paths of a draw are processed in groups of at most 16, and a path's numbers do not depend on
+ *             which other paths share its group
+ *   scratch_limit_bytes : counts 2 T_len m^2 + 2 T_len m + 3 n_paths T_len m doubles per draw (an upper bound; x+ and the filter means of every path)
+ *   ll_out  : [batch][T_len] or NULL: the forward pass on y itself, as in the smoother
+ *   x_out   : [batch][n_paths][T_len][m]      eps_out : [batch][n_paths][T_len][k]      each may be NULL, at least one is given
+ *   status_io : [batch] in/out, as the smoother: a non-zero incoming status or DSGE_ST_FILTER_NONFINITE gives NaN in every path of
+ *               the draw; DSGE_ST_SMOOTHER_SINGULAR gives NaN for that step and all earlier ones in every path, the later steps stay
+ * m <= DSGE_MAX_N and p <= DSGE_MAX_P, else DSGE_ERR_TOO_LARGE.  batch == 0, n_paths == 0 or T_len == 0: success, nothing touched.
+ * T_len == 1: x~ = x+ + a*_filt, shocks NaN.  Chunked over draws on the caller's stream without host synchronisation.
+ */
+int dsge_simulation_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                     const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y, int batch,
+                                     int m, int k, int p, int T_len, double jitter, double missing_fill, double rank_tol,
+                                     size_t scratch_limit_bytes, const double* x0, int x0_batched, const double* eps,
+                                     int eps_batched, const double* eta, int eta_batched, int n_paths, double* ll_out,
+                                     double* x_out, double* eps_out, int32_t* status_io, void* stream);
+int dsge_simulation_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
+                                          int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                          double rank_tol, size_t scratch_limit_bytes, const double* x0, int x0_batched,
+                                          const double* eps, int eps_batched, const double* eta, int eta_batched, int n_paths,
+                                          double* ll_out, double* x_out, double* eps_out, int32_t* status_io);
 
 /*
  * POST-SOLVE DYNAMICS per draw (ABI 11; csrc/dsge_dynamics.hpp, docs/design/dynamics.md): what the reference runs on every retained
