@@ -207,20 +207,27 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   }
   // [T_dy[:,S] | R_dy] = -A1_hat^-1 [A_dy[:,S] | D_red]  (cycle_reduction.py:181, shared.py:74-75; see cr_compact_body)
   wave_sync();
-  blk_store_lds<BSD>(Ah, W, LDW, lr, lc);
+  int lane_f = lane;
+  asm volatile("" : "+v"(lane_f));
   {
+    // block coordinates re-derived from an opaque copy of the lane index, as in crc_iterate: what phase 1 computed from it
+    // would otherwise be kept across the whole iteration -- in scratch, at 256 registers
+    int lane_s = lane;
+    asm volatile("" : "+v"(lane_s));
+    const int lr_s = lane_s >> 3, lc_s = lane_s & 7;
+    blk_store_lds<BSD>(Ah, W, LDW, lr_s, lc_s);
     double t[BSD][BSD];
 #pragma unroll
     for (int i = 0; i < BSD; ++i)
 #pragma unroll
       for (int j = 0; j < BSD; ++j) {
-        const int r = lr * BSD + i, c = lc * BSD + j;
+        const int r = lr_s * BSD + i, c = lc_s * BSD + j;
         t[i][j] = (r < nd && c < s + k) ? rh[(size_t)c * nd + r] : 0.0;
       }
-    blk_store_lds<BSD>(t, G1, LDW, lr, lc);
+    blk_store_lds<BSD>(t, G1, LDW, lr_s, lc_s);
   }
-  gauss_jordan_blocked<BSD>(W, LDW, nd, 2, Lbuf, Ybuf, prow, lane);
-  gj_unpermute<BSD>(W, LDW, nd, 1, 2, prow, lane);
+  gauss_jordan_blocked<BSD>(W, LDW, nd, 2, Lbuf, Ybuf, prow, lane_f);
+  gj_unpermute<BSD>(W, LDW, nd, 1, 2, prow, lane_f);
 
   // ---- phase 3: the static rows, scatter to the caller's variable order -------------------------------------------------
   double y[NPD];  // column `lane` of [T_dy | R_dy]: T_dy[:, v] = -X[:, posS(v)] for a state v, zero otherwise

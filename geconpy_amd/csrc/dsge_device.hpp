@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dsge_filter_conv.hpp"
 
 namespace dsge {
@@ -505,11 +507,31 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
   // gj_replay can apply the SAME elimination to further right-hand sides (with prow, which holds the pivot rows)
   // inv_min / inv_max: smallest and largest |1 / pivot| met (wave-uniform): their ratio is a free lower estimate of the
   // condition number, which crc_iterate uses to decide on a step of iterative refinement
+  //
+  // (round 7) The panel is bound by instruction issue, not by its arithmetic: what follows keeps every floating-point
+  // operation of round 6 with its operands and its order (bit-identical results, tests/test_gpu_cr_bitwise.py) and trims the
+  // integer, select and cross-lane instructions around them -- docs/design/cycle_reduction.md lists each cut with its count.
   constexpr int NP = 8 * BS;
   const int lr = lane >> 3, lc = lane & 7;
   const int wcols = ngroups * NP;
-  unsigned long long used = 0ull;
+  // rows still to be chosen as pivots: bit i = row i exists and has not been a pivot row.  Wave-uniform (a scalar register
+  // pair), handed to the pivot search as the condition of ONE select per pivot (inverse ballot) where every lane used to shift
+  // a 64-bit `used` mask by its own index.
+  const int nrow = (n < NP) ? n : NP;  // (n <= NP for every caller: the tile is chosen from n)
+  unsigned long long avail = (nrow >= 64) ? ~0ull : ((1ull << nrow) - 1ull);
   const int nsteps = (n + BS - 1) / BS;
+  // Lanes >= n take no part in the result of a panel: no pivot is searched there, no other lane reads their registers, and
+  // their Lhat rows are zeros.  So they run the panel on whatever their (clamped) row holds, without a select per loaded
+  // value, and the zero rows n .. NP-1 of Lbuf are written once per elimination instead of once per panel.
+  // Lbuf holds -Lhat, the factor the trailing update multiplies by: loaded as Lhat and negated inside the FMAs, the negation
+  // did not stay an operand modifier -- the register blocks are used by two column groups, the compiler negated them ahead of
+  // both (and back for the skipped group): 65 moves and sign flips per panel.  (-Lhat of a zero row is -0.0.)
+  const int prl = (lane < NP) ? lane : NP - 1;
+  wave_sync();
+  if (lane >= nrow && lane < NP) {
+#pragma unroll
+    for (int b = 0; b < BS; ++b) Lbuf[lane * BS + b] = -0.0;
+  }
   for (int kb = 0; kb < nsteps; ++kb) {
     const int j0 = kb * BS;
     const int bw = (n - j0 < BS) ? (n - j0) : BS;
@@ -518,28 +540,25 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
     // ---- panel: one matrix row per lane, augmented with the identity slots ------------
     double pw[BS], id[BS];
 #pragma unroll
-    for (int c = 0; c < BS; ++c) {
-      pw[c] = (lane < n && c < bw) ? W[lane * ldw + j0 + c] : 0.0;
-      id[c] = 0.0;
-    }
+    for (int c = 0; c < BS; ++c) pw[c] = W[prl * ldw + j0 + c];  // (columns >= bw of a partial panel: inside the tile, never a pivot column)
     int rsel[BS];
     double inv_own = 1.0;  // pivot lanes: 1 / pivot of their row (the row is scaled once, after the panel)
 #pragma unroll
-    for (int c = 0; c < BS; ++c) rsel[c] = 0;
+    for (int c = 0; c < BS; ++c) {
+      rsel[c] = 0;
+      id[c] = 0.0;  // (columns a partial panel does not reach)
+    }
     // one pivot of the panel (column c: a compile-time constant after unrolling)
     auto panel_pivot = [&](int c) {
       // pivot = largest |entry| among the unused rows, compared on the high 32 bits of the double (sign
       // cleared; exponent + 20 mantissa bits; low 6 bits carry 63 - lane so that ties go to the first row):
       // within 2^-14 of the true maximum, which is all partial pivoting needs, at one v_max_u32 per DPP step
-      const bool cand = (lane < n) && !((used >> lane) & 1ull);
-      unsigned key = 0u;
-      if (cand) key = (((unsigned)__double2hiint(pw[c]) & 0x7fffffffu) & ~63u) | (unsigned)(63 - lane);
-      key = wave_max_u32(key);
+      const unsigned own = ((unsigned)__double2hiint(pw[c]) & 0x7fffffc0u) | (unsigned)(63 - lane);
+      const unsigned key = wave_max_u32(__builtin_amdgcn_inverse_ballot_w64(avail) ? own : 0u);
       const int r = 63 - (int)(key & 63u);
       rsel[c] = r;
-      used |= 1ull << r;
+      avail &= ~(1ull << r);
       const bool is_r = (lane == r);
-      if (is_r) id[c] = 1.0;
       // broadcast the pivot lane's row scaled by 1 / pivot and eliminate everywhere else.  The pivot lane itself is
       // left alone (multiplier 0: no divergent branch) and scaled after the panel -- later columns only ever read
       // a row through its own elimination multiplier, which is consistent with the unscaled row.
@@ -548,11 +567,52 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
       inv_max = fmax(inv_max, fabs(inv));
       const double f = is_r ? 0.0 : pw[c];
       inv_own = is_r ? inv : inv_own;
+      // identity slot of this column: 1 on the pivot lane (a select on the high word alone: 0.0 and 1.0 share the low one),
+      // 0 elsewhere, eliminated at once.  The pivot lane's slot IS 1.0, so the broadcast of round 6 (two v_readlane and
+      // 1.0 * inv, which is inv) is not issued.
+      id[c] = fma(-f, inv, __hiloint2double(is_r ? 0x3ff00000 : 0, 0));
 #pragma unroll
       for (int c2 = 0; c2 < BS; ++c2) {
         if (c2 > c) pw[c2] = fma(-f, readlane_dyn_f64(pw[c2], r) * inv, pw[c2]);
-        if (c2 <= c) id[c2] = fma(-f, readlane_dyn_f64(id[c2], r) * inv, id[c2]);
+        if (c2 < c) id[c2] = fma(-f, readlane_dyn_f64(id[c2], r) * inv, id[c2]);
       }
+    };
+    // what a panel leaves behind: Lhat -> Lbuf, the pivot rows of W -> Ybuf, the pivot rows' indices -> prow.  FULL: a
+    // compile-time flag, the per-column tests `< bw` of a partial panel are not issued for a full one.
+    auto panel_store = [&](auto full_tag) {
+      constexpr bool FULL = decltype(full_tag)::value;
+#pragma unroll
+      for (int c = 0; c < BS; ++c) id[c] *= inv_own;  // (pw is dead from here on)
+      // Lhat row of this lane: -id for ordinary rows; pivot lane r_a holds id = Minv[a,:] and needs e_a - Minv[a,:].  Its
+      // negative, nl = id - e_a, is one subtraction of a selected constant: 1.0 on the pivot lane, +0.0 elsewhere (x - (+0.0) is
+      // x, signed zeros included) -- again a select on the high word alone, of the constant the identity slots are made of
+      // (a second one would sit in a register through the whole kernel).  -(1 - x) and x - 1 round alike.
+      if (lane < nrow) {
+        double nl[BS];
+#pragma unroll
+        for (int b = 0; b < BS; ++b) {
+          const bool piv = (FULL || b < bw) && lane == rsel[b];
+          nl[b] = id[b] - __hiloint2double(piv ? 0x3ff00000 : 0, 0);
+        }
+#pragma unroll
+        for (int b = 0; b < BS; ++b) Lbuf[lane * BS + b] = nl[b];
+        if (rec_L) {  // (Lhat itself: gj_replay negates)
+#pragma unroll
+          for (int b = 0; b < BS; ++b) rec_L[((size_t)kb * NP + lane) * BS + b] = -nl[b];
+        }
+      }
+      if (rec_L && lane >= nrow && lane < NP) {
+#pragma unroll
+        for (int b = 0; b < BS; ++b) rec_L[((size_t)kb * NP + lane) * BS + b] = 0.0;
+      }
+      // pivot rows of W (original values) -> Ybuf, one column per lane
+      for (int c = lane; c < wcols; c += 64) {
+#pragma unroll
+        for (int b = 0; b < BS; ++b) Ybuf[b * wcols + c] = (FULL || b < bw) ? W[rsel[b] * ldw + c] : 0.0;
+      }
+#pragma unroll
+      for (int a = 0; a < BS; ++a)
+        if ((FULL || a < bw) && lane == 0) prow[j0 + a] = rsel[a];
     };
     // (round 6) a FULL panel -- every panel but possibly the last -- runs its BS pivots without the per-column test `c < bw`: the
     // (uniform) branches cut the chain of a panel into one basic block per pivot, which the scheduler cannot overlap; same
@@ -560,46 +620,22 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
     if (bw == BS) {
 #pragma unroll
       for (int c = 0; c < BS; ++c) panel_pivot(c);
+      panel_store(std::true_type{});
     } else {
 #pragma unroll
       for (int c = 0; c < BS; ++c)
         if (c < bw) panel_pivot(c);
+      panel_store(std::false_type{});
     }
-#pragma unroll
-    for (int c = 0; c < BS; ++c) id[c] *= inv_own;  // (pw is dead from here on)
-    // Lhat row of this lane: -id for ordinary rows; pivot lane r_a holds id = Minv[a,:] and
-    // needs e_a - Minv[a,:]
-    if (lane < NP) {
-      double lh[BS];
-#pragma unroll
-      for (int b = 0; b < BS; ++b) lh[b] = -id[b];
-#pragma unroll
-      for (int a = 0; a < BS; ++a)
-        if (a < bw && lane == rsel[a]) lh[a] += 1.0;
-#pragma unroll
-      for (int b = 0; b < BS; ++b) Lbuf[lane * BS + b] = (lane < n) ? lh[b] : 0.0;
-      if (rec_L) {
-#pragma unroll
-        for (int b = 0; b < BS; ++b) rec_L[((size_t)kb * NP + lane) * BS + b] = (lane < n) ? lh[b] : 0.0;
-      }
-    }
-    // pivot rows of W (original values) -> Ybuf, one column per lane
-    for (int c = lane; c < wcols; c += 64) {
-#pragma unroll
-      for (int b = 0; b < BS; ++b) Ybuf[b * wcols + c] = (b < bw) ? W[rsel[b] * ldw + c] : 0.0;
-    }
-#pragma unroll
-    for (int a = 0; a < BS; ++a)
-      if (a < bw && lane == 0) prow[j0 + a] = rsel[a];
     wave_sync();
     const long long tk_t = ph ? clock64() : 0;
     if (ph) ph[0] += tk_t - tk_p;
     // ---- trailing update on register blocks: W[i,:] -= Lhat[i,:] Wpiv ---------------------
-    double lh[BS][BS];
+    double nl[BS][BS];  // -Lhat
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll
-      for (int b = 0; b < BS; ++b) lh[i][b] = Lbuf[(lr * BS + i) * BS + b];
+      for (int b = 0; b < BS; ++b) nl[i][b] = Lbuf[(lr * BS + i) * BS + b];
     for (int g = 0; g < ngroups; ++g) {
       // block columns at or left of the panel inside the matrix part are dead (never read again)
       if (g == 0 && lc <= kb) continue;
@@ -618,7 +654,7 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
 #pragma unroll
         for (int i = 0; i < BS; ++i)
 #pragma unroll
-          for (int j = 0; j < BS; ++j) wb[i][j] = fma(-lh[i][b], yb[b][j], wb[i][j]);
+          for (int j = 0; j < BS; ++j) wb[i][j] = fma(nl[i][b], yb[b][j], wb[i][j]);
 #pragma unroll
       for (int i = 0; i < BS; ++i)
 #pragma unroll
