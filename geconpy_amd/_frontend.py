@@ -417,3 +417,110 @@ def forecast(b, name, T, R, Q, a0, *, P0, n_steps, Z, d, Hdiag, q_mode, covarian
     call(b, "dsge_forecast_batched", T=T, R=R, Q=Q, q_mode=code, **obs, a0=a0, P0=P0, status=st, batch=nb, m=m, k=k, p=p,
          n_steps=n_steps, a_out=res["states"], p_out=res["covs"], full_cov=full, y_out=res["observed"], f_out=res["observed_covs"])
     return res
+
+
+# ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
+SOLUTION = ("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
+
+
+def bind_solution(fname, args, kwargs, rest):
+    """The calling convention of the second-order dynamics: ``T, R, g_yy, g_yu, g_uu, g_ss, S`` or, in their place, ONE dict that
+    holds them (what ``second_order_logp_batched(..., return_solution=True)`` returns), followed by ``rest`` = ((name, default), ...)
+    by position or by name.  -> (the solution dict, the dict of the rest)."""
+    packed = bool(args) and isinstance(args[0], dict)
+    names = (("solution",) if packed else SOLUTION) + tuple(name for name, _ in rest)
+    if len(args) > len(names):
+        raise TypeError(f"{fname} takes at most {len(names)} positional arguments; got {len(args)}")
+    bound = dict(zip(names, args))
+    for key, value in kwargs.items():
+        if key not in names or key in bound:
+            raise TypeError(f"{fname}: {'unknown' if key not in names else 'repeated'} argument {key!r}")
+        bound[key] = value
+    sol = bound.pop("solution") if packed else {key: bound.pop(key) for key in SOLUTION if key in bound}
+    missing = [key for key in SOLUTION if key not in sol]
+    if missing:
+        raise TypeError(f"{fname}: the second-order solution lacks {missing}")
+    return sol, {name: bound.get(name, default) for name, default in rest}
+
+
+def _pruned_solution(b, sol):
+    """The validated coefficients as named arguments, and (batch, n, k)."""
+    T, R = _nd(b.inp(sol["T"]), 3), _nd(b.inp(sol["R"]), 3)
+    nb, n, n2 = T.shape
+    if n != n2 or tuple(R.shape[:2]) != (nb, n) or R.shape[2] < 1:
+        raise ValueError(f"T must be (batch, n, n) and R (batch, n, k); got {tuple(T.shape)}, {tuple(R.shape)}")
+    k = R.shape[2]
+    g_yy = _nd(b.inp(sol["g_yy"]), 4)
+    s = g_yy.shape[-1]
+    S = np.asarray(sol["S"])  # (a host index list for both backends, as in the second-order entry)
+    if S.ndim != 1 or len(S) != s or not np.issubdtype(S.dtype, np.integer):
+        raise ValueError(f"S must be an index list of length g_yy.shape[-1] = {s}; got shape {S.shape}, dtype {S.dtype}")
+    if s < 1 or S[0] < 0 or S[-1] >= n or (np.diff(S) <= 0).any():
+        raise ValueError(f"S must be strictly ascending within 0 .. {n - 1}; got {S.tolist()}")
+    _is(g_yy, (nb, n, s, s), "g_yy", "(batch, n, s, s)")
+    g_yu = _is(b.inp(sol["g_yu"]), (nb, n, s, k), "g_yu", "(batch, n, s, k)")
+    g_uu = _is(b.inp(sol["g_uu"]), (nb, n, k, k), "g_uu", "(batch, n, k, k)")
+    g_ss = _is(b.inp(sol["g_ss"]), (nb, n), "g_ss", "(batch, n)")
+    S = np.ascontiguousarray(S, dtype=np.int32)
+    return dict(T=T, R=R, gyy=g_yy, gyu=g_yu, guu=g_uu, gss=g_ss, state_idx=S.ctypes.data, n_state=s, batch=nb, n=n, k=k), S, (nb, n, k)
+
+
+def _pruned_paths(b, eps, x0, n_steps, nb, n, k):
+    """Shocks (may be None: one path without shocks), the initial pair and the step counts as named arguments."""
+    n_paths, n_shock, eb = 1, 0, 0
+    if eps is not None:
+        eps = b.inp(eps)
+        if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+            raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {tuple(eps.shape)}")
+        n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+        eb = shared_or_batched(eps, nb, (n_paths, n_shock, k), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    if n_steps < n_shock:
+        raise ValueError(f"n_steps = {n_steps} is less than the {n_shock} shock steps of eps")
+    xf0 = xs0 = None
+    xb = 0
+    if x0 is not None:
+        if not isinstance(x0, (tuple, list)) or len(x0) != 2:
+            raise ValueError("x0 must be None or a pair (xf0, xs0)")
+        xf0, xs0 = b.inp(x0[0]), b.inp(x0[1])
+        if tuple(xf0.shape) != tuple(xs0.shape):
+            raise ValueError(f"the x0 pair must have one shape; got {tuple(xf0.shape)} and {tuple(xs0.shape)}")
+        xb = shared_or_batched(xf0, nb, (n_paths, n), "x0")
+    return dict(eps=eps, eps_batched=eb, xf0=xf0, xs0=xs0, x0_batched=xb, n_paths=n_paths, n_steps=n_steps, n_shock_steps=n_shock)
+
+
+def simulate_pruned(b, sol, eps, *, n_steps, x0, status, parts, out=None):
+    a, S, (nb, n, k) = _pruned_solution(b, sol)
+    if eps is None:
+        raise ValueError("eps is required: (n_paths, n_shock_steps, k) or (batch, n_paths, n_shock_steps, k)")
+    a.update(_pruned_paths(b, eps, x0, n_steps, nb, n, k))
+    st = check_status(b.inp(status, "int32"), nb)
+    out = out or {}
+    shape = (nb, a["n_paths"], a["n_steps"], n)
+    res = dict(x=_out(b, out.get("x"), shape))
+    for key in ("x_f", "x_s"):
+        if parts or out.get(key) is not None:
+            res[key] = _out(b, out.get(key), shape)
+    call(b, "dsge_simulate_pruned_batched", **a, status=st, x_out=res["x"], xf_out=res.get("x_f"), xs_out=res.get("x_s"))
+    return res
+
+
+def girf_pruned(b, sol, *, n_steps, impulses, eps, x0, status, out=None):
+    a, S, (nb, n, k) = _pruned_solution(b, sol)
+    sb, c = 0, k
+    if impulses is not None:
+        impulses = b.inp(impulses)
+        if impulses.ndim not in (2, 3) or impulses.shape[-2] != k:
+            raise ValueError(f"impulses must be ({k}, c) or (batch, {k}, c); got {tuple(impulses.shape)}")
+        c = impulses.shape[-1]
+        sb = shared_or_batched(impulses, nb, (k, c), "impulses")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError("n_steps must be >= 0")
+    a.update(_pruned_paths(b, eps, x0, n_steps, nb, n, k))
+    if a["n_paths"] < 1:
+        raise ValueError("eps must hold at least one baseline path")
+    st = check_status(b.inp(status, "int32"), nb)
+    girf = _out(b, out, (nb, c, n_steps, n))
+    call(b, "dsge_girf_pruned_batched", **a, S_imp=impulses, s_batched=sb, c=c, status=st, girf_out=girf)
+    return girf

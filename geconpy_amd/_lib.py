@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -83,6 +83,7 @@ _FUSED = f"A B C D Q q_mode {_OBS} y batch n k p T_len solver tol max_iter jitte
 _LOGP = f"{_FUSED} n_state_hint z_selector_hint n_lead_hint logp_out status_out"
 _GRAD = f"A B C D q q_batched {_OBS} y batch n k p T_len solver tol max_iter jitter missing_fill"
 _BARS = "logp_out status_out A_bar B_bar C_bar D_bar q_bar d_bar h_bar"
+_PRUNED = "T R gyy gyu guu gss state_idx n_state"  # what the second-order entry returns, as it returns it
 _PENCIL = "g0 g1 *c psi pi batch N k n_eta tol G1_out C_out impact_out gev_out eu_out status"
 _DEVICE_ENTRIES = {
     "dsge_abi_version": "",
@@ -104,6 +105,7 @@ _DEVICE_ENTRIES = {
     "dsge_debug_gensys_stage_ms": "enable ms_out",
     "dsge_debug_adjoint_refine": "mode",
     "dsge_debug_second_order_phases": "enable cycles_out",
+    "dsge_debug_pruned_phases": "enable cycles_out",
     "dsge_profile_pipeline": f"{_LOGP} reps ms_out stream",
     # every entry below has a host twin (``host_twin``)
     "dsge_cycle_reduction_batched": "A B C batch n max_iter tol T_out status n_iter stream",
@@ -128,6 +130,10 @@ _DEVICE_ENTRIES = {
     "dsge_simulate_batched": "T R eps eps_batched x0 x0_batched status batch m k n_paths n_steps n_shock_steps x_out stream",
     "dsge_irf_batched": "T R S s_batched weights w_batched status batch m k c n_steps irf_out fevd_out stream",
     "dsge_forecast_batched": f"T R Q q_mode {_OBS} a0 P0 status batch m k p n_steps a_out p_out full_cov y_out f_out stream",
+    "dsge_simulate_pruned_batched": (f"{_PRUNED} eps eps_batched xf0 xs0 x0_batched status batch n k n_paths n_steps n_shock_steps "
+                                     "x_out xf_out xs_out stream"),
+    "dsge_girf_pruned_batched": (f"{_PRUNED} S_imp s_batched c eps eps_batched xf0 xs0 x0_batched status batch n k n_paths n_steps "
+                                 "n_shock_steps girf_out stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

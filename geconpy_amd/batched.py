@@ -624,3 +624,38 @@ def second_order_logp_batched(A, B, C, D, hess_idx, hess_val, q, Z, y, d=None, H
     if not return_solution:
         return dict(logp=out["logp"], status=out["status"])
     return dict(out, S=S)
+
+
+def simulate_pruned_batched(*args, **kwargs):
+    """``simulate_pruned_batched(T, R, g_yy, g_yu, g_uu, g_ss, S, eps, n_steps=None, x0=None, status=None, parts=False)`` -- or, in
+    place of the seven solution arguments, the dict ``second_order_logp_batched(..., return_solution=True)`` returns:
+    ``simulate_pruned_batched(solution, eps, ...)``.  Simulated paths of the PRUNED second-order system (Kim, Kim, Schaumburg & Sims;
+    ``oracle.second_order.simulate_pruned``) for every draw and path at once (include/dsge_hip.h, ``dsge_simulate_pruned_batched``):
+
+        x_f' = T x_f + R u;   x_s' = T x_s + 1/2 g_yy (f (x) f) + g_yu (f (x) u) + 1/2 g_uu (u (x) u) + 1/2 g_ss;   x = x_f + x_s
+
+    with f = x_f[S], in the indexing of ``simulate_batched``: ``eps`` (n_paths, n_shock_steps, k) or (batch, n_paths, n_shock_steps,
+    k), ``n_steps`` >= n_shock_steps (later steps carry no shock), ``x0`` None (both parts zero) or a pair ``(xf0, xs0)`` of
+    (n_paths, n) or (batch, n_paths, n) arrays, ``status`` optional (batch,) int32 (a non-zero word gives NaN).  Sizes of the
+    second-order solver: n <= 64, s <= 24, k <= 12.  Returns dict(x (batch, n_paths, n_steps, n)), with ``parts=True`` also ``x_f``
+    and ``x_s`` (``x == x_f + x_s`` to the last bit)."""
+    sol, r = F.bind_solution("simulate_pruned_batched", args, kwargs,
+                             (("eps", None), ("n_steps", None), ("x0", None), ("status", None), ("parts", False)))
+    return F.simulate_pruned(HOST, sol, r["eps"], n_steps=r["n_steps"], x0=r["x0"], status=r["status"], parts=r["parts"])
+
+
+def girf_pruned_batched(*args, **kwargs):
+    """``girf_pruned_batched(T, R, g_yy, g_yu, g_uu, g_ss, S, n_steps=40, impulses=None, eps=None, x0=None, status=None)`` -- or the
+    solution dict first, as ``simulate_pruned_batched``.  Generalised impulse responses of the pruned second-order system
+    (include/dsge_hip.h, ``dsge_girf_pruned_batched``): impulse j is column j of ``impulses`` ((k, c) or (batch, k, c); default
+    ``I_k``), added to the first shock of every baseline path of ``eps`` ((n_paths, n_shock_steps, k) or batched; None: one path
+    without shocks, the deterministic response from ``x0``), and
+
+        girf[b, j, t] = mean over paths p of  x_t(path p with the impulse) - x_t(path p)
+
+    summed in ascending path order, reproducible bit for bit.  Its first-order part is ``impulse_response_batched(T, R, S=impulses)``;
+    the rest depends on the state, the sign and the size of the impulse.  Returns dict(girf (batch, c, n_steps, n))."""
+    sol, r = F.bind_solution("girf_pruned_batched", args, kwargs,
+                             (("n_steps", 40), ("impulses", None), ("eps", None), ("x0", None), ("status", None)))
+    return dict(girf=F.girf_pruned(HOST, sol, n_steps=r["n_steps"], impulses=r["impulses"], eps=r["eps"], x0=r["x0"],
+                                   status=r["status"]))

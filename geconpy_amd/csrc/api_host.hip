@@ -664,6 +664,76 @@ int dsge_irf_batched_host(const double* T, const double* R, const double* S, int
   return hc.finish();
 }
 
+// (state_idx is a host array in the device entries too: it is not staged)
+int dsge_simulate_pruned_batched_host(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                      const double* gss, const int32_t* state_idx, int n_state, const double* eps, int eps_batched,
+                                      const double* xf0, const double* xs0, int x0_batched, const int32_t* status, int batch, int n,
+                                      int k, int n_paths, int n_steps, int n_shock_steps, double* x_out, double* xf_out,
+                                      double* xs_out) {
+  int rc = check_pruned(T, R, gyy, gyu, guu, gss, state_idx, n_state, eps, batch, n, k, n_paths, n_steps, n_shock_steps,
+                        x_out || xf_out || xs_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, s = (size_t)n_state, no = b * n_paths * n_steps * n, nx = (size_t)(x0_batched ? batch : 1) * n_paths * n;
+  const double *dT, *dR, *dyy, *dyu, *duu, *dss, *de, *df0, *ds0;
+  const int32_t* dS;
+  double *dx, *dxf, *dxs;
+  hc.in(&dT, T, b * n * n);
+  hc.in(&dR, R, b * n * k);
+  hc.in(&dyy, gyy, b * n * s * s);
+  hc.in(&dyu, gyu, b * n * s * k);
+  hc.in(&duu, guu, b * n * k * k);
+  hc.in(&dss, gss, b * n);
+  hc.in(&de, eps, (size_t)(eps_batched ? batch : 1) * n_paths * n_shock_steps * k);
+  hc.in(&df0, xf0, nx);
+  hc.in(&ds0, xs0, nx);
+  hc.in(&dS, status, b);
+  hc.out(&dx, x_out, no);
+  hc.out(&dxf, xf_out, no);
+  hc.out(&dxs, xs_out, no);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_simulate_pruned_batched(dT, dR, dyy, dyu, duu, dss, state_idx, n_state, de, eps_batched, df0, ds0, x0_batched, dS, batch,
+                                         n, k, n_paths, n_steps, n_shock_steps, dx, dxf, dxs, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
+int dsge_girf_pruned_batched_host(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                  const double* gss, const int32_t* state_idx, int n_state, const double* S_imp, int s_batched, int c,
+                                  const double* eps, int eps_batched, const double* xf0, const double* xs0, int x0_batched,
+                                  const int32_t* status, int batch, int n, int k, int n_paths, int n_steps, int n_shock_steps,
+                                  double* girf_out) {
+  int rc = check_girf_pruned(T, R, gyy, gyu, guu, gss, state_idx, n_state, S_imp, c, eps, batch, n, k, n_paths, n_steps, n_shock_steps,
+                             girf_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || c == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, s = (size_t)n_state, nx = (size_t)(x0_batched ? batch : 1) * n_paths * n;
+  const double *dT, *dR, *dyy, *dyu, *duu, *dss, *dimp, *de, *df0, *ds0;
+  const int32_t* dS;
+  double* dg;
+  hc.in(&dT, T, b * n * n);
+  hc.in(&dR, R, b * n * k);
+  hc.in(&dyy, gyy, b * n * s * s);
+  hc.in(&dyu, gyu, b * n * s * k);
+  hc.in(&duu, guu, b * n * k * k);
+  hc.in(&dss, gss, b * n);
+  hc.in(&dimp, S_imp, (size_t)(s_batched ? batch : 1) * k * c);
+  hc.in(&de, eps, (size_t)(eps_batched ? batch : 1) * n_paths * n_shock_steps * k);
+  hc.in(&df0, xf0, nx);
+  hc.in(&ds0, xs0, nx);
+  hc.in(&dS, status, b);
+  hc.out(&dg, girf_out, b * c * n_steps * n);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_girf_pruned_batched(dT, dR, dyy, dyu, duu, dss, state_idx, n_state, dimp, s_batched, c, de, eps_batched, df0, ds0,
+                                     x0_batched, dS, batch, n, k, n_paths, n_steps, n_shock_steps, dg, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

@@ -298,6 +298,7 @@ static int debug_counters(long long** slot, int count, int enable, long long* cy
 }
 int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_dbg, 8, enable, cycles_out); }
 int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
+int dsge_debug_pruned_phases(int enable, long long* cycles_out) { return debug_counters(&g_pruned_dbg, 8, enable, cycles_out); }
 int dsge_debug_adjoint_refine(int mode) {
   if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
   g_adj_refine_mode = mode;
@@ -701,6 +702,65 @@ int dsge_irf_batched(const double* T, const double* R, const double* S, int s_ba
     return rc;
   if (second_pass) return launch_fevd(irf, weights, w_draw, status, batch, m, c, n_steps, fevd_out, st);
   return DSGE_SUCCESS;
+}
+
+// ---- second-order dynamics (dsge_pruned.hpp): pruned simulation and generalised impulse responses -----------------------------
+// The panel of the second-order blocks is library scratch, packed per draw; a batch whose panels exceed PRUNED_SCRATCH_BYTES runs
+// in contiguous chunks of draws, one after the other on the caller's stream.
+static constexpr size_t PRUNED_SCRATCH_BYTES = (size_t)1 << 30;
+static int pruned_run(const PrunedProblem& p, int batch, const double* eps, const double* xf0, const double* xs0, const double* imp,
+                      const int32_t* status, double* x_out, double* xf_out, double* xs_out, double* girf_out, hipStream_t st) {
+  const size_t pd = pruned_panel_doubles(p.n, p.s, p.k), fit = PRUNED_SCRATCH_BYTES / (pd * sizeof(double));
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  double* panel = nullptr;
+  ScratchLayout lay;
+  lay.add(&panel, (size_t)chunk * pd);
+  int rc;
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  const size_t n = p.n, s = p.s, k = p.k, sim = (size_t)p.n_paths * p.n_steps * n, gi = (size_t)p.c * p.n_steps * n;
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const size_t o = (size_t)c0;
+    PrunedProblem q = p;
+    q.T += o * n * n; q.R += o * n * k; q.gyy += o * n * s * s; q.gyu += o * n * s * k; q.guu += o * n * k * k; q.gss += o * n;
+    if ((rc = launch_pruned(q, nb, eps ? eps + o * p.eps_draw : nullptr, xf0 ? xf0 + o * p.x0_draw : nullptr,
+                            xs0 ? xs0 + o * p.x0_draw : nullptr, imp ? imp + o * p.imp_draw : nullptr, status ? status + o : nullptr,
+                            panel, x_out ? x_out + o * sim : nullptr, xf_out ? xf_out + o * sim : nullptr,
+                            xs_out ? xs_out + o * sim : nullptr, girf_out ? girf_out + o * gi : nullptr, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
+int dsge_simulate_pruned_batched(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                 const double* gss, const int32_t* state_idx, int n_state, const double* eps, int eps_batched,
+                                 const double* xf0, const double* xs0, int x0_batched, const int32_t* status, int batch, int n, int k,
+                                 int n_paths, int n_steps, int n_shock_steps, double* x_out, double* xf_out, double* xs_out,
+                                 void* stream) {
+  int rc = check_pruned(T, R, gyy, gyu, guu, gss, state_idx, n_state, eps, batch, n, k, n_paths, n_steps, n_shock_steps,
+                        x_out || xf_out || xs_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const PrunedProblem p{T, R, gyy, gyu, guu, gss, state_idx, n, n_state, k, 0, n_paths, n_steps, n_shock_steps,
+                        eps_batched ? (long long)n_paths * n_shock_steps * k : 0, x0_batched ? (long long)n_paths * n : 0, 0};
+  return pruned_run(p, batch, eps, xf0, xs0, nullptr, status, x_out, xf_out, xs_out, nullptr, (hipStream_t)stream);
+}
+
+int dsge_girf_pruned_batched(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                             const double* gss, const int32_t* state_idx, int n_state, const double* S_imp, int s_batched, int c,
+                             const double* eps, int eps_batched, const double* xf0, const double* xs0, int x0_batched,
+                             const int32_t* status, int batch, int n, int k, int n_paths, int n_steps, int n_shock_steps,
+                             double* girf_out, void* stream) {
+  int rc = check_girf_pruned(T, R, gyy, gyu, guu, gss, state_idx, n_state, S_imp, c, eps, batch, n, k, n_paths, n_steps, n_shock_steps,
+                             girf_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || c == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const PrunedProblem p{T, R, gyy, gyu, guu, gss, state_idx, n, n_state, k, c, n_paths, n_steps, n_shock_steps,
+                        eps_batched ? (long long)n_paths * n_shock_steps * k : 0, x0_batched ? (long long)n_paths * n : 0,
+                        s_batched ? (long long)k * c : 0};
+  return pruned_run(p, batch, eps, xf0, xs0, S_imp, status, nullptr, nullptr, nullptr, girf_out, (hipStream_t)stream);
 }
 
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

@@ -294,6 +294,19 @@ int launch_fevd(const double* irf, const double* weights, long long w_draw, cons
 int launch_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, const double* P0,
                     const int32_t* status, int batch, int m, int k, int n_steps, double* a_out, double* p_out, int full_cov,
                     double* y_out, double* f_out, hipStream_t st);  // (of o: Z, d, Hdiag, p)
+// launch_pruned.hip (dsge_pruned.hpp): the pruned second-order recursion.  One description of the problem for both entries; the
+// coefficient pointers are those of the first draw of a chunk, S is a HOST index list.  panel: scratch, [batch] x pruned_panel_doubles.
+// girf_out != nullptr: generalised impulse responses to the c columns of imp (nullptr: unit impulses), else the paths themselves.
+struct PrunedProblem {
+  const double *T, *R, *gyy, *gyu, *guu, *gss;
+  const int32_t* S;
+  int n, s, k, c, n_paths, n_steps, n_shock_steps;
+  long long eps_draw, x0_draw, imp_draw;  // strides from one draw to the next, 0 = shared
+};
+size_t pruned_panel_doubles(int n, int s, int k);
+int launch_pruned(const PrunedProblem& p, int batch, const double* eps, const double* xf0, const double* xs0, const double* imp,
+                  const int32_t* status, double* panel, double* x_out, double* xf_out, double* xs_out, double* girf_out,
+                  hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -346,6 +359,7 @@ int launch_second_order(const double* B, const double* C, const double* T, const
 
 extern int g_adj_refine_mode;          // launch_assemble.hip: 0 = residual rule, 1 = refine every draw, 2 = never (debug)
 extern long long* g_so_dbg;            // launch_second_order.hip: debug phase counters of the second-order filter kernel
+extern long long* g_pruned_dbg;        // launch_pruned.hip: debug phase counters of pruned_propagate_kernel
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
 extern long long* g_big_dbg;          // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
@@ -517,6 +531,30 @@ inline int check_irf(const double* T, const double* R, const double* S, int batc
   if (!irf_out && !fevd_out) return fail(DSGE_ERR_INVALID, "no output requested");
   if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "impulse responses: m exceeds DSGE_MAX_N_BIG");
   return DSGE_SUCCESS;
+}
+// the second-order dynamics entries: sizes of the second-order solver (n <= 64, 1 <= s <= 24, k <= 12; k <= s is not required)
+inline int check_pruned(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu, const double* gss,
+                        const int32_t* S, int s, const double* eps, int batch, int n, int k, int n_paths, int n_steps,
+                        int n_shock_steps, bool any_output) {
+  if (batch < 0 || n < 1 || s < 1 || k < 1 || n_paths < 0 || n_steps < 0 || n_shock_steps < 0)
+    return fail(DSGE_ERR_INVALID, "size out of range");
+  if (n_shock_steps > n_steps) return fail(DSGE_ERR_INVALID, "n_shock_steps > n_steps");
+  if (!T || !R || !gyy || !gyu || !guu || !gss || !S || (!eps && n_shock_steps > 0)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!any_output) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (n > 64 || s > 24 || k > 12)
+    return fail(DSGE_ERR_TOO_LARGE, "pruned dynamics: beyond the second-order solver's sizes (n <= 64, n_state <= 24, k <= 12)");
+  if (s > n) return fail(DSGE_ERR_INVALID, "n_state exceeds n");
+  for (int i = 0; i < s; ++i)
+    if (S[i] < 0 || S[i] >= n || (i > 0 && S[i] <= S[i - 1])) return fail(DSGE_ERR_INVALID, "state_idx must be strictly ascending within 0 .. n-1");
+  return DSGE_SUCCESS;
+}
+// (girf: n_paths baseline paths, at least one; eps == nullptr: baselines without shocks)
+inline int check_girf_pruned(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu, const double* gss,
+                             const int32_t* S, int s, const double* S_imp, int c, const double* eps, int batch, int n, int k, int n_paths,
+                             int n_steps, int n_shock_steps, const double* girf_out) {
+  if (c < 0 || n_paths < 1) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (!S_imp && c != k) return fail(DSGE_ERR_INVALID, "S_imp == NULL means S_imp = I: c must equal k");
+  return check_pruned(T, R, gyy, gyu, guu, gss, S, s, eps, batch, n, k, n_paths, n_steps, n_shock_steps, girf_out != nullptr);
 }
 inline int check_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, int batch, int m,
                           int k, int n_steps, const double* a_out, const double* p_out, const double* y_out, const double* f_out) {

@@ -24,6 +24,8 @@
 //                                          pruned state (207 on the SW-shaped workload): rank-p update on the VALU, the
 //                                          prediction Az P+ Az' + Qz as two products on the FP64 matrix core
 //                                          (dsge_so_gemm.hpp), steady-state switch as in the first-order kernels
+// What USES the solution afterwards -- simulated paths of the pruned system and generalised impulse responses per draw -- is
+// dsge_pruned.hpp (dsge_simulate_pruned_batched, dsge_girf_pruned_batched).
 #pragma once
 #include "dsge_device.hpp"
 #include "dsge_so_gemm.hpp"

@@ -278,6 +278,26 @@ class LogpEngine:
         return F.forecast(self.backend, "forecast", T, R, Q, a0, P0=P0, n_steps=n_steps, Z=Z, d=d, Hdiag=Hdiag, q_mode=q_mode,
                           covariances=covariances, status=status, out=out)
 
+    # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
+    def simulate_pruned(self, *args, out=None, **kwargs):
+        """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as
+        ``batched.simulate_pruned_batched``: the seven solution arguments or one dict of them, then ``eps, n_steps=None, x0=None,
+        status=None, parts=False``), on torch's current stream.  ``S`` is a host index list (``second_order_structure``).  ``out``:
+        optional dict with preallocated ``x`` / ``x_f`` / ``x_s``.  Returns dict(x[, x_f, x_s]); asynchronous."""
+        sol, r = F.bind_solution("simulate_pruned", args, kwargs,
+                                 (("eps", None), ("n_steps", None), ("x0", None), ("status", None), ("parts", False)))
+        return F.simulate_pruned(self.backend, sol, r["eps"], n_steps=r["n_steps"], x0=r["x0"], status=r["status"], parts=r["parts"],
+                                 out=out)
+
+    def girf_pruned(self, *args, out=None, **kwargs):
+        """Generalised impulse responses of the pruned second-order system from device tensors (``dsge_girf_pruned_batched``;
+        arguments as ``batched.girf_pruned_batched``), on torch's current stream.  ``out``: an optional preallocated tensor.
+        Returns dict(girf (batch, c, n_steps, n)); asynchronous."""
+        sol, r = F.bind_solution("girf_pruned", args, kwargs,
+                                 (("n_steps", 40), ("impulses", None), ("eps", None), ("x0", None), ("status", None)))
+        return dict(girf=F.girf_pruned(self.backend, sol, n_steps=r["n_steps"], impulses=r["impulses"], eps=r["eps"], x0=r["x0"],
+                                       status=r["status"], out=out))
+
     def solve_kalman_logp_grad(self, A, B, C, D, q, Z, y, d=None, Hdiag=None, solver="cycle_reduction", tol=1e-6, max_iter=50,
                                jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, n_filter_hint=0, n_lead_hint=0,
                                out=None, options=None, full_covariance=False, dense_z=False):

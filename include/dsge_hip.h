@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 12
+#define DSGE_ABI_VERSION 13
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -48,6 +48,7 @@ extern "C" {
 /* ABI 10: dsge_kalman_smoother_batched (+ _host) and the status bit DSGE_ST_SMOOTHER_SINGULAR are new; nothing else changed. */
 /* ABI 11: dsge_simulate_batched, dsge_irf_batched, dsge_forecast_batched (+ _host) are new; nothing else changed. */
 /* ABI 12: dsge_simulation_smoother_batched (+ _host) is new; nothing else changed. */
+/* ABI 13: dsge_simulate_pruned_batched, dsge_girf_pruned_batched (+ _host) are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -797,6 +798,53 @@ int dsge_forecast_batched_host(const double* T, const double* R, const double* Q
                                double* p_out, int full_cov, double* y_out, double* f_out);
 
 /*
+ * SECOND-ORDER DYNAMICS per draw (ABI 13; csrc/dsge_pruned.hpp, docs/design/dynamics.md): simulation of the pruned system (Kim, Kim,
+ * Schaumburg & Sims 2008) and generalised impulse responses from the policy function dsge_second_order_logp_batched returns -- its
+ * T_out, R_out, gyy_out, gyu_out, guu_out, gss_out and state_idx (a HOST int32 list, strictly ascending) are the first eight
+ * arguments here, layouts unchanged.  With f = x_f[state_idx] and u_t the shock of step t,
+ *       x_f' = T x_f + R u
+ *       x_s' = T x_s + 1/2 g_yy (f (x) f) + g_yu (f (x) u) + 1/2 g_uu (u (x) u) + 1/2 g_ss
+ *       x    = x_f + x_s
+ * in the time indexing of dsge_simulate_batched: output index t holds the state after shock t; steps from n_shock_steps on carry no
+ * shock (x_s keeps receiving 1/2 g_ss and the quadratic term in the decaying f).
+ *   eps      : [batch|1][n_paths][n_shock_steps][k], the caller's draws; may be NULL with n_shock_steps == 0
+ *   xf0, xs0 : [batch|1][n_paths][n] each (one flag, x0_batched, for both) or NULL for zero
+ *   status   : [batch], INPUT, may be NULL; a draw with a non-zero status gets NaN in all its outputs and does not affect the others
+ *
+ * dsge_simulate_pruned_batched:  x_out, xf_out, xs_out: [batch][n_paths][n_steps][n] each, any may be NULL, not all;
+ *   x_out == xf_out + xs_out to the last bit.
+ *
+ * dsge_girf_pruned_batched:  the generalised impulse response to impulse j = column j of S_imp ([batch|1][k][c]; NULL: I_k, c must
+ *   equal k, nothing is read), averaged over n_paths >= 1 baseline shock paths in ascending order,
+ *       girf_out[b][j][t][:] = (1 / n_paths) sum_p ( x_t(shocks of path p with e_0 += S_imp[:, j]) - x_t(shocks of path p) )
+ *   girf_out : [batch][c][n_steps][n].  eps == NULL (n_shock_steps == 0, n_paths == 1): the deterministic response from the
+ *   initial state.  No floating-point atomics: two calls give the same bits.  The x_f part is the linear response T^t R S_imp[:, j].
+ *
+ * Sizes of the second-order solver: n <= 64, 1 <= n_state <= 24, k <= 12 (k <= n_state is NOT required), else DSGE_ERR_TOO_LARGE before
+ * anything is launched.  batch == 0, n_paths == 0 (simulate), c == 0 (girf) or n_steps == 0: success, nothing touched.
+ */
+int dsge_simulate_pruned_batched(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                 const double* gss, const int32_t* state_idx, int n_state, const double* eps, int eps_batched,
+                                 const double* xf0, const double* xs0, int x0_batched, const int32_t* status, int batch, int n, int k,
+                                 int n_paths, int n_steps, int n_shock_steps, double* x_out, double* xf_out, double* xs_out,
+                                 void* stream);
+int dsge_simulate_pruned_batched_host(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                      const double* gss, const int32_t* state_idx, int n_state, const double* eps, int eps_batched,
+                                      const double* xf0, const double* xs0, int x0_batched, const int32_t* status, int batch, int n,
+                                      int k, int n_paths, int n_steps, int n_shock_steps, double* x_out, double* xf_out,
+                                      double* xs_out);
+int dsge_girf_pruned_batched(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                             const double* gss, const int32_t* state_idx, int n_state, const double* S_imp, int s_batched, int c,
+                             const double* eps, int eps_batched, const double* xf0, const double* xs0, int x0_batched,
+                             const int32_t* status, int batch, int n, int k, int n_paths, int n_steps, int n_shock_steps,
+                             double* girf_out, void* stream);
+int dsge_girf_pruned_batched_host(const double* T, const double* R, const double* gyy, const double* gyu, const double* guu,
+                                  const double* gss, const int32_t* state_idx, int n_state, const double* S_imp, int s_batched, int c,
+                                  const double* eps, int eps_batched, const double* xf0, const double* xs0, int x0_batched,
+                                  const int32_t* status, int batch, int n, int k, int n_paths, int n_steps, int n_shock_steps,
+                                  double* girf_out);
+
+/*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw
  * batch (the per-evaluation hot loop of SURVEY.md section 3A; what
  * DSGEStateSpace._setup_policy_matrices + make_symbolic_graph + the filter compute,
@@ -1018,6 +1066,11 @@ int dsge_second_order_logp_batched_host(const double* A, const double* B, const 
  * [1] the pass over Az' (predicted mean, Az K, Az V); [2] the first product; [3] the second product + epilogue; [4] steady
  * steps; [5] = number of full steps, [6] = number of steady steps, [7] = kernel total; cycles_out: host int64[8] or NULL. */
 int dsge_debug_second_order_phases(int enable, long long* cycles_out);
+
+/* Debug hook: enable != 0 makes pruned_propagate_kernel record the shader cycles wavefront 0 of workgroup 0 spends, summed over
+ * the steps, in [0] the x_f product, [1] T x_s, [2] the panel product P mon, [3] the wait at the step's barrier, [4] the slab
+ * (or the GIRF sums); [5] = kernel total, [6] = number of steps, [7] = set-up; cycles_out: host int64[8] or NULL. */
+int dsge_debug_pruned_phases(int enable, long long* cycles_out);
 
 /*
  * Timing hook for bench.py: runs `reps` back-to-back launches of the fused pipeline's

@@ -1,6 +1,7 @@
 """GPU box: wall time (device events) of the post-solve dynamics entries on the SW-shaped workload (m = 40, k = 7, 40 steps).
 
     python tools/dynamics_time.py [draws ...]          (default: 256 4096)
+    python tools/dynamics_time.py --second-order [draws ...]      the second-order rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -9,7 +10,11 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
   * the impulse responses with the on-chip FEVD;
   * LogpEngine.forecast with full covariances (p = 0) against dsge_kalman_filter_outputs_batched with full covariances at
     T_len = 40 on the same draws -- per step the forecast does that kernel's two covariance products and none of its update;
-  * the same two jobs as a host numpy loop over the draws (tests' restatement), for the CPU comparison.
+  * the same two jobs as a host numpy loop over the draws (tests' restatement), for the CPU comparison;
+  * second order (csrc/dsge_pruned.hpp), n = 40, s = 18, k = 7: LogpEngine.simulate_pruned (16 paths) next to the first-order
+    LogpEngine.simulate on the same T, R and shocks in the same run -- the yardstick of the ratio is the K-extent of a step's
+    products, 48 against 48 + 48 + 336 -- then LogpEngine.girf_pruned (7 unit impulses over 16 baseline paths) and the host numpy
+    loop of tests/pruned_dynamics_reference.py (256 draws timed once, scaled).
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -44,8 +49,56 @@ def timed(fn, min_seconds=1.0):
     return total / reps * 1e3  # ms per call
 
 
+def second_order_rows(eng, sizes):
+    from tests import pruned_dynamics_reference as pr
+
+    c = pr.case("n40")
+    nd, n, k = c["R"].shape
+    s = len(c["S"])
+    rng = np.random.default_rng(1)
+    print(f"second order n={n} s={s} k={k}, {N_STEPS} steps, 16 paths")
+    t_cpu = None
+    for nb in sizes:
+        rep = (nb + nd - 1) // nd
+        sol = {key: eng.to_device(np.tile(c[key], (rep,) + (1,) * (c[key].ndim - 1))[:nb]) for key in pr.solution(c) if key != "S"}
+        sol["S"] = c["S"]
+        eps_h = rng.standard_normal((nb, 16, N_STEPS, k)) * 0.01
+        eps = eng.to_device(eps_h)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        x, paths, girf = mk(nb, 16, N_STEPS, n), mk(nb, 16, N_STEPS, n), mk(nb, k, N_STEPS, n)
+        t_first = timed(lambda: eng.simulate(sol["T"], sol["R"], eps, out=paths))
+        t_sim = timed(lambda: eng.simulate_pruned(sol, eps, out=dict(x=x)))
+        t_girf = timed(lambda: eng.girf_pruned(sol, N_STEPS, None, eps, out=girf))
+        print(f"draws={nb:5d} simulate_pruned, 16 paths: {t_sim:8.3f} ms | first-order simulate, same run: {t_first:8.3f} ms | "
+              f"ratio {t_sim / t_first:5.2f} (K-extent of the products: {(48 + 48 + 336) / 48:4.1f})")
+        print(f"draws={nb:5d} girf_pruned, 7 impulses x 16 baseline paths: {t_girf:8.3f} ms")
+        import ctypes
+
+        lib, cyc = _lib.load(), (ctypes.c_longlong * 8)()  # per-phase shader cycles of wavefront 0 of workgroup 0, one call
+        _lib.check(lib.dsge_debug_pruned_phases(1, None))
+        eng.simulate_pruned(sol, eps, out=dict(x=x))
+        _lib.check(lib.dsge_debug_pruned_phases(0, ctypes.addressof(cyc)))
+        names = ("x_f product", "T x_s", "P mon", "barrier wait", "slab")
+        print(f"draws={nb:5d} phases of one workgroup, cycles per step: "
+              + ", ".join(f"{nm} {cyc[i] / max(cyc[6], 1):.0f}" for i, nm in enumerate(names))
+              + f" | total {cyc[5]}, {cyc[6]} steps, set-up {cyc[7]}")
+        if t_cpu is None:  # host numpy loop over 256 draws (or the batch, if smaller), scaled to the batch
+            nc = min(nb, 256)
+            t0 = time.perf_counter()
+            for i in range(nc):
+                T, R, so_ = pr.draw(c, i % nd)
+                for p in range(16):
+                    pr.simulate_pruned(T, R, so_, eps_h[i, p])
+            t_cpu = (time.perf_counter() - t0) / nc * 1e3
+            print(f"host numpy loop: {nc} draws timed, {t_cpu:8.2f} ms per draw")
+        print(f"draws={nb:5d} host numpy loop (scaled): simulate_pruned {t_cpu * nb:9.1f} ms ({t_cpu * nb / t_sim:7.0f}x)")
+
+
 def main():
-    sizes = [int(a) for a in sys.argv[1:]] or [256, 4096]
+    args = [a for a in sys.argv[1:] if a != "--second-order"]
+    sizes = [int(a) for a in args] or [256, 4096]
+    if "--second-order" in sys.argv:
+        return second_order_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
@@ -99,6 +152,7 @@ def main():
         t_cpu_fc = (time.perf_counter() - t0) / nc * nb * 1e3
         print(f"draws={nb:5d} host numpy loop ({nc} draws timed, scaled): impulse responses {t_cpu_irf:9.1f} ms ({t_cpu_irf / t_irf:7.0f}x), "
               f"forecast {t_cpu_fc:9.1f} ms ({t_cpu_fc / t_fc:7.0f}x)")
+    second_order_rows(eng, sizes)
 
 
 if __name__ == "__main__":
