@@ -419,6 +419,75 @@ def forecast(b, name, T, R, Q, a0, *, P0, n_steps, Z, d, Hdiag, q_mode, covarian
     return res
 
 
+def shock_groups(groups, k):
+    """``groups`` (None, or a sequence of sequences of shock indices that partitions 0 .. k-1) -> (group_of_shock int32 (k,), g)."""
+    if groups is None:
+        return np.arange(k, dtype=np.int32), k
+    of = np.full(k, -1, dtype=np.int32)
+    try:
+        members = [[int(j) for j in grp] for grp in groups]
+    except TypeError:
+        raise ValueError("groups must be a sequence of sequences of shock indices") from None
+    for c, grp in enumerate(members):
+        if not grp:
+            raise ValueError(f"groups[{c}] is empty")
+        for j in grp:
+            if not 0 <= j < k:
+                raise ValueError(f"groups[{c}] holds {j}: shock indices are 0 .. {k - 1}")
+            if of[j] >= 0:
+                raise ValueError(f"shock {j} is in groups[{of[j]}] and in groups[{c}]")
+            of[j] = c
+    if (of < 0).any():
+        raise ValueError(f"groups must partition 0 .. {k - 1}: shocks {np.flatnonzero(of < 0).tolist()} are in no group")
+    return of, len(members)
+
+
+def shock_decomposition(b, name, T, R, states, shocks, *, groups, variables, Z, remainder, status, out=None):
+    """``states`` / ``shocks``: (batch, T_len, m) / (batch, T_len, k) of the smoother or (batch, n_paths, T_len, .) of the
+    simulation smoother; the outputs have the same number of leading axes."""
+    T, R, nb, m, k = _TR(b, T, R, name)
+    states, shocks = b.inp(states), b.inp(shocks)
+    if states.ndim not in (3, 4) or shocks.ndim != states.ndim:
+        raise ValueError(f"states and shocks must both be (batch, T_len, .) or (batch, n_paths, T_len, .); got {tuple(states.shape)}, "
+                         f"{tuple(shocks.shape)}")
+    lead = tuple(states.shape[:-1])
+    if lead[0] != nb or states.shape[-1] != m or tuple(shocks.shape) != (*lead, k):
+        raise ValueError(f"states must be {(nb, '...', m)} and shocks {(nb, '...', k)} with the same leading axes; got "
+                         f"{tuple(states.shape)}, {tuple(shocks.shape)}")
+    n_paths, T_len = (1, lead[1]) if len(lead) == 2 else lead[1:]
+    if T_len < 1:
+        raise ValueError("states holds no period")
+    grp, g = shock_groups(groups, k)
+    if variables is None:
+        var = np.arange(m, dtype=np.int32)
+    else:
+        var = np.asarray(list(variables), dtype=np.int64).reshape(-1)
+        if ((var < 0) | (var >= m)).any():
+            raise ValueError(f"variables must be within 0 .. {m - 1}; got {var.tolist()}")
+        if len(np.unique(var)) != len(var):
+            raise ValueError(f"variables holds a variable twice: {var.tolist()}")
+        var = np.ascontiguousarray(var, dtype=np.int32)
+    n_out, p, zb = len(var), 0, 0
+    if Z is not None:
+        Z = b.inp(Z)
+        if Z.ndim not in (2, 3) or Z.shape[-1] != m or Z.shape[-2] < 1:
+            raise ValueError(f"Z must be (p, {m}) or (batch, p, {m}); got {tuple(Z.shape)}")
+        p = Z.shape[-2]
+        zb = shared_or_batched(Z, nb, (p, m), "Z")
+    if n_out == 0 and p == 0:
+        raise ValueError("nothing requested: no variables and no Z")
+    st = check_status(b.inp(status, "int32"), nb)
+    C = g + 1 + bool(remainder)
+    out = out or {}
+    res = dict(contributions=_out(b, out.get("contributions"), (*lead, n_out, C)) if n_out else None,
+               observed=_out(b, out.get("observed"), (*lead, p, C)) if p else None,
+               components=[*range(g), "initial"] + (["remainder"] if remainder else []))
+    call(b, "dsge_shock_decomposition_batched", T=T, R=R, eps=shocks, x=states, group_of_shock=grp.ctypes.data, n_groups=g,
+         var_idx=var.ctypes.data, n_out=n_out, Z=Z, z_batched=zb, status=st, batch=nb, m=m, k=k, p=p, n_paths=n_paths, T_len=T_len,
+         remainder=bool(remainder), contrib_out=res["contributions"], obs_out=res["observed"])
+    return res
+
+
 # ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
 SOLUTION = ("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
 

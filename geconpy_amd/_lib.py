@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -73,8 +73,8 @@ class GensysForward(C.Structure):
 # name is an int, a double or a size_t when it is listed below, a pointer (double* / int32_t* / struct* / stream, passed as a raw
 # host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
 _INTS = ("N T_len batch c correlation d_batched device enable eps_batched eta_batched full_cov h_batched k lag_step m max_iter mode n n_eta "
-         "n_filter_hint n_lags n_lead n_lead_hint n_links n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p q_batched "
-         "q_mode reps s_batched solver w_batched x0_batched z_batched z_selector_hint")
+         "n_filter_hint n_groups n_lags n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p "
+         "q_batched q_mode remainder reps s_batched solver w_batched x0_batched z_batched z_selector_hint")
 _KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
           "scratch_limit_bytes": C.c_size_t}
 _OBS = "Z z_batched d d_batched Hdiag h_batched"
@@ -106,6 +106,7 @@ _DEVICE_ENTRIES = {
     "dsge_debug_adjoint_refine": "mode",
     "dsge_debug_second_order_phases": "enable cycles_out",
     "dsge_debug_pruned_phases": "enable cycles_out",
+    "dsge_debug_shock_decomp_phases": "enable cycles_out",
     "dsge_profile_pipeline": f"{_LOGP} reps ms_out stream",
     # every entry below has a host twin (``host_twin``)
     "dsge_cycle_reduction_batched": "A B C batch n max_iter tol T_out status n_iter stream",
@@ -134,6 +135,8 @@ _DEVICE_ENTRIES = {
                                      "x_out xf_out xs_out stream"),
     "dsge_girf_pruned_batched": (f"{_PRUNED} S_imp s_batched c eps eps_batched xf0 xs0 x0_batched status batch n k n_paths n_steps "
                                  "n_shock_steps girf_out stream"),
+    "dsge_shock_decomposition_batched": ("T R eps x group_of_shock n_groups var_idx n_out Z z_batched status batch m k p n_paths T_len "
+                                         "remainder contrib_out obs_out stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

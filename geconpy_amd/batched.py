@@ -505,6 +505,25 @@ def simulate_batched(T, R, eps, n_steps=None, x0=None, status=None):
     return dict(paths=F.simulate(HOST, "simulate_batched", T, R, eps, n_steps=n_steps, x0=x0, status=status))
 
 
+def shock_decomposition_batched(T, R, states, shocks, groups=None, variables=None, Z=None, remainder=True, status=None):
+    """Historical shock decomposition for a batch of draws: how much of every variable's smoothed path each structural shock
+    explains (include/dsge_hip.h, ``dsge_shock_decomposition_batched``).  From the smoother:
+    ``s = kalman_smoother_batched(T, R, Q, Z, y)`` -> ``shock_decomposition_batched(T, R, s["smoothed_states"],
+    s["smoothed_shocks"])``; from the simulation smoother: ``s = simulation_smoother_batched(T, R, Q, Z, y, n_paths=...)`` ->
+    ``shock_decomposition_batched(T, R, s["states"], s["shocks"])``.  ``states`` / ``shocks``: (batch, T_len, m) / (batch, T_len, k)
+    or (batch, n_paths, T_len, .); period 0 of ``shocks`` (NaN by the smoother's definition) is never read: period 0 is the initial
+    condition alone.  ``groups``: a sequence of sequences of shock indices that partitions 0 .. k-1 (default: every shock its
+    own group; at most 15 groups, so a model with more shocks groups them).  ``variables``: the variables wanted, distinct, any
+    order (default all; ``()`` with ``Z``: the observed decomposition alone).  ``Z``: (p, m) or (batch, p, m), adds the decomposition
+    of ``Z x`` (the intercept d is not a component).  ``remainder``: append ``x - (sum of the other components)`` -- what the filter
+    conventions leave between the smoothed path and the exact path of the smoothed shocks (1e-5 of max|x| by default, rounding
+    with ``jitter_on_P=False``), so that the components add up to ``x``.  ``status``: optional (batch,) int32, a draw with a
+    non-zero word gets NaN.  Returns dict(contributions (..., n_variables, C) or None, observed (..., p, C) or None, components:
+    the names of the last axis -- the group indices, ``"initial"``[, ``"remainder"``])."""
+    return F.shock_decomposition(HOST, "shock_decomposition_batched", T, R, states, shocks, groups=groups, variables=variables, Z=Z,
+                                 remainder=remainder, status=status)
+
+
 def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None):
     """Impulse responses ``irf[b, j, h] = T_b^h R_b S[:, j]`` for a batch of draws -- ``impulse_response_function``
     (gEconpy/model/simulate.py:201-317; its loop over shocks :300-311 calls ``_simulate_linear_system`` :171-182 once per

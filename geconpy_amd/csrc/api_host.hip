@@ -734,6 +734,36 @@ int dsge_girf_pruned_batched_host(const double* T, const double* R, const double
   return hc.finish();
 }
 
+// (group_of_shock and var_idx are host arrays in the device entry too: they are not staged)
+int dsge_shock_decomposition_batched_host(const double* T, const double* R, const double* eps, const double* x,
+                                          const int32_t* group_of_shock, int n_groups, const int32_t* var_idx, int n_out,
+                                          const double* Z, int z_batched, const int32_t* status, int batch, int m, int k, int p,
+                                          int n_paths, int T_len, int remainder, double* contrib_out, double* obs_out) {
+  int rc = check_shock_decomp(T, R, eps, x, group_of_shock, n_groups, var_idx, n_out, Z, batch, m, k, p, n_paths, T_len, remainder,
+                              contrib_out, obs_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, steps = b * n_paths * T_len, C = (size_t)n_groups + 1 + (remainder ? 1 : 0);
+  const double *dT, *dR, *de, *dx, *dZ;
+  const int32_t* dS;
+  double *dc, *dobs;
+  hc.in(&dT, T, b * m * m);
+  hc.in(&dR, R, b * m * k);
+  hc.in(&de, eps, steps * k);
+  hc.in(&dx, x, steps * m);
+  hc.in(&dZ, Z, (size_t)(z_batched ? batch : 1) * (Z ? p : 0) * m);
+  hc.in(&dS, status, b);
+  hc.out(&dc, contrib_out, steps * n_out * C);
+  hc.out(&dobs, obs_out, steps * (Z ? p : 0) * C);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_shock_decomposition_batched(dT, dR, de, dx, group_of_shock, n_groups, var_idx, n_out, dZ, z_batched, dS, batch, m, k, p,
+                                             n_paths, T_len, remainder, dc, dobs, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

@@ -299,6 +299,7 @@ static int debug_counters(long long** slot, int count, int enable, long long* cy
 int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_dbg, 8, enable, cycles_out); }
 int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
 int dsge_debug_pruned_phases(int enable, long long* cycles_out) { return debug_counters(&g_pruned_dbg, 8, enable, cycles_out); }
+int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out) { return debug_counters(&g_shock_decomp_dbg, 8, enable, cycles_out); }
 int dsge_debug_adjoint_refine(int mode) {
   if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
   g_adj_refine_mode = mode;
@@ -761,6 +762,20 @@ int dsge_girf_pruned_batched(const double* T, const double* R, const double* gyy
                         eps_batched ? (long long)n_paths * n_shock_steps * k : 0, x0_batched ? (long long)n_paths * n : 0,
                         s_batched ? (long long)k * c : 0};
   return pruned_run(p, batch, eps, xf0, xs0, S_imp, status, nullptr, nullptr, nullptr, girf_out, (hipStream_t)stream);
+}
+
+// ---- historical shock decomposition (dsge_shock_decomp.hpp): one launch on the caller's stream, no scratch -------------------------
+int dsge_shock_decomposition_batched(const double* T, const double* R, const double* eps, const double* x,
+                                     const int32_t* group_of_shock, int n_groups, const int32_t* var_idx, int n_out, const double* Z,
+                                     int z_batched, const int32_t* status, int batch, int m, int k, int p, int n_paths, int T_len,
+                                     int remainder, double* contrib_out, double* obs_out, void* stream) {
+  int rc = check_shock_decomp(T, R, eps, x, group_of_shock, n_groups, var_idx, n_out, Z, batch, m, k, p, n_paths, T_len, remainder,
+                              contrib_out, obs_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0) return DSGE_SUCCESS;
+  return launch_shock_decomp(T, R, eps, x, group_of_shock, n_groups, var_idx, n_out, Z, z_batched, status, batch, m, k, Z ? p : 0,
+                             n_paths, T_len, remainder, contrib_out, obs_out, (hipStream_t)stream);
 }
 
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

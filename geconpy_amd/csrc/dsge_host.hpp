@@ -307,6 +307,12 @@ size_t pruned_panel_doubles(int n, int s, int k);
 int launch_pruned(const PrunedProblem& p, int batch, const double* eps, const double* xf0, const double* xs0, const double* imp,
                   const int32_t* status, double* panel, double* x_out, double* xf_out, double* xs_out, double* girf_out,
                   hipStream_t st);
+// launch_shock_decomp.hip (dsge_shock_decomp.hpp): the historical shock decomposition, one workgroup per draw and pack of
+// floor(16 / (n_groups + 1)) paths; grp (k entries) and var (n_out entries) are HOST index lists, already checked
+size_t shock_decomp_lds_bytes(int m, int k, int p, int n_groups);
+int launch_shock_decomp(const double* T, const double* R, const double* eps, const double* x, const int32_t* grp, int n_groups,
+                        const int32_t* var, int n_out, const double* Z, int z_batched, const int32_t* status, int batch, int m, int k,
+                        int p, int n_paths, int T_len, int remainder, double* contrib_out, double* obs_out, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -360,6 +366,7 @@ int launch_second_order(const double* B, const double* C, const double* T, const
 extern int g_adj_refine_mode;          // launch_assemble.hip: 0 = residual rule, 1 = refine every draw, 2 = never (debug)
 extern long long* g_so_dbg;            // launch_second_order.hip: debug phase counters of the second-order filter kernel
 extern long long* g_pruned_dbg;        // launch_pruned.hip: debug phase counters of pruned_propagate_kernel
+extern long long* g_shock_decomp_dbg;  // launch_shock_decomp.hip: debug phase counters of shock_decomp_kernel
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
 extern long long* g_big_dbg;          // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
@@ -556,6 +563,45 @@ inline int check_girf_pruned(const double* T, const double* R, const double* gyy
   if (!S_imp && c != k) return fail(DSGE_ERR_INVALID, "S_imp == NULL means S_imp = I: c must equal k");
   return check_pruned(T, R, gyy, gyu, guu, gss, S, s, eps, batch, n, k, n_paths, n_steps, n_shock_steps, girf_out != nullptr);
 }
+// (p: the rows of Z, ignored without Z)
+inline int check_shock_decomp(const double* T, const double* R, const double* eps, const double* x, const int32_t* grp, int g,
+                              const int32_t* var, int n_out, const double* Z, int batch, int m, int k, int p, int n_paths, int T_len,
+                              int remainder, const double* contrib_out, const double* obs_out) {
+  if (batch < 0 || m < 1 || n_paths < 0 || T_len < 1 || g < 1 || n_out < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (k < 1 || k > m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (!T || !R || !x || (!eps && T_len > 1)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!contrib_out && !obs_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (obs_out && !Z) return fail(DSGE_ERR_INVALID, "obs_out needs Z");
+  if (Z && p < 1) return fail(DSGE_ERR_INVALID, "Z given with p < 1");
+  if (m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: m exceeds DSGE_MAX_N_BIG");
+  if (g > 15) return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: more than 15 groups (group the shocks: one tile holds 16 columns)");
+  if (Z && p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: p exceeds DSGE_MAX_P");
+  if (g > k) return fail(DSGE_ERR_INVALID, "n_groups exceeds k");
+  if (!grp && g != k) return fail(DSGE_ERR_INVALID, "group_of_shock == NULL means one group per shock: n_groups must equal k");
+  if (contrib_out && (n_out < 1 || n_out > m)) return fail(DSGE_ERR_INVALID, "n_out out of range (1..m)");
+  if (contrib_out && !var && n_out != m) return fail(DSGE_ERR_INVALID, "var_idx == NULL means all variables: n_out must equal m");
+  if (grp) {
+    bool used[16] = {};
+    for (int j = 0; j < k; ++j) {
+      if (grp[j] < 0 || grp[j] >= g) return fail(DSGE_ERR_INVALID, "group_of_shock out of range (0..n_groups-1)");
+      used[grp[j]] = true;
+    }
+    for (int c = 0; c < g; ++c)
+      if (!used[c]) return fail(DSGE_ERR_INVALID, "group_of_shock: every group must hold a shock");
+  }
+  if (var && contrib_out) {
+    bool seen[DSGE_MAX_N_BIG] = {};
+    for (int i = 0; i < n_out; ++i) {
+      if (var[i] < 0 || var[i] >= m) return fail(DSGE_ERR_INVALID, "var_idx out of range (0..m-1)");
+      if (seen[var[i]]) return fail(DSGE_ERR_INVALID, "var_idx holds a variable twice");
+      seen[var[i]] = true;
+    }
+  }
+  if (shock_decomp_lds_bytes(m, k, Z ? p : 0, g) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: [T | R] does not fit the LDS (m = 96 takes k <= 32)");
+  return DSGE_SUCCESS;
+}
+
 inline int check_forecast(const double* T, const double* R, const ShockCov& q, const ObsModel& o, const double* a0, int batch, int m,
                           int k, int n_steps, const double* a_out, const double* p_out, const double* y_out, const double* f_out) {
   const int p = o.p;

@@ -278,6 +278,16 @@ class LogpEngine:
         return F.forecast(self.backend, "forecast", T, R, Q, a0, P0=P0, n_steps=n_steps, Z=Z, d=d, Hdiag=Hdiag, q_mode=q_mode,
                           covariances=covariances, status=status, out=out)
 
+    # -- historical shock decomposition (csrc/dsge_shock_decomp.hpp) ------------------------------
+    def shock_decomposition(self, T, R, states, shocks, groups=None, variables=None, Z=None, remainder=True, status=None, out=None):
+        """Historical shock decomposition of the whole batch from device tensors (``dsge_shock_decomposition_batched``; see
+        ``batched.shock_decomposition_batched``), one launch on torch's current stream.  From ``kalman_smoother``: ``states =
+        s["smoothed_states"], shocks = s["smoothed_shocks"]``; from ``simulation_smoother``: ``s["states"], s["shocks"]``.
+        ``groups`` / ``variables`` are host index lists.  ``out``: optional dict with preallocated ``contributions`` /
+        ``observed``.  Returns dict(contributions, observed or None, components); asynchronous."""
+        return F.shock_decomposition(self.backend, "shock_decomposition", T, R, states, shocks, groups=groups, variables=variables,
+                                     Z=Z, remainder=remainder, status=status, out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 13
+#define DSGE_ABI_VERSION 14
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -49,6 +49,7 @@ extern "C" {
 /* ABI 11: dsge_simulate_batched, dsge_irf_batched, dsge_forecast_batched (+ _host) are new; nothing else changed. */
 /* ABI 12: dsge_simulation_smoother_batched (+ _host) is new; nothing else changed. */
 /* ABI 13: dsge_simulate_pruned_batched, dsge_girf_pruned_batched (+ _host) are new; nothing else changed. */
+/* ABI 14: dsge_shock_decomposition_batched (+ _host) is new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -845,6 +846,43 @@ int dsge_girf_pruned_batched_host(const double* T, const double* R, const double
                                   double* girf_out);
 
 /*
+ * HISTORICAL SHOCK DECOMPOSITION per draw (ABI 14; csrc/dsge_shock_decomp.hpp, docs/design/shock_decomposition.md): how much of
+ * every variable's smoothed path each structural shock (or group of shocks) explains -- the last step of the chain filter ->
+ * smoother -> simulation smoother.  T: [batch][m][m], R: [batch][m][k]; all arrays float64 and C-contiguous.
+ *   eps : [batch][n_paths][T_len][k]  the shocks, exactly what dsge_simulation_smoother_batched writes as eps_out; the smoother's
+ *   x   : [batch][n_paths][T_len][m]  the states, exactly its x_out;    [batch][T_len][.] outputs are the n_paths == 1 case
+ *   group_of_shock : HOST int32[k] (passed by value like state_idx of the second-order dynamics): the group 0 .. n_groups-1 of
+ *           every shock, every group used; NULL: every shock its own group, n_groups must equal k
+ *   var_idx : HOST int32[n_out]: the variables whose contributions are written, distinct, any order, each < m; NULL: all m in
+ *           order, n_out must equal m
+ *   Z   : [batch|1][p][m] (z_batched) or NULL: the observation matrix of obs_out (the intercept d is not a component)
+ *   status : [batch], INPUT, may be NULL; a draw with a non-zero status gets NaN in all its outputs and does not affect the others
+ * With g = n_groups, G = g + 1 propagated columns and C = G + (remainder != 0) components, in the order groups 0 .. g-1, initial
+ * condition, remainder:  per draw b and path s,
+ *       X_0[:, c] = 0 for c < g,   X_0[:, g] = x[b,s,0,:]
+ *       X_t = T_b X_{t-1} + R_b E_t,   E_t[j, c] = eps[b,s,t,j] if group_of_shock[j] == c else 0,   t = 1 .. T_len-1
+ *       remainder_t = x[b,s,t,:] - sum_{c = 0 .. g} X_t[:, c]      (summed in ascending c; remainder_0 = 0 exactly)
+ *   contrib_out : [batch][n_paths][T_len][n_out][C],  row i = (X_t[var_idx[i], 0 .. g], remainder_t[var_idx[i]])
+ *   obs_out     : [batch][n_paths][T_len][p][C] = Z_b (component c of step t over all m variables); needs Z
+ *   either may be NULL, not both.  eps[b,s,0,:] (NaN by the smoother's definition) is never read.  With the remainder the C
+ *   components of an element add up to x (to Z x) to rounding; the remainder is what the filter conventions leave between the
+ *   smoothed path and the exact path of the smoothed shocks (docs/design/shock_decomposition.md).
+ * One launch on `stream`, no library scratch, no synchronisation, no atomics: two calls give the same bits.
+ * 1 <= m <= DSGE_MAX_N_BIG, n_groups <= 15 (G is at most the 16 columns of one matrix-core tile: a caller with more shocks groups
+ * them), p <= DSGE_MAX_P, and [T | R] must fit the LDS (m = 96: k <= 32), else DSGE_ERR_TOO_LARGE; a malformed call (bad group
+ * list, duplicate var_idx, missing pointers, T_len < 1) is DSGE_ERR_INVALID; both before any device is touched.  batch == 0 or
+ * n_paths == 0: success, nothing touched.
+ */
+int dsge_shock_decomposition_batched(const double* T, const double* R, const double* eps, const double* x,
+                                     const int32_t* group_of_shock, int n_groups, const int32_t* var_idx, int n_out, const double* Z,
+                                     int z_batched, const int32_t* status, int batch, int m, int k, int p, int n_paths, int T_len,
+                                     int remainder, double* contrib_out, double* obs_out, void* stream);
+int dsge_shock_decomposition_batched_host(const double* T, const double* R, const double* eps, const double* x,
+                                          const int32_t* group_of_shock, int n_groups, const int32_t* var_idx, int n_out,
+                                          const double* Z, int z_batched, const int32_t* status, int batch, int m, int k, int p,
+                                          int n_paths, int T_len, int remainder, double* contrib_out, double* obs_out);
+
+/*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw
  * batch (the per-evaluation hot loop of SURVEY.md section 3A; what
  * DSGEStateSpace._setup_policy_matrices + make_symbolic_graph + the filter compute,
@@ -1071,6 +1109,11 @@ int dsge_debug_second_order_phases(int enable, long long* cycles_out);
  * the steps, in [0] the x_f product, [1] T x_s, [2] the panel product P mon, [3] the wait at the step's barrier, [4] the slab
  * (or the GIRF sums); [5] = kernel total, [6] = number of steps, [7] = set-up; cycles_out: host int64[8] or NULL. */
 int dsge_debug_pruned_phases(int enable, long long* cycles_out);
+
+/* Debug hook: enable != 0 makes shock_decomp_kernel record the shader cycles wavefront 0 of workgroup 0 spends, summed over the
+ * steps, in [0] the loads' issue and the product, [1] the wait for the loads and their LDS stores, [2] the wait at the step's
+ * barrier, [3] the outputs; [4] = kernel total, [5] = number of steps, [6] = set-up and period 0; cycles_out: host int64[8] or NULL. */
+int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out);
 
 /*
  * Timing hook for bench.py: runs `reps` back-to-back launches of the fused pipeline's

@@ -2,6 +2,7 @@
 
     python tools/dynamics_time.py [draws ...]          (default: 256 4096)
     python tools/dynamics_time.py --second-order [draws ...]      the second-order rows alone
+    python tools/dynamics_time.py --decomposition [draws ...]     the shock-decomposition rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -15,6 +16,10 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     LogpEngine.simulate on the same T, R and shocks in the same run -- the yardstick of the ratio is the K-extent of a step's
     products, 48 against 48 + 48 + 336 -- then LogpEngine.girf_pruned (7 unit impulses over 16 baseline paths) and the host numpy
     loop of tests/pruned_dynamics_reference.py (256 draws timed once, scaled).
+  * --decomposition (csrc/dsge_shock_decomp.hpp), m = 40, k = 7, identity groups, all 40 variables, T_len = 200: the median of five
+    timings of >= 1 s each of LogpEngine.shock_decomposition (with and without the remainder), of the composed route that was the
+    only one before it -- LogpEngine.simulate with k + 1 paths on an expanded shock array, the expansion by torch timed apart; it
+    still lacks the transpose and the remainder -- and of a plain fill of the output array.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -94,11 +99,64 @@ def second_order_rows(eng, sizes):
         print(f"draws={nb:5d} host numpy loop (scaled): simulate_pruned {t_cpu * nb:9.1f} ms ({t_cpu * nb / t_sim:7.0f}x)")
 
 
+def decomposition_rows(eng, sizes, T_len=200, repeats=5):
+    b = wl.sw_shaped_batch(64)
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k = 40, 7
+    rng = np.random.default_rng(0)
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    print(f"shock decomposition m={m} k={k}, identity groups, all variables, T_len={T_len}; medians of {repeats} timings of >= 1 s")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        T, R = eng.to_device(np.tile(b["T_star"], (rep, 1, 1))[:nb]), eng.to_device(np.tile(R64, (rep, 1, 1))[:nb])
+        e = eng.to_device(rng.standard_normal((nb, T_len, k)) * 0.01)
+        e[:, 0] = float("nan")
+        x0 = eng.to_device(rng.standard_normal((nb, m)) * 0.05)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        # the composed route: path j < k carries shock j alone, path k the initial condition; steps 1 .. T_len-1
+        ex, x0e, paths = torch.zeros(nb, k + 1, T_len - 1, k, dtype=torch.float64, device=eng.device), mk(nb, k + 1, m).zero_(), mk(nb, k + 1, T_len - 1, m)
+        x0e[:, k] = x0
+
+        def expand():
+            ex[:, :k] = torch.diag_embed(e[:, 1:]).permute(0, 2, 1, 3)
+
+        expand()
+        eng.simulate(T, R, ex, x0=x0e, out=paths)
+        x = torch.cat([x0[:, None], paths.sum(dim=1)], dim=1).contiguous()  # a path with a rounding-size remainder
+        full, bare = dict(contributions=mk(nb, T_len, m, k + 2)), dict(contributions=mk(nb, T_len, m, k + 1))
+        eng.shock_decomposition(T, R, x, e, out=full)
+        eng.shock_decomposition(T, R, x, e, remainder=False, out=bare)
+        diff = (bare["contributions"][:, 1:] - paths.permute(0, 2, 3, 1)).abs().max().item()
+        rem = full["contributions"][..., -1].abs().max().item()
+        print(f"draws={nb:5d} entry against the composed route: max difference {diff:.1e}; remainder {rem:.1e} (max|x| {x.abs().max().item():.2f})")
+        t_full = med(lambda: eng.shock_decomposition(T, R, x, e, out=full))
+        t_bare = med(lambda: eng.shock_decomposition(T, R, x, e, remainder=False, out=bare))
+        t_sim = med(lambda: eng.simulate(T, R, ex, x0=x0e, out=paths))
+        t_exp = med(expand)
+        t_fill = med(lambda: full["contributions"].fill_(1.0))
+        gb = full["contributions"].numel() * 8e-9
+        print(f"draws={nb:5d} shock_decomposition: {t_full:8.3f} ms = {gb / t_full:5.2f} TB/s written | without the remainder {t_bare:8.3f} ms | "
+              f"composed route: simulate, {k + 1} paths {t_sim:8.3f} ms + expansion {t_exp:8.3f} ms | fill of the output {t_fill:8.3f} ms | "
+              f"entry / simulate {t_full / t_sim:5.2f}, entry / fill {t_full / t_fill:5.2f}")
+        import ctypes
+
+        lib, cyc = _lib.load(), (ctypes.c_longlong * 8)()  # per-phase shader cycles of wavefront 0 of workgroup 0, one call
+        _lib.check(lib.dsge_debug_shock_decomp_phases(1, None))
+        eng.shock_decomposition(T, R, x, e, out=full)
+        _lib.check(lib.dsge_debug_shock_decomp_phases(0, ctypes.addressof(cyc)))
+        names = ("loads' issue + product", "wait for the loads + LDS stores", "barrier wait", "outputs")
+        print(f"draws={nb:5d} phases of one workgroup, cycles per step: "
+              + ", ".join(f"{nm} {cyc[i] / max(cyc[5], 1):.0f}" for i, nm in enumerate(names))
+              + f" | total {cyc[4]}, {cyc[5]} steps, set-up and period 0 {cyc[6]}")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--second-order"]
+    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
+    if "--decomposition" in sys.argv:
+        return decomposition_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
