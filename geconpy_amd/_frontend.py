@@ -488,6 +488,111 @@ def shock_decomposition(b, name, T, R, states, shocks, *, groups, variables, Z, 
     return res
 
 
+def condition_pattern(conditions, nb, n_paths, p, n_steps):
+    """``conditions``: (h_c, p), (batch, h_c, p) or (batch, n_paths, h_c, p), NaN = free, the same NaN pattern for every draw and
+    path -- or the triple ``(cond_t, cond_j, values)`` with ``values`` (n_cond,), (batch, n_cond) or (batch, n_paths, n_cond), which
+    needs no look at the values (device tensors: no synchronisation).  -> (cond_t int32, cond_j int32, values (..., n_cond))."""
+    if isinstance(conditions, tuple):
+        if len(conditions) != 3:
+            raise ValueError("conditions as a tuple must be (cond_t, cond_j, values)")
+        ct, cj = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in conditions[:2])
+        vals = conditions[2]
+        if len(ct) != len(cj) or vals.shape[-1] != len(ct) or vals.ndim not in (1, 2, 3):
+            raise ValueError(f"conditions: cond_t, cond_j and the last axis of values must have one length; got {len(ct)}, {len(cj)}, "
+                             f"{tuple(vals.shape)}")
+        return ct, cj, vals
+    c = conditions
+    if c.ndim not in (2, 3, 4) or c.shape[-1] != p:
+        raise ValueError(f"conditions must be (h_c, {p}), (batch, h_c, {p}) or (batch, n_paths, h_c, {p}); got {tuple(c.shape)}")
+    if tuple(c.shape[:-2]) not in ((), (nb,), (nb, n_paths)):
+        raise ValueError(f"conditions: leading axes must be (), ({nb},) or ({nb}, {n_paths}); got {tuple(c.shape[:-2])}")
+    h_c = c.shape[-2]
+    if h_c > n_steps:
+        raise ValueError(f"conditions cover {h_c} periods, n_steps is {n_steps}")
+    host = np.asarray(c.cpu() if hasattr(c, "cpu") else c)
+    free = np.isnan(host).reshape(-1, h_c, p)
+    if (free != free[0]).any():
+        raise ValueError("conditions: the NaN pattern (which series is conditioned in which period) must be the same for every draw and path")
+    ct, cj = (np.ascontiguousarray(v, dtype=np.int32) for v in np.nonzero(~free[0]))  # row-major: ascending in (t, j)
+    return ct, cj, c[..., ct.tolist(), cj.tolist()]
+
+
+def conditional_forecast(b, name, T, R, Q, x0, conditions, n_steps, *, Z, d, eps, n_paths, free_shocks, q_mode, status, rank_tol,
+                         out=None):
+    T, R, nb, m, k = _TR(b, T, R, name)
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    if Z is None:
+        raise ValueError(f"{name}: Z is required (the conditions are on d + Z x)")
+    Z = b.inp(Z)
+    if Z.ndim not in (2, 3) or Z.shape[-1] != m or Z.shape[-2] < 1:
+        raise ValueError(f"Z must be (p, {m}) or (batch, p, {m}); got {tuple(Z.shape)}")
+    p = Z.shape[-2]
+    obs = obs_args(b, Z, d, None, nb, p, m)
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError("n_steps must be >= 1")
+    # the number of paths: the shocks say it, else n_paths, else a per-path x0 or conditions, else one
+    eps, eb, n_shock = b.inp(eps), 0, 0
+    x0 = b.inp(x0)
+    if x0.ndim not in (1, 2, 3) or x0.shape[-1] != m:
+        raise ValueError(f"x0 must be ({m},), (batch, {m}) or (batch | 1, n_paths | 1, {m}); got {tuple(x0.shape)}")
+    guess = [eps.shape[-3]] if eps is not None and eps.ndim in (3, 4) else []
+    guess += [int(n_paths)] if n_paths is not None else []
+    guess += [x0.shape[1]] if x0.ndim == 3 and x0.shape[1] != 1 else []
+    guess += [conditions.shape[1]] if not isinstance(conditions, tuple) and conditions.ndim == 4 else []
+    guess += [conditions[2].shape[1]] if isinstance(conditions, tuple) and len(conditions) == 3 and conditions[2].ndim == 3 else []
+    n_paths = guess[0] if guess else 1
+    if n_paths < 1 or any(g != n_paths for g in guess):
+        raise ValueError(f"n_paths must be >= 1 and eps, n_paths, x0 and conditions must agree on it; got {guess}")
+    if eps is not None:
+        if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+            raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {tuple(eps.shape)}")
+        n_shock = eps.shape[-2]
+        eb = shared_or_batched(eps, nb, (n_paths, n_shock, k), "eps")
+        if n_shock > n_steps:
+            raise ValueError(f"n_steps = {n_steps} is less than the {n_shock} shock steps of eps")
+    if x0.ndim == 3:
+        if x0.shape[0] not in (1, nb) or x0.shape[1] not in (1, n_paths):
+            raise ValueError(f"x0 must be (batch | 1, n_paths | 1, {m}); got {tuple(x0.shape)}")
+        xb, xpth = int(x0.shape[0] == nb), int(x0.shape[1] == n_paths)
+    else:
+        xb, xpth = (shared_or_batched(x0, nb, (m,), "x0"), 0)
+    ct, cj, vals = condition_pattern(conditions if isinstance(conditions, tuple) else (b.inp(conditions) if not b.host else
+                                     np.asarray(conditions, dtype=np.float64)), nb, n_paths, p, n_steps)
+    n_cond = len(ct)
+    vals = b.inp(vals if b.host else vals.contiguous())
+    lead = tuple(vals.shape[:-1])
+    if lead not in ((), (nb,), (nb, n_paths)):
+        raise ValueError(f"the values of the conditions must be (n_cond,), ({nb}, n_cond) or ({nb}, {n_paths}, n_cond); got {tuple(vals.shape)}")
+    cvb, cvp = int(len(lead) >= 1), int(len(lead) == 2)
+    if free_shocks is None:
+        free = None
+    else:
+        fs = np.asarray(list(free_shocks))
+        if fs.dtype == bool:
+            if fs.shape != (k,):
+                raise ValueError(f"free_shocks as a mask must have {k} entries")
+            free = np.ascontiguousarray(fs, dtype=np.int32)
+        else:
+            fs = fs.astype(np.int64).reshape(-1)
+            if ((fs < 0) | (fs >= k)).any():
+                raise ValueError(f"free_shocks must be within 0 .. {k - 1}; got {fs.tolist()}")
+            free = np.zeros(k, dtype=np.int32)
+            free[fs] = 1
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    res = dict(x=_out(b, out.get("x"), (nb, n_paths, n_steps, m)), shocks=_out(b, out.get("shocks"), (nb, n_paths, n_steps, k)),
+               observed=_out(b, out.get("observed"), (nb, n_paths, n_steps, p)), status=st)
+    call(b, "dsge_conditional_forecast_batched", T=T, R=R, Q=Q, q_mode=code, Z=obs["Z"], z_batched=obs["z_batched"], d=obs["d"],
+         d_batched=obs["d_batched"], x0=x0, x0_batched=xb, x0_paths=xpth, eps=eps, eps_batched=eb,
+         cond_t=ct.ctypes.data if n_cond else None, cond_j=cj.ctypes.data if n_cond else None, n_cond=n_cond,
+         cond_val=vals if n_cond else None, cv_batched=cvb, cv_paths=cvp, free_shock=None if free is None else free.ctypes.data,
+         status_io=st, batch=nb, m=m, k=k, p=p, n_paths=n_paths, n_steps=n_steps, n_shock_steps=n_shock,
+         rank_tol=0.0 if rank_tol is None else float(rank_tol), x_out=res["x"], eps_out=res["shocks"], obs_out=res["observed"])
+    return res
+
+
 # ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
 SOLUTION = ("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
 

@@ -524,6 +524,28 @@ def shock_decomposition_batched(T, R, states, shocks, groups=None, variables=Non
                                  remainder=remainder, status=status)
 
 
+def conditional_forecast_batched(T, R, Q, x0, conditions, n_steps, Z=None, d=None, eps=None, n_paths=None, free_shocks=None,
+                                 q_mode=None, status=None, rank_tol=0.0):
+    """Conditional forecasts for a batch of draws: paths ``x[t] = T x[t-1] + R e[t]``, ``t = 0 .. n_steps-1``, from the known state
+    ``x[-1] = x0`` that are forced through given future values of some observables ``d + Z x`` -- the hard conditions of Waggoner
+    and Zha (1999); include/dsge_hip.h, ``dsge_conditional_forecast_batched``.  ``conditions``: (h_c, p), (batch, h_c, p) or
+    (batch, n_paths, h_c, p) with NaN = free (the NaN pattern must be the same for all draws and paths, else ``ValueError``), or the
+    triple ``(cond_t, cond_j, values)``.  ``x0``: (m,), (batch, m) or (batch | 1, n_paths | 1, m).  ``eps``: the baseline shocks,
+    (n_paths, n_shock_steps, k) or (batch, n_paths, n_shock_steps, k), None = zeros.  ``free_shocks``: the indices (or a boolean
+    mask) of the shocks that may move, default all; the others keep their baseline values bit for bit.  The free shocks of the
+    periods up to the last conditioned one get the correction of minimum ``Q_FF^-1`` norm that meets the conditions:
+    (1) with all shocks free and ``eps ~ N(0, Q)`` the paths are exact draws from the distribution conditional on the scenario, and
+    with ``eps=None`` the path is its mean (the smoothed mean of a Kalman filter + smoother from the known ``x0`` with the
+    conditions as noiseless observations); (2) with as many conditioned series in EVERY period up to the last conditioned one as
+    there are free shocks the system is square and the answer does not depend on ``Q`` -- the controlled-shock conditional forecast
+    of Dynare; (3) with a full ``Q`` and a proper subset of free shocks the norm uses the block ``Q_FF`` and no distribution is
+    claimed.  A draw whose conditions cannot be met (a Cholesky pivot of ``G <= rank_tol max diag G``, default 1e-10) gets
+    ``ST_COND_SINGULAR`` (512) in ``status`` and NaN everywhere; so does a draw with a non-zero incoming ``status``.
+    Returns dict(x (batch, n_paths, n_steps, m), shocks (.., k): the shocks that generate ``x``, observed (.., p), status)."""
+    return F.conditional_forecast(HOST, "conditional_forecast_batched", T, R, Q, x0, conditions, n_steps, Z=Z, d=d, eps=eps,
+                                  n_paths=n_paths, free_shocks=free_shocks, q_mode=q_mode, status=status, rank_tol=rank_tol)
+
+
 def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None):
     """Impulse responses ``irf[b, j, h] = T_b^h R_b S[:, j]`` for a batch of draws -- ``impulse_response_function``
     (gEconpy/model/simulate.py:201-317; its loop over shocks :300-311 calls ``_simulate_linear_system`` :171-182 once per

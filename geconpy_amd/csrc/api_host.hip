@@ -764,6 +764,47 @@ int dsge_shock_decomposition_batched_host(const double* T, const double* R, cons
   return hc.finish();
 }
 
+// (cond_t, cond_j and free_shock are host arrays in the device entry too: they are not staged)
+int dsge_conditional_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                           int z_batched, const double* d, int d_batched, const double* x0, int x0_batched,
+                                           int x0_paths, const double* eps, int eps_batched, const int32_t* cond_t,
+                                           const int32_t* cond_j, int n_cond, const double* cond_val, int cv_batched, int cv_paths,
+                                           const int32_t* free_shock, int32_t* status_io, int batch, int m, int k, int p,
+                                           int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                           double* eps_out, double* obs_out) {
+  CondFcProblem c{batch, m, k, p, n_paths, n_steps, n_shock_steps, n_cond, x0_batched, x0_paths, eps_batched, cv_batched, cv_paths,
+                  cond_t, cond_j, free_shock, rank_tol};
+  const ShockCov q{Q, q_mode};
+  int rc = check_conditional_forecast(c, T, R, q, Z, x0, eps, cond_val, x_out, eps_out, obs_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, ns = (size_t)n_steps;
+  ShockCov dq;
+  const double *dT, *dR, *dZ, *dd, *dx0, *de, *dcv;
+  double *dx, *deo, *dobs;
+  int32_t* dS;
+  hc.in(&dT, T, b * m * m);
+  hc.in(&dR, R, b * m * k);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dZ, Z, (z_batched ? b : 1) * p * m);
+  hc.in(&dd, d, (d_batched ? b : 1) * p);
+  hc.in(&dx0, x0, (x0_batched ? b : 1) * (x0_paths ? np : 1) * m);
+  hc.in(&de, eps, (eps_batched ? b : 1) * np * n_shock_steps * k);
+  hc.in(&dcv, n_cond > 0 ? cond_val : nullptr, (cv_batched ? b : 1) * (cv_paths ? np : 1) * n_cond);
+  hc.io(&dS, status_io, b);
+  hc.out(&dx, x_out, b * np * ns * m);
+  hc.out(&deo, eps_out, b * np * ns * k);
+  hc.out(&dobs, obs_out, b * np * ns * p);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_conditional_forecast_batched(dT, dR, dq.Q, dq.mode, dZ, z_batched, dd, d_batched, dx0, x0_batched, x0_paths, de,
+                                              eps_batched, cond_t, cond_j, n_cond, dcv, cv_batched, cv_paths, free_shock, dS, batch,
+                                              m, k, p, n_paths, n_steps, n_shock_steps, rank_tol, dx, deo, dobs, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

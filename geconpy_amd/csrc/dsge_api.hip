@@ -300,6 +300,7 @@ int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_count
 int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
 int dsge_debug_pruned_phases(int enable, long long* cycles_out) { return debug_counters(&g_pruned_dbg, 8, enable, cycles_out); }
 int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out) { return debug_counters(&g_shock_decomp_dbg, 8, enable, cycles_out); }
+int dsge_debug_condfc_phases(int enable, long long* cycles_out) { return debug_counters(&g_condfc_dbg, 8, enable, cycles_out); }
 int dsge_debug_adjoint_refine(int mode) {
   if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
   g_adj_refine_mode = mode;
@@ -776,6 +777,37 @@ int dsge_shock_decomposition_batched(const double* T, const double* R, const dou
   if (batch == 0 || n_paths == 0) return DSGE_SUCCESS;
   return launch_shock_decomp(T, R, eps, x, group_of_shock, n_groups, var_idx, n_out, Z, z_batched, status, batch, m, k, Z ? p : 0,
                              n_paths, T_len, remainder, contrib_out, obs_out, (hipStream_t)stream);
+}
+
+// ---- conditional forecast (dsge_condfc.hpp): two launches on the caller's stream; the scratch holds per-draw setup data only ----
+int dsge_conditional_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* x0, int x0_batched, int x0_paths,
+                                      const double* eps, int eps_batched, const int32_t* cond_t, const int32_t* cond_j, int n_cond,
+                                      const double* cond_val, int cv_batched, int cv_paths, const int32_t* free_shock,
+                                      int32_t* status_io, int batch, int m, int k, int p, int n_paths, int n_steps,
+                                      int n_shock_steps, double rank_tol, double* x_out, double* eps_out, double* obs_out,
+                                      void* stream) {
+  CondFcProblem c{batch, m, k, p, n_paths, n_steps, n_shock_steps, n_cond, x0_batched, x0_paths, eps_batched, cv_batched, cv_paths,
+                  cond_t, cond_j, free_shock, rank_tol};
+  const ShockCov q{Q, q_mode};
+  int rc = check_conditional_forecast(c, T, R, q, Z, x0, eps, cond_val, x_out, eps_out, obs_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  double *chol = nullptr, *psi = nullptr, *psiq = nullptr;
+  int32_t* flag = nullptr;
+  if (n_cond > 0) {
+    const size_t b = (size_t)batch, lag = (size_t)(c.t_max + 1) * p * k;
+    ScratchLayout lay;
+    lay.add(&chol, b * n_cond * (n_cond + 1) / 2);
+    lay.add(&psi, b * lag);
+    lay.add(&psiq, b * lag);
+    lay.add(&flag, b);
+    if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  }
+  return launch_condfc(c, T, R, q, Z, z_batched, d, d_batched, x0, eps, cond_val, status_io, chol, psi, psiq, flag, x_out, eps_out,
+                       obs_out, st);
 }
 
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

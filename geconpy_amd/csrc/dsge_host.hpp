@@ -313,6 +313,21 @@ size_t shock_decomp_lds_bytes(int m, int k, int p, int n_groups);
 int launch_shock_decomp(const double* T, const double* R, const double* eps, const double* x, const int32_t* grp, int n_groups,
                         const int32_t* var, int n_out, const double* Z, int z_batched, const int32_t* status, int batch, int m, int k,
                         int p, int n_paths, int T_len, int remainder, double* contrib_out, double* obs_out, hipStream_t st);
+// launch_condfc.hip (dsge_condfc.hpp): the conditional forecast, a setup workgroup per draw, then one workgroup per draw and
+// group of 16 paths.  The sizes, flags and HOST index lists of one call; check_conditional_forecast fills t_max and n_free
+struct CondFcProblem {
+  int batch, m, k, p, n_paths, n_steps, n_shock_steps, n_cond;
+  int x0_batched, x0_paths, eps_batched, cv_batched, cv_paths;
+  const int32_t *cond_t, *cond_j, *free_shock;  // [n_cond], [n_cond], [k] or null (all free)
+  double rank_tol;
+  int t_max = -1, n_free = 0;
+};
+// bytes of the larger of the two kernels' LDS images; lags = t_max + 1
+size_t condfc_lds_bytes(int m, int k, int p, int n_cond, int lags, int n_free);
+int launch_condfc(const CondFcProblem& c, const double* T, const double* R, const ShockCov& q, const double* Z, int z_batched,
+                  const double* d, int d_batched, const double* x0, const double* eps, const double* cond_val, int32_t* status,
+                  double* chol, double* psi, double* psiq, int32_t* flag, double* x_out, double* eps_out, double* obs_out,
+                  hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -367,6 +382,7 @@ extern int g_adj_refine_mode;          // launch_assemble.hip: 0 = residual rule
 extern long long* g_so_dbg;            // launch_second_order.hip: debug phase counters of the second-order filter kernel
 extern long long* g_pruned_dbg;        // launch_pruned.hip: debug phase counters of pruned_propagate_kernel
 extern long long* g_shock_decomp_dbg;  // launch_shock_decomp.hip: debug phase counters of shock_decomp_kernel
+extern long long* g_condfc_dbg;        // launch_condfc.hip: debug phase counters of the two conditional-forecast kernels
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
 extern long long* g_big_dbg;          // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
@@ -599,6 +615,38 @@ inline int check_shock_decomp(const double* T, const double* R, const double* ep
   }
   if (shock_decomp_lds_bytes(m, k, Z ? p : 0, g) > LDS_LIMIT)
     return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: [T | R] does not fit the LDS (m = 96 takes k <= 32)");
+  return DSGE_SUCCESS;
+}
+
+// the conditional forecast: every refusal, before any device is touched; fills c.t_max and c.n_free
+inline int check_conditional_forecast(CondFcProblem& c, const double* T, const double* R, const ShockCov& q, const double* Z,
+                                      const double* x0, const double* eps, const double* cond_val, const double* x_out,
+                                      const double* eps_out, const double* obs_out) {
+  if (c.batch < 0 || c.m < 1 || c.p < 1 || c.n_cond < 0 || c.n_shock_steps < 0) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (c.n_steps < 1 || c.n_paths < 1) return fail(DSGE_ERR_INVALID, "conditional forecast: n_steps and n_paths must be >= 1");
+  if (c.k < 1 || c.k > c.m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (eps && c.n_shock_steps > c.n_steps) return fail(DSGE_ERR_INVALID, "n_shock_steps > n_steps");
+  if (q.mode < DSGE_Q_DIAG_SHARED || q.mode > DSGE_Q_FULL_BATCHED) return fail(DSGE_ERR_INVALID, "q_mode out of range");
+  if (!T || !R || !q.Q || !Z || !x0) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (c.n_cond > 0 && (!c.cond_t || !c.cond_j || !cond_val)) return fail(DSGE_ERR_INVALID, "null pointer (conditions)");
+  if (!x_out && !eps_out && !obs_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (c.m > DSGE_MAX_N_BIG) return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: m exceeds DSGE_MAX_N_BIG");
+  if (c.p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: p exceeds DSGE_MAX_P");
+  if (c.n_cond > 64) return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: more than 64 conditions");
+  c.t_max = -1;
+  for (int i = 0; i < c.n_cond; ++i) {
+    const int t = c.cond_t[i], j = c.cond_j[i];
+    if (t < 0 || t >= c.n_steps) return fail(DSGE_ERR_INVALID, "cond_t out of range (0..n_steps-1)");
+    if (j < 0 || j >= c.p) return fail(DSGE_ERR_INVALID, "cond_j out of range (0..p-1)");
+    if (i > 0 && (t < c.cond_t[i - 1] || (t == c.cond_t[i - 1] && j <= c.cond_j[i - 1])))
+      return fail(DSGE_ERR_INVALID, "the conditions must be strictly ascending in (t, j)");
+    c.t_max = t;
+  }
+  c.n_free = 0;
+  for (int j = 0; j < c.k; ++j) c.n_free += !c.free_shock || c.free_shock[j] != 0;
+  if (c.n_cond > 0 && c.n_free == 0) return fail(DSGE_ERR_INVALID, "conditional forecast: conditions but no free shock");
+  if (condfc_lds_bytes(c.m, c.k, c.p, c.n_cond, c.t_max + 1, c.n_free) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: the LDS image exceeds 160 KB (docs/design/conditional_forecast.md)");
   return DSGE_SUCCESS;
 }
 

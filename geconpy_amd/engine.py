@@ -288,6 +288,18 @@ class LogpEngine:
         return F.shock_decomposition(self.backend, "shock_decomposition", T, R, states, shocks, groups=groups, variables=variables,
                                      Z=Z, remainder=remainder, status=status, out=out)
 
+    # -- conditional forecast (csrc/dsge_condfc.hpp) ---------------------------------------------
+    def conditional_forecast(self, T, R, Q, x0, conditions, n_steps, Z=None, d=None, eps=None, n_paths=None, free_shocks=None,
+                             q_mode=None, status=None, rank_tol=0.0, out=None):
+        """Conditional forecasts of the whole batch from device tensors (``dsge_conditional_forecast_batched``; see
+        ``batched.conditional_forecast_batched``), on torch's current stream.  ``conditions`` as a tensor with NaN = free is read
+        back once to find the pattern (a synchronisation); the triple ``(cond_t, cond_j, values)`` with host index lists and a
+        device tensor of values is asynchronous.  ``status`` (device int32) is updated in place.  ``out``: optional dict with
+        preallocated ``x`` / ``shocks`` / ``observed``.  Returns dict(x, shocks, observed, status)."""
+        return F.conditional_forecast(self.backend, "conditional_forecast", T, R, Q, x0, conditions, n_steps, Z=Z, d=d, eps=eps,
+                                      n_paths=n_paths, free_shocks=free_shocks, q_mode=q_mode, status=status, rank_tol=rank_tol,
+                                      out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

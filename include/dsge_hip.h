@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 14
+#define DSGE_ABI_VERSION 15
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -50,6 +50,7 @@ extern "C" {
 /* ABI 12: dsge_simulation_smoother_batched (+ _host) is new; nothing else changed. */
 /* ABI 13: dsge_simulate_pruned_batched, dsge_girf_pruned_batched (+ _host) are new; nothing else changed. */
 /* ABI 14: dsge_shock_decomposition_batched (+ _host) is new; nothing else changed. */
+/* ABI 15: dsge_conditional_forecast_batched (+ _host) and the status bit DSGE_ST_COND_SINGULAR are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -82,6 +83,7 @@ extern "C" {
 #define DSGE_ST_GRAD_UNSUPPORTED 64 /* gradient path: dense design matrix / reduced model exceeds the tile */
 #define DSGE_ST_SECOND_ORDER_UNSUPPORTED 128 /* second-order path: input violates the declared model structure */
 #define DSGE_ST_SMOOTHER_SINGULAR 256 /* smoother: sym(U' P_pred U) not positive definite at some step (jitter_P = 0 only) */
+#define DSGE_ST_COND_SINGULAR 512 /* conditional forecast: the conditions cannot be met by the free shocks (G singular) */
 
 /* covariance layouts for the Q argument */
 #define DSGE_Q_DIAG_SHARED 0    /* Q = diag(q), q: [k]            */
@@ -883,6 +885,63 @@ int dsge_shock_decomposition_batched_host(const double* T, const double* R, cons
                                           int n_paths, int T_len, int remainder, double* contrib_out, double* obs_out);
 
 /*
+ * CONDITIONAL FORECAST per draw (ABI 15; csrc/dsge_condfc.hpp, docs/design/conditional_forecast.md): a forecast from a known
+ * state that is forced through given future values of some observables -- the hard conditions of Waggoner and Zha (1999).  Time
+ * runs as in dsge_simulate_batched with x0 given:  x[t] = T x[t-1] + R e[t], t = 0 .. n_steps-1, x[-1] = x0;  yhat[t] = d + Z x[t].
+ * T: [batch][m][m], R: [batch][m][k], Q in the layout q_mode (DSGE_Q_*); all arrays float64 and C-contiguous.
+ *   Z   : [batch|1][p][m] (z_batched), required;   d : [batch|1][p] (d_batched) or NULL (zero)
+ *   x0  : [batch|1][n_paths|1][m] (x0_batched, x0_paths): the origin state
+ *   eps : [batch|1][n_paths][n_shock_steps][k] (eps_batched) or NULL: the baseline shocks e+; NULL means zeros (n_shock_steps is
+ *         then ignored); baseline steps at or beyond n_shock_steps count as zero
+ *   cond_t, cond_j : HOST int32[n_cond] (passed by value like var_idx of the shock decomposition): the conditions
+ *         d[cond_j[c]] + Z[cond_j[c], :] x[cond_t[c]] = cond_val[.., c], strictly ascending in (t, j); one pattern for all draws
+ *         and paths.  n_cond == 0 is the unconditional path.
+ *   cond_val : [batch|1][n_paths|1][n_cond] (cv_batched, cv_paths)
+ *   free_shock : HOST int32[k], non-zero = the shock may move; NULL: all shocks are free.  The other shocks keep their baseline
+ *         values, bit for bit.
+ *   status_io : [batch] in/out, may be NULL; a draw with a non-zero incoming word gets NaN in all its outputs
+ * With t_max = max cond_t, F the free shocks, Psi_l = Z T^l R, W[c, (s, f)] = Psi_{cond_t[c] - s}[cond_j[c], f] (s <= cond_t[c],
+ * f in F; zero otherwise), x+ the path of the baseline and r_c = cond_val_c - d[cond_j[c]] - Z[cond_j[c], :] x+[cond_t[c]]:
+ *       G = W (I (x) Q_FF) W' = L L',   lambda = G^-1 r,   Delta = (I (x) Q_FF) W' lambda,   e = e+ + Delta
+ * -- the correction of the free shocks in periods 0 .. t_max of minimum Q_FF^-1 norm.  (1) With all shocks free and e+ ~ N(0, Q)
+ * the paths are exact draws from the distribution conditional on the scenario; with e+ = 0 the path is its mean (the smoothed
+ * mean of a Kalman filter and smoother run from the known x0 with the conditions as noiseless observations).  (2) With |F|
+ * conditioned series in each of the periods 0 .. t_max and |F| free shocks W is square and Delta does not depend on Q: the
+ * controlled-shock conditional forecast.  (3) With a full Q and a proper subset F the norm uses the block Q_FF (NOT the
+ * conditional covariance of the free shocks given the others); no distribution is claimed for that case.  Q must be symmetric.
+ *   x_out   : [batch][n_paths][n_steps][m]
+ *   eps_out : [batch][n_paths][n_steps][k]  the shocks that generate x_out (dsge_simulate_batched on them reproduces it), zero past
+ *             the last shock that can be non-zero
+ *   obs_out : [batch][n_paths][n_steps][p] = d + Z x
+ *   any may be NULL, not all.
+ * A draw is singular when a Cholesky pivot of G is <= rank_tol max_c G[c, c] (rank_tol <= 0: 1e-10) -- more conditioned series in
+ * period 0 than free shocks, free shocks that do not move the conditioned series: status |= DSGE_ST_COND_SINGULAR, NaN in every
+ * output of the draw, the other draws untouched.
+ * One call on `stream`, no host synchronisation, no atomics: two calls give the same bits.  Library scratch holds per-draw data
+ * only (L, Psi_l and Psi_l Q_FF for l <= t_max).  DSGE_ERR_TOO_LARGE: m > DSGE_MAX_N_BIG, p > DSGE_MAX_P, n_cond > 64, or an LDS image
+ * beyond 160 KB, in doubles (ld = the smallest value == 2 (mod 32) that holds 4 ceil(m/4) + 4 ceil(k/4), m16 = 16 ceil(m/16)):
+ *       (m16 + 32) ld + p m + 16 + 17 n_cond + max(n_cond (n_cond + 1) / 2, 16 (t_max + 1) |F|)
+ * of at most 20 480: this carries m <= 64 with k <= 16 and n_cond = 64 with (t_max + 1) |F| <= 256 together, and m = 96 with k <= 8
+ * while 96 p + 17 n_cond + max(.) <= 3 824 (p = 7, n_cond = 36: (t_max + 1) |F| <= 158).  DSGE_ERR_INVALID: unsorted or duplicate pairs,
+ * cond_t >= n_steps, cond_j >= p, n_cond > 0 with no free shock, missing pointers, n_steps < 1 or n_paths < 1, k outside 1 .. m.
+ * All refusals happen before any device is touched.  batch == 0: success, nothing touched.
+ */
+int dsge_conditional_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* x0, int x0_batched, int x0_paths,
+                                      const double* eps, int eps_batched, const int32_t* cond_t, const int32_t* cond_j, int n_cond,
+                                      const double* cond_val, int cv_batched, int cv_paths, const int32_t* free_shock,
+                                      int32_t* status_io, int batch, int m, int k, int p, int n_paths, int n_steps,
+                                      int n_shock_steps, double rank_tol, double* x_out, double* eps_out, double* obs_out,
+                                      void* stream);
+int dsge_conditional_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                           int z_batched, const double* d, int d_batched, const double* x0, int x0_batched,
+                                           int x0_paths, const double* eps, int eps_batched, const int32_t* cond_t,
+                                           const int32_t* cond_j, int n_cond, const double* cond_val, int cv_batched, int cv_paths,
+                                           const int32_t* free_shock, int32_t* status_io, int batch, int m, int k, int p,
+                                           int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                           double* eps_out, double* obs_out);
+
+/*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw
  * batch (the per-evaluation hot loop of SURVEY.md section 3A; what
  * DSGEStateSpace._setup_policy_matrices + make_symbolic_graph + the filter compute,
@@ -1114,6 +1173,11 @@ int dsge_debug_pruned_phases(int enable, long long* cycles_out);
  * steps, in [0] the loads' issue and the product, [1] the wait for the loads and their LDS stores, [2] the wait at the step's
  * barrier, [3] the outputs; [4] = kernel total, [5] = number of steps, [6] = set-up and period 0; cycles_out: host int64[8] or NULL. */
 int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out);
+
+/* Debug hook: enable != 0 makes the two conditional-forecast kernels record the shader cycles wavefront 0 of workgroup 0 spends: of
+ * the setup kernel in [0] the lags (V_l, Psi_l, Psi_l Q_FF), [1] G, [2] the Cholesky factor and its store; of the paths kernel in
+ * [3] the loads and pass 1, [4] the two triangular solves, [5] Delta, [6] pass 2, [7] its total; cycles_out: host int64[8] or NULL. */
+int dsge_debug_condfc_phases(int enable, long long* cycles_out);
 
 /*
  * Timing hook for bench.py: runs `reps` back-to-back launches of the fused pipeline's

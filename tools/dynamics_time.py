@@ -3,6 +3,7 @@
     python tools/dynamics_time.py [draws ...]          (default: 256 4096)
     python tools/dynamics_time.py --second-order [draws ...]      the second-order rows alone
     python tools/dynamics_time.py --decomposition [draws ...]     the shock-decomposition rows alone
+    python tools/dynamics_time.py --conditional [draws ...]       the conditional-forecast rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -20,6 +21,12 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     timings of >= 1 s each of LogpEngine.shock_decomposition (with and without the remainder), of the composed route that was the
     only one before it -- LogpEngine.simulate with k + 1 paths on an expanded shock array, the expansion by torch timed apart; it
     still lacks the transpose and the remainder -- and of a plain fill of the output array.
+  * --conditional (csrc/dsge_condfc.hpp), m = 40, k = 7, p = 7 (selector Z): observables 0, 2, 4 conditioned over 12 periods (36
+    conditions), all shocks free, 40 steps, 16 paths with baseline shocks at every step: the median of five timings of >= 1 s each
+    of LogpEngine.conditional_forecast and of the composed route that was the only one before it -- LogpEngine.simulate (the
+    baseline), LogpEngine.impulse_response (12 steps: Psi), the torch algebra (gather of W, Gram matrix, linalg.cholesky,
+    cholesky_solve, the corrected shocks) and a second LogpEngine.simulate -- each part also timed apart; then the phase stamps of
+    one call (dsge_debug_condfc_phases).
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -150,13 +157,95 @@ def decomposition_rows(eng, sizes, T_len=200, repeats=5):
               + f" | total {cyc[4]}, {cyc[5]} steps, set-up and period 0 {cyc[6]}")
 
 
+def conditional_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, periods=12, series=(0, 2, 4), repeats=5):
+    import ctypes
+
+    b = wl.sw_shaped_batch(64)
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p = 40, 7, 7
+    rng = np.random.default_rng(0)
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    ct = np.repeat(np.arange(periods), len(series)).astype(np.int32)
+    cj = np.tile(np.array(series), periods).astype(np.int32)
+    n_cond = len(ct)
+    print(f"conditional forecast m={m} k={k} p={p}, {n_cond} conditions (series {list(series)} over {periods} periods), all shocks free, "
+          f"{n_steps} steps, {n_paths} paths; medians of {repeats} timings of >= 1 s")
+    # W[c, s k + f] = Psi[t_c - s, series index of c, f] for s <= t_c: the gather of the composed route, built once on the host
+    sidx = np.tile(np.arange(len(series)), periods)
+    s_ = np.arange(periods)[None, :, None]
+    lag = ct[:, None, None] - s_
+    gather = ((np.clip(lag, 0, None) * len(series) + sidx[:, None, None]) * k + np.arange(k)[None, None, :]).reshape(n_cond, periods * k)
+    mask = np.broadcast_to(lag >= 0, (n_cond, periods, k)).reshape(n_cond, periods * k).astype(np.float64)
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        T, R = eng.to_device(np.tile(b["T_star"], (rep, 1, 1))[:nb]), eng.to_device(np.tile(R64, (rep, 1, 1))[:nb])
+        sigma = np.tile(b["sigma"], (rep, 1))[:nb]
+        Q, Z = eng.to_device(sigma ** 2), eng.to_device(np.eye(p, m))
+        eps = eng.to_device(rng.standard_normal((nb, n_paths, n_steps, k)) * sigma[:, None, None, :])
+        x0 = eng.to_device(rng.standard_normal((nb, n_paths, m)) * 0.05)
+        vals = eng.to_device(rng.standard_normal((nb, n_paths, n_cond)) * 0.02)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        out = dict(x=mk(nb, n_paths, n_steps, m), shocks=mk(nb, n_paths, n_steps, k), observed=mk(nb, n_paths, n_steps, p))
+        status = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+        entry = lambda: eng.conditional_forecast(T, R, Q, x0, (ct, cj, vals), n_steps, Z=Z, eps=eps, q_mode="diag_batched",  # noqa: E731
+                                                 status=status, out=out)
+        # the composed route
+        base, irf, paths, eps2 = mk(nb, n_paths, n_steps, m), dict(irf=mk(nb, k, periods, m)), mk(nb, n_paths, n_steps, m), eps.clone()
+        g_idx, g_mask = torch.as_tensor(gather, device=eng.device), eng.to_device(mask)
+        obs_idx = torch.as_tensor(np.array(series), device=eng.device)
+        ct_d, sj_d = torch.as_tensor(ct.astype(np.int64), device=eng.device), torch.as_tensor(cj.astype(np.int64), device=eng.device)
+        sim1 = lambda: eng.simulate(T, R, eps, x0=x0, out=base)  # noqa: E731
+        imp = lambda: eng.impulse_response(T, R, n_steps=periods, out=irf)  # noqa: E731
+
+        def algebra():
+            psi = irf["irf"][:, :, :, obs_idx].permute(0, 2, 3, 1).reshape(nb, -1)  # [l][series][f]
+            W = psi[:, g_idx] * g_mask  # (nb, n_cond, periods k)
+            WQ = W * Q.repeat(1, periods)[:, None, :]
+            L = torch.linalg.cholesky(WQ @ W.transpose(1, 2))
+            r = vals - base[:, :, ct_d, sj_d]  # (nb, n_paths, n_cond); selector Z, d = 0
+            lam = torch.cholesky_solve(r.transpose(1, 2), L)  # (nb, n_cond, n_paths)
+            delta = (WQ.transpose(1, 2) @ lam).transpose(1, 2).reshape(nb, n_paths, periods, k)
+            eps2.copy_(eps)
+            eps2[:, :, :periods] += delta
+
+        sim2 = lambda: eng.simulate(T, R, eps2, x0=x0, out=paths)  # noqa: E731
+
+        def composed():
+            sim1()
+            imp()
+            algebra()
+            sim2()
+
+        entry()
+        composed()
+        torch.cuda.synchronize()
+        assert int(status.abs().max()) == 0
+        diff = (out["x"] - paths).abs().max().item() / paths.abs().max().item()
+        miss = (out["observed"][:, :, ct_d, sj_d] - vals).abs().max().item() / paths.abs().max().item()
+        print(f"draws={nb:5d} entry against the composed route: {diff:.1e} of max|x|; conditions missed by {miss:.1e} of max|x|")
+        t_entry, t_comp = med(entry), med(composed)
+        t_s1, t_imp, t_alg, t_s2 = med(sim1), med(imp), med(algebra), med(sim2)
+        print(f"draws={nb:5d} conditional_forecast: {t_entry:8.3f} ms | composed route {t_comp:8.3f} ms = simulate {t_s1:8.3f} + "
+              f"impulse_response {t_imp:8.3f} + torch algebra {t_alg:8.3f} + simulate {t_s2:8.3f} (sum {t_s1 + t_imp + t_alg + t_s2:8.3f}) | "
+              f"entry / composed {t_entry / t_comp:5.2f}")
+        lib, cyc = _lib.load(), (ctypes.c_longlong * 8)()  # per-phase shader cycles of wavefront 0 of workgroup 0 of both kernels, one call
+        _lib.check(lib.dsge_debug_condfc_phases(1, None))
+        entry()
+        _lib.check(lib.dsge_debug_condfc_phases(0, ctypes.addressof(cyc)))
+        names = ("setup: lags", "setup: G", "setup: Cholesky", "paths: loads + pass 1", "paths: solves", "paths: Delta", "paths: pass 2",
+                 "paths: total")
+        print(f"draws={nb:5d} phases of workgroup 0, cycles: " + ", ".join(f"{nm} {cyc[i]}" for i, nm in enumerate(names)))
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition")]
+    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
     if "--decomposition" in sys.argv:
         return decomposition_rows(LogpEngine(0), sizes)
+    if "--conditional" in sys.argv:
+        return conditional_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
