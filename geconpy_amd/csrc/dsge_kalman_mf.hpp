@@ -67,6 +67,9 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
   // more than five groups of tiles (TM = 7: 28 upper tiles): the per-element tables of where a value is stored would push the kernel
   // past 256 registers -- the Pc offsets are recomputed where they are used and the selector values come from an LDS table
   constexpr bool LEAN = NG > 5;
+  // the steady test's old values of the state block are requested at the top of the step where there are registers for them: not in
+  // the seven-group instances, nor in the record instance (at its 256 registers four more doubles across the elimination are scratch)
+  constexpr bool OLD_EARLY = !LEAN && !REC;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* Tc = smem;                // NM x LDK   transition, states-first ordering (columns >= s exactly zero)
   double* Wt = Tc + NM * LDK;       // WT         W' : Wt[j][k] = (P+[S,S] Tc')[k][j]
@@ -421,6 +424,13 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         }
       };
       if constexpr (!LEAN) load_panel();  // (LEAN: requested in phase (d) -- 72 registers less across the elimination)
+      // the steady test's old values of the state block, requested here with the rest: Pc is not written between the previous step's
+      // KMF_STORE_PC and this one's, and the latency sits under the elimination (otherwise: read in phase (e))
+      double oldv[OLD_EARLY ? NG : 1];
+      if constexpr (OLD_EARLY) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) oldv[g] = Pc[pcw0(g)];
+      }
       __builtin_amdgcn_sched_barrier(0);
       bool steady = false;
       double pm = 0.0;  // max |P_{t|t-1}| = the largest diagonal entry (P is positive semi-definite)
@@ -574,19 +584,18 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
           for (int g = 0; g < NG; ++g) sg[(size_t)g * 64 + lane] = Pt[g];
         }
         if (steady_tol > 0.0) {
-          // (the old values are read UNCONDITIONALLY and together -- volatile: under the predicate the compiler turned each read into
-          //  a branch with its own wait, four LDS round trips in a row)
-          if constexpr (!LEAN) {
-            double oldv[NG];
-#pragma unroll
-            for (int g = 0; g < NG; ++g) oldv[g] = *reinterpret_cast<const volatile double*>(&Pc[pcw0(g)]);
+          if constexpr (OLD_EARLY) {  // (old values: read at the top of the step)
 #pragma unroll
             for (int g = 0; g < NG; ++g) dmax = fmax(dmax, (pcw0(g) != PC_DUMP) ? fabs(Pt[g] - oldv[g]) : 0.0);
-          } else {  // (seven groups: one at a time, the registers are needed elsewhere)
+          } else {
+            // (one at a time, the registers are needed elsewhere.  Read UNCONDITIONALLY -- volatile: under the predicate
+            //  the compiler turned each read into a branch with its own wait -- and through an LDS pointer: a volatile access through
+            //  a generic pointer is a flat load, a round trip through the vector memory path with a full wait behind it)
+            using LdsCVD = const volatile __attribute__((address_space(3))) double*;
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
               const int at = pcw0(g);
-              const double old = *reinterpret_cast<const volatile double*>(&Pc[at]);
+              const double old = *(LdsCVD)(&Pc[at]);
               dmax = fmax(dmax, (at != PC_DUMP) ? fabs(Pt[g] - old) : 0.0);
             }
           }
@@ -656,52 +665,81 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
           finv_row[q] = (lane < 8) ? fr[q] * inv_own : 0.0;
           kr_ss[q] = (lane < m) ? Ks[lane * PS + q] : 0.0;
         }
-        while (t + 1 < T_len) {
-          const double yt_s = yt_next;
-          const bool obs_s = (lane < p) && (yt_s == yt_s) && (yt_s != missing_fill);
-          if (__ballot(obs_s) != omask) break;
-          ++t;
-          yt_next = y[(size_t)((t + 1 < T_len) ? t + 1 : t) * p + r8c];
-          if constexpr (REC) {
-            double* sgs = rec_d + (size_t)t * RC::STEP;
-            if (lane < 8 * RBS) sgs[RC::OFF_A + lane] = av_reg;
-            if (lane == 0) sgs[RC::OFF_SRC] = (double)seg_src;
-          }
-          const double av_sel = __shfl(av_reg, v_zpos, 64);
-          double v_s = 0.0;
-          if (lane < p) v_s = (obs_s ? yt_s : 0.0) - (((obs_s || !cv.mask_d) ? v_dd : 0.0) + (obs_s ? 1.0 : 0.0) * (v_zv * av_sel));
-          double vsc[8];
+        // What does not change while the loop runs (it runs while the mask is omask): which of this lane's entries is observed, the
+        // intercept that goes with it, the 0 / 1 factor of the selector.
+        const bool obs_l = (lane < p) && ((omask >> lane) & 1ull);
+        const double d_l = (obs_l || !cv.mask_d) ? v_dd : 0.0, one_l = obs_l ? 1.0 : 0.0;
+        const unsigned long long pbits = (1ull << p) - 1ull;  // (p <= 8)
+        // NC: columns of Tc the mean prediction runs over -- the padded state block, or two less when the last pair of columns is
+        // padding (18 state variables in 20 columns: trow is +0 there and s0, s1 are never -0, so fma(+0, afi, acc) == acc).  That, and
+        // the missing select on the predicted mean below, assume a FINITE filtered mean: with an Inf or NaN in afi the parent's
+        // 0 * afi poisoned every lane's sum where this one skips the column, and lanes >= m (which the record's OFF_A store may cover)
+        // hold NaN instead of 0.  Such a draw's likelihood is already non-finite and flagged DSGE_ST_FILTER_NONFINITE either way.
+        auto steady_loop = [&](auto nc_tag) {
+          constexpr int NC = decltype(nc_tag)::value;
+          while (t + 1 < T_len) {
+            const double yt_s = yt_next;
+            // the mask test as a scalar compare: the ballot of the comparison itself, cut to the p observations
+            // (one ballot per comparison: each is the comparison's own scalar result, their conjunction a scalar AND)
+            if ((__builtin_amdgcn_ballot_w64(yt_s == yt_s) & __builtin_amdgcn_ballot_w64(yt_s != missing_fill) & pbits) != omask) break;
+            ++t;
+            yt_next = y[(size_t)((t + 1 < T_len) ? t + 1 : t) * p + r8c];
+            if constexpr (REC) {
+              double* sgs = rec_d + (size_t)t * RC::STEP;
+              if (lane < 8 * RBS) sgs[RC::OFF_A + lane] = av_reg;
+              if (lane == 0) sgs[RC::OFF_SRC] = (double)seg_src;
+            }
+            const double av_sel = __shfl(av_reg, v_zpos, 64);
+            const double v_s = (lane < p) ? (obs_l ? yt_s : 0.0) - (d_l + one_l * (v_zv * av_sel)) : 0.0;
+            double vsc[8];
 #pragma unroll
-          for (int o = 0; o < 8; ++o) vsc[o] = readlane_f64(v_s, o);
-          double w0 = 0.0, w1 = 0.0, a0 = av_reg, a1 = 0.0;
+            for (int o = 0; o < 8; ++o) vsc[o] = readlane_f64(v_s, o);
+            double w0 = 0.0, w1 = 0.0, a0 = av_reg, a1 = 0.0;
 #pragma unroll
-          for (int o = 0; o < 8; o += 2) {
-            w0 = fma(finv_row[o], vsc[o], w0);
-            w1 = fma(finv_row[o + 1], vsc[o + 1], w1);
-            a0 = fma(kr_ss[o], vsc[o], a0);
-            a1 = fma(kr_ss[o + 1], vsc[o + 1], a1);
-          }
-          if (n_obs > 0) {
-            const double yk = v_s * (w0 + w1) - quad_comp;  // lanes >= 8 hold finv_row = 0
-            const double tk = quad_sum + yk;
-            quad_comp = (tk - quad_sum) - yk;
-            quad_sum = tk;
-            int e;
-            ld_mant = frexp(ld_mant * step_mant, &e);
-            ld_exp += e + step_exp;
-            ++n_ll_steps;
-            n_obs_entries += n_obs;
-          }
-          const double afi = a0 + a1;
-          double s0 = 0.0, s1 = 0.0;
+            for (int o = 0; o < 8; o += 2) {
+              w0 = fma(finv_row[o], vsc[o], w0);
+              w1 = fma(finv_row[o + 1], vsc[o + 1], w1);
+              a0 = fma(kr_ss[o], vsc[o], a0);
+              a1 = fma(kr_ss[o + 1], vsc[o + 1], a1);
+            }
+            if (n_obs > 0) {
+              const double yk = v_s * (w0 + w1) - quad_comp;  // lanes >= 8 hold finv_row = 0
+              const double tk = quad_sum + yk;
+              quad_comp = (tk - quad_sum) - yk;
+              quad_sum = tk;
+              int e;
+              ld_mant = frexp(ld_mant * step_mant, &e);
+              ld_exp += e + step_exp;
+              ++n_ll_steps;
+              n_obs_entries += n_obs;
+            }
+            const double afi = a0 + a1;
+            // the broadcasts of afi in batches of six to eight columns into SGPR pairs of their own -- the pairs vsc[] has just left --
+            // then the batch's FMAs in their order: a read-lane into the pair the previous FMA still reads needs a hazard nop in
+            // front of every FMA; all the columns at once would spill scalar registers elsewhere in the kernel
+            double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-          for (int kk = 0; kk < NS; kk += 2) {
-            s0 = fma(trow[kk], readlane_f64(afi, kk), s0);
-            s1 = fma(trow[kk + 1], readlane_f64(afi, kk + 1), s1);
+            for (int b0 = 0; b0 < NC; b0 += 6) {
+              const int b1 = (NC - b0 <= 8) ? NC : b0 + 6;
+              double afs[8];
+#pragma unroll
+              for (int kk = b0; kk < b1; ++kk) afs[kk - b0] = readlane_f64(afi, kk);
+#pragma unroll
+              for (int kk = b0; kk < b1; kk += 2) {
+                s0 = fma(trow[kk], afs[kk - b0], s0);
+                s1 = fma(trow[kk + 1], afs[kk + 1 - b0], s1);
+              }
+              if (b1 == NC) break;
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            av_reg = s0 + s1;  // (rows >= m of Tc are zero: +0 there for a finite afi, no select)
+            if constexpr (DBG) ++ph[6];
           }
-          av_reg = (lane < m) ? s0 + s1 : 0.0;
-          if constexpr (DBG) ++ph[6];
-        }
+        };
+        if (s <= NS - 2)
+          steady_loop(std::integral_constant<int, NS - 2>{});
+        else
+          steady_loop(std::integral_constant<int, NS>{});
         if (lane < m) av[lane] = av_reg;
       }
       wave_sync();
