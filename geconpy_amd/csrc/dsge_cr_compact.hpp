@@ -61,7 +61,8 @@ __device__ __forceinline__ unsigned long long blk_colmask(const double (&x)[BS][
   return mask;
 }
 
-// The cycle-reduction iteration on the compact form (register blocks A1, A1_hat, R = [A0c | A2c]; W = [A1 | R] in LDS).
+// The cycle-reduction iteration on the compact form (register blocks A1, A1_hat, R = [A0c | A2c]; W = [A1 | R] in LDS, R there
+// as the products' left operands only: the elimination works on the register block).
 // ph (nullable): debug stamps [0] GJ panels, [1] GJ trailing updates, [2] row gather + staging, [3] products,
 // [4] scatter/update/norms.
 template <int BS, typename IT>
@@ -84,7 +85,9 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     int lane = lane_in;
     asm volatile("" : "+v"(lane));
     const int lr = lane >> 3, lc = lane & 7;
-    // W = [A1 | R] -> [. | A1^-1 R] (rows in pivot order)
+    // [A1 | R] -> A1^-1 R, rows in pivot order.  (round 9) R is eliminated where it already is, in the register block Rb: the
+    // trailing updates neither load nor store column group 1.  G1 keeps the untouched R -- nothing writes it during the
+    // elimination -- as the left operands [A0c | A2c] of the two products below.
     blk_store_lds<BS>(A1, W, LDW, lr, lc);
     if (scan_mode && lr == lc) {  // stabilize(A1): 1e-16 on the diagonal of the solve only (shared.py:6-9)
 #pragma unroll
@@ -92,7 +95,7 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     }
     blk_store_lds<BS>(Rb, G1, LDW, lr, lc);
     double inv_lo = 1e300, inv_hi = 0.0;
-    gauss_jordan_blocked<BS>(W, LDW, n, 2, Lbuf, Ybuf, prow, lane, ph, inv_lo, inv_hi);  // syncs on entry and exit
+    gauss_jordan_blocked_rhs<BS>(W, LDW, n, Rb, Lbuf, Ybuf, prow, lane, ph, inv_lo, inv_hi);  // syncs on entry and exit
     // One step of iterative refinement, X += A1^-1 (R - A1 X), in every iteration whose pivots span more than
     // CR_REFINE_PIVOT_RATIO: the blocked Gauss-Jordan loses ~1e-15 x cond(A1) where the reference's LAPACK LU
     // (cycle_reduction.py:150-160) keeps 1e-10, and the worst A1 of a draw may come as late as the third or fourth iteration
@@ -102,9 +105,20 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     // precision (mm_residual_dot2): the corrected X is then better than the reference's own LU on the systems where float64
     // algorithms cannot agree to 1e-9 (cond(A1) ~ 1e6: tools/cr_accuracy_study.py, tests/golden/cr_ill_conditioned_54.npz).
     if (__builtin_amdgcn_readfirstlane((int)(inv_hi > cr_refine_ratio<BS>() * inv_lo))) {
-      gj_unpermute<BS>(W, LDW, n, 1, 2, prow, lane);  // X in natural row order (syncs inside)
+      // X (registers, pivot order) -> natural row order through the dead column group 0; Rb takes the original R back from G1
       double xh[BS][BS], rr[BS][BS];
-      blk_load_lds<BS>(xh, G1, LDW, lr, lc);
+      blk_store_lds<BS>(Rb, W, LDW, lr, lc);
+      wave_sync();
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const int r = lr * BS + i;
+        const int src = (r < n) ? prow[r] : r;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) xh[i][j] = W[src * LDW + lc * BS + j];
+      }
+      blk_load_lds<BS>(Rb, G1, LDW, lr, lc);
+      wave_sync();
+      blk_store_lds<BS>(xh, G1, LDW, lr, lc);
       blk_store_lds<BS>(A1, W, LDW, lr, lc);
       if (scan_mode && lr == lc) {
 #pragma unroll
@@ -118,17 +132,18 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
       gj_unpermute<BS>(W, LDW, n, 1, 2, prow, lane);
       blk_load_lds<BS>(rr, G1, LDW, lr, lc);
       wave_sync();
+      blk_store_lds<BS>(Rb, G1, LDW, lr, lc);  // the original R again: what the products read
 #pragma unroll
       for (int i = 0; i < BS; ++i)
 #pragma unroll
-        for (int j = 0; j < BS; ++j) xh[i][j] += rr[i][j];
-      blk_store_lds<BS>(xh, G1, LDW, lr, lc);
-      if (lane < NP) prow[lane] = lane;  // the solution sits in natural row order now
+        for (int j = 0; j < BS; ++j) Rb[i][j] = xh[i][j] + rr[i][j];  // the solution, where the common path expects it
+      if (lane < NP) prow[lane] = lane;  // it sits in natural row order now
       wave_sync();
     }
     long long tk0 = ph ? clock64() : 0;
-    // gather the rows S then L of the solution into compact order: XC[r] = X[cmap[r]]
+    // the solution -> dead column group 0, its rows S then L gathered there into compact order: XC[r] = X[cmap[r]]
     if (lane < NP) rsrc[lane] = (IT)((lane < wr) ? prow[cmap[lane]] : 0);
+    blk_store_lds<BS>(Rb, W, LDW, lr, lc);
     wave_sync();
     {
       double t[BS][BS];
@@ -136,12 +151,11 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
       for (int i = 0; i < BS; ++i) {
         const int src = rsrc[lr * BS + i];
 #pragma unroll
-        for (int j = 0; j < BS; ++j) t[i][j] = G1[src * LDW + lc * BS + j];
+        for (int j = 0; j < BS; ++j) t[i][j] = W[src * LDW + lc * BS + j];
       }
       wave_sync();
-      blk_store_lds<BS>(t, G1, LDW, lr, lc);
+      blk_store_lds<BS>(t, W, LDW, lr, lc);
     }
-    blk_store_lds<BS>(Rb, W, LDW, lr, lc);  // left operands [A0c | A2c] -> dead column group 0
     wave_sync();
     if (ph) {
       const long long tk1 = clock64();
@@ -151,8 +165,8 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     double acc1[BS][BS], acc2[BS][BS];
     blk_zero<BS>(acc1);
     blk_zero<BS>(acc2);
-    mm_acc<BS, false>(acc1, W, LDW, G1, LDW, s, lr, lc);                    // [m00 | m02] = A0c X[S,:]
-    mm_acc<BS, false>(acc2, W + s, LDW, G1 + s * LDW, LDW, l, lr, lc);      // [m20 | m22] = A2c X[L,:]
+    mm_acc<BS, false>(acc1, G1, LDW, W, LDW, s, lr, lc);                    // [m00 | m02] = A0c X[S,:]
+    mm_acc<BS, false>(acc2, G1 + s, LDW, W + s * LDW, LDW, l, lr, lc);      // [m20 | m22] = A2c X[L,:]
     wave_sync();
     if (ph) {
       const long long tk1 = clock64();

@@ -499,10 +499,12 @@ __device__ __forceinline__ constexpr double cr_refine_ratio() {
   return (BS <= 3 || BS > 5) ? 1e3 : 3e3;
 }
 
-template <int BS>
-__device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, int ngroups, double* Lbuf, double* Ybuf,
-                                                     int* prow, int lane, long long* ph, double& inv_min, double& inv_max,
-                                                     double* rec_L = nullptr) {
+// RHS_REG (round 9, gauss_jordan_blocked_rhs below): the right-hand sides -- column group 1 of two -- live in the caller's
+// register block Rg instead of W; false is the LDS form every other caller uses, which never touches Rg.
+template <int BS, bool RHS_REG>
+__device__ __forceinline__ void gauss_jordan_blocked_impl(double* W, int ldw, int n, int ngroups, double* Lbuf, double* Ybuf,
+                                                          int* prow, int lane, long long* ph, double& inv_min, double& inv_max,
+                                                          double* rec_L, double (&Rg)[BS][BS]) {
   // rec_L (optional, nsteps x NP x BS doubles): the elimination's multipliers Lhat of every block step are kept, so that
   // gj_replay can apply the SAME elimination to further right-hand sides (with prow, which holds the pivot rows)
   // inv_min / inv_max: smallest and largest |1 / pivot| met (wave-uniform): their ratio is a free lower estimate of the
@@ -606,9 +608,37 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
         for (int b = 0; b < BS; ++b) rec_L[((size_t)kb * NP + lane) * BS + b] = 0.0;
       }
       // pivot rows of W (original values) -> Ybuf, one column per lane
-      for (int c = lane; c < wcols; c += 64) {
+      for (int c = lane; c < (RHS_REG ? NP : wcols); c += 64) {
 #pragma unroll
         for (int b = 0; b < BS; ++b) Ybuf[b * wcols + c] = (FULL || b < bw) ? W[rsel[b] * ldw + c] : 0.0;
+      }
+      if constexpr (RHS_REG) {
+        // ... and of the register-resident group (the values before this panel's update, as the copy from W takes them).  Every
+        // index into the register block is a compile-time constant: row i of a lane's block is matrix row lr * BS + i, and the
+        // lane asks which pivot of the panel, if any, that row is -- compares against the wave-uniform rsel[b] and selects of
+        // the target row of Ybuf, then ONE exec-masked row store per position i.  (A uniform branch per pivot on its position
+        // rsel[b] % BS was built first: four cascades of scalar branches per panel cost what the saved LDS traffic gained.)
+        double* ycol = Ybuf + NP + lc * BS;
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const int row = lr * BS + i;
+          int yoff = -1;
+#pragma unroll
+          for (int b = 0; b < BS; ++b)
+            if (FULL || b < bw) yoff = (row == rsel[b]) ? b * wcols : yoff;
+          if (yoff >= 0) {
+#pragma unroll
+            for (int j = 0; j < BS; ++j) ycol[yoff + j] = Rg[i][j];
+          }
+        }
+        if (!FULL && lr == 0) {  // (rows a partial panel does not reach: zero rows, their FMAs are issued)
+#pragma unroll
+          for (int b = 0; b < BS; ++b)
+            if (b >= bw) {
+#pragma unroll
+              for (int j = 0; j < BS; ++j) ycol[b * wcols + j] = 0.0;
+            }
+        }
       }
 #pragma unroll
       for (int a = 0; a < BS; ++a)
@@ -636,7 +666,7 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
     for (int i = 0; i < BS; ++i)
 #pragma unroll
       for (int b = 0; b < BS; ++b) nl[i][b] = Lbuf[(lr * BS + i) * BS + b];
-    for (int g = 0; g < ngroups; ++g) {
+    for (int g = 0; g < (RHS_REG ? 1 : ngroups); ++g) {
       // block columns at or left of the panel inside the matrix part are dead (never read again)
       if (g == 0 && lc <= kb) continue;
       const int c0 = g * NP + lc * BS;
@@ -660,6 +690,19 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
 #pragma unroll
         for (int j = 0; j < BS; ++j) W[(lr * BS + i) * ldw + c0 + j] = wb[i][j];
     }
+    if constexpr (RHS_REG) {  // the same FMAs on the register block: no load of the block, no store
+      double yb[BS][BS];
+#pragma unroll
+      for (int b = 0; b < BS; ++b)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) yb[b][j] = Ybuf[b * wcols + NP + lc * BS + j];
+#pragma unroll
+      for (int b = 0; b < BS; ++b)
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+          for (int j = 0; j < BS; ++j) Rg[i][j] = fma(nl[i][b], yb[b][j], Rg[i][j]);
+    }
     if (ph) ph[1] += clock64() - tk_t;
   }
   wave_sync();
@@ -667,9 +710,30 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
 
 template <int BS>
 __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, int ngroups, double* Lbuf, double* Ybuf,
+                                                     int* prow, int lane, long long* ph, double& inv_min, double& inv_max,
+                                                     double* rec_L = nullptr) {
+  double none[BS][BS];  // (never read or written by the LDS form)
+  gauss_jordan_blocked_impl<BS, false>(W, ldw, n, ngroups, Lbuf, Ybuf, prow, lane, ph, inv_min, inv_max, rec_L, none);
+}
+
+template <int BS>
+__device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, int ngroups, double* Lbuf, double* Ybuf,
                                                      int* prow, int lane, long long* ph = nullptr, double* rec_L = nullptr) {
   double lo = 1e300, hi = 0.0;
   gauss_jordan_blocked<BS>(W, ldw, n, ngroups, Lbuf, Ybuf, prow, lane, ph, lo, hi, rec_L);
+}
+
+// (round 9) [A | R] -> [. | A^-1 R] with the right-hand sides in the caller's register block: W holds the matrix in column group
+// 0 (row stride ldw, as for two groups; its group 1 is neither read nor written), Rg the block (lr, lc) of R on entry and of
+// A^-1 R on return, rows in pivot order exactly as the LDS form leaves them in W (row j of the solution sits in row prow[j];
+// there is no row swap).  Ybuf as for two groups.  Every FMA of the LDS form with its operands and its order: bit-identical.
+// What it saves is LDS traffic: per panel the block of group 1 is neither loaded nor stored (BS rows each way), and only the
+// BS pivot rows go through Ybuf, one exec-masked row store each.
+template <int BS>
+__device__ __forceinline__ void gauss_jordan_blocked_rhs(double* W, int ldw, int n, double (&Rg)[BS][BS], double* Lbuf,
+                                                         double* Ybuf, int* prow, int lane, long long* ph, double& inv_min,
+                                                         double& inv_max) {
+  gauss_jordan_blocked_impl<BS, true>(W, ldw, n, 2, Lbuf, Ybuf, prow, lane, ph, inv_min, inv_max, nullptr, Rg);
 }
 
 // The elimination recorded by gauss_jordan_blocked (rec_L, prow) applied to ONE more right-hand-side column group Wg (NP columns,
