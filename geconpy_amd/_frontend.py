@@ -593,6 +593,73 @@ def conditional_forecast(b, name, T, R, Q, x0, conditions, n_steps, *, Z, d, eps
     return res
 
 
+def spectral_freqs(n_grid):
+    """The grid ``w_n = 2 pi n / N``, ``n = 0 .. N/2`` (host float64); ``N`` even and within 4 .. 4096."""
+    n_grid = int(n_grid)
+    if n_grid < 4 or n_grid > 4096 or n_grid % 2:
+        raise ValueError(f"n_grid must be even and within 4 .. 4096; got {n_grid}")
+    return 2.0 * np.pi * np.arange(n_grid // 2 + 1) / n_grid
+
+
+def hp_gain(n_grid, lam=1600.0):
+    """The squared gain of the Hodrick-Prescott cyclical filter on the grid of ``spectral_moments``:
+    ``(4 lam (1 - cos w)^2 / (1 + 4 lam (1 - cos w)^2))^2``, exactly 0 at ``w = 0``."""
+    c = 4.0 * float(lam) * (1.0 - np.cos(spectral_freqs(n_grid))) ** 2
+    g = (c / (1.0 + c)) ** 2
+    g[0] = 0.0
+    return g
+
+
+def bandpass_gain(n_grid, low=6, high=32):
+    """The squared gain of the ideal band-pass filter that keeps the periods ``low .. high``: 1 where
+    ``2 pi / high <= w <= 2 pi / low``, else 0."""
+    if not 0 < low <= high:
+        raise ValueError(f"bandpass_gain needs 0 < low <= high; got {low}, {high}")
+    n = np.arange(len(spectral_freqs(n_grid)))
+    # w_n = 2 pi n / N within [2 pi / high, 2 pi / low], decided without rounding the grid: an edge on a grid point is in the band
+    return ((n * high >= n_grid) & (n * low <= n_grid)).astype(np.float64)
+
+
+def spectral_moments(b, name, T, R, Q, *, n_grid, n_lags, Z, Hdiag, gain, correlation, spectrum, acov=True, q_mode, status, rank_tol,
+                     scratch_limit_bytes, out=None):
+    T, R, nb, m, k = _TR(b, T, R, name)
+    Q = b.inp(Q)
+    code = q_layout(Q.shape, q_mode, nb, k)
+    freqs = spectral_freqs(n_grid)
+    n_grid, nf, n_lags = int(n_grid), len(freqs), int(n_lags)
+    if n_lags < 0 or n_lags > n_grid // 2:
+        raise ValueError(f"n_lags must be within 0 .. n_grid / 2 = {n_grid // 2}; got {n_lags}")
+    if Z is None:
+        if Hdiag is not None:
+            raise ValueError(f"{name}: Hdiag (measurement noise) needs Z")
+        obs, p, dim = dict(Z=None, z_batched=0, Hdiag=None, h_batched=0), 0, m
+    else:
+        Z = b.inp(Z)
+        if Z.ndim not in (2, 3) or Z.shape[-1] != m or Z.shape[-2] < 1:
+            raise ValueError(f"Z must be (p, {m}) or (batch, p, {m}); got {tuple(Z.shape)}")
+        p = dim = Z.shape[-2]
+        obs = obs_args(b, Z, None, Hdiag, nb, p, m)
+        obs = {key: obs[key] for key in ("Z", "z_batched", "Hdiag", "h_batched")}
+    gain = b.inp(gain)
+    if gain is not None:
+        _is(gain, (nf,), "gain", f"({nf},) = (n_grid / 2 + 1,)")
+    if not (acov or spectrum):
+        raise ValueError(f"{name}: nothing to compute (acov and spectrum are both off)")
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    res = dict(acov=_out(b, out.get("acov"), (nb, n_lags + 1, dim, dim)) if acov else None, freqs=freqs, status=st)
+    spec = _out(b, out.get("spectrum"), (nb, nf, dim, dim), "complex128") if spectrum else None
+    if spectrum:
+        res["spectrum"] = spec
+    call(b, "dsge_spectral_moments_batched", T=T, R=R, Q=Q, q_mode=code, **obs, gain=gain, batch=nb, m=m, k=k, p=p, n_grid=n_grid,
+         n_lags=n_lags, correlation=int(bool(correlation)), rank_tol=0.0 if rank_tol is None else float(rank_tol),
+         scratch_limit_bytes=limit, acov_out=res["acov"], spectrum_out=spec, status_io=st)
+    return res
+
+
 # ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
 SOLUTION = ("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
 

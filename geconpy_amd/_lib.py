@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -31,6 +31,7 @@ ST_GRAD_UNSUPPORTED = 64
 ST_SECOND_ORDER_UNSUPPORTED = 128
 ST_SMOOTHER_SINGULAR = 256
 ST_COND_SINGULAR = 512
+ST_SPECTRAL_SINGULAR = 1024
 
 Q_DIAG_SHARED, Q_DIAG_BATCHED, Q_FULL_SHARED, Q_FULL_BATCHED = 0, 1, 2, 3
 SOLVER_CYCLE_REDUCTION, SOLVER_GENSYS, SOLVER_BACKWARD_DIRECT, SOLVER_SCAN_CYCLE_REDUCTION = 0, 1, 2, 3
@@ -74,7 +75,7 @@ class GensysForward(C.Structure):
 # name is an int, a double or a size_t when it is listed below, a pointer (double* / int32_t* / struct* / stream, passed as a raw
 # host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
 _INTS = ("N T_len batch c correlation cv_batched cv_paths d_batched device enable eps_batched eta_batched full_cov h_batched k lag_step m "
-         "max_iter mode n n_cond n_eta n_filter_hint n_groups n_lags n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state "
+         "max_iter mode n n_cond n_eta n_filter_hint n_grid n_groups n_lags n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state "
          "n_state_hint n_steps nnz p q_batched q_mode remainder reps s_batched solver w_batched x0_batched x0_paths z_batched "
          "z_selector_hint")
 _KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
@@ -143,6 +144,8 @@ _DEVICE_ENTRIES = {
     "dsge_conditional_forecast_batched": ("T R Q q_mode Z z_batched d d_batched x0 x0_batched x0_paths eps eps_batched cond_t cond_j "
                                           "n_cond cond_val cv_batched cv_paths free_shock status_io batch m k p n_paths n_steps "
                                           "n_shock_steps rank_tol x_out eps_out obs_out stream"),
+    "dsge_spectral_moments_batched": ("T R Q q_mode Z z_batched Hdiag h_batched gain batch m k p n_grid n_lags correlation rank_tol "
+                                      "scratch_limit_bytes acov_out spectrum_out status_io stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

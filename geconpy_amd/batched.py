@@ -546,6 +546,28 @@ def conditional_forecast_batched(T, R, Q, x0, conditions, n_steps, Z=None, d=Non
                                   n_paths=n_paths, free_shocks=free_shocks, q_mode=q_mode, status=status, rank_tol=rank_tol)
 
 
+hp_gain, bandpass_gain = F.hp_gain, F.bandpass_gain
+
+
+def spectral_moments_batched(T, R, Q, n_grid=512, n_lags=10, Z=None, Hdiag=None, gain=None, correlation=False, spectrum=False,
+                             q_mode=None, status=None, rank_tol=None, scratch_limit_bytes=None, acov=True):
+    """Spectral densities and the exact autocovariances of linearly filtered series for a batch of draws -- the frequency-domain
+    route of Dynare's ``hp_filter`` theoretical moments; include/dsge_hip.h, ``dsge_spectral_moments_batched``.  The series are
+    ``w = Z x`` (``Z`` (p, m) or (batch, p, m); None: the states themselves) of ``x_t = T x_{t-1} + R e_t``, ``e ~ (0, Q)``, plus
+    white noise ``Hdiag``.  On the grid ``w_n = 2 pi n / n_grid``, ``n = 0 .. n_grid / 2``: ``F_n = H_n Q H_n^H (+ diag(Hdiag))``,
+    ``H_n = Z (I - exp(-i w_n) T)^-1 R``; ``spectrum[b, n] = F_n / 2 pi`` (unfiltered) and
+    ``acov[b, j] = (1 / N) sum_n c_n gain_n Re(F_n exp(i w_n j)) = E[w_t w_{t-j}']`` of the filtered series, ``j = 0 .. n_lags``.
+    ``gain`` (n_grid / 2 + 1,): the squared gain of the filter (``hp_gain``, ``bandpass_gain``, or any), None = ones.  ``n_grid`` is
+    part of the definition: the unfiltered autocovariances are folded modulo ``n_grid``.  ``correlation``: every lag divided by
+    ``std std'``.  A draw with a root of ``T`` on the unit circle at a solved grid frequency gets ``ST_SPECTRAL_SINGULAR`` (1024)
+    in ``status`` and NaN; frequencies of zero gain are not solved unless ``spectrum`` is wanted, so HP-filtered moments of a
+    unit-root model are finite.  ``rho(T) > 1`` is not detected: pass the solver's ``status``.  ``acov=False``: the spectrum only.
+    Returns dict(acov (batch, n_lags + 1, dim, dim), [spectrum complex128 (batch, nf, dim, dim)], freqs (nf,), status)."""
+    return F.spectral_moments(HOST, "spectral_moments_batched", T, R, Q, n_grid=n_grid, n_lags=n_lags, Z=Z, Hdiag=Hdiag, gain=gain,
+                              correlation=correlation, spectrum=spectrum, acov=acov, q_mode=q_mode, status=status,
+                              rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes)
+
+
 def impulse_response_batched(T, R, n_steps=40, S=None, weights=None, fevd=False, irf=True, status=None):
     """Impulse responses ``irf[b, j, h] = T_b^h R_b S[:, j]`` for a batch of draws -- ``impulse_response_function``
     (gEconpy/model/simulate.py:201-317; its loop over shocks :300-311 calls ``_simulate_linear_system`` :171-182 once per

@@ -805,6 +805,38 @@ int dsge_conditional_forecast_batched_host(const double* T, const double* R, con
   return hc.finish();
 }
 
+int dsge_spectral_moments_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                       const double* Hdiag, int h_batched, const double* gain, int batch, int m, int k, int p,
+                                       int n_grid, int n_lags, int correlation, double rank_tol, size_t scratch_limit_bytes,
+                                       double* acov_out, double* spectrum_out, int32_t* status_io) {
+  const SpectralProblem s{batch, m, k, p, n_grid, n_lags, correlation, z_batched, h_batched, rank_tol};
+  const ShockCov q{Q, q_mode};
+  int rc = check_spectral_moments(s, T, R, q, Z, Hdiag, acov_out, spectrum_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, dim = Z ? p : m, nf = (size_t)n_grid / 2 + 1;
+  ShockCov dq;
+  const double *dT, *dR, *dZ, *dH, *dg;
+  double *dacov, *dspec;
+  int32_t* dS;
+  hc.in(&dT, T, b * m * m);
+  hc.in(&dR, R, b * m * k);
+  hc.in(&dq, q, batch, k);
+  hc.in(&dZ, Z, (z_batched ? b : 1) * p * m);
+  hc.in(&dH, Hdiag, (h_batched ? b : 1) * p);
+  hc.in(&dg, gain, nf);
+  hc.io(&dS, status_io, b);
+  hc.out(&dacov, acov_out, b * (n_lags + 1) * dim * dim);
+  hc.out(&dspec, spectrum_out, b * nf * dim * dim * 2);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_spectral_moments_batched(dT, dR, dq.Q, dq.mode, dZ, z_batched, dH, h_batched, dg, batch, m, k, p, n_grid, n_lags,
+                                          correlation, rank_tol, scratch_limit_bytes, dacov, dspec, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

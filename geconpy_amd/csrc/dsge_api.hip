@@ -810,6 +810,42 @@ int dsge_conditional_forecast_batched(const double* T, const double* R, const do
                        obs_out, st);
 }
 
+// ---- spectral moments (dsge_spectral.hpp): two launches per chunk of draws on the caller's stream; the scratch holds the
+// per-frequency F_n of the chunk's draws and a flag per draw ----
+int dsge_spectral_moments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                  const double* Hdiag, int h_batched, const double* gain, int batch, int m, int k, int p,
+                                  int n_grid, int n_lags, int correlation, double rank_tol, size_t scratch_limit_bytes,
+                                  double* acov_out, double* spectrum_out, int32_t* status_io, void* stream) {
+  SpectralProblem s{batch, m, k, p, n_grid, n_lags, correlation, z_batched, h_batched, rank_tol};
+  const ShockCov q{Q, q_mode};
+  int rc = check_spectral_moments(s, T, R, q, Z, Hdiag, acov_out, spectrum_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  const size_t dim = Z ? p : m, nf = (size_t)n_grid / 2 + 1, dd = dim * dim;
+  const size_t per_draw = acov_out ? 2 * nf * dd * sizeof(double) : sizeof(int32_t);
+  const size_t fit = scratch_limit_bytes / per_draw;
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  double* F = nullptr;
+  int32_t* flag = nullptr;
+  ScratchLayout lay;
+  if (acov_out) lay.add(&F, (size_t)chunk * 2 * nf * dd);
+  lay.add(&flag, (size_t)chunk);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const size_t o = (size_t)c0;
+    s.batch = batch - c0 < chunk ? batch - c0 : chunk;
+    if ((rc = launch_spectral(s, T + o * m * m, R + o * m * k, q.at(o, k), Z && z_batched ? Z + o * p * m : Z,
+                              Hdiag && h_batched ? Hdiag + o * p : Hdiag, gain, status_io ? status_io + o : nullptr, flag, F,
+                              acov_out ? acov_out + o * (n_lags + 1) * dd : nullptr,
+                              spectrum_out ? spectrum_out + o * nf * dd * 2 : nullptr, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
                           const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,

@@ -328,6 +328,17 @@ int launch_condfc(const CondFcProblem& c, const double* T, const double* R, cons
                   const double* d, int d_batched, const double* x0, const double* eps, const double* cond_val, int32_t* status,
                   double* chol, double* psi, double* psiq, int32_t* flag, double* x_out, double* eps_out, double* obs_out,
                   hipStream_t st);
+// launch_spectral.hip (dsge_spectral.hpp): spectral densities and filtered autocovariances, a wavefront per draw and frequency
+// group, then a reduction workgroup per draw.  The sizes and flags of one call
+struct SpectralProblem {
+  int batch, m, k, p, n_grid, n_lags, correlation, z_batched, h_batched;
+  double rank_tol;
+};
+// bytes of the solve kernel's LDS image (the reduction's is 8 (2 n_grid + dim), at most 66 KB)
+size_t spectral_lds_bytes(int m, int k, int p, int has_z);
+int launch_spectral(const SpectralProblem& s, const double* T, const double* R, const ShockCov& q, const double* Z,
+                    const double* Hdiag, const double* gain, int32_t* status, int32_t* flag, double* F, double* acov_out,
+                    double* spectrum_out, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -647,6 +658,27 @@ inline int check_conditional_forecast(CondFcProblem& c, const double* T, const d
   if (c.n_cond > 0 && c.n_free == 0) return fail(DSGE_ERR_INVALID, "conditional forecast: conditions but no free shock");
   if (condfc_lds_bytes(c.m, c.k, c.p, c.n_cond, c.t_max + 1, c.n_free) > LDS_LIMIT)
     return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: the LDS image exceeds 160 KB (docs/design/conditional_forecast.md)");
+  return DSGE_SUCCESS;
+}
+
+// the spectral moments: every refusal, before any device is touched
+inline int check_spectral_moments(const SpectralProblem& s, const double* T, const double* R, const ShockCov& q, const double* Z,
+                                  const double* Hdiag, const double* acov_out, const double* spectrum_out) {
+  if (s.batch < 0 || s.m < 1) return fail(DSGE_ERR_INVALID, "size out of range");
+  if (s.n_grid < 4 || s.n_grid > DSGE_SPECTRAL_MAX_GRID || (s.n_grid & 1))
+    return fail(DSGE_ERR_INVALID, "spectral moments: n_grid must be even and within 4 .. 4096");
+  if (s.n_lags < 0 || s.n_lags > s.n_grid / 2) return fail(DSGE_ERR_INVALID, "spectral moments: n_lags out of range (0 .. n_grid / 2)");
+  if (s.k < 1 || s.k > s.m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (q.mode < DSGE_Q_DIAG_SHARED || q.mode > DSGE_Q_FULL_BATCHED) return fail(DSGE_ERR_INVALID, "q_mode out of range");
+  if (!T || !R || !q.Q) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (Hdiag && !Z) return fail(DSGE_ERR_INVALID, "spectral moments: Hdiag without Z");
+  if (Z && s.p < 1) return fail(DSGE_ERR_INVALID, "spectral moments: p must be >= 1 with Z");
+  if (!acov_out && !spectrum_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (s.m > DSGE_MAX_N) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: m exceeds DSGE_MAX_N");
+  if (s.k > DSGE_SPECTRAL_MAX_K) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: k exceeds DSGE_SPECTRAL_MAX_K");
+  if (Z && s.p > DSGE_SPECTRAL_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: p exceeds DSGE_SPECTRAL_MAX_P");
+  if (spectral_lds_bytes(s.m, s.k, s.p, Z != nullptr) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "spectral moments: the LDS image exceeds 160 KB (docs/design/spectral_moments.md)");
   return DSGE_SUCCESS;
 }
 

@@ -300,6 +300,17 @@ class LogpEngine:
                                       n_paths=n_paths, free_shocks=free_shocks, q_mode=q_mode, status=status, rank_tol=rank_tol,
                                       out=out)
 
+    # -- spectral densities and filtered moments (csrc/dsge_spectral.hpp) --------------------------
+    def spectral_moments(self, T, R, Q, n_grid=512, n_lags=10, Z=None, Hdiag=None, gain=None, correlation=False, spectrum=False,
+                         q_mode=None, status=None, rank_tol=None, scratch_limit_bytes=None, acov=True, out=None):
+        """Spectral densities and filtered autocovariances of the whole batch from device tensors
+        (``dsge_spectral_moments_batched``; see ``batched.spectral_moments_batched``), on torch's current stream.  ``gain`` is a
+        device tensor (``torch.as_tensor(batched.hp_gain(n_grid), device=...)``).  ``status`` (device int32) is updated in place.
+        ``out``: optional dict with preallocated ``acov`` / ``spectrum`` (complex128).  ``freqs`` comes back as a host array."""
+        return F.spectral_moments(self.backend, "spectral_moments", T, R, Q, n_grid=n_grid, n_lags=n_lags, Z=Z, Hdiag=Hdiag,
+                                  gain=gain, correlation=correlation, spectrum=spectrum, acov=acov, q_mode=q_mode, status=status,
+                                  rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes, out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

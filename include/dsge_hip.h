@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 15
+#define DSGE_ABI_VERSION 16
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -51,6 +51,7 @@ extern "C" {
 /* ABI 13: dsge_simulate_pruned_batched, dsge_girf_pruned_batched (+ _host) are new; nothing else changed. */
 /* ABI 14: dsge_shock_decomposition_batched (+ _host) is new; nothing else changed. */
 /* ABI 15: dsge_conditional_forecast_batched (+ _host) and the status bit DSGE_ST_COND_SINGULAR are new; nothing else changed. */
+/* ABI 16: dsge_spectral_moments_batched (+ _host) and the status bit DSGE_ST_SPECTRAL_SINGULAR are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -62,6 +63,9 @@ extern "C" {
                                   variables, of which there may be at most 64 (else DSGE_ERR_TOO_LARGE); every other entry point
                                   keeps the limits above */
 #define DSGE_MAX_P 16      /* observed series */
+#define DSGE_SPECTRAL_MAX_K 32     /* dsge_spectral_moments_batched: shocks */
+#define DSGE_SPECTRAL_MAX_P 64     /* dsge_spectral_moments_batched: rows of Z */
+#define DSGE_SPECTRAL_MAX_GRID 4096 /* dsge_spectral_moments_batched: grid points N */
 
 /* call-level return codes */
 #define DSGE_SUCCESS 0
@@ -84,6 +88,7 @@ extern "C" {
 #define DSGE_ST_SECOND_ORDER_UNSUPPORTED 128 /* second-order path: input violates the declared model structure */
 #define DSGE_ST_SMOOTHER_SINGULAR 256 /* smoother: sym(U' P_pred U) not positive definite at some step (jitter_P = 0 only) */
 #define DSGE_ST_COND_SINGULAR 512 /* conditional forecast: the conditions cannot be met by the free shocks (G singular) */
+#define DSGE_ST_SPECTRAL_SINGULAR 1024 /* spectral moments: I - exp(-i w) T singular at a solved grid frequency */
 
 /* covariance layouts for the Q argument */
 #define DSGE_Q_DIAG_SHARED 0    /* Q = diag(q), q: [k]            */
@@ -940,6 +945,53 @@ int dsge_conditional_forecast_batched_host(const double* T, const double* R, con
                                            const int32_t* free_shock, int32_t* status_io, int batch, int m, int k, int p,
                                            int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
                                            double* eps_out, double* obs_out);
+
+/*
+ * SPECTRAL DENSITIES AND FILTERED MOMENTS per draw (ABI 16; csrc/dsge_spectral.hpp, docs/design/spectral_moments.md): the exact
+ * second moments of linearly filtered series of x[t] = T x[t-1] + R e[t], e ~ (0, Q) -- HP-filtered (lambda = 1600), band-pass
+ * filtered, first differences, any gain -- and the spectra behind them, by the frequency-domain route of Dynare's hp_filter
+ * theoretical moments.  T: [batch][m][m], R: [batch][m][k], Q in the layout q_mode (DSGE_Q_*); all arrays float64, C-contiguous.
+ * The series are w = Zm x:  Z : [batch|1][p][m] (z_batched), Zm = Z, dim = p;  Z == NULL: Zm = I, dim = m.
+ *   Hdiag : [batch|1][p] (h_batched) or NULL, only with Z: white measurement noise on w
+ *   gain  : [N/2 + 1] or NULL (ones): the squared gain |h(w_n)|^2 of the filter, shared by all draws, used as given
+ * The grid: N = n_grid even, w_n = 2 pi n / N, n = 0 .. N/2, nf = N/2 + 1:
+ *       H_n = Zm (I - exp(-i w_n) T)^-1 R          (dim x k)
+ *       F_n = H_n Q H_n^H (+ diag(Hdiag))          (dim x dim, Hermitian)
+ *       spectrum_out[b][n] = F_n / (2 pi)          (unfiltered: the gain is NOT applied)
+ *       acov_out[b][j] = (1/N) sum_n c_n gain_n Re(F_n exp(i w_n j)),  j = 0 .. n_lags,  c_n = 1 for n in {0, N/2}, else 2
+ * acov[j] = E[w_t w_{t-j}'], the lag convention of dsge_autocorrelation_batched.  The sum is the exact autocovariance of the
+ * circularly filtered process whose unfiltered autocovariances are folded modulo N: N is part of the definition.  With gain == 1
+ * and no aliasing acov[j] = Zm T^j P Zm' (+ diag(Hdiag) at lag 0).  correlation != 0 divides every lag by std std',
+ * std = sqrt(diag(acov[0])), as dsge_autocorrelation_batched does (a zero variance gives inf / NaN in its row and column).
+ *   acov_out     : [batch][n_lags + 1][dim][dim]
+ *   spectrum_out : [batch][nf][dim][dim][2] (re, im)
+ *   either may be NULL, not both.
+ *   status_io : [batch] in/out, may be NULL; a draw with a non-zero incoming word is skipped and gets NaN in every output.
+ * A draw is singular when, at a solved frequency, the elimination with partial pivoting meets |pivot| <= rank_tol max|I - exp(-i w) T|
+ * (rank_tol <= 0: 1e-12; the maximum is over the entries) -- a root of T on the unit circle at a grid frequency:
+ * status |= DSGE_ST_SPECTRAL_SINGULAR, NaN in every output of the draw, the other draws untouched.  Frequencies with gain_n == 0
+ * are not solved when spectrum_out is NULL: HP-filtered moments (gain 0 at w = 0) of a model with an exact unit root are finite,
+ * and a singularity there is not reported.  rho(T) > 1 is NOT detected: pass the solver's status word.
+ * Two launches per chunk of draws on `stream`, no host synchronisation, no atomics; the sum over n runs in ascending n for every
+ * output entry: two calls give the same bits, and a draw's bits do not depend on the batch it is in.  Library scratch holds F_n
+ * of a chunk of draws, 16 nf dim^2 bytes per draw; scratch_limit_bytes (0: 2 GiB) bounds that buffer by chunking the draws (at
+ * least one per chunk; a 4-byte flag per draw and the padding of the layout are not counted; with acov_out == NULL no F_n is stored
+ * and the draws are not chunked).
+ * DSGE_ERR_TOO_LARGE: m > DSGE_MAX_N (64), k > DSGE_SPECTRAL_MAX_K (32), p > DSGE_SPECTRAL_MAX_P (64), or an LDS image beyond
+ * 160 KB, in doubles (lk = k | 1, the bracket rounded up to even):
+ *       [m (m | 1) + m lk + k^2 + (Z ? p m + p : 0)] + 2 (m + dim + (Z ? p : 0)) lk  <=  20 480
+ * -- every m <= 64, k <= 32 with Z == NULL or p <= 45 fits; m = 64, k = 32 with p = 46 .. 64 does not.  DSGE_ERR_INVALID:
+ * N odd, N < 4 or N > DSGE_SPECTRAL_MAX_GRID, n_lags < 0 or > N/2, Hdiag without Z, missing T / R / Q, both outputs NULL,
+ * k outside 1 .. m, p < 1 with Z.  All refusals happen before any device is touched.  batch == 0: success, nothing touched.
+ */
+int dsge_spectral_moments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                  const double* Hdiag, int h_batched, const double* gain, int batch, int m, int k, int p,
+                                  int n_grid, int n_lags, int correlation, double rank_tol, size_t scratch_limit_bytes,
+                                  double* acov_out, double* spectrum_out, int32_t* status_io, void* stream);
+int dsge_spectral_moments_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                       const double* Hdiag, int h_batched, const double* gain, int batch, int m, int k, int p,
+                                       int n_grid, int n_lags, int correlation, double rank_tol, size_t scratch_limit_bytes,
+                                       double* acov_out, double* spectrum_out, int32_t* status_io);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw

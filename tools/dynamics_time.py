@@ -4,6 +4,7 @@
     python tools/dynamics_time.py --second-order [draws ...]      the second-order rows alone
     python tools/dynamics_time.py --decomposition [draws ...]     the shock-decomposition rows alone
     python tools/dynamics_time.py --conditional [draws ...]       the conditional-forecast rows alone
+    python tools/dynamics_time.py --spectral [draws ...]          the spectral-moments rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -27,6 +28,11 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     baseline), LogpEngine.impulse_response (12 steps: Psi), the torch algebra (gather of W, Gram matrix, linalg.cholesky,
     cholesky_solve, the corrected shocks) and a second LogpEngine.simulate -- each part also timed apart; then the phase stamps of
     one call (dsge_debug_condfc_phases).
+  * --spectral (csrc/dsge_spectral.hpp), m = 40, k = 7, p = 7 (selector Z), N = 512 (257 frequencies), n_lags = 10, HP gain,
+    autocovariances only: the median of five timings of >= 1 s each of LogpEngine.spectral_moments and of the composed route that
+    was the only exact one before it -- torch.linalg.solve on the complex128 stack (draws x 257, 40, 40) (the real 80 x 80
+    embedding in float64 if this torch has no complex batched solve on the device), the einsum for H Q H^H and the cosine / sine
+    sums, chunked over 512 draws -- with its parts timed apart and the agreement of the two routes.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -237,8 +243,82 @@ def conditional_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, periods=12, series
         print(f"draws={nb:5d} phases of workgroup 0, cycles: " + ", ".join(f"{nm} {cyc[i]}" for i, nm in enumerate(names)))
 
 
+def spectral_rows(eng, sizes, n_grid=512, n_lags=10, chunk=512, repeats=5):
+    from geconpy_amd import batched
+
+    b = wl.sw_shaped_batch(64)
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p, nf = 40, 7, 7, n_grid // 2 + 1
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    dev = eng.device
+    g_h = batched.hp_gain(n_grid)
+    gain, Z = eng.to_device(g_h), eng.to_device(np.eye(p, m))
+    w = 2.0 * np.pi * np.arange(nf) / n_grid
+    z = torch.as_tensor(np.exp(-1j * w), device=dev)  # (nf,)
+    cn = np.where((np.arange(nf) == 0) | (2 * np.arange(nf) == n_grid), 1.0, 2.0)
+    wts = torch.as_tensor(cn * g_h * np.exp(1j * np.outer(np.arange(n_lags + 1), w)) / n_grid, device=dev)  # (lags, nf)
+    eye = torch.eye(m, dtype=torch.complex128, device=dev)
+    try:
+        torch.linalg.solve(eye[None].repeat(2, 1, 1), eye[None, :, :k].repeat(2, 1, 1))
+        complex_solve = True
+    except RuntimeError:
+        complex_solve = False
+    print(f"spectral moments m={m} k={k} p={p} (selector), N={n_grid} ({nf} frequencies), n_lags={n_lags}, HP gain, acov only; "
+          f"medians of {repeats} timings of >= 1 s; composed route: {'complex128' if complex_solve else 'real 2m x 2m'} batched solve, "
+          f"{chunk} draws per chunk")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        T, R = eng.to_device(np.tile(b["T_star"], (rep, 1, 1))[:nb]), eng.to_device(np.tile(R64, (rep, 1, 1))[:nb])
+        Q = eng.to_device((np.tile(b["sigma"], (rep, 1))[:nb]) ** 2)
+        status = torch.zeros(nb, dtype=torch.int32, device=dev)
+        out = dict(acov=torch.empty(nb, n_lags + 1, p, p, dtype=torch.float64, device=dev))
+        entry = lambda: eng.spectral_moments(T, R, Q, n_grid=n_grid, n_lags=n_lags, Z=Z, gain=gain, q_mode="diag_batched",  # noqa: E731
+                                             status=status, out=out)
+        acov2 = torch.empty_like(out["acov"])
+        Hbuf = torch.empty(min(nb, chunk), nf, p, k, dtype=torch.complex128, device=dev)
+
+        def solve(c0, c1):
+            Tc, Rc = T[c0:c1], R[c0:c1]
+            if complex_solve:
+                A = eye - z[None, :, None, None] * Tc[:, None]
+                X = torch.linalg.solve(A, Rc[:, None].to(torch.complex128).expand(-1, nf, -1, -1))
+            else:  # [[Ar, -Ai], [Ai, Ar]] [Xr; Xi] = [R; 0]
+                Ar = torch.eye(m, dtype=torch.float64, device=dev) - z.real[None, :, None, None] * Tc[:, None]
+                Ai = -z.imag[None, :, None, None] * Tc[:, None]
+                A2 = torch.cat([torch.cat([Ar, -Ai], dim=-1), torch.cat([Ai, Ar], dim=-1)], dim=-2)
+                B2 = torch.cat([Rc, torch.zeros_like(Rc)], dim=-2)[:, None].expand(-1, nf, -1, -1)
+                X2 = torch.linalg.solve(A2, B2)
+                X = torch.complex(X2[..., :m, :], X2[..., m:, :])
+            Hbuf[: c1 - c0] = X[:, :, :p]  # selector Z
+
+        def sums(c0, c1):
+            H = Hbuf[: c1 - c0]
+            F = torch.einsum("bnik,bk,bnjk->bnij", H, Q[c0:c1].to(torch.complex128), H.conj())
+            acov2[c0:c1] = torch.einsum("ln,bnij->blij", wts, F).real
+
+        def composed(parts=(True, True)):
+            for c0 in range(0, nb, chunk):
+                c1 = min(nb, c0 + chunk)
+                if parts[0]:
+                    solve(c0, c1)
+                if parts[1]:
+                    sums(c0, c1)
+
+        entry()
+        composed()
+        torch.cuda.synchronize()
+        assert int(status.abs().max()) == 0
+        scale = acov2[:, 0].abs().amax(dim=(1, 2))
+        diff = ((out["acov"] - acov2).abs().amax(dim=(1, 2, 3)) / scale).max().item()
+        print(f"draws={nb:5d} entry against the composed route: {diff:.1e} of max|acov[0]| per draw")
+        t_entry, t_comp = med(entry), med(composed)
+        t_solve, t_sums = med(lambda: composed((True, False))), med(lambda: composed((False, True)))
+        print(f"draws={nb:5d} spectral_moments: {t_entry:8.3f} ms | composed route {t_comp:8.3f} ms = batched solve {t_solve:8.3f} + "
+              f"einsums {t_sums:8.3f} (sum {t_solve + t_sums:8.3f}) | entry / composed {t_entry / t_comp:5.2f}")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional")]
+    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
@@ -246,6 +326,8 @@ def main():
         return decomposition_rows(LogpEngine(0), sizes)
     if "--conditional" in sys.argv:
         return conditional_rows(LogpEngine(0), sizes)
+    if "--spectral" in sys.argv:
+        return spectral_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
