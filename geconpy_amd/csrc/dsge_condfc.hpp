@@ -17,8 +17,9 @@
 // recursion, no third propagation, and PsiQ exists already because G needs it); pass 2 propagates e+ + Delta and writes each
 // slab of x, e and d + Z x once, with one barrier per step.  No atomics: two calls give the same bits.  A shock that is not free
 // is never added to, so it comes back with the bits it came with.
+// Shared pieces (dsge_postsolve.hpp) this file calls, and the lines it keeps: docs/design/dynamics.md, "the shared pieces".
 #pragma once
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"
 
 namespace dsge {
 
@@ -26,9 +27,6 @@ constexpr int CF_THREADS = 256, CF_COLS = 16, CF_MAX_COND = 64;
 constexpr int CF_ST_SINGULAR = 512;  // DSGE_ST_COND_SINGULAR
 constexpr int CF_EPF = 6;  // CF_EPF * CF_THREADS >= CF_COLS * DSGE_MAX_N_BIG: the shocks of one step in flight
 
-__host__ __device__ inline int cf_r4(int x) { return (x + 3) & ~3; }
-// row stride of the [T | R] and [x ; e] images, the rule of dsge_dynamics.hpp: the smallest value == 2 (mod 32) that holds m4 + k4
-__host__ __device__ inline int cf_ld(int m, int k) { return (cf_r4(m) + cf_r4(k) + 29) / 32 * 32 + 2; }
 
 __host__ __device__ inline size_t cf_tri(int n) { return (size_t)n * (n + 1) / 2; }
 // the setup kernel: T, two V images, R, the masked Q, two Psi_l, G [n_cond][n_cond + 1], the diagonal of L
@@ -40,7 +38,7 @@ __host__ __device__ inline size_t cf_setup_lds_doubles(int m, int k, int n_cond)
 // Delta [(t_max + 1) |F|][16] (after them)
 __host__ __device__ inline size_t cf_paths_lds_doubles(int m, int k, int p, int n_cond, int lags, int n_free) {
   const size_t tri = cf_tri(n_cond), del = (size_t)lags * n_free * CF_COLS;
-  return (size_t)(ks_mp(m) + 2 * CF_COLS) * cf_ld(m, k) + (size_t)p * m + CF_COLS + (size_t)n_cond * (CF_COLS + 1) +
+  return (size_t)(ks_mp(m) + 2 * CF_COLS) * ps_ld(m, k) + (size_t)p * m + CF_COLS + (size_t)n_cond * (CF_COLS + 1) +
          (tri > del ? tri : del);
 }
 
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(CF_THREADS) void condfc_setup_kernel(CondFcArgs a) 
   }
   const bool prof = a.dbg != nullptr && blockIdx.x == 0 && tid < 64;
   const long long p_begin = prof ? clock64() : 0;
-  const int ld = ks_ld(m), mt = ks_mp(m) / 16, m4 = cf_r4(m), ldg = n + 1, pk = p * k;
+  const int ld = ks_ld(m), mt = ks_mp(m) / 16, m4 = ps_r4(m), ldg = n + 1, pk = p * k;
   ks_lds* Tm = (ks_lds*)smem;             // [mp][ld]
   ks_lds* Vc = Tm + ks_mat(m);            // [NC][ld]: row o of V_l in Vc[o ld + 0 .. m-1]
   ks_lds* Vn = Vc + NC * ld;
@@ -221,7 +219,7 @@ __global__ __launch_bounds__(CF_THREADS) void condfc_paths_kernel(CondFcArgs a) 
   }
   const bool prof = a.dbg != nullptr && blockIdx.x == 0 && tid < 64;
   const long long p_begin = prof ? clock64() : 0;
-  const int m4 = cf_r4(m), k4 = cf_r4(k), mp = ks_mp(m), mt = mp / 16, ld = cf_ld(m, k), lags = a.t_max + 1, nF = a.n_free;
+  const int m4 = ps_r4(m), k4 = ps_r4(k), mp = ks_mp(m), mt = mp / 16, ld = ps_ld(m, k), lags = a.t_max + 1, nF = a.n_free;
   ks_lds* TR = (ks_lds*)smem;       // [mp][ld]: T in columns 0 .. m-1, R in columns m4 .. m4+k-1
   ks_lds* cur = TR + mp * ld;       // [NC][ld]: x_{t-1} of path j in cur[j ld + 0 .. m-1], e_t in cur[j ld + m4 .. m4+k-1]
   ks_lds* nxt = cur + NC * ld;
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(CF_THREADS) void condfc_paths_kernel(CondFcArgs a) 
   {
     const double* Zg = a.Z + (a.z_batched ? (size_t)draw * p * m : 0);
     for (int idx = tid; idx < p * m; idx += NT) Zm[idx] = Zg[idx];
-    if (tid < p) dv[tid] = a.d ? a.d[(a.d_batched ? (size_t)draw * p : 0) + tid] : 0.0;
+    if (tid < p) dv[tid] = a.d ? ps_obs_slice(a.d, a.d_batched, draw, p)[tid] : 0.0;
   }
   const double* xg = a.x0 + (size_t)draw * a.x0_draw + (size_t)s0 * a.x0_path;
   auto load_x0 = [&]() {
@@ -303,9 +301,7 @@ __global__ __launch_bounds__(CF_THREADS) void condfc_paths_kernel(CondFcArgs a) 
         }
       }
       c_lo = c_hi;
-      ks_lds* sw = cur;
-      cur = nxt;
-      nxt = sw;
+      ps_swap(cur, nxt);
     }
     const double* Lg = a.chol + (size_t)draw * cf_tri(n);
     for (int idx = tid; idx < (int)cf_tri(n); idx += NT) Lp[idx] = Lg[idx];
@@ -396,9 +392,7 @@ __global__ __launch_bounds__(CF_THREADS) void condfc_paths_kernel(CondFcArgs a) 
         for (int i = 0; i < m; ++i) s = fma(Zm[o * m + i], nxt[j * ld + i], s);
         oo[((size_t)j * n_steps + t) * p + o] = dv[o] + s;
       }
-    ks_lds* sw = cur;
-    cur = nxt;
-    nxt = sw;
+    ps_swap(cur, nxt);
   }
   if (prof && tid == 0) {
     const long long p_end = clock64();

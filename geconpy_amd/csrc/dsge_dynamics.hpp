@@ -18,20 +18,18 @@
 // at m = 49..64), sym(R Q R') formed once per draw and kept in registers by the threads that own its elements; per step
 //     a = T a;   W = P T';   P = T W;   P = sym(P) + sym(R Q R')      (the prediction step of dsge_kalman_out.hpp)
 // with the two square products on the FP64 matrix core, then y = Z a + d, F = sym(Z P Z') + diag(H) on the VALU (p <= 16).
+// Shared pieces (dsge_postsolve.hpp) this file calls, and the lines it keeps: docs/design/dynamics.md, "the shared pieces".
 #pragma once
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"
 
 namespace dsge {
 
 constexpr int DY_THREADS = 256, DY_COLS = 16;
 constexpr int DY_EPF = 6;  // DY_EPF * DY_THREADS >= DY_COLS * DSGE_MAX_N_BIG: the shocks of one step in flight
 
-__host__ __device__ inline int dy_r4(int x) { return (x + 3) & ~3; }
-// row stride of the [T | R] and [x ; e] images: the smallest value == 2 (mod 32) that holds m4 + k4 doubles
-__host__ __device__ inline int dy_ld(int m, int k) { return (dy_r4(m) + dy_r4(k) + 29) / 32 * 32 + 2; }
 __host__ __device__ inline int dy_ldc(int m) { return m | 1; }  // row stride of the FEVD sums (odd: read along either index)
 __host__ __device__ inline size_t dy_lds_doubles(int m, int k) {
-  return (size_t)(ks_mp(m) + 2 * DY_COLS) * dy_ld(m, k) + (size_t)DY_COLS * dy_ldc(m) + m + DY_COLS;
+  return (size_t)(ks_mp(m) + 2 * DY_COLS) * ps_ld(m, k) + (size_t)DY_COLS * dy_ldc(m) + m + DY_COLS;
 }
 __host__ __device__ inline size_t dy_fevd_lds_doubles(int m, int c) { return (size_t)c * dy_ldc(m) + m + c; }
 
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(DY_THREADS) void dynamics_propagate_kernel(DynArgs 
     if (fo) for (size_t i = tid; i < path_sz * a.n_paths; i += NT) fo[i] = NAN;
     return;
   }
-  const int m4 = dy_r4(m), k4 = dy_r4(k), mp = ks_mp(m), mt = mp / 16, ld = dy_ld(m, k), ldc = dy_ldc(m);
+  const int m4 = ps_r4(m), k4 = ps_r4(k), mp = ks_mp(m), mt = mp / 16, ld = ps_ld(m, k), ldc = dy_ldc(m);
   ks_lds* TR = (ks_lds*)smem;      // [mp][ld]: T in columns 0 .. m-1, R in columns m4 .. m4+k-1
   ks_lds* cur = TR + mp * ld;      // [NC][ld]: x_{t-1} of path j in cur[j ld + 0 .. m-1], e_t in cur[j ld + m4 .. m4+k-1]
   ks_lds* nxt = cur + NC * ld;
@@ -172,7 +170,7 @@ __global__ __launch_bounds__(DY_THREADS) void dynamics_fevd_kernel(FevdArgs a) {
   const size_t path_sz = (size_t)a.n_steps * m;
   double* fo = a.fevd + (size_t)draw * path_sz * c;
   if (a.status && a.status[draw] != 0) {
-    for (size_t i = tid; i < path_sz * c; i += NT) fo[i] = NAN;
+    ps_fill_nan(fo, path_sz * c, tid, NT);
     return;
   }
   ks_lds* cum = (ks_lds*)smem;  // [c][ldc]
@@ -228,14 +226,14 @@ __global__ __launch_bounds__(FC_THREADS) void dynamics_forecast_kernel(FcArgs a)
   double* y_o = a.y_out ? a.y_out + (size_t)draw * n * p : nullptr;
   double* f_o = a.f_out ? a.f_out + (size_t)draw * n * p * p : nullptr;
   if (a.status && a.status[draw] != 0) {  // failed solve: EVERY requested output of the draw is NaN
-    if (a_o) for (size_t i = tid; i < nv; i += NT) a_o[i] = NAN;
-    if (p_o) for (size_t i = tid; i < ncv; i += NT) p_o[i] = NAN;
-    if (y_o) for (size_t i = tid; i < (size_t)n * p; i += NT) y_o[i] = NAN;
-    if (f_o) for (size_t i = tid; i < (size_t)n * p * p; i += NT) f_o[i] = NAN;
+    if (a_o) ps_fill_nan(a_o, nv, tid, NT);
+    if (p_o) ps_fill_nan(p_o, ncv, tid, NT);
+    if (y_o) ps_fill_nan(y_o, (size_t)n * p, tid, NT);
+    if (f_o) ps_fill_nan(f_o, (size_t)n * p * p, tid, NT);
     return;
   }
   const bool cov = p_o || f_o;
-  const int ld = ks_ld(m), mt = ks_mp(m) / 16, m4 = dy_r4(m);
+  const int ld = ks_ld(m), mt = ks_mp(m) / 16, m4 = ps_r4(m);
   const size_t MAT = ks_mat(m);
   ks_lds* Tm = (ks_lds*)smem;
   ks_lds* P = Tm + MAT;
@@ -247,29 +245,24 @@ __global__ __launch_bounds__(FC_THREADS) void dynamics_forecast_kernel(FcArgs a)
   ks_lds* an = ac + 64;            // a_h
   ks_lds* dv = an + 64;
   ks_lds* hv = dv + PM;
-  const double* Tg = a.T + (size_t)draw * mm;
   const double* Rg = a.R + (size_t)draw * m * k;
   for (size_t idx = tid; idx < 3 * MAT; idx += NT) Tm[idx] = 0.0;  // (the padding of the three images stays zero)
   __syncthreads();
-  for (int idx = tid; idx < mm; idx += NT) {
-    const int i = idx / m, j = idx - i * m;
-    Tm[i * ld + j] = Tg[idx];
-  }
+  ps_stage_T(Tm, ld, a.T + (size_t)draw * mm, m, tid, NT);
   if (p > 0) {
-    const double* Zg = a.Z + (a.z_batched ? (size_t)draw * p * m : 0);
+    const double* Zg = ps_obs_slice(a.Z, a.z_batched, draw, p * m);
     for (int idx = tid; idx < p * m; idx += NT) Zm[idx] = Zg[idx];
     if (tid < p) {
-      dv[tid] = a.d ? a.d[(a.d_batched ? (size_t)draw * p : 0) + tid] : 0.0;
-      hv[tid] = a.Hdiag ? a.Hdiag[(a.h_batched ? (size_t)draw * p : 0) + tid] : 0.0;
+      dv[tid] = a.d ? ps_obs_slice(a.d, a.d_batched, draw, p)[tid] : 0.0;
+      hv[tid] = a.Hdiag ? ps_obs_slice(a.Hdiag, a.h_batched, draw, p)[tid] : 0.0;
     }
   }
   if (tid < m) ac[tid] = a.a0[(size_t)draw * m + tid];
   // G = sym(R Q R'), once per draw: R -> P, R Q -> W, then element idx = tid + q NT of G (upper triangle) in g[q]
   double g[FC_PF] = {};
   if (cov) {
-    const bool qb = a.q_mode == DSGE_Q_DIAG_BATCHED || a.q_mode == DSGE_Q_FULL_BATCHED;
-    const bool qf = a.q_mode == DSGE_Q_FULL_SHARED || a.q_mode == DSGE_Q_FULL_BATCHED;
-    const double* Qg = a.Q + (qb ? (size_t)draw * (qf ? k * k : k) : 0);
+    bool qf;
+    const double* Qg = ps_q_slice(a.Q, a.q_mode, draw, k, &qf);
     for (int idx = tid; idx < m * k; idx += NT) {
       const int i = idx / k, c = idx - i * k;
       P[i * ld + c] = Rg[idx];

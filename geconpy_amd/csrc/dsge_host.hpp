@@ -181,6 +181,24 @@ int set_lds(K kernel, size_t bytes) {
   return DSGE_SUCCESS;
 }
 
+// One launch with a dynamic LDS image: refused beyond LDS_LIMIT (DSGE_ERR_TOO_LARGE, message `what`), else set_lds, launch, check.
+template <typename K, typename A>
+int launch_with_lds(K kernel, unsigned grid, int threads, size_t lds_bytes, hipStream_t stream, const A& args, const char* what) {
+  if (lds_bytes > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, what);
+  if (int rc = set_lds(kernel, lds_bytes)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds_bytes, stream, args);
+  HIP_TRY(hipGetLastError());
+  return DSGE_SUCCESS;
+}
+
+// grid = batch x units workgroups; beyond 2^31 - 1 the call is refused (DSGE_ERR_TOO_LARGE, `what` is the message)
+inline int batch_grid(int batch, int units, const char* what, unsigned* grid) {
+  const long long g = (long long)batch * units;
+  if (g > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, what);
+  *grid = (unsigned)g;
+  return DSGE_SUCCESS;
+}
+
 #define DISPATCH_BS(bs, MAXBS, ...)                                                  \
   switch (bs) {                                                                      \
     case 1: { constexpr int BS = 1; __VA_ARGS__; } break;                            \

@@ -30,7 +30,7 @@
 #pragma once
 #include <type_traits>
 
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"  // the slice of Q, the padding rule and the NaN fill (docs/design/dynamics.md, "the shared pieces")
 
 namespace dsge {
 
@@ -76,9 +76,8 @@ __global__ __launch_bounds__(KS_THREADS) void smoother_basis_kernel(KsArgs a) {
   double* pvs = hv + m;                // [2]: pivot norm^2, pivot index
   const double* Tg = a.T + (size_t)draw * m * m;
   const double* Rg = a.R + (size_t)draw * m * k;
-  const bool qb = a.q_mode == DSGE_Q_DIAG_BATCHED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const bool qf = a.q_mode == DSGE_Q_FULL_SHARED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const double* Qg = a.Q + (qb ? (size_t)draw * (qf ? k * k : k) : 0);
+  bool qf;
+  const double* Qg = ps_q_slice(a.Q, a.q_mode, draw, k, &qf);
   for (int idx = tid; idx < m * nc; idx += NT) {
     const int i = idx / nc, c = idx - i * nc;
     double v;
@@ -189,14 +188,14 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
   double* ps_o = a.p_s ? a.p_s + (size_t)draw * ncv : nullptr;
   double* es_o = a.e_s ? a.e_s + (size_t)draw * ne : nullptr;
   if (a.status[draw] != 0) {  // failed solve or filter: EVERY requested output of the draw is NaN
-    if (as_o) for (size_t i = tid; i < nv; i += NT) as_o[i] = NAN;
-    if (ps_o) for (size_t i = tid; i < ncv; i += NT) ps_o[i] = NAN;
-    if (es_o) for (size_t i = tid; i < ne; i += NT) es_o[i] = NAN;
+    if (as_o) ps_fill_nan(as_o, nv, tid, NT);
+    if (ps_o) ps_fill_nan(ps_o, ncv, tid, NT);
+    if (es_o) ps_fill_nan(es_o, ne, tid, NT);
     return;
   }
-  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = (m + 3) & ~3;
+  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = ps_r4(m);
   const size_t MAT = ks_mat(m);
-  const int r = a.rank[draw], rt = (r + 15) / 16, r4 = (r + 3) & ~3;
+  const int r = a.rank[draw], rt = (r + 15) / 16, r4 = ps_r4(r);
   const bool cov = ps_o != nullptr;
   ks_lds* V = (ks_lds*)smem;
   ks_lds* Pf = V + MAT;
@@ -231,9 +230,8 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
   ks_lds* apv = pl; pl += 64;   // a_pred[t+1]
   ks_lds* afv = pl; pl += 64;   // a_filt[t]
   ks_lds* qd = pl; pl += 64;    // diagonal Q
-  const bool qb = a.q_mode == DSGE_Q_DIAG_BATCHED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const bool qf = a.q_mode == DSGE_Q_FULL_SHARED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const double* Qg = a.Q + (qb ? (size_t)draw * (qf ? k * k : k) : 0);
+  bool qf;
+  const double* Qg = ps_q_slice(a.Q, a.q_mode, draw, k, &qf);
   const double* apg = a.a_pred + (size_t)draw * nv;
   const double* afg = a.a_filt + (size_t)draw * nv;
   const double* ppg = a.p_pred + (size_t)draw * nv * m;
@@ -324,9 +322,9 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
       __syncthreads();
       const double dk = Pp[kk * ld + kk];
       if (!(dk > 0.0)) {  // (uniform) this step and every earlier one are NaN, the later ones stay
-        if (as_o) for (size_t i = tid; i < ot + m; i += NT) as_o[i] = NAN;
-        if (ps_o) for (size_t i = tid; i < (a.full_cov ? (ot + m) * m : ot + m); i += NT) ps_o[i] = NAN;
-        if (es_o) for (size_t i = tid; i < (size_t)(t + 2) * k; i += NT) es_o[i] = NAN;
+        if (as_o) ps_fill_nan(as_o, ot + m, tid, NT);
+        if (ps_o) ps_fill_nan(ps_o, a.full_cov ? (ot + m) * m : ot + m, tid, NT);
+        if (es_o) ps_fill_nan(es_o, (size_t)(t + 2) * k, tid, NT);
         if (tid == 0) a.status[draw] |= DSGE_ST_SMOOTHER_SINGULAR;
         return;
       }

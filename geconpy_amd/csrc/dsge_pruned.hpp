@@ -12,7 +12,7 @@
 // is stored in FRAGMENT ORDER: the 64 A values of v_mfma_f64_16x16x4_f64 for (row tile, four columns) are contiguous, one coalesced
 // 512-byte load per wavefront and product.
 //
-// pruned_propagate_kernel: one workgroup of 256 threads per (draw, group of 16 paths), on the scheme of dynamics_propagate_kernel:
+// pruned_propagate_kernel: one workgroup of 256 threads per (draw, group of 16 paths), on the scheme of the first-order propagation:
 // [T | R] in one padded LDS image, [x_f ; u_t] of the 16 paths path-major and double-buffered, x_s likewise.  A step is
 //     x_f' = [T | R] [x_f ; u]                                     ks_gemm, K = n4 + k4
 //     x_s' = T x_s + P mon                                         one accumulator per row tile: T out of LDS, P out of L2
@@ -23,21 +23,21 @@
 // Generalised impulse responses: one workgroup per (draw, impulse), baseline path p in column p and the same path with the impulse
 // added to e_0 in column 8 + p, 8 pairs per pass; after each step thread i adds the differences of the pass in ascending path
 // order to girf[t][i] (the same thread at every pass: no atomics, the mean is reproducible bit for bit).
+// Padding, stride, [T | R] staging, the x_f product step and the NaN fill: dsge_postsolve.hpp (docs/design/dynamics.md).
 #pragma once
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"
 
 namespace dsge {
 
 constexpr int PR_THREADS = 256, PR_COLS = 16, PR_PAIRS = 8;
 constexpr int PR_MAX_N = 64, PR_MAX_S = 24, PR_MAX_K = 12;
 
-__host__ __device__ inline int pr_r4(int x) { return (x + 3) & ~3; }
 // columns of the panel: the monomials, padded to four products (16 columns) per pass of the product loop
 __host__ __device__ inline int pr_kp(int s, int k) { return s * (s + 1) / 2 + s * k + k * (k + 1) / 2 + 1; }
 __host__ __device__ inline int pr_kp16(int s, int k) { return (pr_kp(s, k) + 15) & ~15; }
-// row stride of the [T | R] and [x_f ; u ; 1 ; 0] images / of the x_s images: the smallest value == 2 (mod 32) that holds the row
-__host__ __device__ inline int pr_ld(int n, int k) { return (pr_r4(n) + pr_r4(k) + 2 + 29) / 32 * 32 + 2; }
-__host__ __device__ inline int pr_lds(int n) { return (pr_r4(n) + 29) / 32 * 32 + 2; }
+// row stride of the [T | R] and [x_f ; u ; 1 ; 0] images (two columns behind the shocks) / of the x_s images (no shocks)
+__host__ __device__ inline int pr_ld(int n, int k) { return ps_ld(n, k, 2); }
+__host__ __device__ inline int pr_lds(int n) { return ps_ld(n, 0); }
 __host__ __device__ inline size_t pr_panel_doubles(int n, int s, int k) { return (size_t)ks_mp(n) * pr_kp16(s, k); }
 __host__ __device__ inline size_t pr_lds_doubles(int n, int s, int k) {
   return (size_t)(ks_mp(n) + 2 * PR_COLS) * pr_ld(n, k) + (size_t)2 * PR_COLS * pr_lds(n) + pr_kp16(s, k) / 2;
@@ -134,19 +134,17 @@ __global__ __launch_bounds__(PR_THREADS) void pruned_propagate_kernel(PrunedArgs
   double* go = a.girf ? a.girf_out + ((size_t)draw * a.units + unit) * path_sz : nullptr;
   if (a.status && a.status[draw] != 0) {  // failed solve: EVERY output of the draw is NaN
     if (a.girf) {
-      for (size_t i = tid; i < path_sz; i += NT) go[i] = NAN;
+      ps_fill_nan(go, path_sz, tid, NT);
     } else {
       const int s0 = unit * NC, nc = a.n_paths - s0 < NC ? a.n_paths - s0 : NC;
       const size_t o = ((size_t)draw * a.n_paths + s0) * path_sz;
-      for (size_t i = tid; i < (size_t)nc * path_sz; i += NT) {
-        if (a.x_out) a.x_out[o + i] = NAN;
-        if (a.xf_out) a.xf_out[o + i] = NAN;
-        if (a.xs_out) a.xs_out[o + i] = NAN;
-      }
+      if (a.x_out) ps_fill_nan(a.x_out + o, (size_t)nc * path_sz, tid, NT);
+      if (a.xf_out) ps_fill_nan(a.xf_out + o, (size_t)nc * path_sz, tid, NT);
+      if (a.xs_out) ps_fill_nan(a.xs_out + o, (size_t)nc * path_sz, tid, NT);
     }
     return;
   }
-  const int n4 = pr_r4(n), k4 = pr_r4(k), mp = ks_mp(n), mt = mp / 16, ld = pr_ld(n, k), lds = pr_lds(n);
+  const int n4 = ps_r4(n), k4 = ps_r4(k), mp = ks_mp(n), mt = mp / 16, ld = pr_ld(n, k), lds = pr_lds(n);
   const int kp16 = pr_kp16(s, k), nk4 = kp16 / 4, one = n4 + k4, zero = one + 1;
   ks_lds* TR = (ks_lds*)smem;     // [mp][ld]: T in columns 0 .. n-1, R in columns n4 .. n4+k-1
   ks_lds* fcur = TR + mp * ld;    // [NC][ld]: x_f of column j in 0 .. n-1, u_t in n4 .. n4+k-1, 1 at `one`, 0 at `zero`
@@ -156,16 +154,7 @@ __global__ __launch_bounds__(PR_THREADS) void pruned_propagate_kernel(PrunedArgs
   __attribute__((address_space(3))) int* tab = (__attribute__((address_space(3))) int*)(snxt + NC * lds);  // [kp16]: p | q << 16
   for (size_t idx = tid; idx < pr_lds_doubles(n, s, k); idx += NT) TR[idx] = 0.0;
   __syncthreads();
-  const double* Tg = a.T + (size_t)draw * n * n;
-  const double* Rg = a.R + (size_t)draw * n * k;
-  for (int idx = tid; idx < n * n; idx += NT) {
-    const int i = idx / n, j = idx - i * n;
-    TR[i * ld + j] = Tg[idx];
-  }
-  for (int idx = tid; idx < n * k; idx += NT) {
-    const int i = idx / k, c = idx - i * k;
-    TR[i * ld + n4 + c] = Rg[idx];
-  }
+  ps_stage_TR(TR, ld, n4, a.T + (size_t)draw * n * n, a.R + (size_t)draw * n * k, n, k, tid, NT);
   if (tid < 2 * NC) (tid < NC ? fcur : fnxt)[(tid & (NC - 1)) * ld + one] = 1.0;
   for (int c = tid; c < kp16; c += NT) {
     int p, q, e;
@@ -218,9 +207,7 @@ __global__ __launch_bounds__(PR_THREADS) void pruned_propagate_kernel(PrunedArgs
     for (int t = 0; t < a.n_steps; ++t) {
       long long p0 = prof ? clock64() : 0, p1 = 0, p2 = 0;
       const double ev = shock(t + 1);  // u_{t+1}, in flight while this step multiplies (zero behind the last shock)
-      ks_gemm<false, true>((const ks_lds*)TR, ld, (const ks_lds*)fcur, ld, mt, 1, n4 + k4, 0, 4, [&](int i, int j, double v) {
-        if (i < n4) fnxt[j * ld + i] = v;
-      });
+      ps_step(TR, fcur, fnxt, ld, mt, n4 + k4, n4);
       if (prof) p1 = clock64();
       for (int ti = wave; ti < mt; ti += 4) {  // x_s' = T x_s + P mon: one accumulator per row tile
         ks_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
@@ -280,12 +267,8 @@ __global__ __launch_bounds__(PR_THREADS) void pruned_propagate_kernel(PrunedArgs
         pc[0] += p1 - p0; pc[1] += p2 - p1; pc[2] += p3 - p2; pc[3] += p4 - p3; pc[4] += clock64() - p4;
         ++p_steps;
       }
-      ks_lds* sw = fcur;
-      fcur = fnxt;
-      fnxt = sw;
-      sw = scur;
-      scur = snxt;
-      snxt = sw;
+      ps_swap(fcur, fnxt);
+      ps_swap(scur, snxt);
     }
   }
   if (prof && lane == 0) {

@@ -12,20 +12,18 @@
 // e_{t+1} and x_{t+1} are in flight while step t multiplies.  After the step's only barrier every thread reads finished columns:
 // the n_out x C block of a path and step is written contiguously, the place of each of its elements looked up in a table built
 // once (no division in the step loop), the remainder formed by the thread that writes it, in ascending component order.
+// Shared pieces (dsge_postsolve.hpp) this file calls, and the lines it keeps: docs/design/dynamics.md, "the shared pieces".
 #pragma once
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"
 
 namespace dsge {
 
 constexpr int SD_THREADS = 256, SD_COLS = 16, SD_MAX_PACK = 8;  // (G >= 2: at most 8 paths in a tile)
 constexpr int SD_PF = 3;  // SD_PF * SD_THREADS >= SD_MAX_PACK * DSGE_MAX_N_BIG: x (and e, k <= m) of one step in flight
 
-__host__ __device__ inline int sd_r4(int x) { return (x + 3) & ~3; }
-// row stride of the [T | R] and [X ; E] images, the rule of dsge_dynamics.hpp: the smallest value == 2 (mod 32) that holds m4 + k4
-__host__ __device__ inline int sd_ld(int m, int k) { return (sd_r4(m) + sd_r4(k) + 29) / 32 * 32 + 2; }
 __host__ __device__ inline size_t sd_lds_doubles(int m, int k, int p, int pack) {
   // [T | R], two [X ; E] images, two copies of x_t of the pack, Z, the table of the largest output block (int32, two per double)
-  return (size_t)(ks_mp(m) + 2 * SD_COLS) * sd_ld(m, k) + 2 * (size_t)pack * m + (size_t)p * m + ((size_t)m * (SD_COLS / pack + 1) + 1) / 2;
+  return (size_t)(ks_mp(m) + 2 * SD_COLS) * ps_ld(m, k) + 2 * (size_t)pack * m + (size_t)p * m + ((size_t)m * (SD_COLS / pack + 1) + 1) / 2;
 }
 
 struct ShockDecompArgs {
@@ -62,7 +60,7 @@ __global__ __launch_bounds__(SD_THREADS) void shock_decomp_kernel(ShockDecompArg
   }
   const bool prof = a.dbg != nullptr && blockIdx.x == 0 && tid < 64;
   long long pc[4] = {0, 0, 0, 0}, p_begin = prof ? clock64() : 0;
-  const int m4 = sd_r4(m), k4 = sd_r4(k), mp = ks_mp(m), mt = mp / 16, ld = sd_ld(m, k);
+  const int m4 = ps_r4(m), k4 = ps_r4(k), mp = ks_mp(m), mt = mp / 16, ld = ps_ld(m, k);
   ks_lds* TR = (ks_lds*)smem;            // [mp][ld]: T in columns 0 .. m-1, R in columns m4 .. m4+k-1
   ks_lds* cur = TR + mp * ld;            // [NC][ld]: column q G + c of X_{t-1} in cur[(q G + c) ld + 0 .. m-1], of E_t behind m4
   ks_lds* nxt = cur + NC * ld;

@@ -22,7 +22,7 @@
 #pragma once
 #include <type_traits>
 
-#include "dsge_mfma_f64.hpp"
+#include "dsge_postsolve.hpp"  // staging of T, the per-draw slices, the padding rule, the NaN fill (docs/design/dynamics.md)
 
 namespace dsge {
 
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(SS_THREADS) void simsmooth_forward_kernel(SsArgs a)
   if (g == 0 && tid == 0) a.snap[draw] = stw;
   if (stw != 0) return;  // failed solve or filter: the backward kernel fills the outputs with NaN
   const int s0 = g * NC, nc = a.n_paths - s0 < NC ? a.n_paths - s0 : NC;
-  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = (m + 3) & ~3;
+  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = ps_r4(m);
   ks_lds* Tm = (ks_lds*)smem;               // [mp][ld]
   ks_lds* AP = Tm + ks_mat(m);              // [NC][ld]  a*_pred of the step, path-major
   ks_lds* AF = AP + NC * ld;                // [NC][ld]  a*_filt
@@ -96,23 +96,19 @@ __global__ __launch_bounds__(SS_THREADS) void simsmooth_forward_kernel(SsArgs a)
   const size_t nlds = ssf_lds_doubles(m, p);
   for (size_t idx = tid; idx < nlds; idx += NT) Tm[idx] = 0.0;
   __syncthreads();
-  const double* Tg = a.T + (size_t)draw * mm;
-  const double* Zg = a.Z + (a.z_batched ? (size_t)draw * p * m : 0);
+  const double* Zg = ps_obs_slice(a.Z, a.z_batched, draw, p * m);
   const double* ppg = a.p_pred + (size_t)draw * n * mm;
   const size_t path_sz = (size_t)n * m, pbase = ((size_t)draw * a.n_paths + s0) * path_sz;
   const double* xpg = a.xp + pbase;
   double* apo = a.a_pred + pbase;
   double* afo = a.a_filt + pbase;
   const double* etg = a.eta ? a.eta + (size_t)draw * a.eta_draw + (size_t)s0 * n * p : nullptr;
-  for (int idx = tid; idx < mm; idx += NT) {
-    const int i = idx / m, j = idx - i * m;
-    Tm[i * ld + j] = Tg[idx];
-    P[idx] = ppg[idx];
-  }
+  ps_stage_T(Tm, ld, a.T + (size_t)draw * mm, m, tid, NT);
+  for (int idx = tid; idx < mm; idx += NT) P[idx] = ppg[idx];
   for (int idx = tid; idx < p * m; idx += NT) Zm[idx] = Zg[idx];
   if (tid < p) {
-    dv[tid] = a.d ? a.d[(a.d_batched ? (size_t)draw * p : 0) + tid] : 0.0;
-    hv[tid] = a.Hdiag ? a.Hdiag[(a.h_batched ? (size_t)draw * p : 0) + tid] : 0.0;
+    dv[tid] = a.d ? ps_obs_slice(a.d, a.d_batched, draw, p)[tid] : 0.0;
+    hv[tid] = a.Hdiag ? ps_obs_slice(a.Hdiag, a.h_batched, draw, p)[tid] : 0.0;
   }
   __syncthreads();
   for (int t = 0; t < n; ++t) {
@@ -231,13 +227,13 @@ __global__ __launch_bounds__(SS_THREADS) void simsmooth_backward_kernel(SsArgs a
   double* xo = a.x_out ? a.x_out + pbase : nullptr;
   double* eo = a.e_out ? a.e_out + ebase : nullptr;
   if (a.snap[draw] != 0) {  // failed solve or filter: EVERY path of the draw is NaN
-    if (xo) for (size_t i = tid; i < (size_t)nc * path_sz; i += NT) xo[i] = NAN;
-    if (eo) for (size_t i = tid; i < (size_t)nc * eps_sz; i += NT) eo[i] = NAN;
+    if (xo) ps_fill_nan(xo, (size_t)nc * path_sz, tid, NT);
+    if (eo) ps_fill_nan(eo, (size_t)nc * eps_sz, tid, NT);
     return;
   }
-  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = (m + 3) & ~3, kt = (k + 15) / 16;
+  const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = ps_r4(m), kt = (k + 15) / 16;
   const size_t MAT = ks_mat(m);
-  const int r = a.rank[draw], rt = (r + 15) / 16, r4 = (r + 3) & ~3;
+  const int r = a.rank[draw], rt = (r + 15) / 16, r4 = ps_r4(r);
   ks_lds* Pf = (ks_lds*)smem;
   ks_lds* Pp = Pf + MAT;
   ks_lds* W = Pp + MAT;
@@ -268,9 +264,8 @@ __global__ __launch_bounds__(SS_THREADS) void simsmooth_backward_kernel(SsArgs a
     UT = UTl;
     UR = URl;
   }
-  const bool qb = a.q_mode == DSGE_Q_DIAG_BATCHED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const bool qf = a.q_mode == DSGE_Q_FULL_SHARED || a.q_mode == DSGE_Q_FULL_BATCHED;
-  const double* Qg = a.Q + (qb ? (size_t)draw * (qf ? k * k : k) : 0);
+  bool qf;
+  const double* Qg = ps_q_slice(a.Q, a.q_mode, draw, k, &qf);
   const double* xpg = a.xp + pbase;
   const double* apg = a.a_pred + pbase;
   const double* afg = a.a_filt + pbase;
@@ -336,8 +331,8 @@ __global__ __launch_bounds__(SS_THREADS) void simsmooth_backward_kernel(SsArgs a
       const double dk = Pp[kk * ld + kk];
       if (!(dk > 0.0)) {  // (uniform, and the same verdict in every group of the draw) this step and every earlier one are NaN
         for (int j = 0; j < nc; ++j) {
-          if (xo) for (size_t i = tid; i < ot + m; i += NT) xo[(size_t)j * path_sz + i] = NAN;
-          if (eo) for (size_t i = tid; i < (size_t)(t + 2) * k; i += NT) eo[(size_t)j * eps_sz + i] = NAN;
+          if (xo) ps_fill_nan(xo + (size_t)j * path_sz, ot + m, tid, NT);
+          if (eo) ps_fill_nan(eo + (size_t)j * eps_sz, (size_t)(t + 2) * k, tid, NT);
         }
         if (g == 0 && tid == 0) a.status[draw] |= DSGE_ST_SMOOTHER_SINGULAR;
         return;

@@ -13,7 +13,7 @@
 // sums the stored F_n over n in ascending order with cosines and sines from an LDS table -- no atomics, and no dependence on the
 // grouping above -- and writes the NaN and the status bit of a skipped or singular draw.
 #pragma once
-#include "dsge_device.hpp"
+#include "dsge_postsolve.hpp"  // the per-draw slices of Q, Z, Hdiag and the NaN fill (docs/design/dynamics.md, "the shared pieces")
 
 #include "../../include/dsge_hip.h"
 
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void spectral_solve_kernel(SpectralArgs a) {
   if (has_z) {
     const double* Zg = a.Z + (a.z_batched ? (size_t)draw * p * m : 0);
     for (int i = lane; i < p * m; i += 64) Zs[i] = Zg[i];
-    for (int i = lane; i < p; i += 64) Hd[i] = a.Hdiag ? a.Hdiag[(a.h_batched ? (size_t)draw * p : 0) + i] : 0.0;
+    for (int i = lane; i < p; i += 64) Hd[i] = a.Hdiag ? ps_obs_slice(a.Hdiag, a.h_batched, draw, p)[i] : 0.0;
   }
   const double tol = a.rank_tol > 0.0 ? a.rank_tol : 1e-12;
   const double inv_2pi = 0.15915494309189535;

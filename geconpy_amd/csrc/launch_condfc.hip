@@ -40,19 +40,13 @@ int launch_condfc(const CondFcProblem& c, const double* T, const double* R, cons
   }
   const size_t lds_setup = c.n_cond > 0 ? dsge::cf_setup_lds_doubles(c.m, c.k, c.n_cond) * sizeof(double) : 0;
   const size_t lds_paths = dsge::cf_paths_lds_doubles(c.m, c.k, c.p, c.n_cond, c.n_cond > 0 ? c.t_max + 1 : 0, c.n_free) * sizeof(double);
-  if (lds_setup > LDS_LIMIT || lds_paths > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: the LDS image exceeds 160 KB");
-  const long long grid = (long long)c.batch * a.groups;
-  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "conditional forecast: batch x path groups exceeds the grid");
-  int rc;
-  if (c.n_cond > 0) {
-    if ((rc = set_lds(dsge::condfc_setup_kernel, lds_setup))) return rc;
-    hipLaunchKernelGGL(dsge::condfc_setup_kernel, dim3((unsigned)c.batch), dim3(dsge::CF_THREADS), lds_setup, st, a);
-    HIP_TRY(hipGetLastError());
-  }
-  if ((rc = set_lds(dsge::condfc_paths_kernel, lds_paths))) return rc;
-  hipLaunchKernelGGL(dsge::condfc_paths_kernel, dim3((unsigned)grid), dim3(dsge::CF_THREADS), lds_paths, st, a);
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  const char* too_large = "conditional forecast: the LDS image exceeds 160 KB";
+  if (lds_setup > LDS_LIMIT || lds_paths > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before the grid's refusal and any launch)
+  unsigned grid;
+  if (int rc = batch_grid(c.batch, a.groups, "conditional forecast: batch x path groups exceeds the grid", &grid)) return rc;
+  if (c.n_cond > 0)
+    if (int rc = launch_with_lds(dsge::condfc_setup_kernel, c.batch, dsge::CF_THREADS, lds_setup, st, a, too_large)) return rc;
+  return launch_with_lds(dsge::condfc_paths_kernel, grid, dsge::CF_THREADS, lds_paths, st, a, too_large);
 }
 
 }  // namespace dsge_host

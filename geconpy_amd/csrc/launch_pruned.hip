@@ -14,10 +14,11 @@ int launch_pruned(const PrunedProblem& p, int batch, const double* eps, const do
                   hipStream_t st) {
   const int n = p.n, s = p.s, k = p.k;
   const size_t lds = dsge::pr_lds_doubles(n, s, k) * sizeof(double);
-  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "pruned dynamics: LDS budget exceeded");
+  const char* too_large = "pruned dynamics: LDS budget exceeded";
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before the grid's refusal and the pack kernel)
   const int units = girf_out ? p.c : (p.n_paths + dsge::PR_COLS - 1) / dsge::PR_COLS;
-  const long long grid = (long long)batch * units;
-  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "pruned dynamics: batch x path groups exceeds the grid");
+  unsigned grid;
+  if (int rc = batch_grid(batch, units, "pruned dynamics: batch x path groups exceeds the grid", &grid)) return rc;
   dsge::PrunedPackArgs pk{};
   pk.gyy = p.gyy; pk.gyu = p.gyu; pk.guu = p.guu; pk.gss = p.gss; pk.status = status; pk.panel = panel; pk.batch = batch; pk.n = n;
   pk.s = s; pk.k = k;
@@ -29,11 +30,7 @@ int launch_pruned(const PrunedProblem& p, int batch, const double* eps, const do
   a.n = n; a.s = s; a.k = k; a.n_paths = p.n_paths; a.n_steps = p.n_steps; a.n_shock_steps = p.n_shock_steps; a.units = units;
   a.girf = girf_out ? 1 : 0; a.dbg = g_pruned_dbg;
   for (int i = 0; i < s; ++i) a.S[i] = (unsigned char)p.S[i];
-  int rc;
-  if ((rc = set_lds(dsge::pruned_propagate_kernel, lds))) return rc;
-  hipLaunchKernelGGL(dsge::pruned_propagate_kernel, dim3((unsigned)grid), dim3(dsge::PR_THREADS), lds, st, a);
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  return launch_with_lds(dsge::pruned_propagate_kernel, grid, dsge::PR_THREADS, lds, st, a, too_large);
 }
 
 }  // namespace dsge_host

@@ -22,15 +22,12 @@ int launch_shock_decomp(const double* T, const double* R, const double* eps, con
   a.units = (n_paths + a.pack - 1) / a.pack;
   for (int j = 0; j < k; ++j) a.grp[j] = (unsigned char)(grp ? grp[j] : j);
   for (int i = 0; i < n_out; ++i) a.var[i] = (unsigned char)(var ? var[i] : i);
+  const char* too_large = "shock decomposition: [T | R] does not fit the LDS";
   const size_t lds = shock_decomp_lds_bytes(m, k, obs_out ? p : 0, n_groups);
-  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: [T | R] does not fit the LDS");
-  const long long grid = (long long)batch * a.units;
-  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "shock decomposition: batch x path packs exceeds the grid");
-  int rc;
-  if ((rc = set_lds(dsge::shock_decomp_kernel, lds))) return rc;
-  hipLaunchKernelGGL(dsge::shock_decomp_kernel, dim3((unsigned)grid), dim3(dsge::SD_THREADS), lds, st, a);
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (the LDS refusal comes before the grid's)
+  unsigned grid;
+  if (int rc = batch_grid(batch, a.units, "shock decomposition: batch x path packs exceeds the grid", &grid)) return rc;
+  return launch_with_lds(dsge::shock_decomp_kernel, grid, dsge::SD_THREADS, lds, st, a, too_large);
 }
 
 }  // namespace dsge_host

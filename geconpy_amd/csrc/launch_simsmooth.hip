@@ -18,22 +18,13 @@ int launch_simulation_smoother(const double* T, const ShockCov& q, const ObsMode
   a.q_mode = q.mode; a.z_batched = o.z_batched; a.d_batched = o.d_batched; a.h_batched = o.h_batched; a.cv = filter_conv(o.jitter);
   a.missing_fill = o.missing_fill;
   const size_t lds_f = dsge::ssf_lds_doubles(m, o.p) * sizeof(double), lds_b = dsge::ssb_lds_doubles(m) * sizeof(double);
-  if (lds_f > LDS_LIMIT || lds_b > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "simulation smoother: LDS budget exceeded");
-  const long long grid = (long long)batch * a.groups;
-  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "simulation smoother: batch x path groups exceeds the grid");
-  int rc;
-  if ((rc = set_lds(dsge::simsmooth_forward_kernel, lds_f))) return rc;
-  hipLaunchKernelGGL(dsge::simsmooth_forward_kernel, dim3((unsigned)grid), dim3(dsge::SS_THREADS), lds_f, st, a);
-  HIP_TRY(hipGetLastError());
-  if (dsge::ss_u_global(m)) {
-    if ((rc = set_lds(dsge::simsmooth_backward_kernel<true>, lds_b))) return rc;
-    hipLaunchKernelGGL(dsge::simsmooth_backward_kernel<true>, dim3((unsigned)grid), dim3(dsge::SS_THREADS), lds_b, st, a);
-  } else {
-    if ((rc = set_lds(dsge::simsmooth_backward_kernel<false>, lds_b))) return rc;
-    hipLaunchKernelGGL(dsge::simsmooth_backward_kernel<false>, dim3((unsigned)grid), dim3(dsge::SS_THREADS), lds_b, st, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  const char* too_large = "simulation smoother: LDS budget exceeded";
+  if (lds_f > LDS_LIMIT || lds_b > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before the grid's refusal and any launch)
+  unsigned grid;
+  if (int rc = batch_grid(batch, a.groups, "simulation smoother: batch x path groups exceeds the grid", &grid)) return rc;
+  if (int rc = launch_with_lds(dsge::simsmooth_forward_kernel, grid, dsge::SS_THREADS, lds_f, st, a, too_large)) return rc;
+  if (dsge::ss_u_global(m)) return launch_with_lds(dsge::simsmooth_backward_kernel<true>, grid, dsge::SS_THREADS, lds_b, st, a, too_large);
+  return launch_with_lds(dsge::simsmooth_backward_kernel<false>, grid, dsge::SS_THREADS, lds_b, st, a, too_large);
 }
 
 }  // namespace dsge_host

@@ -12,13 +12,8 @@ int launch_smoother_basis(const double* T, const double* R, const ShockCov& q, i
   dsge::KsArgs a{};
   a.T = T; a.R = R; a.Q = q.Q; a.U = U; a.UT = UT; a.UR = UR; a.rank = rank; a.status = status; a.batch = batch; a.m = m; a.k = k;
   a.q_mode = q.mode; a.rank_tol = rank_tol;
-  int rc;
-  const size_t lds_b = dsge::ksb_lds_doubles(m, k) * sizeof(double);
-  if (lds_b > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "smoother: LDS budget exceeded");
-  if ((rc = set_lds(dsge::smoother_basis_kernel, lds_b))) return rc;
-  hipLaunchKernelGGL(dsge::smoother_basis_kernel, dim3(batch), dim3(dsge::KS_THREADS), lds_b, st, a);
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  return launch_with_lds(dsge::smoother_basis_kernel, batch, dsge::KS_THREADS, dsge::ksb_lds_doubles(m, k) * sizeof(double), st, a,
+                         "smoother: LDS budget exceeded");
 }
 
 int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, int T_len,
@@ -29,19 +24,12 @@ int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, 
   a.T = T; a.R = R; a.Q = q.Q; a.U = U; a.UT = UT; a.UR = UR; a.rank = rank; a.a_pred = a_pred; a.a_filt = a_filt; a.p_pred = p_pred;
   a.p_filt = p_filt; a.a_s = a_s; a.p_s = p_s; a.e_s = e_s; a.status = status; a.batch = batch; a.m = m; a.k = k;
   a.T_len = T_len; a.q_mode = q.mode; a.full_cov = full_cov; a.rank_tol = rank_tol;
-  int rc;
+  const char* too_large = "smoother: LDS budget exceeded";
   const size_t lds = dsge::ks_lds_doubles(m) * sizeof(double);
-  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "smoother: LDS budget exceeded");
-  if ((rc = launch_smoother_basis(T, R, q, batch, m, k, rank_tol, U, UT, UR, rank, status, st))) return rc;
-  if (dsge::ks_u_global(m)) {
-    if ((rc = set_lds(dsge::kalman_smoother_kernel<true>, lds))) return rc;
-    hipLaunchKernelGGL(dsge::kalman_smoother_kernel<true>, dim3(batch), dim3(dsge::KS_THREADS), lds, st, a);
-  } else {
-    if ((rc = set_lds(dsge::kalman_smoother_kernel<false>, lds))) return rc;
-    hipLaunchKernelGGL(dsge::kalman_smoother_kernel<false>, dim3(batch), dim3(dsge::KS_THREADS), lds, st, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  if (lds > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before the basis kernel runs)
+  if (int rc = launch_smoother_basis(T, R, q, batch, m, k, rank_tol, U, UT, UR, rank, status, st)) return rc;
+  if (dsge::ks_u_global(m)) return launch_with_lds(dsge::kalman_smoother_kernel<true>, batch, dsge::KS_THREADS, lds, st, a, too_large);
+  return launch_with_lds(dsge::kalman_smoother_kernel<false>, batch, dsge::KS_THREADS, lds, st, a, too_large);
 }
 
 }  // namespace dsge_host

@@ -23,32 +23,26 @@ int launch_spectral(const SpectralProblem& s, const double* T, const double* R, 
   a.groups = groups < 1 ? 1 : (groups > a.nf ? a.nf : groups);
   const size_t lds_solve = spectral_lds_bytes(s.m, s.k, s.p, Z != nullptr);
   const size_t lds_reduce = dsge::sp_reduce_lds_doubles(s.n_grid, a.dim) * sizeof(double);
-  if (lds_solve > LDS_LIMIT || lds_reduce > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: the LDS image exceeds 160 KB");
-  const long long grid = (long long)s.batch * a.groups;
-  if (grid > 0x7fffffffLL) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: batch x frequency groups exceeds the grid");
+  const char* too_large = "spectral moments: the LDS image exceeds 160 KB";
+  if (lds_solve > LDS_LIMIT || lds_reduce > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before anything is enqueued)
+  unsigned grid;
   int rc;
+  if ((rc = batch_grid(s.batch, a.groups, "spectral moments: batch x frequency groups exceeds the grid", &grid))) return rc;
   HIP_TRY(hipMemsetAsync(flag, 0, (size_t)s.batch * sizeof(int32_t), st));
   // NC: the register row of the solve kernel, the multiple of 16 that holds m + k complex entries
-#define SPECTRAL_SOLVE(NC)                                                                                       \
-  {                                                                                                              \
-    if ((rc = set_lds(dsge::spectral_solve_kernel<NC>, lds_solve))) return rc;                                   \
-    hipLaunchKernelGGL(dsge::spectral_solve_kernel<NC>, dim3((unsigned)grid), dim3(64), lds_solve, st, a);      \
-  }
+#define SPECTRAL_SOLVE(NC) rc = launch_with_lds(dsge::spectral_solve_kernel<NC>, grid, 64, lds_solve, st, a, too_large)
   switch ((s.m + s.k + 15) / 16) {
-    case 1: SPECTRAL_SOLVE(16) break;
-    case 2: SPECTRAL_SOLVE(32) break;
-    case 3: SPECTRAL_SOLVE(48) break;
-    case 4: SPECTRAL_SOLVE(64) break;
-    case 5: SPECTRAL_SOLVE(80) break;
-    case 6: SPECTRAL_SOLVE(96) break;
+    case 1: SPECTRAL_SOLVE(16); break;
+    case 2: SPECTRAL_SOLVE(32); break;
+    case 3: SPECTRAL_SOLVE(48); break;
+    case 4: SPECTRAL_SOLVE(64); break;
+    case 5: SPECTRAL_SOLVE(80); break;
+    case 6: SPECTRAL_SOLVE(96); break;
     default: return fail(DSGE_ERR_TOO_LARGE, "spectral moments: m + k exceeds 96");
   }
 #undef SPECTRAL_SOLVE
-  HIP_TRY(hipGetLastError());
-  if ((rc = set_lds(dsge::spectral_reduce_kernel, lds_reduce))) return rc;
-  hipLaunchKernelGGL(dsge::spectral_reduce_kernel, dim3((unsigned)s.batch), dim3(dsge::SP_REDUCE_THREADS), lds_reduce, st, a);
-  HIP_TRY(hipGetLastError());
-  return DSGE_SUCCESS;
+  if (rc) return rc;
+  return launch_with_lds(dsge::spectral_reduce_kernel, s.batch, dsge::SP_REDUCE_THREADS, lds_reduce, st, a, too_large);
 }
 
 }  // namespace dsge_host
