@@ -660,8 +660,90 @@ def spectral_moments(b, name, T, R, Q, *, n_grid, n_lags, Z, Hdiag, gain, correl
     return res
 
 
+# ---- anticipated shocks ----------------------------------------------------------------------------------------------------------
+ANT_MODES = {"perfect_foresight": _lib.ANT_PERFECT_FORESIGHT, "news": _lib.ANT_NEWS}
+ANT_OUTPUTS = ("x", "w", "observed", "G")
+
+
+def expected_shocks_from_news(nu):
+    """Arrivals of news -> expected shocks (host arrays).  ``nu[..., t, j, :]`` is what is learnt at ``t`` about the shock of
+    ``t + j`` (``j = 0 .. n_lead``); the result ``e[..., t, j, :] = E_t eps_{t+j} = sum_{i = 0 .. min(t, n_lead - j)} nu[..., t - i, j + i, :]``
+    is what ``anticipated_paths`` takes in news mode."""
+    nu = np.asarray(nu, dtype=np.float64)
+    if nu.ndim < 3:
+        raise ValueError(f"nu must be (..., n_shock_steps, n_lead + 1, k); got {nu.shape}")
+    steps, leads = nu.shape[-3], nu.shape[-2]
+    e = np.zeros_like(nu)
+    for i in range(min(steps, leads)):  # what was learnt i periods earlier
+        e[..., i:, :leads - i, :] += nu[..., :steps - i, i:, :]
+    return e
+
+
+def anticipated_paths(b, name, B, C, T, R, eps, *, n_steps, mode, x0, Z, d, status, rank_tol, outputs, out=None):
+    T, R, nb, n, k = _TR(b, T, R, name)
+    if n > _lib.MAX_N:
+        raise ValueError(f"{name}: n = {n}, at most {_lib.MAX_N} variables (models of 65 .. {_lib.MAX_N_BIG} are out of scope here)")
+    B, C = _nd(b.inp(B), 3), _nd(b.inp(C), 3)
+    if tuple(B.shape) != (nb, n, n) or tuple(C.shape) != (nb, n, n):
+        raise ValueError(f"B and C must be {(nb, n, n)} like T; got {tuple(B.shape)}, {tuple(C.shape)}")
+    if mode not in ANT_MODES:
+        raise ValueError(f"mode must be one of {sorted(ANT_MODES)}; got {mode!r}")
+    news = int(mode == "news")
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in ANT_OUTPUTS for o in outputs):
+        raise ValueError(f"outputs must name at least one of {ANT_OUTPUTS}; got {outputs}")
+    eps = b.inp(eps)
+    tail = "n_shock_steps, n_lead + 1" if news else "n_shock_steps"
+    if eps.ndim not in (3 + news, 4 + news) or eps.shape[-1] != k:
+        raise ValueError(f"eps must be (n_paths, {tail}, {k}) or (batch, n_paths, {tail}, {k}) in mode {mode!r}; got {tuple(eps.shape)}")
+    n_paths, n_shock = eps.shape[-3 - news], eps.shape[-2 - news]
+    n_lead = eps.shape[-2] - 1 if news else 0
+    if n_lead < 0 or n_lead > _lib.ANT_MAX_LEAD:
+        raise ValueError(f"{name}: n_lead = {n_lead} is outside 0 .. {_lib.ANT_MAX_LEAD}")
+    eb = shared_or_batched(eps, nb, tuple(eps.shape[-3 - news:]), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    if n_steps < 0 or (news and n_steps < n_shock):
+        raise ValueError(f"n_steps = {n_steps}: news needs at least the {n_shock} shock steps of eps, perfect foresight at least 0")
+    # x0: (n,) shared by all, (n_paths, n) per path as ``simulate`` takes it, or (batch | 1, n_paths | 1, n)
+    x0 = b.inp(x0)
+    xb = xpth = 0
+    if x0 is not None:
+        shape = tuple(x0.shape)
+        if shape == (n,):
+            pass
+        elif shape == (n_paths, n):
+            xpth = 1
+        elif len(shape) == 3 and shape[0] in (1, nb) and shape[1] in (1, n_paths) and shape[2] == n:
+            xb, xpth = int(shape[0] == nb), int(shape[1] == n_paths)
+        else:
+            raise ValueError(f"x0 must be ({n},), ({n_paths}, {n}) or (batch | 1, n_paths | 1, {n}); got {shape}")
+    if Z is None:
+        if d is not None or "observed" in outputs:
+            raise ValueError(f"{name}: d and the output 'observed' need Z")
+        obs, p = dict(Z=None, z_batched=0, d=None, d_batched=0), 0
+    else:
+        Z = b.inp(Z)
+        if Z.ndim not in (2, 3) or Z.shape[-1] != n or Z.shape[-2] < 1:
+            raise ValueError(f"Z must be (p, {n}) or (batch, p, {n}); got {tuple(Z.shape)}")
+        p = Z.shape[-2]
+        if p > _lib.MAX_P:
+            raise ValueError(f"{name}: p = {p}, at most {_lib.MAX_P} observed series")
+        obs = obs_args(b, Z, d, None, nb, p, n)
+        obs = {key: obs[key] for key in ("Z", "z_batched", "d", "d_batched")}
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    shapes = dict(x=(nb, n_paths, n_steps, n), w=(nb, n_paths, n_steps, n), observed=(nb, n_paths, n_steps, p), G=(nb, n, n))
+    res = {key: _out(b, out.get(key), shapes[key]) for key in ANT_OUTPUTS if key in outputs}
+    res["status"] = st
+    call(b, "dsge_anticipated_paths_batched", B=B, C=C, T=T, R=R, eps=eps if n_shock > 0 else None, eps_batched=eb,
+         mode=ANT_MODES[mode], n_lead=n_lead, x0=x0, x0_batched=xb, x0_paths=xpth, **obs, status_io=st, batch=nb, n=n, k=k, p=p,
+         n_paths=n_paths, n_steps=n_steps, n_shock_steps=n_shock, rank_tol=0.0 if rank_tol is None else float(rank_tol),
+         x_out=res.get("x"), w_out=res.get("w"), obs_out=res.get("observed"), G_out=res.get("G"))
+    return res
+
+
 # ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
-SOLUTION = ("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
+SOLUTION =("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
 
 
 def bind_solution(fname, args, kwargs, rest):

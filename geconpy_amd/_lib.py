@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -32,6 +32,9 @@ ST_SECOND_ORDER_UNSUPPORTED = 128
 ST_SMOOTHER_SINGULAR = 256
 ST_COND_SINGULAR = 512
 ST_SPECTRAL_SINGULAR = 1024
+ST_ANTICIPATION_SINGULAR = 2048
+ANT_PERFECT_FORESIGHT, ANT_NEWS = 0, 1  # DSGE_ANT_*: the information structures of dsge_anticipated_paths_batched
+ANT_MAX_LEAD = 63
 
 Q_DIAG_SHARED, Q_DIAG_BATCHED, Q_FULL_SHARED, Q_FULL_BATCHED = 0, 1, 2, 3
 SOLVER_CYCLE_REDUCTION, SOLVER_GENSYS, SOLVER_BACKWARD_DIRECT, SOLVER_SCAN_CYCLE_REDUCTION = 0, 1, 2, 3
@@ -146,6 +149,8 @@ _DEVICE_ENTRIES = {
                                           "n_shock_steps rank_tol x_out eps_out obs_out stream"),
     "dsge_spectral_moments_batched": ("T R Q q_mode Z z_batched Hdiag h_batched gain batch m k p n_grid n_lags correlation rank_tol "
                                       "scratch_limit_bytes acov_out spectrum_out status_io stream"),
+    "dsge_anticipated_paths_batched": ("B C T R eps eps_batched mode n_lead x0 x0_batched x0_paths Z z_batched d d_batched status_io "
+                                       "batch n k p n_paths n_steps n_shock_steps rank_tol x_out w_out obs_out G_out stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

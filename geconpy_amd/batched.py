@@ -546,6 +546,30 @@ def conditional_forecast_batched(T, R, Q, x0, conditions, n_steps, Z=None, d=Non
                                   n_paths=n_paths, free_shocks=free_shocks, q_mode=q_mode, status=status, rank_tol=rank_tol)
 
 
+expected_shocks_from_news = F.expected_shocks_from_news
+
+
+def anticipated_paths_batched(B, C, T, R, eps, n_steps=None, mode="perfect_foresight", x0=None, Z=None, d=None, status=None,
+                              rank_tol=0.0, outputs=("x",)):
+    """Paths with ANTICIPATED shocks for a batch of draws -- forward guidance, a pre-announced fiscal path, news shocks; the
+    linearised counterpart of the reference's stacked-time perfect-foresight solver (gEconpy/model/perfect_foresight/);
+    include/dsge_hip.h, ``dsge_anticipated_paths_batched``.  The model is ``A x[t-1] + B x[t] + C E_t x[t+1] + D eps[t] = 0`` with
+    the solution ``T`` and ``R = -(B + C T)^-1 D`` as the solver entries return them; with ``G = -(B + C T)^-1 C``:
+    ``x[t] = T x[t-1] + w[t]``, ``w[t] = sum_j G^j R E_t eps[t+j]``, ``x[-1] = x0``, ``t = 0 .. n_steps-1``.
+    ``mode="perfect_foresight"``: ``eps`` (n_paths, n_shock_steps, k) or (batch, n_paths, n_shock_steps, k) is the whole shock
+    path, known at ``t = 0``; ``n_shock_steps`` may exceed ``n_steps`` (default n_shock_steps).  ``mode="news"``: ``eps``
+    (n_paths, n_shock_steps, n_lead + 1, k) or with a leading batch axis holds the expected shocks ``e[t][j] = E_t eps[t+j]``
+    (``expected_shocks_from_news`` makes them from arrivals); ``n_steps >= n_shock_steps``; ``n_lead = 0`` is ``simulate_batched``.
+    ``x0``: (n,), (n_paths, n) or (batch | 1, n_paths | 1, n), default zero.  ``Z`` (p, n) or (batch, p, n) and ``d`` (p,) or
+    (batch, p): the observation equation of the output ``"observed"``.  ``outputs``: any of ``"x"``, ``"w"`` (the anticipation
+    term ``x[t] - T x[t-1]``), ``"observed"``, ``"G"``.  A draw whose ``B + C T`` is singular (a pivot ``<= rank_tol max|M|``,
+    default 1e-14) gets ``ST_ANTICIPATION_SINGULAR`` (2048) in ``status`` and NaN everywhere; so does a draw with a non-zero
+    incoming ``status``.  At most 64 variables.  Returns dict(x, w (batch, n_paths, n_steps, n), observed (.., p), G (batch, n, n)
+    -- those requested -- and status)."""
+    return F.anticipated_paths(HOST, "anticipated_paths_batched", B, C, T, R, eps, n_steps=n_steps, mode=mode, x0=x0, Z=Z, d=d,
+                               status=status, rank_tol=rank_tol, outputs=outputs)
+
+
 hp_gain, bandpass_gain = F.hp_gain, F.bandpass_gain
 
 

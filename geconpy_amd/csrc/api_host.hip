@@ -837,6 +837,44 @@ int dsge_spectral_moments_batched_host(const double* T, const double* R, const d
   return hc.finish();
 }
 
+int dsge_anticipated_paths_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                        int eps_batched, int mode, int n_lead, const double* x0, int x0_batched, int x0_paths,
+                                        const double* Z, int z_batched, const double* d, int d_batched, int32_t* status_io,
+                                        int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
+                                        double rank_tol, double* x_out, double* w_out, double* obs_out, double* G_out) {
+  const AnticipatedProblem c{batch, n, k, p, n_paths, n_steps, n_shock_steps, mode, n_lead, eps_batched, x0_batched, x0_paths,
+                             z_batched, d_batched, rank_tol};
+  int rc = check_anticipated_paths(c, B, C, T, R, eps, Z, x_out, w_out, obs_out, G_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, ns = (size_t)n_steps, nn = (size_t)n * n;
+  const size_t rows = (size_t)n_shock_steps * (mode == DSGE_ANT_NEWS ? n_lead + 1 : 1);
+  const double *dB, *dC, *dT, *dR, *de, *dx0, *dZ, *dd;
+  double *dx, *dw, *dobs, *dG;
+  int32_t* dS;
+  hc.in(&dB, B, b * nn);
+  hc.in(&dC, C, b * nn);
+  hc.in(&dT, T, b * nn);
+  hc.in(&dR, R, b * n * k);
+  hc.in(&de, eps, (eps_batched ? b : 1) * np * rows * k);
+  hc.in(&dx0, x0, (x0_batched ? b : 1) * (x0_paths ? np : 1) * n);
+  hc.in(&dZ, Z, (z_batched ? b : 1) * p * n);
+  hc.in(&dd, d, (d_batched ? b : 1) * p);
+  hc.io(&dS, status_io, b);
+  hc.out(&dx, x_out, b * np * ns * n);
+  hc.out(&dw, w_out, b * np * ns * n);
+  hc.out(&dobs, obs_out, b * np * ns * p);
+  hc.out(&dG, G_out, b * nn);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_anticipated_paths_batched(dB, dC, dT, dR, de, eps_batched, mode, n_lead, dx0, x0_batched, x0_paths, dZ, z_batched,
+                                           dd, d_batched, dS, batch, n, k, p, n_paths, n_steps, n_shock_steps, rank_tol, dx, dw,
+                                           dobs, dG, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

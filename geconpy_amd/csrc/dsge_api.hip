@@ -846,6 +846,31 @@ int dsge_spectral_moments_batched(const double* T, const double* R, const double
   return DSGE_SUCCESS;
 }
 
+// ---- anticipated shocks (dsge_anticipated.hpp): two launches on the caller's stream; the scratch holds G and a flag per draw, and
+// the parked anticipation term only when neither x_out nor w_out is there to park it in ----
+int dsge_anticipated_paths_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                   int eps_batched, int mode, int n_lead, const double* x0, int x0_batched, int x0_paths,
+                                   const double* Z, int z_batched, const double* d, int d_batched, int32_t* status_io, int batch,
+                                   int n, int k, int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                   double* w_out, double* obs_out, double* G_out, void* stream) {
+  const AnticipatedProblem c{batch, n, k, p, n_paths, n_steps, n_shock_steps, mode, n_lead, eps_batched, x0_batched, x0_paths,
+                             z_batched, d_batched, rank_tol};
+  int rc = check_anticipated_paths(c, B, C, T, R, eps, Z, x_out, w_out, obs_out, G_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t b = (size_t)batch;
+  double *G = G_out, *park = w_out ? w_out : x_out;
+  int32_t* flag = nullptr;
+  ScratchLayout lay;
+  if (!G) lay.add(&G, b * n * n);
+  lay.add(&flag, b);
+  if (!park && obs_out) lay.add(&park, b * n_paths * n_steps * n);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  return launch_anticipated(c, B, C, T, R, eps, x0, Z, d, status_io, G, G_out != nullptr, flag, park, x_out, w_out, obs_out, st);
+}
+
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
                           const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,

@@ -357,6 +357,20 @@ size_t spectral_lds_bytes(int m, int k, int p, int has_z);
 int launch_spectral(const SpectralProblem& s, const double* T, const double* R, const ShockCov& q, const double* Z,
                     const double* Hdiag, const double* gain, int32_t* status, int32_t* flag, double* F, double* acov_out,
                     double* spectrum_out, hipStream_t st);
+// launch_anticipated.hip (dsge_anticipated.hpp): paths with anticipated shocks, a setup workgroup per draw (G = -(B + C T)^-1 C),
+// then one workgroup per draw and group of 16 paths.  The sizes and flags of one call
+struct AnticipatedProblem {
+  int batch, m, k, p, n_paths, n_steps, n_shock_steps, mode, n_lead;
+  int eps_batched, x0_batched, x0_paths, z_batched, d_batched;
+  double rank_tol;
+};
+// bytes of the larger of the two kernels' LDS images
+size_t anticipated_lds_bytes(int m, int k, int p);
+// G: G_out (g_is_out) or scratch [batch][m][m]; flag: scratch [batch]; park: where w_t waits for the forward pass -- w_out if
+// given, else x_out, else scratch [batch][n_paths][n_steps][m]; nullptr: no path output is wanted (G alone)
+int launch_anticipated(const AnticipatedProblem& c, const double* B, const double* C, const double* T, const double* R,
+                       const double* eps, const double* x0, const double* Z, const double* d, int32_t* status, double* G,
+                       int g_is_out, int32_t* flag, double* park, double* x_out, double* w_out, double* obs_out, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -697,6 +711,32 @@ inline int check_spectral_moments(const SpectralProblem& s, const double* T, con
   if (Z && s.p > DSGE_SPECTRAL_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "spectral moments: p exceeds DSGE_SPECTRAL_MAX_P");
   if (spectral_lds_bytes(s.m, s.k, s.p, Z != nullptr) > LDS_LIMIT)
     return fail(DSGE_ERR_TOO_LARGE, "spectral moments: the LDS image exceeds 160 KB (docs/design/spectral_moments.md)");
+  return DSGE_SUCCESS;
+}
+
+// the anticipated-shock paths: every refusal, before any device is touched
+inline int check_anticipated_paths(const AnticipatedProblem& c, const double* B, const double* C, const double* T, const double* R,
+                                   const double* eps, const double* Z, const double* x_out, const double* w_out,
+                                   const double* obs_out, const double* G_out) {
+  if (c.batch < 0 || c.m < 1 || c.p < 0 || c.n_paths < 0 || c.n_steps < 0 || c.n_shock_steps < 0)
+    return fail(DSGE_ERR_INVALID, "size out of range");
+  if (c.k < 1 || c.k > c.m) return fail(DSGE_ERR_INVALID, "k out of range (1..m)");
+  if (c.mode != DSGE_ANT_PERFECT_FORESIGHT && c.mode != DSGE_ANT_NEWS) return fail(DSGE_ERR_INVALID, "anticipated paths: mode out of range");
+  if (c.n_lead < 0) return fail(DSGE_ERR_INVALID, "anticipated paths: n_lead < 0");
+  if (c.mode == DSGE_ANT_PERFECT_FORESIGHT && c.n_lead != 0)
+    return fail(DSGE_ERR_INVALID, "anticipated paths: n_lead must be 0 with perfect foresight");
+  if (c.mode == DSGE_ANT_NEWS && c.n_shock_steps > c.n_steps) return fail(DSGE_ERR_INVALID, "news: n_shock_steps > n_steps");
+  if (!B || !C || !T || !R || (!eps && c.n_shock_steps > 0)) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (!x_out && !w_out && !obs_out && !G_out) return fail(DSGE_ERR_INVALID, "no output requested");
+  if (c.p > 0 && !Z) return fail(DSGE_ERR_INVALID, "p > 0 without Z");
+  if (obs_out && c.p == 0) return fail(DSGE_ERR_INVALID, "obs_out requested with p == 0");
+  if (c.m > DSGE_MAX_N) return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: n exceeds DSGE_MAX_N (65 .. 96 variables are out of scope)");
+  if (c.p > DSGE_MAX_P) return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: p exceeds DSGE_MAX_P");
+  if (c.n_lead > DSGE_ANT_MAX_LEAD) return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: n_lead exceeds DSGE_ANT_MAX_LEAD");
+  if ((long long)c.n_shock_steps * (c.n_lead + 1) > 0x7fffffffLL / c.k)
+    return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: n_shock_steps (n_lead + 1) k exceeds 2^31 - 1");
+  if (anticipated_lds_bytes(c.m, c.k, c.p) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: the LDS image exceeds 160 KB (docs/design/anticipated_shocks.md)");
   return DSGE_SUCCESS;
 }
 

@@ -311,6 +311,16 @@ class LogpEngine:
                                   gain=gain, correlation=correlation, spectrum=spectrum, acov=acov, q_mode=q_mode, status=status,
                                   rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes, out=out)
 
+    # -- anticipated shocks (csrc/dsge_anticipated.hpp) -------------------------------------------
+    def anticipated_paths(self, B, C, T, R, eps, n_steps=None, mode="perfect_foresight", x0=None, Z=None, d=None, status=None,
+                          rank_tol=0.0, outputs=("x",), out=None):
+        """Paths with anticipated shocks (perfect foresight or news) of the whole batch from device tensors
+        (``dsge_anticipated_paths_batched``; see ``batched.anticipated_paths_batched``), on torch's current stream.  ``status``
+        (device int32) is updated in place.  ``out``: optional dict with preallocated ``x`` / ``w`` / ``observed`` / ``G``.
+        Returns dict(those of x, w, observed, G that ``outputs`` names, status); asynchronous."""
+        return F.anticipated_paths(self.backend, "anticipated_paths", B, C, T, R, eps, n_steps=n_steps, mode=mode, x0=x0, Z=Z, d=d,
+                                   status=status, rank_tol=rank_tol, outputs=outputs, out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 16
+#define DSGE_ABI_VERSION 17
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -52,6 +52,7 @@ extern "C" {
 /* ABI 14: dsge_shock_decomposition_batched (+ _host) is new; nothing else changed. */
 /* ABI 15: dsge_conditional_forecast_batched (+ _host) and the status bit DSGE_ST_COND_SINGULAR are new; nothing else changed. */
 /* ABI 16: dsge_spectral_moments_batched (+ _host) and the status bit DSGE_ST_SPECTRAL_SINGULAR are new; nothing else changed. */
+/* ABI 17: dsge_anticipated_paths_batched (+ _host) and the status bit DSGE_ST_ANTICIPATION_SINGULAR are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -66,6 +67,7 @@ extern "C" {
 #define DSGE_SPECTRAL_MAX_K 32     /* dsge_spectral_moments_batched: shocks */
 #define DSGE_SPECTRAL_MAX_P 64     /* dsge_spectral_moments_batched: rows of Z */
 #define DSGE_SPECTRAL_MAX_GRID 4096 /* dsge_spectral_moments_batched: grid points N */
+#define DSGE_ANT_MAX_LEAD 63       /* dsge_anticipated_paths_batched: n_lead, the furthest a news shock is known ahead */
 
 /* call-level return codes */
 #define DSGE_SUCCESS 0
@@ -89,6 +91,11 @@ extern "C" {
 #define DSGE_ST_SMOOTHER_SINGULAR 256 /* smoother: sym(U' P_pred U) not positive definite at some step (jitter_P = 0 only) */
 #define DSGE_ST_COND_SINGULAR 512 /* conditional forecast: the conditions cannot be met by the free shocks (G singular) */
 #define DSGE_ST_SPECTRAL_SINGULAR 1024 /* spectral moments: I - exp(-i w) T singular at a solved grid frequency */
+#define DSGE_ST_ANTICIPATION_SINGULAR 2048 /* anticipated paths: B + C T singular to rank_tol */
+
+/* information structures of dsge_anticipated_paths_batched */
+#define DSGE_ANT_PERFECT_FORESIGHT 0 /* the whole shock path is known at t = 0 */
+#define DSGE_ANT_NEWS 1              /* eps holds the expected shocks e[t][j] = E_t eps_{t+j}, j = 0 .. n_lead */
 
 /* covariance layouts for the Q argument */
 #define DSGE_Q_DIAG_SHARED 0    /* Q = diag(q), q: [k]            */
@@ -992,6 +999,52 @@ int dsge_spectral_moments_batched_host(const double* T, const double* R, const d
                                        const double* Hdiag, int h_batched, const double* gain, int batch, int m, int k, int p,
                                        int n_grid, int n_lags, int correlation, double rank_tol, size_t scratch_limit_bytes,
                                        double* acov_out, double* spectrum_out, int32_t* status_io);
+
+/*
+ * ANTICIPATED SHOCKS per draw (ABI 17; csrc/dsge_anticipated.hpp, docs/design/anticipated_shocks.md): paths of the linearised model
+ *       A x[t-1] + B x[t] + C E_t x[t+1] + D eps[t] = 0
+ * when agents know shocks before they arrive -- forward guidance, a pre-announced fiscal path, news shocks.  With the solution T
+ * (A + B T + C T^2 = 0), M = B + C T, R = -M^-1 D and G = -M^-1 C:
+ *       x[t] = T x[t-1] + w[t],   w[t] = sum_{j >= 0} G^j R E_t eps[t+j],   x[-1] = x0,   t = 0 .. n_steps-1.
+ * B, C, T: [batch][n][n];  R: [batch][n][k], as the solver entries return it; all arrays float64 and C-contiguous.
+ *   mode == DSGE_ANT_PERFECT_FORESIGHT: eps [batch|1][n_paths][n_shock_steps][k] (eps_batched) is the whole shock path, known at
+ *         t = 0:  w[n_shock_steps] = 0,  w[t] = G w[t+1] + R eps[t].  n_shock_steps may exceed n_steps: a shock beyond the horizon
+ *         still moves the path inside it.  n_lead must be 0.
+ *   mode == DSGE_ANT_NEWS: eps [batch|1][n_paths][n_shock_steps][n_lead + 1][k] holds the expected shocks e[t][j] = E_t eps[t+j]:
+ *         w[t] = R e[t][0] + G (R e[t][1] + G (... R e[t][n_lead])).  Periods at or beyond n_shock_steps have e = 0;
+ *         n_shock_steps <= n_steps.  With n_lead == 0 this is dsge_simulate_batched.
+ *   eps may be NULL with n_shock_steps == 0.
+ *   x0  : [batch|1][n_paths|1][n] (x0_batched, x0_paths) or NULL (zero)
+ *   Z   : [batch|1][p][n] (z_batched);  d : [batch|1][p] (d_batched) or NULL (zero);  Z may be NULL with p == 0
+ *   status_io : [batch] in/out, may be NULL; a draw with a non-zero incoming word gets NaN in all its outputs
+ *   x_out   : [batch][n_paths][n_steps][n]
+ *   w_out   : [batch][n_paths][n_steps][n]  the anticipation term x[t] - T x[t-1] (dsge_simulate_batched on it with R = I reproduces x)
+ *   obs_out : [batch][n_paths][n_steps][p] = d + Z x  (needs p >= 1)
+ *   G_out   : [batch][n][n]
+ *   any may be NULL, not all.
+ * A draw is singular when a pivot of the row-pivoted elimination of M is <= rank_tol max|M_ij| in absolute value
+ * (rank_tol <= 0: 1e-14): status |= DSGE_ST_ANTICIPATION_SINGULAR, NaN in every output of the draw, the other draws untouched.
+ * rho(G) >= 1 (an indeterminate solution) is NOT detected: pass the solver's status word.
+ * Two launches on `stream`, no host synchronisation, no atomics: two calls give the same bits.  Library scratch holds G and a flag
+ * per draw and, only when obs_out is wanted without x_out and w_out, one [batch][n_paths][n_steps][n] buffer.
+ * DSGE_ERR_TOO_LARGE: n > DSGE_MAX_N (64; models of 65 .. 96 variables are out of scope of this entry), p > DSGE_MAX_P,
+ * n_lead > DSGE_ANT_MAX_LEAD (63).  The LDS images -- in doubles n (2 n + 1) + 4 + ceil(n/2) for the setup and (n16 + 32) ld + p n + 16
+ * for the paths (ld = the smallest value == 2 (mod 32) that holds 4 ceil(n/4) + 4 ceil(k/4), n16 = 16 ceil(n/16)) -- take at most
+ * 13 520 doubles of the 20 480 within these limits, so no size inside them is refused.
+ * DSGE_ERR_INVALID: mode outside the two above, n_lead < 0 or n_lead != 0 with perfect foresight, news with n_shock_steps > n_steps,
+ * missing pointers, all outputs NULL, obs_out with p == 0, k outside 1 .. n.  All refusals happen before any device is touched.
+ * batch == 0, n_paths == 0 or n_steps == 0: success, nothing touched.
+ */
+int dsge_anticipated_paths_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                   int eps_batched, int mode, int n_lead, const double* x0, int x0_batched, int x0_paths,
+                                   const double* Z, int z_batched, const double* d, int d_batched, int32_t* status_io, int batch,
+                                   int n, int k, int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                   double* w_out, double* obs_out, double* G_out, void* stream);
+int dsge_anticipated_paths_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                        int eps_batched, int mode, int n_lead, const double* x0, int x0_batched, int x0_paths,
+                                        const double* Z, int z_batched, const double* d, int d_batched, int32_t* status_io,
+                                        int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
+                                        double rank_tol, double* x_out, double* w_out, double* obs_out, double* G_out);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw

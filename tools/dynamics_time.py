@@ -5,6 +5,7 @@
     python tools/dynamics_time.py --decomposition [draws ...]     the shock-decomposition rows alone
     python tools/dynamics_time.py --conditional [draws ...]       the conditional-forecast rows alone
     python tools/dynamics_time.py --spectral [draws ...]          the spectral-moments rows alone
+    python tools/dynamics_time.py --anticipated [draws ...]       the anticipated-shock rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -33,6 +34,12 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     was the only exact one before it -- torch.linalg.solve on the complex128 stack (draws x 257, 40, 40) (the real 80 x 80
     embedding in float64 if this torch has no complex batched solve on the device), the einsum for H Q H^H and the cosine / sine
     sums, chunked over 512 draws -- with its parts timed apart and the agreement of the two routes.
+  * --anticipated (csrc/dsge_anticipated.hpp), the SW-shaped (B, C, T) with a dense impact matrix D = randn(n, k) / sqrt(n) and
+    R = -(B + C T)^-1 D (on the generator's own D anticipation does nothing: tests/anticipated_cases.py), m = 40, k = 7, 40 steps, 16
+    paths: the median of five timings of >= 1 s each of LogpEngine.anticipated_paths -- perfect foresight with shocks at every step,
+    and news with n_lead = 4 -- and of the composed route that was the only one before it: torch.linalg.solve for G, a bmm loop
+    for w (backward over the 40 periods; news: five Horner products on all periods at once) and LogpEngine.simulate with R = I;
+    the parts timed apart, the setup kernel alone (outputs=("G",)), and the agreement of the two routes.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -317,8 +324,82 @@ def spectral_rows(eng, sizes, n_grid=512, n_lags=10, chunk=512, repeats=5):
               f"einsums {t_sums:8.3f} (sum {t_solve + t_sums:8.3f}) | entry / composed {t_entry / t_comp:5.2f}")
 
 
+def anticipated_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, n_lead=4, repeats=5):
+    b = wl.sw_shaped_batch(64)
+    m, k = 40, 7
+    rng = np.random.default_rng(0)
+    D64 = rng.standard_normal((64, m, k)) / np.sqrt(m)
+    R64 = np.stack([np.linalg.solve(b["B"][i] + b["C"][i] @ b["T_star"][i], -D64[i]) for i in range(64)])
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    print(f"anticipated paths m={m} k={k}, dense impact matrix, {n_steps} steps, {n_paths} paths, shocks at every step; news: n_lead={n_lead}; "
+          f"medians of {repeats} timings of >= 1 s")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        B, C, T, R = (eng.to_device(np.tile(a, (rep, 1, 1))[:nb]) for a in (b["B"], b["C"], b["T_star"], R64))
+        eps = eng.to_device(rng.standard_normal((nb, n_paths, n_steps, k)) * 0.01)
+        exp = eng.to_device(rng.standard_normal((nb, n_paths, n_steps, n_lead + 1, k)) * 0.01)
+        x0 = eng.to_device(rng.standard_normal((nb, n_paths, m)) * 0.05)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        out, out_n, g_only = dict(x=mk(nb, n_paths, n_steps, m)), dict(x=mk(nb, n_paths, n_steps, m)), dict(G=mk(nb, m, m))
+        status = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+        pf = lambda: eng.anticipated_paths(B, C, T, R, eps, x0=x0, status=status, out=out)  # noqa: E731
+        news = lambda: eng.anticipated_paths(B, C, T, R, exp, mode="news", x0=x0, status=status, out=out_n)  # noqa: E731
+        setup = lambda: eng.anticipated_paths(B, C, T, R, eps, status=status, outputs=("G",), out=g_only)  # noqa: E731
+        # the composed route
+        eye = torch.eye(m, dtype=torch.float64, device=eng.device).expand(nb, m, m).contiguous()
+        hold, W, paths = {}, mk(nb, n_paths, n_steps, m), mk(nb, n_paths, n_steps, m)
+
+        def solve():
+            hold["G"] = torch.linalg.solve(torch.baddbmm(B, C, T), -C)
+
+        def w_pf():
+            G, w = hold["G"], None
+            for t in range(n_steps - 1, -1, -1):  # (nb, m, n_paths) per period
+                re = torch.bmm(R, eps[:, :, t].transpose(1, 2))
+                w = re if w is None else torch.baddbmm(re, G, w)
+                W[:, :, t] = w.transpose(1, 2)
+
+        def w_news():
+            G, acc = hold["G"], None
+            for j in range(n_lead, -1, -1):  # all periods at once: (nb, m, n_paths n_steps)
+                re = torch.bmm(R, exp[:, :, :, j].reshape(nb, n_paths * n_steps, k).transpose(1, 2))
+                acc = re if acc is None else torch.baddbmm(re, G, acc)
+            W.copy_(acc.transpose(1, 2).reshape(nb, n_paths, n_steps, m))
+
+        sim = lambda: eng.simulate(T, eye, W, x0=x0, out=paths)  # noqa: E731
+
+        def composed_pf():
+            solve()
+            w_pf()
+            sim()
+
+        def composed_news():
+            solve()
+            w_news()
+            sim()
+
+        pf()
+        news()
+        composed_pf()
+        torch.cuda.synchronize()
+        assert int(status.abs().max()) == 0
+        d_pf = (out["x"] - paths).abs().max().item() / paths.abs().max().item()
+        composed_news()
+        torch.cuda.synchronize()
+        d_news = (out_n["x"] - paths).abs().max().item() / paths.abs().max().item()
+        print(f"draws={nb:5d} entry against the composed route: perfect foresight {d_pf:.1e}, news {d_news:.1e} of max|x|")
+        t_pf, t_cpf, t_news, t_cnews = med(pf), med(composed_pf), med(news), med(composed_news)
+        t_setup, t_solve, t_wpf, t_wnews, t_sim = med(setup), med(solve), med(w_pf), med(w_news), med(sim)
+        print(f"draws={nb:5d} perfect foresight: {t_pf:8.3f} ms | composed route {t_cpf:8.3f} ms = linalg.solve {t_solve:8.3f} + bmm loop "
+              f"{t_wpf:8.3f} + simulate(R = I) {t_sim:8.3f} (sum {t_solve + t_wpf + t_sim:8.3f}) | entry / composed {t_pf / t_cpf:5.2f}")
+        print(f"draws={nb:5d} news, n_lead={n_lead}:   {t_news:8.3f} ms | composed route {t_cnews:8.3f} ms = linalg.solve {t_solve:8.3f} + Horner bmm "
+              f"{t_wnews:8.3f} + simulate(R = I) {t_sim:8.3f} (sum {t_solve + t_wnews + t_sim:8.3f}) | entry / composed {t_news / t_cnews:5.2f}")
+        print(f"draws={nb:5d} phase split of the entry: setup kernel alone {t_setup:8.3f} ms, paths kernel (entry - setup): perfect foresight "
+              f"{t_pf - t_setup:8.3f} ms, news {t_news - t_setup:8.3f} ms")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral")]
+    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
@@ -328,6 +409,8 @@ def main():
         return conditional_rows(LogpEngine(0), sizes)
     if "--spectral" in sys.argv:
         return spectral_rows(LogpEngine(0), sizes)
+    if "--anticipated" in sys.argv:
+        return anticipated_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
