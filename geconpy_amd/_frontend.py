@@ -679,6 +679,40 @@ def expected_shocks_from_news(nu):
     return e
 
 
+def _ant_x0(b, x0, nb, n_paths, n):
+    """x0: (n,) shared by all, (n_paths, n) per path as ``simulate`` takes it, or (batch | 1, n_paths | 1, n) -> (x0, x0_batched,
+    x0_paths)."""
+    x0 = b.inp(x0)
+    xb = xpth = 0
+    if x0 is not None:
+        shape = tuple(x0.shape)
+        if shape == (n,):
+            pass
+        elif shape == (n_paths, n):
+            xpth = 1
+        elif len(shape) == 3 and shape[0] in (1, nb) and shape[1] in (1, n_paths) and shape[2] == n:
+            xb, xpth = int(shape[0] == nb), int(shape[1] == n_paths)
+        else:
+            raise ValueError(f"x0 must be ({n},), ({n_paths}, {n}) or (batch | 1, n_paths | 1, {n}); got {shape}")
+    return x0, xb, xpth
+
+
+def _ant_obs(b, name, Z, d, outputs, nb, n):
+    """The observation equation of the output "observed" -> (dict(Z, z_batched, d, d_batched), p)."""
+    if Z is None:
+        if d is not None or "observed" in outputs:
+            raise ValueError(f"{name}: d and the output 'observed' need Z")
+        return dict(Z=None, z_batched=0, d=None, d_batched=0), 0
+    Z = b.inp(Z)
+    if Z.ndim not in (2, 3) or Z.shape[-1] != n or Z.shape[-2] < 1:
+        raise ValueError(f"Z must be (p, {n}) or (batch, p, {n}); got {tuple(Z.shape)}")
+    p = Z.shape[-2]
+    if p > _lib.MAX_P:
+        raise ValueError(f"{name}: p = {p}, at most {_lib.MAX_P} observed series")
+    obs = obs_args(b, Z, d, None, nb, p, n)
+    return {key: obs[key] for key in ("Z", "z_batched", "d", "d_batched")}, p
+
+
 def anticipated_paths(b, name, B, C, T, R, eps, *, n_steps, mode, x0, Z, d, status, rank_tol, outputs, out=None):
     T, R, nb, n, k = _TR(b, T, R, name)
     if n > _lib.MAX_N:
@@ -704,32 +738,8 @@ def anticipated_paths(b, name, B, C, T, R, eps, *, n_steps, mode, x0, Z, d, stat
     n_steps = n_shock if n_steps is None else int(n_steps)
     if n_steps < 0 or (news and n_steps < n_shock):
         raise ValueError(f"n_steps = {n_steps}: news needs at least the {n_shock} shock steps of eps, perfect foresight at least 0")
-    # x0: (n,) shared by all, (n_paths, n) per path as ``simulate`` takes it, or (batch | 1, n_paths | 1, n)
-    x0 = b.inp(x0)
-    xb = xpth = 0
-    if x0 is not None:
-        shape = tuple(x0.shape)
-        if shape == (n,):
-            pass
-        elif shape == (n_paths, n):
-            xpth = 1
-        elif len(shape) == 3 and shape[0] in (1, nb) and shape[1] in (1, n_paths) and shape[2] == n:
-            xb, xpth = int(shape[0] == nb), int(shape[1] == n_paths)
-        else:
-            raise ValueError(f"x0 must be ({n},), ({n_paths}, {n}) or (batch | 1, n_paths | 1, {n}); got {shape}")
-    if Z is None:
-        if d is not None or "observed" in outputs:
-            raise ValueError(f"{name}: d and the output 'observed' need Z")
-        obs, p = dict(Z=None, z_batched=0, d=None, d_batched=0), 0
-    else:
-        Z = b.inp(Z)
-        if Z.ndim not in (2, 3) or Z.shape[-1] != n or Z.shape[-2] < 1:
-            raise ValueError(f"Z must be (p, {n}) or (batch, p, {n}); got {tuple(Z.shape)}")
-        p = Z.shape[-2]
-        if p > _lib.MAX_P:
-            raise ValueError(f"{name}: p = {p}, at most {_lib.MAX_P} observed series")
-        obs = obs_args(b, Z, d, None, nb, p, n)
-        obs = {key: obs[key] for key in ("Z", "z_batched", "d", "d_batched")}
+    x0, xb, xpth = _ant_x0(b, x0, nb, n_paths, n)
+    obs, p = _ant_obs(b, name, Z, d, outputs, nb, n)
     st = check_status(b.status_io(status, nb), nb)
     out = out or {}
     shapes = dict(x=(nb, n_paths, n_steps, n), w=(nb, n_paths, n_steps, n), observed=(nb, n_paths, n_steps, p), G=(nb, n, n))
@@ -739,6 +749,64 @@ def anticipated_paths(b, name, B, C, T, R, eps, *, n_steps, mode, x0, Z, d, stat
          mode=ANT_MODES[mode], n_lead=n_lead, x0=x0, x0_batched=xb, x0_paths=xpth, **obs, status_io=st, batch=nb, n=n, k=k, p=p,
          n_paths=n_paths, n_steps=n_steps, n_shock_steps=n_shock, rank_tol=0.0 if rank_tol is None else float(rank_tol),
          x_out=res.get("x"), w_out=res.get("w"), obs_out=res.get("observed"), G_out=res.get("G"))
+    return res
+
+
+# ---- occasionally binding bound ----------------------------------------------------------------------------------------------------
+OBC_OUTPUTS = ("x", "w", "observed", "nu", "gap", "Mz", "path_status", "iters")
+
+
+def constrained_paths(b, name, B, C, T, R, eps, c, bound, shock, horizon, *, n_steps, x0, Z, d, status, rank_tol, max_iter, outputs,
+                      out=None):
+    T, R, nb, n, k = _TR(b, T, R, name)
+    if n > _lib.MAX_N:
+        raise ValueError(f"{name}: n = {n}, at most {_lib.MAX_N} variables (models of 65 .. {_lib.MAX_N_BIG} are out of scope here)")
+    B, C = _nd(b.inp(B), 3), _nd(b.inp(C), 3)
+    if tuple(B.shape) != (nb, n, n) or tuple(C.shape) != (nb, n, n):
+        raise ValueError(f"B and C must be {(nb, n, n)} like T; got {tuple(B.shape)}, {tuple(C.shape)}")
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in OBC_OUTPUTS for o in outputs):
+        raise ValueError(f"outputs must name at least one of {OBC_OUTPUTS}; got {outputs}")
+    eps = b.inp(eps)
+    if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+        raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {tuple(eps.shape)}")
+    n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+    eb = shared_or_batched(eps, nb, tuple(eps.shape[-3:]), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    shock, horizon = int(shock), int(horizon)
+    if not 0 <= shock < k:
+        raise ValueError(f"{name}: shock = {shock} is outside 0 .. {k - 1}")
+    if not 1 <= horizon <= _lib.OBC_MAX_HORIZON:
+        raise ValueError(f"{name}: horizon = {horizon} is outside 1 .. {_lib.OBC_MAX_HORIZON}")
+    if n_steps < 0 or (n_steps > 0 and horizon > n_steps):
+        raise ValueError(f"{name}: n_steps = {n_steps} must hold the horizon of {horizon} periods")
+    if c is None or bound is None:
+        raise ValueError(f"{name}: the constraint row c and the bound are needed")
+    c = b.inp(c)
+    cb = shared_or_batched(c, nb, (n,), "c", f"({n},) or (batch, {n})")
+    if isinstance(bound, (int, float)):
+        value, bound = float(bound), b.empty((1,))
+        bound[...] = value
+    bound = b.inp(bound)
+    if tuple(bound.shape) not in ((), (1,), (nb,)):
+        raise ValueError(f"bound must be a number, (1,) or (batch,); got {tuple(bound.shape)}")
+    bb = int(tuple(bound.shape) == (nb,) and nb > 1)
+    x0, xb, xpth = _ant_x0(b, x0, nb, n_paths, n)
+    obs, p = _ant_obs(b, name, Z, d, outputs, nb, n)
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    path = (nb, n_paths, n_steps)
+    shapes = dict(x=path + (n,), w=path + (n,), observed=path + (p,), nu=(nb, n_paths, horizon), gap=path, Mz=(nb, horizon, horizon),
+                  path_status=(nb, n_paths), iters=(nb, n_paths))
+    res = {key: _out(b, out.get(key), shapes[key], "int32" if key in ("path_status", "iters") else "float64")
+           for key in OBC_OUTPUTS if key in outputs}
+    res["status"] = st
+    call(b, "dsge_constrained_paths_batched", B=B, C=C, T=T, R=R, eps=eps if n_shock > 0 else None, eps_batched=eb, x0=x0,
+         x0_batched=xb, x0_paths=xpth, **obs, c_row=c, c_batched=cb, bound=bound, bound_batched=bb, shock=shock, horizon=horizon,
+         max_iter=0 if max_iter is None else int(max_iter), status_io=st, batch=nb, n=n, k=k, p=p, n_paths=n_paths, n_steps=n_steps,
+         n_shock_steps=n_shock, rank_tol=0.0 if rank_tol is None else float(rank_tol), x_out=res.get("x"), w_out=res.get("w"),
+         obs_out=res.get("observed"), nu_out=res.get("nu"), gap_out=res.get("gap"), Mz_out=res.get("Mz"),
+         path_status_out=res.get("path_status"), iters_out=res.get("iters"))
     return res
 
 

@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -35,6 +35,9 @@ ST_SPECTRAL_SINGULAR = 1024
 ST_ANTICIPATION_SINGULAR = 2048
 ANT_PERFECT_FORESIGHT, ANT_NEWS = 0, 1  # DSGE_ANT_*: the information structures of dsge_anticipated_paths_batched
 ANT_MAX_LEAD = 63
+ST_CONSTRAINT_UNRESOLVED = 4096
+OBC_NO_REGIME, OBC_SINGULAR, OBC_BEYOND_HORIZON, OBC_SKIPPED = 1, 2, 4, 8  # DSGE_OBC_*: the bits of a path of dsge_constrained_paths_batched
+OBC_MAX_HORIZON = 64
 
 Q_DIAG_SHARED, Q_DIAG_BATCHED, Q_FULL_SHARED, Q_FULL_BATCHED = 0, 1, 2, 3
 SOLVER_CYCLE_REDUCTION, SOLVER_GENSYS, SOLVER_BACKWARD_DIRECT, SOLVER_SCAN_CYCLE_REDUCTION = 0, 1, 2, 3
@@ -77,10 +80,10 @@ class GensysForward(C.Structure):
 # entry -> its argument names in the order of include/dsge_hip.h (tests/test_abi_and_host.py compares both, names and kinds).  A
 # name is an int, a double or a size_t when it is listed below, a pointer (double* / int32_t* / struct* / stream, passed as a raw
 # host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
-_INTS = ("N T_len batch c correlation cv_batched cv_paths d_batched device enable eps_batched eta_batched full_cov h_batched k lag_step m "
-         "max_iter mode n n_cond n_eta n_filter_hint n_grid n_groups n_lags n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state "
-         "n_state_hint n_steps nnz p q_batched q_mode remainder reps s_batched solver w_batched x0_batched x0_paths z_batched "
-         "z_selector_hint")
+_INTS = ("N T_len batch bound_batched c c_batched correlation cv_batched cv_paths d_batched device enable eps_batched "
+         "eta_batched full_cov h_batched horizon k lag_step m max_iter mode n n_cond n_eta n_filter_hint n_grid n_groups n_lags "
+         "n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p q_batched q_mode "
+         "remainder reps s_batched shock solver w_batched x0_batched x0_paths z_batched z_selector_hint")
 _KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
           "scratch_limit_bytes": C.c_size_t}
 _OBS = "Z z_batched d d_batched Hdiag h_batched"
@@ -151,6 +154,9 @@ _DEVICE_ENTRIES = {
                                       "scratch_limit_bytes acov_out spectrum_out status_io stream"),
     "dsge_anticipated_paths_batched": ("B C T R eps eps_batched mode n_lead x0 x0_batched x0_paths Z z_batched d d_batched status_io "
                                        "batch n k p n_paths n_steps n_shock_steps rank_tol x_out w_out obs_out G_out stream"),
+    "dsge_constrained_paths_batched": ("B C T R eps eps_batched x0 x0_batched x0_paths Z z_batched d d_batched c_row c_batched bound "
+                                       "bound_batched shock horizon max_iter status_io batch n k p n_paths n_steps n_shock_steps rank_tol "
+                                       "x_out w_out obs_out nu_out gap_out Mz_out path_status_out iters_out stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

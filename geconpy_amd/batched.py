@@ -570,6 +570,24 @@ def anticipated_paths_batched(B, C, T, R, eps, n_steps=None, mode="perfect_fores
                                status=status, rank_tol=rank_tol, outputs=outputs)
 
 
+def constrained_paths_batched(B, C, T, R, eps, c, bound, shock, horizon, n_steps=None, x0=None, Z=None, d=None, status=None,
+                              rank_tol=0.0, max_iter=0, outputs=("x",)):
+    """Perfect-foresight paths under an OCCASIONALLY BINDING BOUND for a batch of draws -- the zero lower bound on a policy rate;
+    include/dsge_hip.h, ``dsge_constrained_paths_batched``.  The model, ``eps`` (n_paths, n_shock_steps, k) or (batch, n_paths,
+    n_shock_steps, k), ``x0``, ``Z``, ``d`` and ``status`` are those of ``anticipated_paths_batched`` in mode "perfect_foresight".
+    ``c'x[t] >= bound`` is enforced in the periods ``t < horizon`` (1 .. 64, at most ``n_steps``) by anticipated shadow shocks
+    ``nu[t] >= 0`` on shock column ``shock``: ``w[t] = G w[t+1] + R (eps[t] + nu[t] e_shock)``, ``gap[t] = c'x[t] - bound``,
+    ``nu[h] gap[h] = 0``; the regime iteration of the header solves for them (at most ``max_iter`` solves, default 64).
+    ``c``: (n,) or (batch, n); ``bound``: a number or (batch,).  ``outputs``: any of ``"x"``, ``"w"``, ``"observed"``, ``"nu"``
+    (batch, n_paths, horizon), ``"gap"`` (batch, n_paths, n_steps), ``"Mz"`` (batch, horizon, horizon), ``"path_status"`` and
+    ``"iters"`` (batch, n_paths) int32.  ``path_status`` bits: ``OBC_NO_REGIME`` (1), ``OBC_SINGULAR`` (2) -- NaN in the path, and
+    ``ST_CONSTRAINT_UNRESOLVED`` (4096) in the draw's ``status`` --, ``OBC_BEYOND_HORIZON`` (4: the bound is violated at some
+    ``t >= horizon``; the path is returned), ``OBC_SKIPPED`` (8: the draw came in failed or ``B + C T`` is singular).  Returns
+    dict(those requested, status)."""
+    return F.constrained_paths(HOST, "constrained_paths_batched", B, C, T, R, eps, c, bound, shock, horizon, n_steps=n_steps, x0=x0, Z=Z,
+                               d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs)
+
+
 hp_gain, bandpass_gain = F.hp_gain, F.bandpass_gain
 
 

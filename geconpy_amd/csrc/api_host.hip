@@ -875,6 +875,54 @@ int dsge_anticipated_paths_batched_host(const double* B, const double* C, const 
   return hc.finish();
 }
 
+int dsge_constrained_paths_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                        int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z,
+                                        int z_batched, const double* d, int d_batched, const double* c_row, int c_batched,
+                                        const double* bound, int bound_batched, int shock, int horizon, int max_iter,
+                                        int32_t* status_io, int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
+                                        double rank_tol, double* x_out, double* w_out, double* obs_out, double* nu_out, double* gap_out,
+                                        double* Mz_out, int32_t* path_status_out, int32_t* iters_out) {
+  const ConstrainedProblem c{{batch, n, k, p, n_paths, n_steps, n_shock_steps, DSGE_ANT_PERFECT_FORESIGHT, 0, eps_batched, x0_batched,
+                              x0_paths, z_batched, d_batched, rank_tol},
+                             c_batched, bound_batched, shock, horizon, max_iter};
+  const void* other = nu_out ? (const void*)nu_out : gap_out ? (const void*)gap_out : Mz_out ? (const void*)Mz_out
+                      : path_status_out ? (const void*)path_status_out : (const void*)iters_out;
+  int rc = check_constrained_paths(c, B, C, T, R, eps, Z, c_row, bound, x_out, w_out, obs_out, other);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, ns = (size_t)n_steps, nn = (size_t)n * n, H = (size_t)horizon;
+  const double *dB, *dC, *dT, *dR, *de, *dx0, *dZ, *dd, *dc, *dbound;
+  double *dx, *dw, *dobs, *dnu, *dgap, *dMz;
+  int32_t *dS, *dps, *dit;
+  hc.in(&dB, B, b * nn);
+  hc.in(&dC, C, b * nn);
+  hc.in(&dT, T, b * nn);
+  hc.in(&dR, R, b * n * k);
+  hc.in(&de, eps, (eps_batched ? b : 1) * np * n_shock_steps * k);
+  hc.in(&dx0, x0, (x0_batched ? b : 1) * (x0_paths ? np : 1) * n);
+  hc.in(&dZ, Z, (z_batched ? b : 1) * p * n);
+  hc.in(&dd, d, (d_batched ? b : 1) * p);
+  hc.in(&dc, c_row, (c_batched ? b : 1) * n);
+  hc.in(&dbound, bound, bound_batched ? b : 1);
+  hc.io(&dS, status_io, b);
+  hc.out(&dx, x_out, b * np * ns * n);
+  hc.out(&dw, w_out, b * np * ns * n);
+  hc.out(&dobs, obs_out, b * np * ns * p);
+  hc.out(&dnu, nu_out, b * np * H);
+  hc.out(&dgap, gap_out, b * np * ns);
+  hc.out(&dMz, Mz_out, b * H * H);
+  hc.out(&dps, path_status_out, b * np);
+  hc.out(&dit, iters_out, b * np);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_constrained_paths_batched(dB, dC, dT, dR, de, eps_batched, dx0, x0_batched, x0_paths, dZ, z_batched, dd, d_batched, dc,
+                                           c_batched, dbound, bound_batched, shock, horizon, max_iter, dS, batch, n, k, p, n_paths,
+                                           n_steps, n_shock_steps, rank_tol, dx, dw, dobs, dnu, dgap, dMz, dps, dit, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

@@ -871,6 +871,45 @@ int dsge_anticipated_paths_batched(const double* B, const double* C, const doubl
   return launch_anticipated(c, B, C, T, R, eps, x0, Z, d, status_io, G, G_out != nullptr, flag, park, x_out, w_out, obs_out, st);
 }
 
+// ---- occasionally binding bound (dsge_obc.hpp): a chain of launches on the caller's stream (launch_obc.hip); the scratch holds G and
+// a flag per draw, the unit shocks, Mz, the parked terms of a chunk of unit paths, e', max|q| and the bits per path, and the paths
+// themselves when x_out is not there to hold them ----
+int dsge_constrained_paths_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                   int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z, int z_batched,
+                                   const double* d, int d_batched, const double* c_row, int c_batched, const double* bound,
+                                   int bound_batched, int shock, int horizon, int max_iter, int32_t* status_io, int batch, int n, int k,
+                                   int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out, double* w_out,
+                                   double* obs_out, double* nu_out, double* gap_out, double* Mz_out, int32_t* path_status_out,
+                                   int32_t* iters_out, void* stream) {
+  const ConstrainedProblem c{{batch, n, k, p, n_paths, n_steps, n_shock_steps, DSGE_ANT_PERFECT_FORESIGHT, 0, eps_batched, x0_batched,
+                              x0_paths, z_batched, d_batched, rank_tol},
+                             c_batched, bound_batched, shock, horizon, max_iter};
+  const void* other = nu_out ? (const void*)nu_out : gap_out ? (const void*)gap_out : Mz_out ? (const void*)Mz_out
+                      : path_status_out ? (const void*)path_status_out : (const void*)iters_out;
+  int rc = check_constrained_paths(c, B, C, T, R, eps, Z, c_row, bound, x_out, w_out, obs_out, other);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, H = (size_t)horizon;
+  const size_t nsp = (size_t)n_shock_steps > H ? (size_t)n_shock_steps : H;
+  ConstrainedBuffers buf{B, C, T, R, eps, x0, Z, d, c_row, bound, status_io, x_out, w_out, obs_out, nu_out, gap_out, Mz_out,
+                         path_status_out, iters_out};
+  buf.xbuf = x_out;
+  ScratchLayout lay;
+  lay.add(&buf.G, b * n * n);
+  lay.add(&buf.flag, b);
+  lay.add(&buf.unit, H * H * k);
+  lay.add(&buf.mzt, b * H * H);
+  lay.add(&buf.mzpark, (size_t)constrained_chunk(batch, n, horizon) * H * H * n);
+  if (!buf.xbuf) lay.add(&buf.xbuf, b * np * n_steps * n);
+  lay.add(&buf.eps2, b * np * nsp * k);
+  lay.add(&buf.qmax, b * np);
+  lay.add(&buf.pstat, b * np);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  return launch_constrained(c, buf, st);
+}
+
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
                           const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,

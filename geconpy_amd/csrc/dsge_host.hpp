@@ -367,10 +367,38 @@ struct AnticipatedProblem {
 // bytes of the larger of the two kernels' LDS images
 size_t anticipated_lds_bytes(int m, int k, int p);
 // G: G_out (g_is_out) or scratch [batch][m][m]; flag: scratch [batch]; park: where w_t waits for the forward pass -- w_out if
-// given, else x_out, else scratch [batch][n_paths][n_steps][m]; nullptr: no path output is wanted (G alone)
+// given, else x_out, else scratch [batch][n_paths][n_steps][m]; nullptr: no path output is wanted (G alone).  phases: which of the
+// two launches are made (launch_obc.hip runs the setup once and the paths kernel several times on its G and flag)
+constexpr int ANT_SETUP = 1, ANT_PATHS = 2;
 int launch_anticipated(const AnticipatedProblem& c, const double* B, const double* C, const double* T, const double* R,
                        const double* eps, const double* x0, const double* Z, const double* d, int32_t* status, double* G,
-                       int g_is_out, int32_t* flag, double* park, double* x_out, double* w_out, double* obs_out, hipStream_t st);
+                       int g_is_out, int32_t* flag, double* park, double* x_out, double* w_out, double* obs_out, hipStream_t st,
+                       int phases = ANT_SETUP | ANT_PATHS);
+// launch_obc.hip (dsge_obc.hpp): perfect-foresight paths under an occasionally binding bound -- the two kernels above, the regime
+// kernel and the gap kernel, a chain on one stream.  `a`: the sizes and flags of the paths (mode perfect foresight, n_lead 0)
+struct ConstrainedProblem {
+  AnticipatedProblem a;
+  int c_batched, bound_batched, shock, horizon, max_iter;
+};
+// what the caller gave (inputs, outputs: any may be null) and the library's scratch of one call
+struct ConstrainedBuffers {
+  const double *B, *C, *T, *R, *eps, *x0, *Z, *d, *c_row, *bound;
+  int32_t* status;
+  double *x_out, *w_out, *obs_out, *nu_out, *gap_out, *Mz_out;
+  int32_t *path_status_out, *iters_out;
+  double* G;        // [batch][m][m]
+  int32_t* flag;    // [batch]
+  double* unit;     // [H][H][k]
+  double* mzt;      // [batch][H][H]
+  double* mzpark;   // [constrained_chunk()][H][H][m]
+  double* xbuf;     // [batch][n_paths][n_steps][m]: x_out, or scratch without it
+  double* eps2;     // [batch][n_paths][max(n_shock_steps, H)][k]
+  double* qmax;     // [batch][n_paths]
+  int32_t* pstat;   // [batch][n_paths]
+};
+// draws per launch of the unit paths: their parked anticipation terms, H H m doubles per draw, take at most 256 MB of scratch
+int constrained_chunk(int batch, int m, int horizon);
+int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
@@ -737,6 +765,23 @@ inline int check_anticipated_paths(const AnticipatedProblem& c, const double* B,
     return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: n_shock_steps (n_lead + 1) k exceeds 2^31 - 1");
   if (anticipated_lds_bytes(c.m, c.k, c.p) > LDS_LIMIT)
     return fail(DSGE_ERR_TOO_LARGE, "anticipated paths: the LDS image exceeds 160 KB (docs/design/anticipated_shocks.md)");
+  return DSGE_SUCCESS;
+}
+
+// the paths under an occasionally binding bound: every refusal of the anticipated-shock paths (with one observation row more: the
+// unit paths observe c'x), then its own, before any device is touched.  `other`: non-null if an output besides x, w and observed
+// is wanted.  n_steps == 0 is the empty call, whatever the horizon
+inline int check_constrained_paths(const ConstrainedProblem& c, const double* B, const double* C, const double* T, const double* R,
+                                   const double* eps, const double* Z, const double* c_row, const double* bound, const double* x_out,
+                                   const double* w_out, const double* obs_out, const void* other) {
+  if (int rc = check_anticipated_paths(c.a, B, C, T, R, eps, Z, x_out, w_out, obs_out, (const double*)other)) return rc;
+  if (!c_row || !bound) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (c.horizon < 1 || c.horizon > DSGE_OBC_MAX_HORIZON)
+    return fail(DSGE_ERR_INVALID, "constrained paths: horizon out of range (1..DSGE_OBC_MAX_HORIZON)");
+  if (c.a.n_steps > 0 && c.horizon > c.a.n_steps) return fail(DSGE_ERR_INVALID, "constrained paths: horizon > n_steps");
+  if (c.shock < 0 || c.shock >= c.a.k) return fail(DSGE_ERR_INVALID, "constrained paths: shock out of range (0..k-1)");
+  if (anticipated_lds_bytes(c.a.m, c.a.k, c.a.p > 1 ? c.a.p : 1) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "constrained paths: the LDS image exceeds 160 KB (docs/design/occasionally_binding.md)");
   return DSGE_SUCCESS;
 }
 

@@ -12,7 +12,8 @@ size_t anticipated_lds_bytes(int m, int k, int p) {
 
 int launch_anticipated(const AnticipatedProblem& c, const double* B, const double* C, const double* T, const double* R,
                        const double* eps, const double* x0, const double* Z, const double* d, int32_t* status, double* G,
-                       int g_is_out, int32_t* flag, double* park, double* x_out, double* w_out, double* obs_out, hipStream_t st) {
+                       int g_is_out, int32_t* flag, double* park, double* x_out, double* w_out, double* obs_out, hipStream_t st,
+                       int phases) {
   dsge::AntArgs a{};
   a.B = B; a.C = C; a.T = T; a.R = R; a.eps = eps; a.x0 = x0; a.Z = Z; a.d = d; a.status = status; a.G = G; a.g_is_out = g_is_out;
   a.flag = flag; a.park = park; a.x_out = x_out; a.w_out = w_out; a.obs_out = obs_out; a.rank_tol = c.rank_tol;
@@ -31,8 +32,9 @@ int launch_anticipated(const AnticipatedProblem& c, const double* B, const doubl
   if (lds_setup > LDS_LIMIT || lds_paths > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, too_large);  // (before any launch)
   unsigned grid;
   if (int rc = batch_grid(c.batch, a.groups, "anticipated paths: batch x path groups exceeds the grid", &grid)) return rc;
-  if (int rc = launch_with_lds(dsge::ant_setup_kernel, c.batch, dsge::AN_THREADS, lds_setup, st, a, too_large)) return rc;
-  if (!park) return DSGE_SUCCESS;  // G alone
+  if (phases & ANT_SETUP)
+    if (int rc = launch_with_lds(dsge::ant_setup_kernel, c.batch, dsge::AN_THREADS, lds_setup, st, a, too_large)) return rc;
+  if (!park || !(phases & ANT_PATHS)) return DSGE_SUCCESS;  // G alone
   // News with a lead on a grid of at most WIDE_GRID workgroups (two per CU of a 256-CU device: the steps' latency is not hidden by
   // other workgroups) runs AN_PB periods per Horner step, if its wider images fit; the bits are those of one period per step
   constexpr unsigned WIDE_GRID = 512;

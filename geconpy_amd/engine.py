@@ -321,6 +321,16 @@ class LogpEngine:
         return F.anticipated_paths(self.backend, "anticipated_paths", B, C, T, R, eps, n_steps=n_steps, mode=mode, x0=x0, Z=Z, d=d,
                                    status=status, rank_tol=rank_tol, outputs=outputs, out=out)
 
+    # -- occasionally binding bound (csrc/dsge_obc.hpp) -------------------------------------------
+    def constrained_paths(self, B, C, T, R, eps, c, bound, shock, horizon, n_steps=None, x0=None, Z=None, d=None, status=None,
+                          rank_tol=0.0, max_iter=0, outputs=("x",), out=None):
+        """Perfect-foresight paths under an occasionally binding bound of the whole batch from device tensors
+        (``dsge_constrained_paths_batched``; see ``batched.constrained_paths_batched``), on torch's current stream.  ``bound``: a
+        number or a device tensor (batch,).  ``status`` (device int32) is updated in place.  ``out``: optional dict with preallocated
+        outputs.  Returns dict(those of x, w, observed, nu, gap, Mz, path_status, iters that ``outputs`` names, status); asynchronous."""
+        return F.constrained_paths(self.backend, "constrained_paths", B, C, T, R, eps, c, bound, shock, horizon, n_steps=n_steps, x0=x0,
+                                   Z=Z, d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs, out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

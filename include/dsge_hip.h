@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 17
+#define DSGE_ABI_VERSION 18
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -53,6 +53,8 @@ extern "C" {
 /* ABI 15: dsge_conditional_forecast_batched (+ _host) and the status bit DSGE_ST_COND_SINGULAR are new; nothing else changed. */
 /* ABI 16: dsge_spectral_moments_batched (+ _host) and the status bit DSGE_ST_SPECTRAL_SINGULAR are new; nothing else changed. */
 /* ABI 17: dsge_anticipated_paths_batched (+ _host) and the status bit DSGE_ST_ANTICIPATION_SINGULAR are new; nothing else changed. */
+/* ABI 18: dsge_constrained_paths_batched (+ _host) and the status bit DSGE_ST_CONSTRAINT_UNRESOLVED are new (new entry and status
+ * bit, nothing else changed). */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -68,6 +70,7 @@ extern "C" {
 #define DSGE_SPECTRAL_MAX_P 64     /* dsge_spectral_moments_batched: rows of Z */
 #define DSGE_SPECTRAL_MAX_GRID 4096 /* dsge_spectral_moments_batched: grid points N */
 #define DSGE_ANT_MAX_LEAD 63       /* dsge_anticipated_paths_batched: n_lead, the furthest a news shock is known ahead */
+#define DSGE_OBC_MAX_HORIZON 64    /* dsge_constrained_paths_batched: horizon, the periods in which the bound is enforced */
 
 /* call-level return codes */
 #define DSGE_SUCCESS 0
@@ -92,6 +95,13 @@ extern "C" {
 #define DSGE_ST_COND_SINGULAR 512 /* conditional forecast: the conditions cannot be met by the free shocks (G singular) */
 #define DSGE_ST_SPECTRAL_SINGULAR 1024 /* spectral moments: I - exp(-i w) T singular at a solved grid frequency */
 #define DSGE_ST_ANTICIPATION_SINGULAR 2048 /* anticipated paths: B + C T singular to rank_tol */
+#define DSGE_ST_CONSTRAINT_UNRESOLVED 4096 /* constrained paths: a path of the draw has DSGE_OBC_NO_REGIME or DSGE_OBC_SINGULAR */
+
+/* per-path bits of dsge_constrained_paths_batched (path_status_out) */
+#define DSGE_OBC_NO_REGIME 1      /* the regime iteration found no fixed point within max_iter solves */
+#define DSGE_OBC_SINGULAR 2       /* a pivot of Mz[S,S] <= rank_tol max|Mz|, or a pivot or q[h] not finite */
+#define DSGE_OBC_BEYOND_HORIZON 4 /* gap[t] < -1e-12 max|q| at some t >= horizon: reported, the path is returned as it is */
+#define DSGE_OBC_SKIPPED 8        /* the draw came in with a non-zero status word, or B + C T is singular */
 
 /* information structures of dsge_anticipated_paths_batched */
 #define DSGE_ANT_PERFECT_FORESIGHT 0 /* the whole shock path is known at t = 0 */
@@ -1045,6 +1055,56 @@ int dsge_anticipated_paths_batched_host(const double* B, const double* C, const 
                                         const double* Z, int z_batched, const double* d, int d_batched, int32_t* status_io,
                                         int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
                                         double rank_tol, double* x_out, double* w_out, double* obs_out, double* G_out);
+
+/*
+ * OCCASIONALLY BINDING BOUND per draw (ABI 18; csrc/dsge_obc.hpp, docs/design/occasionally_binding.md): perfect-foresight paths of
+ * the linearised model of dsge_anticipated_paths_batched on which c'x[t] may not fall below a bound in the periods t < horizon -- the
+ * zero lower bound on a policy rate.  The bound is enforced by anticipated "shadow" shocks nu[0 .. horizon-1] >= 0, known at t = 0 like
+ * eps and added to shock column `shock` (Holden and Paetz):
+ *       x[t] = T x[t-1] + w[t],   w[t] = G w[t+1] + R (eps[t] + nu[t] e_shock),   gap[t] = c'x[t] - bound,
+ *       gap[h] >= 0,  nu[h] >= 0,  nu[h] gap[h] = 0   for h < horizon.
+ * Periods at or beyond the horizon are not constrained: a violation there is reported (DSGE_OBC_BEYOND_HORIZON), not repaired.
+ * Mz[h][j] = c'x[h] of the path from x0 = 0 with a unit shock on column `shock` at period j alone; q[h] = c'xu[h] - bound on the
+ * unconstrained path xu of the call's eps and x0; gap = q + Mz nu on h < horizon.  The regime iteration: S = {h : q[h] < 0}; at each
+ * iteration nu = 0 off S, Mz[S,S] nu[S] = -q[S], gap = q + Mz nu, S' = {h in S : nu[h] > 0} u {h not in S : gap[h] < 0}; it stops when
+ * S' == S, and the number of solves is iters (an empty first S: one iteration, nu = 0).  Every comparison is strict, without a
+ * tolerance.  max_iter solves without a fixed point (max_iter <= 0: 64): DSGE_OBC_NO_REGIME.  The solve is a row-pivoted elimination;
+ * a pivot with |pivot| <= rank_tol max|Mz| (rank_tol <= 0: 1e-14, the rule of B + C T), or a pivot or q[h] that is not finite:
+ * DSGE_OBC_SINGULAR.  The iteration finds the solution when Mz is a P-matrix; whether it is one is not tested.
+ * Inputs as dsge_anticipated_paths_batched in mode DSGE_ANT_PERFECT_FORESIGHT (B, C, T, R, eps, x0, Z, d, status_io, rank_tol), and
+ *   c_row : [batch|1][n] (c_batched);  bound : [batch|1] (bound_batched);  shock in 0 .. k-1;  horizon in 1 .. DSGE_OBC_MAX_HORIZON,
+ *   horizon <= n_steps.
+ * Outputs, any may be NULL, not all:
+ *   x_out, w_out : [batch][n_paths][n_steps][n]  (w includes the shadow shocks' term);  obs_out : [batch][n_paths][n_steps][p]
+ *   nu_out  : [batch][n_paths][horizon]
+ *   gap_out : [batch][n_paths][n_steps]
+ *   Mz_out  : [batch][horizon][horizon]
+ *   path_status_out, iters_out : [batch][n_paths] int32, the DSGE_OBC_* bits and the number of solves
+ * A path with DSGE_OBC_NO_REGIME, DSGE_OBC_SINGULAR or DSGE_OBC_SKIPPED has NaN in x, w, observed, nu and gap; every other path of
+ * every draw is untouched, bit for bit.  status_io |= DSGE_ST_CONSTRAINT_UNRESOLVED for a draw with a NO_REGIME or SINGULAR path;
+ * DSGE_ST_ANTICIPATION_SINGULAR keeps its meaning (its draw's paths are DSGE_OBC_SKIPPED, Mz is NaN).
+ * A chain of launches on `stream` (setup, horizon unit-shock paths for Mz, the unconstrained paths, the regime iteration, the final
+ * paths, the gap), no host synchronisation, no atomics: two calls give the same bits, any subset of the outputs the bits of the full
+ * call.  Library scratch: G, Mz, eps + nu e_shock, the paths when x_out is NULL, and at most 256 MB for the unit paths, which run
+ * in chunks of draws (docs/design/occasionally_binding.md).
+ * Refusals, all before any device is touched: those of dsge_anticipated_paths_batched with its size limits; DSGE_ERR_INVALID for
+ * horizon outside 1 .. DSGE_OBC_MAX_HORIZON, horizon > n_steps (n_steps > 0), shock outside 0 .. k-1, c_row or bound NULL.
+ * batch == 0, n_paths == 0 or n_steps == 0: success, nothing touched.
+ */
+int dsge_constrained_paths_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                   int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z, int z_batched,
+                                   const double* d, int d_batched, const double* c_row, int c_batched, const double* bound,
+                                   int bound_batched, int shock, int horizon, int max_iter, int32_t* status_io, int batch, int n, int k,
+                                   int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out, double* w_out,
+                                   double* obs_out, double* nu_out, double* gap_out, double* Mz_out, int32_t* path_status_out,
+                                   int32_t* iters_out, void* stream);
+int dsge_constrained_paths_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                        int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z,
+                                        int z_batched, const double* d, int d_batched, const double* c_row, int c_batched,
+                                        const double* bound, int bound_batched, int shock, int horizon, int max_iter,
+                                        int32_t* status_io, int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
+                                        double rank_tol, double* x_out, double* w_out, double* obs_out, double* nu_out, double* gap_out,
+                                        double* Mz_out, int32_t* path_status_out, int32_t* iters_out);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw

@@ -6,6 +6,7 @@
     python tools/dynamics_time.py --conditional [draws ...]       the conditional-forecast rows alone
     python tools/dynamics_time.py --spectral [draws ...]          the spectral-moments rows alone
     python tools/dynamics_time.py --anticipated [draws ...]       the anticipated-shock rows alone
+    python tools/dynamics_time.py --constrained [draws ...]       the occasionally-binding-bound rows alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -40,6 +41,13 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     and news with n_lead = 4 -- and of the composed route that was the only one before it: torch.linalg.solve for G, a bmm loop
     for w (backward over the 40 periods; news: five Horner products on all periods at once) and LogpEngine.simulate with R = I;
     the parts timed apart, the setup kernel alone (outputs=("G",)), and the agreement of the two routes.
+  * --constrained (csrc/dsge_obc.hpp), the model of --anticipated, 40 steps, 16 paths with shocks at every step, the bound on
+    the variable shock 0 moves most, at half the minimum of the draw's unconstrained paths, H = 32, x the only output: the median
+    of five timings of >= 1 s each of LogpEngine.constrained_paths and of the composed route that was the only one before it --
+    LogpEngine.anticipated_paths three times (the H unit paths observed through c for Mz, the unconstrained paths, the final paths
+    on eps + nu e_s) around a torch loop of batched torch.linalg.solve on the identity-padded systems with the same updates of S,
+    one host round trip per iteration -- with the agreement of the two routes, the parts of the entry timed apart through its own
+    subsets of outputs and the anticipated-shock entry, and the mean and largest iters.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -398,8 +406,95 @@ def anticipated_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, n_lead=4, repeats=
               f"{t_pf - t_setup:8.3f} ms, news {t_news - t_setup:8.3f} ms")
 
 
+def constrained_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, horizon=32, shock=0, repeats=5):
+    b = wl.sw_shaped_batch(64)
+    m, k, H = 40, 7, horizon
+    rng = np.random.default_rng(0)
+    D64 = rng.standard_normal((64, m, k)) / np.sqrt(m)
+    R64 = np.stack([np.linalg.solve(b["B"][i] + b["C"][i] @ b["T_star"][i], -D64[i]) for i in range(64)])
+    var = np.argmax(np.abs(R64[:, :, shock]), axis=1)
+    c64 = np.zeros((64, m))
+    c64[np.arange(64), var] = np.sign(R64[np.arange(64), var, shock])
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    print(f"constrained paths m={m} k={k}, dense impact matrix, {n_steps} steps, {n_paths} paths, shocks at every step, H={H}, bound at half "
+          f"the unconstrained minimum; medians of {repeats} timings of >= 1 s")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        B, C, T, R = (eng.to_device(np.tile(a, (rep, 1, 1))[:nb]) for a in (b["B"], b["C"], b["T_star"], R64))
+        c = eng.to_device(np.tile(c64, (rep, 1))[:nb])
+        eps = eng.to_device(rng.standard_normal((nb, n_paths, n_steps, k)) * 0.01)
+        x0 = eng.to_device(rng.standard_normal((nb, n_paths, m)) * 0.05)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        xu = eng.anticipated_paths(B, C, T, R, eps, x0=x0)["x"]
+        bound = (0.5 * torch.einsum("bptn,bn->bpt", xu, c).amin(dim=(1, 2))).contiguous()
+        out, out_nu = dict(x=mk(nb, n_paths, n_steps, m)), dict(nu=mk(nb, n_paths, H))
+        entry = lambda: eng.constrained_paths(B, C, T, R, eps, c, bound, shock, H, x0=x0, out=out)  # noqa: E731
+        to_nu = lambda: eng.constrained_paths(B, C, T, R, eps, c, bound, shock, H, x0=x0, outputs=("nu",), out=out_nu)  # noqa: E731
+        # the composed route
+        unit = torch.zeros(H, H, k, dtype=torch.float64, device=eng.device)
+        unit[torch.arange(H), torch.arange(H), shock] = 1.0
+        Zc = c.reshape(nb, 1, m).contiguous()
+        o_mz, o_xu, o_x, g_only = dict(observed=mk(nb, H, H, 1)), dict(x=mk(nb, n_paths, H, m)), dict(x=mk(nb, n_paths, n_steps, m)), dict(G=mk(nb, m, m))
+        eye = torch.eye(H, dtype=torch.float64, device=eng.device)
+        hold = {}
+
+        def mz_paths():
+            eng.anticipated_paths(B, C, T, R, unit, n_steps=H, Z=Zc, outputs=("observed",), out=o_mz)
+
+        def unconstrained():
+            eng.anticipated_paths(B, C, T, R, eps, n_steps=H, x0=x0, out=o_xu)
+
+        def regime_loop():
+            Mz = o_mz["observed"][..., 0].transpose(1, 2)  # (nb, h, j)
+            q = torch.einsum("bptn,bn->bpt", o_xu["x"], c) - bound[:, None, None]
+            S, iters = q < 0.0, 0
+            while True:
+                iters += 1
+                d = S.to(torch.float64)
+                K = eye + d[..., :, None] * (Mz[:, None] - eye) * d[..., None, :]
+                nu = torch.linalg.solve(K, (-q * d)[..., None])[..., 0]
+                gap = q + torch.einsum("bhj,bpj->bph", Mz, nu)
+                S_new = torch.where(S, nu > 0.0, gap < 0.0)
+                if bool((S_new == S).all()) or iters >= 64:  # (the host round trip of every iteration)
+                    break
+                S = torch.where((S_new == S).all(dim=-1, keepdim=True), S, S_new)  # a path that has its regime keeps it
+            hold["eps2"] = eps.clone()
+            hold["eps2"][:, :, :H, shock] += nu
+            hold["iters"] = iters
+
+        def final():
+            eng.anticipated_paths(B, C, T, R, hold["eps2"], x0=x0, out=o_x)
+
+        def composed():
+            mz_paths()
+            unconstrained()
+            regime_loop()
+            final()
+
+        setup = lambda: eng.anticipated_paths(B, C, T, R, eps, outputs=("G",), out=g_only)  # noqa: E731
+        entry()
+        composed()
+        torch.cuda.synchronize()
+        it = eng.constrained_paths(B, C, T, R, eps, c, bound, shock, H, x0=x0, outputs=("iters", "path_status"))
+        torch.cuda.synchronize()
+        ok = (it["path_status"] & (_lib.OBC_NO_REGIME | _lib.OBC_SINGULAR | _lib.OBC_SKIPPED)) == 0  # (the others are NaN by the entry)
+        diff = (out["x"][ok] - o_x["x"][ok]).abs().max().item() / o_x["x"][ok].abs().max().item()
+        assert diff <= 1e-9, diff
+        print(f"draws={nb:5d} paths without a regime: {int((~ok).sum())} of {ok.numel()}; status words seen {sorted(set(it['status'].tolist()))}")
+        print(f"draws={nb:5d} entry against the composed route: {diff:.1e} of max|x|; iters mean {it['iters'].double().mean().item():.2f} max "
+              f"{int(it['iters'].max())} (composed loop: {hold['iters']} round trips); path_status bits seen {sorted(set(it['path_status'].flatten().tolist()))}")
+        t_entry, t_comp, t_nu = med(entry), med(composed), med(to_nu)
+        t_setup, t_mz, t_xu, t_loop, t_final = med(setup), med(mz_paths), med(unconstrained), med(regime_loop), med(final)
+        print(f"draws={nb:5d} entry {t_entry:8.3f} ms | composed route {t_comp:8.3f} ms = Mz paths {t_mz:8.3f} + unconstrained {t_xu:8.3f} + torch "
+              f"regime loop {t_loop:8.3f} + final paths {t_final:8.3f} (sum {t_mz + t_xu + t_loop + t_final:8.3f}) | entry / composed {t_entry / t_comp:5.2f}")
+        print(f"draws={nb:5d} phase split of the entry: setup {t_setup:8.3f} ms, Mz paths {t_mz - t_setup:8.3f}, unconstrained paths (H periods) "
+              f"{t_xu - t_setup:8.3f}, regime + gap kernels (outputs=('nu',) less the three before) {t_nu - t_mz - t_xu + t_setup:8.3f}, final paths "
+              f"and the gap over them (entry less outputs=('nu',)) {t_entry - t_nu:8.3f}")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated")]
+    args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated",
+                                                 "--constrained")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
@@ -411,6 +506,8 @@ def main():
         return spectral_rows(LogpEngine(0), sizes)
     if "--anticipated" in sys.argv:
         return anticipated_rows(LogpEngine(0), sizes)
+    if "--constrained" in sys.argv:
+        return constrained_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
