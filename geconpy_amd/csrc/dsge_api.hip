@@ -86,6 +86,8 @@ int check_options(const dsge_options* o) {
   if (!(o->kalman_steady_tol >= 0.0) || o->kalman_steady_tol > 1e-6)
     return fail(DSGE_ERR_INVALID, "kalman_steady_tol must be in [0, 1e-6]");
   if (o->kalman_order < 0 || o->kalman_order > 2) return fail(DSGE_ERR_INVALID, "kalman_order must be 0, 1 or 2");
+  if (o->kalman_block < 0 || o->kalman_block > 2) return fail(DSGE_ERR_INVALID, "kalman_block must be 0, 1 or 2");
+  if (o->kalman_mfma < 0 || o->kalman_mfma > 2) return fail(DSGE_ERR_INVALID, "kalman_mfma must be 0, 1 or 2");
   if (o->pipeline_chunks < 0 || o->pipeline_chunks > 64) return fail(DSGE_ERR_INVALID, "pipeline_chunks must be in 0..64");
   if (o->gensys_split < 0 || o->gensys_split > 2) return fail(DSGE_ERR_INVALID, "gensys_split must be 0, 1 or 2");
   if (o->gensys_doubling < 0 || o->gensys_doubling > 3) return fail(DSGE_ERR_INVALID, "gensys_doubling must be 0, 1, 2 or 3");

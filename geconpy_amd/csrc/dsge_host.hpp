@@ -277,10 +277,6 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                   const double* Rsel = nullptr, const ShockCov& q = ShockCov{}, int k_shocks = 0,  // R folded into the filter, see below
                   const unsigned long long* colmask = nullptr,
                   int rerun_all = 0);  // 1: every launch is a second pass -- only the draws flagged DSGE_ST_INTERNAL_RERUN are filtered
-// launch_kalman_mf.hip: the tile-layout filter kernel (dsge_kalman_mf.hpp) in front of launch_kalman's cascade
-int launch_kalman_mf(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, dsge::FilterConv cv,
-                     int n_state_hint, double* logp, int32_t* status, hipStream_t st, const int32_t* order, const double* Rsel, const ShockCov& q, int k_shocks,
-                     const unsigned long long* colmask, int rerun_first, int* launched, bool* covers);
 int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, double* ll,
                           double* a_pred, double* a_filt, double* p_pred, double* p_filt, int full_cov, int32_t* status, hipStream_t st);
 // launch_smooth.hip (dsge_kalman_smooth.hpp): basis of range(P_pred) per draw (U, UT, UR: [batch] images of smoother_image_doubles(m)
@@ -400,7 +396,8 @@ struct ConstrainedBuffers {
 int constrained_chunk(int batch, int m, int horizon);
 int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
-// fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only)
+// fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only).  It is `fold` of the plan
+// launch_kalman executes (dsge_kalman_plan.hpp), so the two cannot disagree.
 bool kalman_folds_rqr(int m, int p, int k, int n_state_hint, int z_selector_hint);
 // launch_grad.hip: reverse sweep of the Kalman filter + reverse of the assembly (dsge_kalman_grad.hpp)
 int launch_persistence_key(const double* T, const int32_t* status, int batch, int n, int32_t* key, hipStream_t st);

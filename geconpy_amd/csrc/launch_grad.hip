@@ -1,9 +1,6 @@
 // Launchers of the gradient kernels: Kalman reverse sweep and the reverse of the state-space assembly.
 #include <cstdlib>
-#include "dsge_host.hpp"
-#include "dsge_kalman_grad.hpp"
-#include "dsge_kalman_mf.hpp"
-#include "dsge_kalman_nt.hpp"
+#include "dsge_kalman_launch.hpp"
 
 namespace dsge_host {
 
@@ -32,8 +29,10 @@ int launch_kalman_grad(const double* T, const double* RQR, const ObsModel& o, in
     HIP_TRY(hipGetLastError());
     order = order_buf;
   }
-  const dsge::FilterConv cv = filter_conv(o.jitter);
-  const double stol = opt().kalman_steady_tol;
+  FilterArgs a;  // the forward sweeps: the logp kernels with record output, no P0, nothing folded
+  a.T = T; a.RQR = RQR; a.o = o; a.batch = batch; a.m = m; a.cv = filter_conv(o.jitter); a.steady_tol = opt().kalman_steady_tol;
+  a.logp = logp; a.status = status; a.order = order; a.rec_store = store;
+  const GradBars bars{Tbar, Gbar, dbar, hbar};
   DISPATCH_BS(bs, 8, {
     const size_t lds = dsge::KgSmem<BS>::bytes;
     if (lds > LDS_LIMIT) return fail(DSGE_ERR_INVALID, "gradient kernel: model too large for the 160 KB LDS");
@@ -46,66 +45,43 @@ int launch_kalman_grad(const double* T, const double* RQR, const ObsModel& o, in
     //  come from kalman_grad_kernel<BS, true>; tools/grad_phases.py reads the one-kernel path's stamps otherwise)
     static const bool dbg_split = std::getenv("DSGE_DBG_SPLIT_PHASES") != nullptr;
     const bool split = opt().kalman_grad_split != 0 && (!g_kalman_dbg || dbg_split) && o.p <= 8 && lds_f <= LDS_LIMIT;
-    if (split) {
-      rc = set_lds(dsge::kalman_nt_kernel<BS, false, 8 * BS, false, true>, lds_f);
-      if (rc == DSGE_SUCCESS) rc = set_lds(dsge::kalman_grad_kernel<BS, true>, lds);
-      if (rc == DSGE_SUCCESS) rc = set_lds(dsge::kalman_grad_kernel<BS, false>, lds);
-      // Round 6: on the 24-wide tile the forward sweep is the tile-layout filter with record output (kalman_mf_kernel<5, 5, .., REC>:
-      // up to 20 retained variables, selector Z; P+ recorded as its upper tiles, which the reverse sweep scatters); what it cannot
-      // take it flags, and kalman_nt_kernel<.., REC> then runs as a second pass over those draws only.
-      int nt_rerun = 0;
+    FilterArgs r = a;  // the reverse sweep: stamps of draw 0 under the hook
+    r.dbg = g_kalman_dbg;
+    if (!split) {
+      rc = launch_grad<BS, false>(batch, st, lds, r, bars, 0);
+    } else {
       // the forward sweep reports every draw's first steady step into the (consumed) key buffer: the reverse launches -- whose time
       // per draw is the number of full steps -- then start their draws in THAT order (round 6; the key of the forward launch, the
       // solver's iteration count, is a proxy for it)
       int32_t* const steps_key = order ? order_key : nullptr;
+      a.steady_at = steps_key;
+      a.s_cap = 8 * BS;
+      rc = DSGE_SUCCESS;
+      // Round 6: on the 24-wide tile the forward sweep is the tile-layout filter with record output (kalman_mf_kernel<5, 5, .., REC>:
+      // up to 20 retained variables, selector Z; P+ recorded as its upper tiles, which the reverse sweep scatters); what it cannot
+      // take it flags, and kalman_nt_kernel<.., REC> then runs as a second pass over those draws only.
       if constexpr (BS == 3) {
-        using SMF = dsge::KmfSmem<5, 5>;
-        if (rc == DSGE_SUCCESS && opt().kalman_mfma == 2 && opt().kalman_nt_products && u_hint > 0 && u_hint <= 20) {
-          rc = set_lds(dsge::kalman_mf_kernel<5, 5, false, true, 3>, SMF::bytes);
-          if (rc == DSGE_SUCCESS) {
-            hipLaunchKernelGGL((dsge::kalman_mf_kernel<5, 5, false, true, 3>), dim3(batch), dim3(64), SMF::bytes, st, T, RQR,
-                               (const double*)nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv,
-                               o.missing_fill, stol, logp, status, (long long*)nullptr, 0, steps_key, order,
-                               (const double*)nullptr, (const double*)nullptr, 0, 0, (const unsigned long long*)nullptr, store);
-            nt_rerun = 1;
-          }
+        if (opt().kalman_mfma == 2 && opt().kalman_nt_products && u_hint > 0 && u_hint <= 20) {
+          rc = launch_mf<5, 5, false, true, 3>(batch, st, dsge::KmfSmem<5, 5>::bytes, a);
+          a.rerun = 1;
         }
       }
-      if (rc == DSGE_SUCCESS) {
-        hipLaunchKernelGGL((dsge::kalman_nt_kernel<BS, false, 8 * BS, false, true>), dim3(batch), dim3(64), lds_f, st, T, RQR,
-                           (const double*)nullptr, o.Z, o.z_batched, o.d, o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, 8 * BS, cv,
-                           o.missing_fill, stol, logp, status, (long long*)nullptr, nt_rerun, steps_key, order,
-                           (const double*)nullptr, (const double*)nullptr, 0, 0, (const unsigned long long*)nullptr,
-                           (double*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr, store);
-        // the reverse mean side of every draw's LAST steady segment at two wavefronts per SIMD (kalman_grad_tail_kernel); the
-        // reverse sweep then starts at that segment's source step (kalman_grad_split = 2; the default is 1: without it)
-        if (steps_key) {
-          hipLaunchKernelGGL(dsge::kalman_order_kernel<1024>, dim3(1), dim3(1024), 0, st, (const int32_t*)steps_key, batch, order_buf,
-                             o.T_len);
-        }
-        const int with_tail = opt().kalman_grad_split >= 2;
-        if (with_tail)
-          hipLaunchKernelGGL((dsge::kalman_grad_tail_kernel<BS>), dim3(batch), dim3(64), 0, st, T, o.Z, o.z_batched, o.d,
-                             o.d_batched, o.y,
-                             batch, m, o.p, o.T_len, cv, o.missing_fill, store, (const int32_t*)status, order);
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, true>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
-                           o.d_batched,
-                           o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
-                           hbar, g_kalman_dbg, order, 0, with_tail);
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
-                           o.d_batched, o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar,
-                           dbar, hbar, (long long*)nullptr, (const int32_t*)nullptr, 1, 0);
-        HIP_TRY(hipGetLastError());
+      if (rc == DSGE_SUCCESS) rc = launch_nt<BS, false, 8 * BS, false, true>(batch, st, lds_f, a);
+      if (rc) return rc;
+      if (steps_key) {
+        hipLaunchKernelGGL(dsge::kalman_order_kernel<1024>, dim3(1), dim3(1024), 0, st, (const int32_t*)steps_key, batch, order_buf,
+                           o.T_len);
       }
-    } else {
-      rc = set_lds(dsge::kalman_grad_kernel<BS, false>, lds);
-      if (rc == DSGE_SUCCESS) {
-        hipLaunchKernelGGL((dsge::kalman_grad_kernel<BS, false>), dim3(batch), dim3(64), lds, st, T, RQR, o.Z, o.z_batched, o.d,
-                           o.d_batched,
-                           o.Hdiag, o.h_batched, o.y, batch, m, o.p, o.T_len, cv, o.missing_fill, stol, store, logp, status, Tbar, Gbar, dbar,
-                           hbar, g_kalman_dbg, order, 0, 0);
-        HIP_TRY(hipGetLastError());
-      }
+      // the reverse mean side of every draw's LAST steady segment at two wavefronts per SIMD (kalman_grad_tail_kernel); the
+      // reverse sweep then starts at that segment's source step (kalman_grad_split = 2, the default; 1: without it)
+      const int with_tail = opt().kalman_grad_split >= 2;
+      if (with_tail)
+        hipLaunchKernelGGL((dsge::kalman_grad_tail_kernel<BS>), dim3(batch), dim3(64), 0, st, T, o.Z, o.z_batched, o.d,
+                           o.d_batched, o.y,
+                           batch, m, o.p, o.T_len, a.cv, o.missing_fill, store, (const int32_t*)status, order);
+      if ((rc = launch_grad<BS, true>(batch, st, lds, r, bars, with_tail))) return rc;
+      r.dbg = nullptr; r.order = nullptr; r.rerun = 1;  // what the forward sweep flagged: the one-kernel path, second pass
+      rc = launch_grad<BS, false>(batch, st, lds, r, bars, 0);
     }
   });
   return rc;

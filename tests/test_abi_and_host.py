@@ -224,6 +224,15 @@ def test_options_struct_defaults_and_scope():
     bad = _lib.make_options()
     bad.ll_constant = 3
     assert lib.dsge_options_push(ctypes.addressof(bad)) != 0
+    # the kernel selectors of the filter's dispatch take 0, 1 or 2 and nothing else (DSGE_ERR_INVALID = 1)
+    for field in ("kalman_mfma", "kalman_block"):
+        for value, refused in ((-1, True), (0, False), (1, False), (2, False), (3, True)):
+            sel = _lib.make_options()
+            setattr(sel, field, value)
+            rc = lib.dsge_options_push(ctypes.addressof(sel))
+            assert (rc == 1) if refused else (rc == 0 and lib.dsge_options_pop() == 0), (field, value, rc)
+            if refused:
+                assert field in lib.dsge_last_error().decode()
     assert lib.dsge_forget_measured_shapes() == 0  # (host-side records only: no GPU needed)
 
 
