@@ -810,6 +810,64 @@ def constrained_paths(b, name, B, C, T, R, eps, c, bound, shock, horizon, *, n_s
     return res
 
 
+# ---- stochastic simulation at the bound ----------------------------------------------------------------------------------------------
+OBC_SIM_OUTPUTS = ("x", "observed", "gap", "shadow", "plan", "duration", "iters", "Mz", "path_status", "fail_step")
+
+
+def constrained_simulate(b, name, B, C, T, R, eps, c, bound, shock, horizon, *, n_steps, x0, Z, d, status, rank_tol, max_iter,
+                         outputs, out=None):
+    T, R, nb, n, k = _TR(b, T, R, name)
+    if n > _lib.MAX_N:
+        raise ValueError(f"{name}: n = {n}, at most {_lib.MAX_N} variables (models of 65 .. {_lib.MAX_N_BIG} are out of scope here)")
+    B, C = _nd(b.inp(B), 3), _nd(b.inp(C), 3)
+    if tuple(B.shape) != (nb, n, n) or tuple(C.shape) != (nb, n, n):
+        raise ValueError(f"B and C must be {(nb, n, n)} like T; got {tuple(B.shape)}, {tuple(C.shape)}")
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in OBC_SIM_OUTPUTS for o in outputs):
+        raise ValueError(f"outputs must name at least one of {OBC_SIM_OUTPUTS}; got {outputs}")
+    eps = b.inp(eps)
+    if eps.ndim not in (3, 4) or eps.shape[-1] != k:
+        raise ValueError(f"eps must be (n_paths, n_shock_steps, {k}) or (batch, n_paths, n_shock_steps, {k}); got {tuple(eps.shape)}")
+    n_paths, n_shock = eps.shape[-3], eps.shape[-2]
+    eb = shared_or_batched(eps, nb, tuple(eps.shape[-3:]), "eps")
+    n_steps = n_shock if n_steps is None else int(n_steps)
+    shock, horizon = int(shock), int(horizon)
+    if not 0 <= shock < k:
+        raise ValueError(f"{name}: shock = {shock} is outside 0 .. {k - 1}")
+    if not 1 <= horizon <= _lib.OBC_MAX_HORIZON:
+        raise ValueError(f"{name}: horizon = {horizon} is outside 1 .. {_lib.OBC_MAX_HORIZON}")
+    if n_steps < 0 or n_shock > n_steps:
+        raise ValueError(f"{name}: n_steps = {n_steps} must be at least the {n_shock} shock steps of eps")
+    if c is None or bound is None:
+        raise ValueError(f"{name}: the constraint row c and the bound are needed")
+    c = b.inp(c)
+    cb = shared_or_batched(c, nb, (n,), "c", f"({n},) or (batch, {n})")
+    if isinstance(bound, (int, float)):
+        value, bound = float(bound), b.empty((1,))
+        bound[...] = value
+    bound = b.inp(bound)
+    if tuple(bound.shape) not in ((), (1,), (nb,)):
+        raise ValueError(f"bound must be a number, (1,) or (batch,); got {tuple(bound.shape)}")
+    bb = int(tuple(bound.shape) == (nb,) and nb > 1)
+    x0, xb, xpth = _ant_x0(b, x0, nb, n_paths, n)
+    obs, p = _ant_obs(b, name, Z, d, outputs, nb, n)
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    path = (nb, n_paths, n_steps)
+    shapes = dict(x=path + (n,), observed=path + (p,), gap=path, shadow=path, plan=path + (horizon,), duration=path, iters=path,
+                  Mz=(nb, horizon, horizon), path_status=(nb, n_paths), fail_step=(nb, n_paths))
+    ints = ("duration", "iters", "path_status", "fail_step")
+    res = {key: _out(b, out.get(key), shapes[key], "int32" if key in ints else "float64") for key in OBC_SIM_OUTPUTS if key in outputs}
+    res["status"] = st
+    call(b, "dsge_constrained_simulate_batched", B=B, C=C, T=T, R=R, eps=eps if n_shock > 0 else None, eps_batched=eb, x0=x0,
+         x0_batched=xb, x0_paths=xpth, **obs, c_row=c, c_batched=cb, bound=bound, bound_batched=bb, shock=shock, horizon=horizon,
+         max_iter=0 if max_iter is None else int(max_iter), status_io=st, batch=nb, n=n, k=k, p=p, n_paths=n_paths, n_steps=n_steps,
+         n_shock_steps=n_shock, rank_tol=0.0 if rank_tol is None else float(rank_tol), x_out=res.get("x"), obs_out=res.get("observed"),
+         gap_out=res.get("gap"), shadow_out=res.get("shadow"), plan_out=res.get("plan"), duration_out=res.get("duration"),
+         iters_out=res.get("iters"), Mz_out=res.get("Mz"), path_status_out=res.get("path_status"), fail_step_out=res.get("fail_step"))
+    return res
+
+
 # ---- second-order dynamics: the pruned recursion on the solution of ``second_order_logp`` ----------------------------------------
 SOLUTION =("T", "R", "g_yy", "g_yu", "g_uu", "g_ss", "S")
 

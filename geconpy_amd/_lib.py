@@ -12,7 +12,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libdsge_hip.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE = 1, 2, 3
 MAX_N = 64
 MAX_N_CR = 64
@@ -37,6 +37,7 @@ ANT_PERFECT_FORESIGHT, ANT_NEWS = 0, 1  # DSGE_ANT_*: the information structures
 ANT_MAX_LEAD = 63
 ST_CONSTRAINT_UNRESOLVED = 4096
 OBC_NO_REGIME, OBC_SINGULAR, OBC_BEYOND_HORIZON, OBC_SKIPPED = 1, 2, 4, 8  # DSGE_OBC_*: the bits of a path of dsge_constrained_paths_batched
+OBC_HORIZON_SHORT = 16  # a bit of a path of dsge_constrained_simulate_batched alone
 OBC_MAX_HORIZON = 64
 
 Q_DIAG_SHARED, Q_DIAG_BATCHED, Q_FULL_SHARED, Q_FULL_BATCHED = 0, 1, 2, 3
@@ -157,6 +158,10 @@ _DEVICE_ENTRIES = {
     "dsge_constrained_paths_batched": ("B C T R eps eps_batched x0 x0_batched x0_paths Z z_batched d d_batched c_row c_batched bound "
                                        "bound_batched shock horizon max_iter status_io batch n k p n_paths n_steps n_shock_steps rank_tol "
                                        "x_out w_out obs_out nu_out gap_out Mz_out path_status_out iters_out stream"),
+    "dsge_constrained_simulate_batched": ("B C T R eps eps_batched x0 x0_batched x0_paths Z z_batched d d_batched c_row c_batched "
+                                          "bound bound_batched shock horizon max_iter status_io batch n k p n_paths n_steps "
+                                          "n_shock_steps rank_tol x_out obs_out gap_out shadow_out plan_out duration_out iters_out "
+                                          "Mz_out path_status_out fail_step_out stream"),
     "dsge_solve_kalman_logp_batched": f"{_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_batched_opt": f"opt {_LOGP} T_out R_out resid_out n_iter_out stream",
     "dsge_solve_kalman_logp_augmented_batched": (f"{_FUSED} m inv_var_order n_links link_rows link_cols n_state_hint z_selector_hint "

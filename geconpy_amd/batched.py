@@ -588,6 +588,26 @@ def constrained_paths_batched(B, C, T, R, eps, c, bound, shock, horizon, n_steps
                                d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs)
 
 
+def constrained_simulate_batched(B, C, T, R, eps, c, bound, shock, horizon, n_steps=None, x0=None, Z=None, d=None, status=None,
+                                 rank_tol=0.0, max_iter=0, outputs=("x",)):
+    """STOCHASTIC SIMULATION at an occasionally binding bound for a batch of draws; include/dsge_hip.h,
+    ``dsge_constrained_simulate_batched``.  The model, ``c``, ``bound``, ``shock``, ``horizon`` (1 .. 64, no relation to ``n_steps``),
+    ``x0``, ``Z``, ``d``, ``status``, ``rank_tol`` and ``max_iter`` are those of ``constrained_paths_batched``, but ``eps``
+    (n_paths, n_shock_steps, k) or (batch, n_paths, n_shock_steps, k) holds SURPRISE shocks: ``eps[t]`` arrives at ``t``, agents
+    re-plan, and the linear complementarity problem is solved again every period.  With ``xu = T x[t-1] + R eps[t]``:
+    ``q[h] = c'T^h xu - bound``, the plan ``nu >= 0`` of the regime iteration on ``(Mz, q)``, ``x[t] = xu + W nu``,
+    ``W[:, j] = G^j R[:, shock]``.  ``n_steps`` defaults to the shock steps and may not be below them (zero shocks afterwards).
+    ``outputs``: any of ``"x"``, ``"observed"``, ``"gap"`` (``c'x[t] - bound``), ``"shadow"`` (``nu[0]`` of the plan of ``t``, the
+    shadow shock realised) (batch, n_paths, n_steps[, n | p]), ``"plan"`` (batch, n_paths, n_steps, horizon), ``"duration"`` (the
+    periods the bound is expected to bind in the plan of ``t``) and ``"iters"`` (batch, n_paths, n_steps) int32, ``"Mz"`` (batch,
+    horizon, horizon), ``"path_status"`` and ``"fail_step"`` (batch, n_paths) int32.  ``path_status`` bits: ``OBC_NO_REGIME`` (1),
+    ``OBC_SINGULAR`` (2) -- the path keeps the periods before ``fail_step`` and has NaN from it on, and its draw gets
+    ``ST_CONSTRAINT_UNRESOLVED`` (4096) --, ``OBC_SKIPPED`` (8), ``OBC_HORIZON_SHORT`` (16: in some period the last period of the
+    plan binds; the path is returned).  Returns dict(those requested, status)."""
+    return F.constrained_simulate(HOST, "constrained_simulate_batched", B, C, T, R, eps, c, bound, shock, horizon, n_steps=n_steps, x0=x0,
+                                  Z=Z, d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs)
+
+
 hp_gain, bandpass_gain = F.hp_gain, F.bandpass_gain
 
 

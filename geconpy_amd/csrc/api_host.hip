@@ -923,6 +923,59 @@ int dsge_constrained_paths_batched_host(const double* B, const double* C, const 
   return hc.finish();
 }
 
+int dsge_constrained_simulate_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                           int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z,
+                                           int z_batched, const double* d, int d_batched, const double* c_row, int c_batched,
+                                           const double* bound, int bound_batched, int shock, int horizon, int max_iter,
+                                           int32_t* status_io, int batch, int n, int k, int p, int n_paths, int n_steps,
+                                           int n_shock_steps, double rank_tol, double* x_out, double* obs_out, double* gap_out,
+                                           double* shadow_out, double* plan_out, int32_t* duration_out, int32_t* iters_out,
+                                           double* Mz_out, int32_t* path_status_out, int32_t* fail_step_out) {
+  const ConstrainedProblem c{{batch, n, k, p, n_paths, n_steps, n_shock_steps, DSGE_ANT_PERFECT_FORESIGHT, 0, eps_batched, x0_batched,
+                              x0_paths, z_batched, d_batched, rank_tol},
+                             c_batched, bound_batched, shock, horizon, max_iter};
+  const void* outs[] = {gap_out, shadow_out, plan_out, duration_out, iters_out, Mz_out, path_status_out, fail_step_out};
+  const void* other = nullptr;
+  for (const void* o : outs) other = other ? other : o;
+  int rc = check_constrained_simulate(c, B, C, T, R, eps, Z, c_row, bound, x_out, obs_out, other);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, ns = (size_t)n_steps, nn = (size_t)n * n, H = (size_t)horizon;
+  const double *dB, *dC, *dT, *dR, *de, *dx0, *dZ, *dd, *dc, *dbound;
+  double *dx, *dobs, *dgap, *dsh, *dplan, *dMz;
+  int32_t *dS, *ddur, *dit, *dps, *dfs;
+  hc.in(&dB, B, b * nn);
+  hc.in(&dC, C, b * nn);
+  hc.in(&dT, T, b * nn);
+  hc.in(&dR, R, b * n * k);
+  hc.in(&de, eps, (eps_batched ? b : 1) * np * n_shock_steps * k);
+  hc.in(&dx0, x0, (x0_batched ? b : 1) * (x0_paths ? np : 1) * n);
+  hc.in(&dZ, Z, (z_batched ? b : 1) * p * n);
+  hc.in(&dd, d, (d_batched ? b : 1) * p);
+  hc.in(&dc, c_row, (c_batched ? b : 1) * n);
+  hc.in(&dbound, bound, bound_batched ? b : 1);
+  hc.io(&dS, status_io, b);
+  hc.out(&dx, x_out, b * np * ns * n);
+  hc.out(&dobs, obs_out, b * np * ns * p);
+  hc.out(&dgap, gap_out, b * np * ns);
+  hc.out(&dsh, shadow_out, b * np * ns);
+  hc.out(&dplan, plan_out, b * np * ns * H);
+  hc.out(&ddur, duration_out, b * np * ns);
+  hc.out(&dit, iters_out, b * np * ns);
+  hc.out(&dMz, Mz_out, b * H * H);
+  hc.out(&dps, path_status_out, b * np);
+  hc.out(&dfs, fail_step_out, b * np);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_constrained_simulate_batched(dB, dC, dT, dR, de, eps_batched, dx0, x0_batched, x0_paths, dZ, z_batched, dd, d_batched,
+                                              dc, c_batched, dbound, bound_batched, shock, horizon, max_iter, dS, batch, n, k, p,
+                                              n_paths, n_steps, n_shock_steps, rank_tol, dx, dobs, dgap, dsh, dplan, ddur, dit, dMz, dps,
+                                              dfs, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_forecast_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                const double* P0, const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out,

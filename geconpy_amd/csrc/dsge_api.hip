@@ -912,6 +912,47 @@ int dsge_constrained_paths_batched(const double* B, const double* C, const doubl
   return launch_constrained(c, buf, st);
 }
 
+// ---- stochastic simulation at the bound (dsge_obc_sim.hpp): a chain of launches on the caller's stream (launch_obc_sim.hip); the
+// scratch holds what the Mz chain of the entry above needs (G, a flag per draw, the unit shocks, Mz, the parked terms of a chunk of
+// unit paths), the tables Cq and W per draw and the bits per path ----
+int dsge_constrained_simulate_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                      int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* c_row, int c_batched, const double* bound,
+                                      int bound_batched, int shock, int horizon, int max_iter, int32_t* status_io, int batch, int n,
+                                      int k, int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                      double* obs_out, double* gap_out, double* shadow_out, double* plan_out, int32_t* duration_out,
+                                      int32_t* iters_out, double* Mz_out, int32_t* path_status_out, int32_t* fail_step_out,
+                                      void* stream) {
+  const ConstrainedProblem c{{batch, n, k, p, n_paths, n_steps, n_shock_steps, DSGE_ANT_PERFECT_FORESIGHT, 0, eps_batched, x0_batched,
+                              x0_paths, z_batched, d_batched, rank_tol},
+                             c_batched, bound_batched, shock, horizon, max_iter};
+  const void* outs[] = {gap_out, shadow_out, plan_out, duration_out, iters_out, Mz_out, path_status_out, fail_step_out};
+  const void* other = nullptr;
+  for (const void* o : outs) other = other ? other : o;
+  int rc = check_constrained_simulate(c, B, C, T, R, eps, Z, c_row, bound, x_out, obs_out, other);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || n_paths == 0 || n_steps == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t b = (size_t)batch, np = (size_t)n_paths, H = (size_t)horizon;
+  ConstrainedSimBuffers buf{};
+  buf.mz = ConstrainedBuffers{B, C, T, R, eps, x0, Z, d, c_row, bound, status_io};
+  buf.x_out = x_out; buf.obs_out = obs_out; buf.gap_out = gap_out; buf.shadow_out = shadow_out; buf.plan_out = plan_out;
+  buf.duration_out = duration_out; buf.iters_out = iters_out; buf.Mz_out = Mz_out; buf.path_status_out = path_status_out;
+  buf.fail_step_out = fail_step_out;
+  ScratchLayout lay;
+  lay.add(&buf.mz.G, b * n * n);
+  lay.add(&buf.mz.flag, b);
+  lay.add(&buf.mz.unit, H * H * k);
+  lay.add(&buf.mz.mzt, b * H * H);
+  lay.add(&buf.mz.mzpark, (size_t)constrained_chunk(batch, n, horizon) * H * H * n);
+  lay.add(&buf.cq, b * H * n);
+  lay.add(&buf.wt, b * H * n);
+  lay.add(&buf.pstat, b * np);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  return launch_constrained_sim(c, buf, st);
+}
+
 int dsge_forecast_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0, const double* P0,
                           const int32_t* status, int batch, int m, int k, int p, int n_steps, double* a_out, double* p_out,

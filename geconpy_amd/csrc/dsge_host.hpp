@@ -395,6 +395,23 @@ struct ConstrainedBuffers {
 // draws per launch of the unit paths: their parked anticipation terms, H H m doubles per draw, take at most 256 MB of scratch
 int constrained_chunk(int batch, int m, int horizon);
 int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st);
+// its first two steps alone: G, the flag and Mz (mzt) of every draw, from B, C, T, R, c_row, status, unit and mzpark of `b`
+int launch_constrained_mz(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st);
+// launch_obc_sim.hip (dsge_obc_sim.hpp): the stochastic simulation at the bound -- surprise shocks, the regime iteration every
+// period.  `mz`: the inputs and the scratch of launch_constrained_mz (its outputs are not used); n_shock_steps <= n_steps
+struct ConstrainedSimBuffers {
+  ConstrainedBuffers mz;
+  double *x_out, *obs_out, *gap_out, *shadow_out, *plan_out;
+  int32_t *duration_out, *iters_out;
+  double* Mz_out;
+  int32_t *path_status_out, *fail_step_out;
+  double* cq;      // [batch][H][m]
+  double* wt;      // [batch][H][m]
+  int32_t* pstat;  // [batch][n_paths]
+};
+// bytes of the simulation kernel's LDS image (R inside it where that fits LDS_LIMIT)
+size_t constrained_sim_lds_bytes(int m, int k, int horizon);
+int launch_constrained_sim(const ConstrainedProblem& c, const ConstrainedSimBuffers& b, hipStream_t st);
 // true if launch_kalman, given the selection matrix R and a diagonal Q of k shocks (Rsel, q, k_shocks), forms sym(R Q R')[U,U] inside the
 // fast filter kernel: the caller then skips the full-size product (RQR is filled for handed-on draws only).  It is `fold` of the plan
 // launch_kalman executes (dsge_kalman_plan.hpp), so the two cannot disagree.
@@ -779,6 +796,22 @@ inline int check_constrained_paths(const ConstrainedProblem& c, const double* B,
   if (c.shock < 0 || c.shock >= c.a.k) return fail(DSGE_ERR_INVALID, "constrained paths: shock out of range (0..k-1)");
   if (anticipated_lds_bytes(c.a.m, c.a.k, c.a.p > 1 ? c.a.p : 1) > LDS_LIMIT)
     return fail(DSGE_ERR_TOO_LARGE, "constrained paths: the LDS image exceeds 160 KB (docs/design/occasionally_binding.md)");
+  return DSGE_SUCCESS;
+}
+
+// the stochastic simulation at the bound: the refusals of check_constrained_paths less horizon <= n_steps (a plan may look beyond
+// the simulated periods), plus shocks beyond the last period.  `other`: non-null if an output besides x and observed is wanted
+inline int check_constrained_simulate(const ConstrainedProblem& c, const double* B, const double* C, const double* T, const double* R,
+                                      const double* eps, const double* Z, const double* c_row, const double* bound,
+                                      const double* x_out, const double* obs_out, const void* other) {
+  if (int rc = check_anticipated_paths(c.a, B, C, T, R, eps, Z, x_out, nullptr, obs_out, (const double*)other)) return rc;
+  if (!c_row || !bound) return fail(DSGE_ERR_INVALID, "null pointer");
+  if (c.horizon < 1 || c.horizon > DSGE_OBC_MAX_HORIZON)
+    return fail(DSGE_ERR_INVALID, "constrained simulation: horizon out of range (1..DSGE_OBC_MAX_HORIZON)");
+  if (c.shock < 0 || c.shock >= c.a.k) return fail(DSGE_ERR_INVALID, "constrained simulation: shock out of range (0..k-1)");
+  if (anticipated_lds_bytes(c.a.m, c.a.k, c.a.p > 1 ? c.a.p : 1) > LDS_LIMIT || constrained_sim_lds_bytes(c.a.m, c.a.k, c.horizon) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "constrained simulation: the LDS image exceeds 160 KB (docs/design/stochastic_bound.md)");
+  if (c.a.n_shock_steps > c.a.n_steps) return fail(DSGE_ERR_INVALID, "constrained simulation: n_shock_steps > n_steps");
   return DSGE_SUCCESS;
 }
 

@@ -15,22 +15,18 @@
 //                      iteration the rows of K = Mz[S,S] (a row off S, and a column off S, is not touched) in registers,
 //                      Gauss-Jordan with row pivoting and NO row exchange -- pivot by the wave maximum of dsge_device.hpp (the lowest
 //                      row among equal maxima), the pivot row through readlane_dyn_f64 -- S a 64-bit ballot, the fixed-point test a
-//                      comparison of two scalars.  A pivot with |pivot| <= rank_tol max|Mz| (or not finite), or a q_h that is not
+//                      comparison of two scalars (the iteration itself: obc_regime_iterate of dsge_obc_regime.hpp, which the
+//                      simulation kernel of dsge_obc_sim.hpp calls once per period).  A pivot with |pivot| <= rank_tol max|Mz| (or not finite), or a q_h that is not
 //                      finite -> OBC_SINGULAR; max_iter solves without a fixed point -> OBC_NO_REGIME.  Writes nu, iters, the path's
 //                      bits, max|q| and e' (zero rows up to max(n_shock_steps, H));
 //   obc_gap_kernel     one wavefront per (draw, path): gap_t = c'x_t - bound on the final path, OBC_BEYOND_HORIZON when
 //                      gap_t < -1e-12 max|q| at some t >= H, NaN over every output of a failed path, and the draw's status bit.
 // No atomics: two calls give the same bits.
 #pragma once
-#include "dsge_postsolve.hpp"
+#include "dsge_obc_regime.hpp"
 
 namespace dsge {
 
-constexpr int OBC_THREADS = 256, OBC_WAVES = 4;  // paths (wavefronts) per workgroup
-constexpr int OBC_MAX_H = 64;                     // DSGE_OBC_MAX_HORIZON
-constexpr int OBC_NO_REGIME = 1, OBC_SINGULAR = 2, OBC_BEYOND = 4, OBC_SKIPPED = 8;  // DSGE_OBC_*
-constexpr int OBC_FAILED = OBC_NO_REGIME | OBC_SINGULAR | OBC_SKIPPED;
-constexpr int OBC_ST_UNRESOLVED = 4096;           // DSGE_ST_CONSTRAINT_UNRESOLVED
 constexpr double OBC_BEYOND_TOL = 1e-12;
 
 __host__ __device__ inline int obc_ld(int H) { return H + 1; }
@@ -70,7 +66,7 @@ __global__ __launch_bounds__(OBC_THREADS) void obc_unit_kernel(double* u, int H,
   u[idx] = t == j && c == s ? 1.0 : 0.0;
 }
 
-// HM: 32 or 64, the rows of K a lane holds
+// HM: 32 or 64, the rows of K a lane holds (obc_regime_iterate, dsge_obc_regime.hpp)
 template <int HM>
 __global__ __launch_bounds__(OBC_THREADS) void obc_regime_kernel(ObcArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -121,74 +117,8 @@ __global__ __launch_bounds__(OBC_THREADS) void obc_regime_kernel(ObcArgs a) {
     }
     const double thr = (a.rank_tol > 0.0 ? a.rank_tol : 1e-14) * mmax;
     const int max_iter = a.max_iter > 0 ? a.max_iter : 64;
-    if (__ballot(act && !(fabs(q) < INFINITY)) != 0ull) {
-      st = OBC_SINGULAR;
-    } else {
-      unsigned long long S = __ballot(act && q < 0.0);
-      for (;;) {
-        ++iters;
-        nu = 0.0;
-        const bool in_s = (S >> lane) & 1ull;
-        if (S != 0ull) {
-          double kr[HM];
-#pragma unroll
-          for (int c = 0; c < HM; ++c) kr[c] = in_s && ((S >> c) & 1ull) ? Mz[lane * ld + c] : 0.0;
-          double rhs = in_s ? -q : 0.0, pv = 1.0;
-          unsigned long long avail = S;  // rows that have not been a pivot row
-          int mycol = lane;              // the column whose solution this row ends up holding
-          bool singular = false;
-#pragma unroll
-          for (int j = 0; j < HM; ++j) {
-            if (singular || !((S >> j) & 1ull)) continue;  // (wave-uniform)
-            double v = fabs(kr[j]);
-            if (!(v == v)) v = INFINITY;  // a NaN wins, and fails the test below
-            const unsigned long long key = (avail >> lane) & 1ull ? (unsigned long long)__double_as_longlong(v) : 0ull;
-            const unsigned long long best = wave_max_u64(key);
-            const unsigned long long who = __ballot(((avail >> lane) & 1ull) && key == best);
-            const int r = __builtin_ctzll(who);  // (a row is left whenever a column of S is)
-            const double piv = readlane_dyn_f64(kr[j], r);
-            if (!(fabs(piv) > thr) || !(fabs(piv) < INFINITY)) {
-              singular = true;
-              continue;
-            }
-            avail &= ~(1ull << r);
-            const bool is_r = lane == r;
-            if (is_r) {
-              mycol = j;
-              pv = piv;
-            }
-            const double f = is_r ? 0.0 : kr[j] / piv;
-#pragma unroll
-            for (int c = j + 1; c < HM; ++c)
-              if ((S >> c) & 1ull) kr[c] = fma(-f, readlane_dyn_f64(kr[c], r), kr[c]);
-            rhs = fma(-f, readlane_dyn_f64(rhs, r), rhs);
-          }
-          if (singular) {
-            st = OBC_SINGULAR;
-            break;
-          }
-          // row r holds the solution of column mycol; rows off S hold zero for their own column
-          __builtin_amdgcn_wave_barrier();
-          nub[mycol] = in_s ? rhs / pv : 0.0;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          nu = nub[lane];
-        }
-        double gp = q;
-        if (act)
-          for (unsigned long long bits = S; bits != 0ull; bits &= bits - 1ull) {
-            const int j = __builtin_ctzll(bits);
-            gp = fma(Mz[lane * ld + j], nub[j], gp);
-          }
-        const unsigned long long Sn = __ballot(act && (in_s ? nu > 0.0 : gp < 0.0));
-        if (Sn == S) break;
-        if (iters >= max_iter) {
-          st = OBC_NO_REGIME;
-          break;
-        }
-        S = Sn;
-      }
-    }
+    unsigned long long S;
+    st = obc_regime_iterate<HM>(Mz, ld, nub, lane, act, q, thr, max_iter, nu, iters, S);
   }
   const bool failed = st != 0;
   if (lane == 0) {

@@ -15,14 +15,10 @@ int constrained_chunk(int batch, int m, int horizon) {
   return chunks <= 1 ? batch : (int)(((size_t)batch + chunks - 1) / chunks);
 }
 
-int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st) {
+// G, the flag and Mz of every draw (steps 1 and 2 of launch_constrained; launch_obc_sim.hip runs the same chain)
+int launch_constrained_mz(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st) {
   const AnticipatedProblem& p = c.a;
   const int H = c.horizon, m = p.m, k = p.k;
-  const int nsp = p.n_shock_steps > H ? p.n_shock_steps : H;
-  const bool final_paths = b.x_out || b.w_out || b.obs_out || b.gap_out || b.path_status_out;
-  const int groups = (p.n_paths + dsge::OBC_WAVES - 1) / dsge::OBC_WAVES;
-  unsigned grid;
-  if (int rc = batch_grid(p.batch, groups, "constrained paths: batch x path groups exceeds the grid", &grid)) return rc;
 
   // 1. G and the flag of every draw
   if (int rc = launch_anticipated(p, b.B, b.C, b.T, b.R, nullptr, nullptr, nullptr, nullptr, b.status, b.G, 0, b.flag, nullptr, nullptr,
@@ -46,6 +42,20 @@ int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b,
                                     b.flag + o, b.mzpark, nullptr, nullptr, b.mzt + o * H * H, st, ANT_PATHS))
       return rc;
   }
+  return DSGE_SUCCESS;
+}
+
+int launch_constrained(const ConstrainedProblem& c, const ConstrainedBuffers& b, hipStream_t st) {
+  const AnticipatedProblem& p = c.a;
+  const int H = c.horizon, m = p.m, k = p.k;
+  const int nsp = p.n_shock_steps > H ? p.n_shock_steps : H;
+  const bool final_paths = b.x_out || b.w_out || b.obs_out || b.gap_out || b.path_status_out;
+  const int groups = (p.n_paths + dsge::OBC_WAVES - 1) / dsge::OBC_WAVES;
+  unsigned grid;
+  if (int rc = batch_grid(p.batch, groups, "constrained paths: batch x path groups exceeds the grid", &grid)) return rc;
+
+  // 1., 2. G, the flag and Mz
+  if (int rc = launch_constrained_mz(c, b, st)) return rc;
 
   // 3. the unconstrained paths, periods < H, into the x buffer
   AnticipatedProblem q = p;

@@ -331,6 +331,17 @@ class LogpEngine:
         return F.constrained_paths(self.backend, "constrained_paths", B, C, T, R, eps, c, bound, shock, horizon, n_steps=n_steps, x0=x0,
                                    Z=Z, d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs, out=out)
 
+    # -- stochastic simulation at the bound (csrc/dsge_obc_sim.hpp) --------------------------------
+    def constrained_simulate(self, B, C, T, R, eps, c, bound, shock, horizon, n_steps=None, x0=None, Z=None, d=None, status=None,
+                             rank_tol=0.0, max_iter=0, outputs=("x",), out=None):
+        """Stochastic simulation at an occasionally binding bound of the whole batch from device tensors
+        (``dsge_constrained_simulate_batched``; see ``batched.constrained_simulate_batched``), on torch's current stream: surprise
+        shocks, the plan re-solved every period inside one kernel.  ``bound``: a number or a device tensor (batch,).  ``status``
+        (device int32) is updated in place.  ``out``: optional dict with preallocated outputs.  Returns dict(those of x, observed, gap,
+        shadow, plan, duration, iters, Mz, path_status, fail_step that ``outputs`` names, status); asynchronous."""
+        return F.constrained_simulate(self.backend, "constrained_simulate", B, C, T, R, eps, c, bound, shock, horizon, n_steps=n_steps,
+                                      x0=x0, Z=Z, d=d, status=status, rank_tol=rank_tol, max_iter=max_iter, outputs=outputs, out=out)
+
     # -- second-order dynamics (csrc/dsge_pruned.hpp) -------------------------------------------
     def simulate_pruned(self, *args, out=None, **kwargs):
         """Simulated paths of the pruned second-order system from device tensors (``dsge_simulate_pruned_batched``; arguments as

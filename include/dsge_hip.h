@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSGE_ABI_VERSION 18
+#define DSGE_ABI_VERSION 19
 
 /* ABI 8: the process-wide dsge_set_* switches (deprecated at ABI 7) are GONE -- they edited defaults shared by every host
  * thread and stream of the process, which a library called from several PyMC chains must not have.  Every switch is a field
@@ -55,6 +55,7 @@ extern "C" {
 /* ABI 17: dsge_anticipated_paths_batched (+ _host) and the status bit DSGE_ST_ANTICIPATION_SINGULAR are new; nothing else changed. */
 /* ABI 18: dsge_constrained_paths_batched (+ _host) and the status bit DSGE_ST_CONSTRAINT_UNRESOLVED are new (new entry and status
  * bit, nothing else changed). */
+/* ABI 19: dsge_constrained_simulate_batched (+ _host) and the path bit DSGE_OBC_HORIZON_SHORT are new; nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -97,11 +98,12 @@ extern "C" {
 #define DSGE_ST_ANTICIPATION_SINGULAR 2048 /* anticipated paths: B + C T singular to rank_tol */
 #define DSGE_ST_CONSTRAINT_UNRESOLVED 4096 /* constrained paths: a path of the draw has DSGE_OBC_NO_REGIME or DSGE_OBC_SINGULAR */
 
-/* per-path bits of dsge_constrained_paths_batched (path_status_out) */
+/* per-path bits of dsge_constrained_paths_batched and dsge_constrained_simulate_batched (path_status_out) */
 #define DSGE_OBC_NO_REGIME 1      /* the regime iteration found no fixed point within max_iter solves */
 #define DSGE_OBC_SINGULAR 2       /* a pivot of Mz[S,S] <= rank_tol max|Mz|, or a pivot or q[h] not finite */
 #define DSGE_OBC_BEYOND_HORIZON 4 /* gap[t] < -1e-12 max|q| at some t >= horizon: reported, the path is returned as it is */
 #define DSGE_OBC_SKIPPED 8        /* the draw came in with a non-zero status word, or B + C T is singular */
+#define DSGE_OBC_HORIZON_SHORT 16 /* dsge_constrained_simulate_batched: in some period the last period of the plan binds */
 
 /* information structures of dsge_anticipated_paths_batched */
 #define DSGE_ANT_PERFECT_FORESIGHT 0 /* the whole shock path is known at t = 0 */
@@ -1105,6 +1107,57 @@ int dsge_constrained_paths_batched_host(const double* B, const double* C, const 
                                         int32_t* status_io, int batch, int n, int k, int p, int n_paths, int n_steps, int n_shock_steps,
                                         double rank_tol, double* x_out, double* w_out, double* obs_out, double* nu_out, double* gap_out,
                                         double* Mz_out, int32_t* path_status_out, int32_t* iters_out);
+
+/*
+ * STOCHASTIC SIMULATION AT AN OCCASIONALLY BINDING BOUND per draw (ABI 19; csrc/dsge_obc_sim.hpp, docs/design/stochastic_bound.md):
+ * the bound of dsge_constrained_paths_batched with SURPRISE shocks.  eps[t] is not known before t; in every period agents re-plan
+ * under perfect foresight of zero shocks from t + 1 on, and the bound binds for as long as they then expect it to.  The model, T, R,
+ * M = B + C T, G, Mz, the regime iteration, rank_tol and max_iter are exactly those of dsge_constrained_paths_batched.  With
+ * xu = T x[t-1] + R eps[t] the state of period t if no shadow shock is used:
+ *       q[h]  = c'T^h xu - bound,  h < horizon        (the gaps expected on that path)
+ *       plan  = nu(t)[0 .. horizon-1] >= 0 :  gap = q + Mz nu(t),  gap >= 0,  nu(t) gap = 0      (the regime iteration on (Mz, q))
+ *       x[t]  = xu + W nu(t),   W[:, j] = G^j R[:, shock]                                        (period 0 of the plan's path)
+ * which is period 0 of dsge_constrained_paths_batched with eps = eps[t] alone, x0 = x[t-1] and n_steps = horizon.  Only nu(t)[0], the
+ * shadow shock of period t, is realised; the rest of the plan is revised in t + 1.
+ * Inputs as dsge_constrained_paths_batched, except: n_shock_steps <= n_steps (zero shocks afterwards), and horizon in
+ * 1 .. DSGE_OBC_MAX_HORIZON bears no relation to n_steps.
+ * Outputs, any may be NULL, not all:
+ *   x_out   : [batch][n_paths][n_steps][n];   obs_out : [batch][n_paths][n_steps][p]  (Z x[t] + d)
+ *   gap_out, shadow_out : [batch][n_paths][n_steps]        gap[t] = c'x[t] - bound;  shadow[t] = nu(t)[0]
+ *   plan_out : [batch][n_paths][n_steps][horizon]          the whole nu(t)
+ *   duration_out, iters_out : [batch][n_paths][n_steps] int32: the periods the bound is expected to bind in the plan of t (the size
+ *                             of the final binding set), and the solves of the regime iteration of t
+ *   Mz_out  : [batch][horizon][horizon], the bits of dsge_constrained_paths_batched's
+ *   path_status_out, fail_step_out : [batch][n_paths] int32
+ * Per-path bits: DSGE_OBC_NO_REGIME, DSGE_OBC_SINGULAR, DSGE_OBC_SKIPPED as above; DSGE_OBC_HORIZON_SHORT: in some period the last
+ * period of the plan binds, so the horizon may be too short -- reported, the path is returned as it is.  DSGE_OBC_BEYOND_HORIZON is not
+ * used.  A path that fails in period f (NO_REGIME, SINGULAR, or a q that is not finite) keeps every output of the periods < f and has
+ * NaN in them from f on (iters: the count at f, then 0; duration: -1); fail_step_out holds f, or -1 for a path that did not fail.
+ * status_io |= DSGE_ST_CONSTRAINT_UNRESOLVED for a draw with a NO_REGIME or SINGULAR path.  A skipped draw (incoming status, B + C T
+ * singular): DSGE_OBC_SKIPPED, NaN everywhere (iters 0, duration -1, Mz NaN), fail_step 0.  Every other path of every draw is untouched,
+ * bit for bit.
+ * A chain of launches on `stream` (the setup and the unit-shock paths for Mz of dsge_constrained_paths_batched, the tables c'T^h and
+ * W per draw, one simulation kernel with the time loop inside, the draws' status bits), no host synchronisation, no atomics: two calls
+ * give the same bits, any subset of the outputs the bits of the full call.
+ * Refusals, all before any device is touched: those of dsge_constrained_paths_batched less horizon > n_steps; DSGE_ERR_INVALID for
+ * n_shock_steps > n_steps.  batch == 0, n_paths == 0 or n_steps == 0: success, nothing touched.
+ */
+int dsge_constrained_simulate_batched(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                      int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* c_row, int c_batched, const double* bound,
+                                      int bound_batched, int shock, int horizon, int max_iter, int32_t* status_io, int batch, int n,
+                                      int k, int p, int n_paths, int n_steps, int n_shock_steps, double rank_tol, double* x_out,
+                                      double* obs_out, double* gap_out, double* shadow_out, double* plan_out, int32_t* duration_out,
+                                      int32_t* iters_out, double* Mz_out, int32_t* path_status_out, int32_t* fail_step_out,
+                                      void* stream);
+int dsge_constrained_simulate_batched_host(const double* B, const double* C, const double* T, const double* R, const double* eps,
+                                           int eps_batched, const double* x0, int x0_batched, int x0_paths, const double* Z,
+                                           int z_batched, const double* d, int d_batched, const double* c_row, int c_batched,
+                                           const double* bound, int bound_batched, int shock, int horizon, int max_iter,
+                                           int32_t* status_io, int batch, int n, int k, int p, int n_paths, int n_steps,
+                                           int n_shock_steps, double rank_tol, double* x_out, double* obs_out, double* gap_out,
+                                           double* shadow_out, double* plan_out, int32_t* duration_out, int32_t* iters_out,
+                                           double* Mz_out, int32_t* path_status_out, int32_t* fail_step_out);
 
 /*
  * Fused evaluation A,B,C,D -> T,R -> P0 -> logp: one call per MCMC step for the whole draw

@@ -7,6 +7,7 @@
     python tools/dynamics_time.py --spectral [draws ...]          the spectral-moments rows alone
     python tools/dynamics_time.py --anticipated [draws ...]       the anticipated-shock rows alone
     python tools/dynamics_time.py --constrained [draws ...]       the occasionally-binding-bound rows alone
+    python tools/dynamics_time.py --stochastic-bound [draws ...]  the rows of the stochastic simulation at the bound alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -65,20 +66,20 @@ from tests import dynamics_reference as dr
 N_STEPS = 40
 
 
-def timed(fn, min_seconds=1.0):
-    for _ in range(2):
+def timed(fn, min_seconds=1.0, warm=2, calls=4):
+    for _ in range(warm):
         fn()
     torch.cuda.synchronize()
     reps, total = 0, 0.0
     while total < min_seconds:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(4):
+        for _ in range(calls):
             fn()
         e1.record()
         e1.synchronize()
         total += e0.elapsed_time(e1) * 1e-3
-        reps += 4
+        reps += calls
     return total / reps * 1e3  # ms per call
 
 
@@ -492,9 +493,105 @@ def constrained_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, horizon=32, shock=
               f"and the gap over them (entry less outputs=('nu',)) {t_entry - t_nu:8.3f}")
 
 
+def stochastic_bound_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, horizon=32, shock=0, repeats=5):
+    """The workload of --constrained with fresh (surprise) shocks every period: LogpEngine.constrained_simulate against the composed
+    route of the public calls before it -- Mz and G once from constrained_paths(outputs=("Mz",)) and anticipated_paths(outputs=("G",)),
+    the tables Cq and W by torch products, then per period bmm for xu and q, the torch regime loop of --constrained, and the update."""
+    b = wl.sw_shaped_batch(64)
+    m, k, H = 40, 7, horizon
+    rng = np.random.default_rng(0)
+    D64 = rng.standard_normal((64, m, k)) / np.sqrt(m)
+    R64 = np.stack([np.linalg.solve(b["B"][i] + b["C"][i] @ b["T_star"][i], -D64[i]) for i in range(64)])
+    var = np.argmax(np.abs(R64[:, :, shock]), axis=1)
+    c64 = np.zeros((64, m))
+    c64[np.arange(64), var] = np.sign(R64[np.arange(64), var, shock])
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    print(f"stochastic simulation at the bound m={m} k={k}, dense impact matrix, {n_steps} steps, {n_paths} paths, surprise shocks at every "
+          f"step, H={H}, bound at half the unconstrained simulated minimum; medians of {repeats} timings of >= 1 s")
+    for nb in sizes:
+        rep = (nb + 63) // 64
+        B, C, T, R = (eng.to_device(np.tile(a, (rep, 1, 1))[:nb]) for a in (b["B"], b["C"], b["T_star"], R64))
+        c = eng.to_device(np.tile(c64, (rep, 1))[:nb])
+        eps = eng.to_device(rng.standard_normal((nb, n_paths, n_steps, k)) * 0.01)
+        x0 = eng.to_device(rng.standard_normal((nb, n_paths, m)) * 0.05)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        cx, x = [], x0  # the unconstrained simulation, for the bound
+        for t in range(n_steps):
+            x = torch.baddbmm(torch.bmm(eps[:, :, t], R.transpose(1, 2)), x, T.transpose(1, 2))
+            cx.append(torch.einsum("bpn,bn->bp", x, c))
+        bound = (0.5 * torch.stack(cx, dim=-1).amin(dim=(1, 2))).contiguous()
+        out, out_mz = dict(x=mk(nb, n_paths, n_steps, m)), dict(Mz=mk(nb, H, H))
+        entry = lambda: eng.constrained_simulate(B, C, T, R, eps, c, bound, shock, H, x0=x0, out=out)  # noqa: E731
+        to_mz = lambda: eng.constrained_simulate(B, C, T, R, eps, c, bound, shock, H, x0=x0, outputs=("Mz",), out=out_mz)  # noqa: E731
+        # the composed route
+        eye = torch.eye(H, dtype=torch.float64, device=eng.device)
+        o_mz, g_only, x_c = dict(Mz=mk(nb, H, H)), dict(G=mk(nb, m, m)), mk(nb, n_paths, n_steps, m)
+        hold, e1 = dict(iters=0), eps[:, :1, :1].contiguous()  # (Mz and G do not depend on the shocks)
+
+        def tables():
+            eng.constrained_paths(B, C, T, R, e1, c, bound, shock, H, n_steps=H, outputs=("Mz",), out=o_mz)
+            eng.anticipated_paths(B, C, T, R, e1, outputs=("G",), out=g_only)
+            rows, cols = [c[:, None, :]], [R[:, :, shock:shock + 1]]
+            for _ in range(H - 1):
+                rows.append(torch.bmm(rows[-1], T))
+                cols.append(torch.bmm(g_only["G"], cols[-1]))
+            hold["Cq"], hold["W"] = torch.cat(rows, dim=1), torch.cat(cols, dim=2)  # (nb, H, m), (nb, m, H)
+
+        def periods():
+            Mz, Cq, W = o_mz["Mz"], hold["Cq"], hold["W"]
+            x = x0
+            alive = torch.ones(nb, n_paths, dtype=torch.bool, device=eng.device)
+            for t in range(n_steps):
+                xu_t = torch.baddbmm(torch.bmm(eps[:, :, t], R.transpose(1, 2)), x, T.transpose(1, 2))  # (nb, n_paths, m)
+                q = torch.bmm(xu_t, Cq.transpose(1, 2)) - bound[:, None, None]
+                S, iters = q < 0.0, 0
+                while True:
+                    iters += 1
+                    d = S.to(torch.float64)
+                    K = eye + d[..., :, None] * (Mz[:, None] - eye) * d[..., None, :]
+                    nu = torch.linalg.solve(K, (-q * d)[..., None])[..., 0]
+                    gap = q + torch.einsum("bhj,bpj->bph", Mz, nu)
+                    S_new = torch.where(S, nu > 0.0, gap < 0.0)
+                    same = (S_new == S).all(dim=-1)
+                    if bool(same.all()) or iters >= 64:  # (the host round trip of every iteration)
+                        break
+                    S = torch.where(same[..., None], S, S_new)  # a path that has its regime keeps it
+                alive = alive & same
+                hold["iters"] = max(hold["iters"], iters)
+                x = xu_t + torch.bmm(nu, W.transpose(1, 2))
+                x_c[:, :, t] = x
+            hold["alive"] = alive
+
+        entry()
+        tables()
+        periods()
+        torch.cuda.synchronize()
+        it = eng.constrained_simulate(B, C, T, R, eps, c, bound, shock, H, x0=x0, outputs=("iters", "duration", "path_status", "fail_step"))
+        torch.cuda.synchronize()
+        ok = ((it["path_status"] & (_lib.OBC_NO_REGIME | _lib.OBC_SINGULAR | _lib.OBC_SKIPPED)) == 0) & hold["alive"]
+        diff = (out["x"][ok] - x_c[ok]).abs().max().item() / x_c[ok].abs().max().item()
+        good = it["fail_step"] < 0
+        print(f"draws={nb:5d} failed paths: {int((~good).sum())} of {good.numel()} (composed route: {int((~hold['alive']).sum())} without a regime "
+              f"in some period); path_status bits seen {sorted(set(it['path_status'].flatten().tolist()))}; status words seen "
+              f"{sorted(set(it['status'].tolist()))}")
+        print(f"draws={nb:5d} entry against the composed route on the paths both resolve: {diff:.1e} of max|x|; iters mean "
+              f"{it['iters'][good].double().mean().item():.2f} max {int(it['iters'].max())}, duration mean "
+              f"{it['duration'][good].double().mean().item():.2f} max {int(it['duration'].max())} (composed loop: up to {hold['iters']} round "
+              f"trips in a period)")
+        assert diff <= 1e-9, diff
+        t_entry, t_mz, t_tab = med(entry), med(to_mz), med(tables)
+        # (the period loop has run once above; a call of it takes seconds where paths without a regime hold it for 64 round trips)
+        t_per = float(np.median([timed(periods, warm=0, calls=1) for _ in range(repeats)]))
+        t_comp = t_tab + t_per
+        print(f"draws={nb:5d} entry {t_entry:8.3f} ms | composed route {t_comp:8.3f} ms = Mz, G and tables {t_tab:8.3f} + {n_steps} periods "
+              f"{t_per:8.3f} | entry / composed {t_entry / t_comp:5.2f}")
+        print(f"draws={nb:5d} phase split of the entry: outputs=('Mz',) (Mz chain, tables, a simulation that writes only Mz) {t_mz:8.3f} ms, "
+              f"entry less that {t_entry - t_mz:8.3f} ms")
+
+
 def main():
     args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated",
-                                                 "--constrained")]
+                                                 "--constrained", "--stochastic-bound")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
@@ -508,6 +605,8 @@ def main():
         return anticipated_rows(LogpEngine(0), sizes)
     if "--constrained" in sys.argv:
         return constrained_rows(LogpEngine(0), sizes)
+    if "--stochastic-bound" in sys.argv:
+        return stochastic_bound_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
