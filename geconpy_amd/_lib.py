@@ -106,6 +106,7 @@ _DEVICE_ENTRIES = {
     "dsge_options_pop": "",
     "dsge_forget_measured_shapes": "",
     "dsge_debug_cr_phases": "enable cycles_out",
+    "dsge_debug_cr_fused_phases": "enable cycles_out",
     "dsge_debug_kalman_steady_steps": "steady_at_device",
     "dsge_debug_kalman_timeline": "timeline_device",
     "dsge_debug_kalman_phases": "enable cycles_out",

@@ -299,6 +299,7 @@ static int debug_counters(long long** slot, int count, int enable, long long* cy
   return DSGE_SUCCESS;
 }
 int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_dbg, 8, enable, cycles_out); }
+int dsge_debug_cr_fused_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_fused_dbg, 16, enable, cycles_out); }
 int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
 int dsge_debug_pruned_phases(int enable, long long* cycles_out) { return debug_counters(&g_pruned_dbg, 8, enable, cycles_out); }
 int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out) { return debug_counters(&g_shock_decomp_dbg, 8, enable, cycles_out); }

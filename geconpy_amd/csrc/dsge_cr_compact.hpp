@@ -19,6 +19,8 @@
 
 #include "../../include/dsge_hip.h"
 
+#include <limits>
+
 namespace dsge {
 
 // Bank conflicts of the even (BS = 4) tile, measured 39 % of its LDS cycles.  ds_read_b128 is served in four groups of 16
@@ -35,6 +37,20 @@ struct CrcSmem {
   static constexpr int NP = Tile<BS>::NP, LDW = 2 * NP + (BS % 2 == 0 ? 2 : 1);  // even tiles: rows of a register block are 16-byte aligned (b128 LDS accesses; half the conflict cycles of the odd stride on the 4 x 4 tile: 0.90 -> 0.84 ms)
   // W = [A1 | R], Gauss-Jordan scratch (Lbuf NP*BS, Ybuf BS*2NP), ints: prow, cmap, posS, posL, rsrc
   static constexpr size_t bytes = sizeof(double) * (size_t)(NP * LDW + NP * BS + BS * 2 * NP) + sizeof(int) * 5 * NP;
+};
+
+// (round 12) What the position tables posS / posL hold for a variable that is no state / no lead variable.  The scatter of
+// crc_iterate subtracts column posL(v) of W and column posS(v) of G1 = W + NP from A1 for every variable v, and +0.0 where v has
+// no such column.  `pad`: the tables then name the first pad column of the row stride LDW (column 2 NP of W, which is column NP of
+// G1) -- zeroed with W once per draw and never written again: every block store, the panel copies and the trailing updates end
+// at column 2 NP - 1 -- so the scatter reads its +0.0 there, without a compare and a 64-bit select per entry.  (Not the spare
+// columns of the products: those turn NaN when an operand is Inf.)  Where 2 NP does not fit the table type the tables keep -1
+// and crc_iterate its selects.
+template <int BS, typename IT>
+struct CrcPos {
+  static constexpr int NP = 8 * BS;
+  static constexpr bool pad = 2 * NP <= (int)std::numeric_limits<IT>::max();
+  static constexpr int noS = pad ? NP : -1, noL = pad ? 2 * NP : -1;
 };
 
 // non-zero column mask of a register-block matrix (bit v = column v has a non-zero or NaN entry)
@@ -190,8 +206,14 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
 #pragma unroll
       for (int j = 0; j < BS; ++j) {
         const int row = lr * BS + i, c = lc * BS + j;
-        const double d02 = (vL[j] >= 0) ? W[row * LDW + vL[j]] : 0.0;   // m02[:, posL(v)]
-        const double d20 = (vS[j] >= 0) ? G1[row * LDW + vS[j]] : 0.0;  // m20[:, posS(v)]
+        double d02, d20;  // m02[:, posL(v)], m20[:, posS(v)]; +0.0 for a variable without the column (CrcPos)
+        if constexpr (CrcPos<BS, IT>::pad) {
+          d02 = W[row * LDW + vL[j]];
+          d20 = G1[row * LDW + vS[j]];
+        } else {
+          d02 = (vL[j] >= 0) ? W[row * LDW + vL[j]] : 0.0;
+          d20 = (vS[j] >= 0) ? G1[row * LDW + vS[j]] : 0.0;
+        }
         A1[i][j] -= d02;
         A1[i][j] -= d20;
         Ah[i][j] -= d20;
@@ -233,8 +255,8 @@ __device__ __forceinline__ void cr_compact_body(const double* __restrict__ A, co
   double* Ybuf = Lbuf + NP * BS;
   int* prow = (int*)(Ybuf + BS * 2 * NP);
   int* cmap = prow + NP;   // compact column -> variable (S first, then L)
-  int* posS = cmap + NP;   // variable -> compact column of R if it is a state, else -1
-  int* posL = posS + NP;   // variable -> compact column of R if it is a lead variable, else -1
+  int* posS = cmap + NP;   // variable -> compact column of R if it is a state, else CrcPos::noS
+  int* posL = posS + NP;   // variable -> compact column of R if it is a lead variable, else CrcPos::noL
   int* rsrc = posL + NP;   // compact row r of X sits in row rsrc[r] of W after the elimination
   const int lane = threadIdx.x, lr = lane >> 3, lc = lane & 7;
 
@@ -260,8 +282,8 @@ __device__ __forceinline__ void cr_compact_body(const double* __restrict__ A, co
       const unsigned long long below = (1ull << lane) - 1ull;
       const bool isS = (maskS >> lane) & 1ull, isL = (maskL >> lane) & 1ull;
       const int ps = __popcll(maskS & below), pl = s + __popcll(maskL & below);
-      posS[lane] = isS ? ps : -1;
-      posL[lane] = isL ? pl : -1;
+      posS[lane] = isS ? ps : CrcPos<BS, int>::noS;
+      posL[lane] = isL ? pl : CrcPos<BS, int>::noL;
       if (isS) cmap[ps] = lane;
       if (isL) cmap[pl] = lane;
     }
@@ -337,7 +359,7 @@ __device__ __forceinline__ void cr_compact_body(const double* __restrict__ A, co
       for (int i = 0; i < BS; ++i)
 #pragma unroll
         for (int j = 0; j < BS; ++j)
-          Tb[i][j] = (vS[j] >= 0) ? -G1[(lr * BS + i) * LDW + vS[j]] : 0.0;
+          Tb[i][j] = (vS[j] != CrcPos<BS, int>::noS) ? -G1[(lr * BS + i) * LDW + vS[j]] : 0.0;
       if (r_fits) {
         for (int idx = lane; idx < n * k; idx += 64) {
           const int r = idx / k, c = idx - r * k;

@@ -138,13 +138,14 @@ __device__ __forceinline__ bool crd_col_source(int cv, const double* __restrict_
 // the first chunk) are B_st itself: lane j publishes pivot column j to LDS (V), from where every lane (and a later chunk,
 // for systems with more columns than one pass holds) reads it as a broadcast; no wave reductions anywhere.  Rows 0..h-1 of
 // Q'[...] go to `tp` (h x ncols, row-major); on return col[q] holds the rows of the REDUCED system (rows 0..nd-1, zeros
-// below).
+// below) for every column but the h columns of B_st, which have none: their registers hold nothing of use.
 template <int NM, int NC, typename IT>
 __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const double* __restrict__ B,
                                              const double* __restrict__ C, const double* __restrict__ D, size_t off,
                                              size_t offk, int n, int k, int h, int c0, const IT* dyi, const IT* sti,
                                              double* V, double* __restrict__ tp, int lane, double (&col)[NC][NM],
-                                             bool (&act)[NC], bool skip_zero_ac = false) {
+                                             bool (&act)[NC], bool skip_zero_ac = false,
+                                             long long* t_loaded = nullptr) {  // debug stamp: the columns have arrived
   const int ncols = h + 3 * (n - h) + k;
   const double* src[NC];
   int ss[NC], cv[NC];
@@ -179,6 +180,7 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       wr[q] = act[q] && (nz || !ac);
     }
   }
+  if (t_loaded) *t_loaded = clock64();
   // Row j is final once reflector j has been applied: it goes straight to the top block and the columns are shifted
   // up by one row, so that the pivot is always register row 0 (no index-dependent selects, which cost a scalar lane
   // mask each) and what is left after h reflectors is the reduced system, rows 0..nd-1.
@@ -235,13 +237,15 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       const double topv = lf ? ((lane == j) ? beta : 0.0) : col[q][0] + w;
       if (wr[q]) tp[(size_t)j * ncols + cv[q]] = topv;
       const double ws = w * scal;
-      // update and shift up by one row
-      col[q][0] = lf ? 0.0 : fma(t0.y, ws, col[q][1]);
+      // update and shift up by one row.  (round 12) No select on `lf` here: the registers of a column at or left of the pivot
+      // are dead -- lane j published its column before reflector j, B_st has no rows in the reduced system (no caller deposits
+      // or scans a column < h), and w, the top entry above and with them everything that is stored take their selects as before.
+      col[q][0] = fma(t0.y, ws, col[q][1]);
 #pragma unroll
       for (int r2 = 1; r2 < NM / 2; ++r2) {
         const double2 t = vj2[r2];
-        col[q][2 * r2 - 1] = lf ? 0.0 : fma(t.x, ws, col[q][2 * r2]);
-        col[q][2 * r2] = lf ? 0.0 : fma(t.y, ws, col[q][2 * r2 + 1]);
+        col[q][2 * r2 - 1] = fma(t.x, ws, col[q][2 * r2]);
+        col[q][2 * r2] = fma(t.y, ws, col[q][2 * r2 + 1]);
       }
       col[q][NM - 1] = 0.0;
     }

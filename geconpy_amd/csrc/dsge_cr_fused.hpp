@@ -50,14 +50,19 @@ __device__ __forceinline__ unsigned long long crf_place(unsigned long long b, in
 }
 
 // NC = columns of [B_st | B_dy | A_dy | C_dy | D] per lane: 2 for h + 3 nd + k <= 128, 3 up to 192 (n = 46 .. 64)
-template <int BSF, int BSD, int NC>
+// DBG (round 12): the stamped instance.  Shader cycles of draw 0 go to dbg (int64[16]): [0..4] the five stamps of crc_iterate,
+// [5] final solve, [6] total, [7] iterations, [8] phase-1 loads + scans (static mask, index tables, the columns' loads),
+// [9] the h reflectors, [10] deposit (column masks, tables, W, the parked right-hand sides, the register blocks), [11] phase 3.
+// With DBG = false nothing of it is compiled: the listing of the default instance is the one without the flag.
+template <int BSF, int BSD, int NC, bool DBG = false>
 __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, const double* __restrict__ B,
                                               const double* __restrict__ C, const double* __restrict__ D, int batch, int n,
                                               int k, int h, int max_iter, double tol, double* __restrict__ top,
                                               double* __restrict__ rhs, double* __restrict__ T_out,
                                               double* __restrict__ R_out, int32_t* __restrict__ status,
                                               int32_t* __restrict__ n_iter_out,
-                                              unsigned long long* __restrict__ colmask_out) {
+                                              unsigned long long* __restrict__ colmask_out,
+                                              long long* __restrict__ dbg = nullptr) {
   using SM = CrfSmem<BSF, BSD>;
   constexpr int NMF = SM::NMF, NPD = SM::NPD, LDW = SM::LDW, HM = CRD_HMAX;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -87,6 +92,8 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   if (colmask_out && lane == 0) colmask_out[draw] = ~0ull;  // "not known" until the solve has succeeded
 
   // ---- phase 1: deflation ----------------------------------------------------------------------------------------------
+  long long tk_start = 0, tk_ld = 0, tk_qr = 0;
+  if constexpr (DBG) tk_start = clock64();
   unsigned long long smask = crd_static_mask<NMF>(A, C, off, n, lane);
   if (__popcll(smask) < h) return hand_over();
   smask = crd_first_bits(smask, h);
@@ -99,7 +106,8 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
     double col[NC][NMF];
     bool act[NC];
     crd_qr_chunk<NMF, NC>(A, B, C, D, off, offk, n, k, h, 0, dyi, sti, /*V=*/smem, tp, lane, col, act,
-                          /*skip_zero_ac=*/true);
+                          /*skip_zero_ac=*/true, DBG ? &tk_ld : nullptr);
+    if constexpr (DBG) tk_qr = clock64();
     // block (0 B, 1 A, 2 C, 3 D, -1 none) and column inside the block of this lane's columns 64 q + lane
     int blk[NC], dcol[NC];
     unsigned long long bS = 0ull, bL = 0ull;  // non-zero columns of A_dy (states) / C_dy (leads), over the reduced variables
@@ -137,8 +145,8 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
       const unsigned long long below = (1ull << lane) - 1ull;
       const bool isS = (maskS >> lane) & 1ull, isL = (maskL >> lane) & 1ull;
       const int ps = __popcll(maskS & below), pl = s + __popcll(maskL & below);
-      posS[lane] = (idx_t)(isS ? ps : -1);
-      posL[lane] = (idx_t)(isL ? pl : -1);
+      posS[lane] = (idx_t)(isS ? ps : CrcPos<BSD, idx_t>::noS);
+      posL[lane] = (idx_t)(isL ? pl : CrcPos<BSD, idx_t>::noL);
       if (isS) cmap[ps] = (idx_t)lane;
       if (isL) cmap[pl] = (idx_t)lane;
     }
@@ -194,8 +202,12 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   wave_sync();
   bool converged, saw_nan;
   int it;
-  crc_iterate<BSD>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, nd, s, l, max_iter, tol, 0, lane, nullptr, it,
-                   converged, saw_nan);
+  long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long tk_dep = 0, tk_it = 0, tk_fin = 0;
+  if constexpr (DBG) tk_dep = clock64();
+  crc_iterate<BSD>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, nd, s, l, max_iter, tol, 0, lane,
+                   DBG ? ph : nullptr, it, converged, saw_nan);
+  if constexpr (DBG) tk_it = clock64();
   if (lane == 0) {
     status[draw] = converged ? DSGE_ST_OK : (DSGE_ST_NOT_CONVERGED | (saw_nan ? DSGE_ST_NAN : 0));
     if (n_iter_out) n_iter_out[draw] = it;
@@ -216,6 +228,9 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
     asm volatile("" : "+v"(lane_s));
     const int lr_s = lane_s >> 3, lc_s = lane_s & 7;
     blk_store_lds<BSD>(Ah, W, LDW, lr_s, lc_s);
+    // (round 12) the right-hand sides go from the park straight into the register block the elimination works on, as in the
+    // iterations (gauss_jordan_blocked_rhs: the FMAs of the LDS form, operand for operand): column group 1 is neither
+    // loaded nor stored per panel
     double t[BSD][BSD];
 #pragma unroll
     for (int i = 0; i < BSD; ++i)
@@ -224,22 +239,25 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
         const int r = lr_s * BSD + i, c = lc_s * BSD + j;
         t[i][j] = (r < nd && c < s + k) ? rh[(size_t)c * nd + r] : 0.0;
       }
-    blk_store_lds<BSD>(t, G1, LDW, lr_s, lc_s);
+    double inv_lo = 1e300, inv_hi = 0.0;  // (not looked at: the final solve is never refined)
+    gauss_jordan_blocked_rhs<BSD>(W, LDW, nd, t, Lbuf, Ybuf, prow, lane_f, nullptr, inv_lo, inv_hi);
+    blk_store_lds<BSD>(t, G1, LDW, lr_s, lc_s);  // rows in pivot order: row q of the solution sits in row prow[q]
   }
-  gauss_jordan_blocked<BSD>(W, LDW, nd, 2, Lbuf, Ybuf, prow, lane_f);
-  gj_unpermute<BSD>(W, LDW, nd, 1, 2, prow, lane_f);
+  wave_sync();
 
   // ---- phase 3: the static rows, scatter to the caller's variable order -------------------------------------------------
+  if constexpr (DBG) tk_fin = clock64();
   double y[NPD];  // column `lane` of [T_dy | R_dy]: T_dy[:, v] = -X[:, posS(v)] for a state v, zero otherwise
   {
     const int ntot = nd + k;
     int src = -1;
     if (lane < nd)
-      src = posS[lane];
+      src = (posS[lane] != CrcPos<BSD, idx_t>::noS) ? posS[lane] : -1;
     else if (lane < ntot)
       src = s + (lane - nd);
+    // (read through prow where the elimination left the rows: no pass that restores the natural order)
 #pragma unroll
-    for (int q = 0; q < NPD; ++q) y[q] = (q < nd && src >= 0) ? -G1[q * LDW + src] : 0.0;
+    for (int q = 0; q < NPD; ++q) y[q] = (q < nd && src >= 0) ? -G1[prow[q < nd ? q : 0] * LDW + src] : 0.0;
   }
   wave_sync();  // the solution is in registers: W becomes the work space of the back-substitution
   const CrdInflateLds<NPD> L(smem);
@@ -252,6 +270,19 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   crd_inflate_chunk<NPD>(0, y, tp, n, k, h, lane, L, dyi, sti, T_out + off, R_out + offk, maskS_red);
   // every other column of T is exactly zero (written so): the filter kernel need not look for them
   if (colmask_out && lane == 0) colmask_out[draw] = state_cols;
+  if constexpr (DBG) {
+    if (dbg && draw == 0 && lane == 0) {
+      const long long tk_end = clock64();
+      for (int q = 0; q < 5; ++q) dbg[q] = ph[q];
+      dbg[5] = tk_fin - tk_it;
+      dbg[6] = tk_end - tk_start;
+      dbg[7] = it;
+      dbg[8] = tk_ld - tk_start;
+      dbg[9] = tk_qr - tk_ld;
+      dbg[10] = tk_dep - tk_qr;
+      dbg[11] = tk_end - tk_fin;
+    }
+  }
 }
 
 template <int BSF, int BSD, int NC = 2>
@@ -273,6 +304,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
     unsigned long long* __restrict__ colmask_out) {
   cr_fused_body<BSF, BSD, 2>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out);
+}
+
+// The stamped instance of the kernel above (body flag DBG; dsge_debug_cr_fused_phases).  A kernel of its own because of the
+// one argument more: the default kernel keeps its argument list and its code.
+template <int BSF, int BSD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void cr_fused_kernel_occ2_dbg(
+    const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ C, const double* __restrict__ D,
+    int batch, int n, int k, int h, int max_iter, double tol, double* __restrict__ top, double* __restrict__ rhs,
+    double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
+    unsigned long long* __restrict__ colmask_out, long long* __restrict__ dbg) {
+  cr_fused_body<BSF, BSD, 2, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out,
+                                   colmask_out, dbg);
 }
 
 }  // namespace dsge

@@ -469,7 +469,8 @@ extern long long* g_pruned_dbg;        // launch_pruned.hip: debug phase counter
 extern long long* g_shock_decomp_dbg;  // launch_shock_decomp.hip: debug phase counters of shock_decomp_kernel
 extern long long* g_condfc_dbg;        // launch_condfc.hip: debug phase counters of the two conditional-forecast kernels
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
-extern long long* g_big_dbg;          // launch_big.hip: debug phase cycles of cr_big_kernel
+extern long long* g_cr_fused_dbg;      // launch_solvers.hip: debug phase counters of the fused CR kernel (stamped instance)
+extern long long* g_big_dbg;         // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
 extern long long* g_gensys_win_dbg;   // launch_gensys.hip: debug phase stamps of the window kernels (device int64[32])
 extern float* g_gensys_stage_ms;      // launch_gensys.hip: debug, host float[8]: launch durations of the window path (dsge_debug_gensys_stage_ms)

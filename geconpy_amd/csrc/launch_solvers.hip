@@ -12,7 +12,7 @@
 namespace dsge_host {
 
 long long* g_cr_dbg = nullptr;  // debug: device int64[8], phase cycles of draw 0 of the compact kernel
-
+long long* g_cr_fused_dbg = nullptr;  // debug: device int64[16], phase cycles of draw 0 of cr_fused_kernel_occ2_dbg<5, 4>
 
 int launch_cr(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol,
               double* T_out, int32_t* status, int32_t* n_iter, hipStream_t st, int scan_mode, const double* D, int k,
@@ -85,6 +85,15 @@ int launch_cr_fused_inst(const double* A, const double* B, const double* C, cons
   int rc;
   if constexpr (BSD == 4 && NC == 2) {
     if (opt().cr_two_waves) {
+      if constexpr (BSF == 5) {  // the stamped instance (the bench's shape only)
+        if (g_cr_fused_dbg) {
+          if ((rc = set_lds(dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>, SM::bytes))) return rc;
+          hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n,
+                             k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, g_cr_fused_dbg);
+          HIP_TRY(hipGetLastError());
+          return DSGE_SUCCESS;
+        }
+      }
       if ((rc = set_lds(dsge::cr_fused_kernel_occ2<BSF, BSD>, SM::bytes))) return rc;
       hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n, k, h,
                          max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask);

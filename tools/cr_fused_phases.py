@@ -1,0 +1,25 @@
+"""GPU box: per-phase shader cycles of the fused deflation + cycle-reduction launch (draw 0 inside a batch of SW-shaped draws),
+from the stamped instance cr_fused_kernel_occ2_dbg<5, 4> (dsge_debug_cr_fused_phases): python tools/cr_fused_phases.py [batch]"""
+import ctypes, sys, os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from geconpy_amd import _lib, batched, workloads as wl
+nb = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+b = wl.sw_shaped_batch(min(nb, 64))
+om = wl.sw_shaped_observation_model()
+rep = (nb + 63) // 64
+t = {x: np.tile(b[x], (rep,) + (1,) * (b[x].ndim - 1))[:nb] for x in ("A", "B", "C", "D", "sigma")}
+lib = _lib.load()
+_lib.check(lib.dsge_debug_cr_fused_phases(1, None))
+for _ in range(2):
+    r = batched.solve_kalman_logp_batched(t["A"], t["B"], t["C"], t["D"], t["sigma"] ** 2, om["Z"], om["y"], Hdiag=om["Hdiag"],
+                                          q_mode=1, tol=1e-8, max_iter=1000, options={"n_static_hint": batched.static_hint(t["A"][:1], t["C"][:1])})
+cyc = (ctypes.c_longlong * 16)()
+_lib.check(lib.dsge_debug_cr_fused_phases(0, ctypes.addressof(cyc)))
+c = np.array(list(cyc)); it = max(int(c[7]), 1)
+assert (r["status"] == 0).all() and c[6] > 0, "the stamped instance did not run (not the 40 -> 30 variable shape?)"
+names = ["GJ panels", "GJ trailing", "gather+stage", "products", "scatter+norms"]
+print("iterations", int(c[7]), "total", int(c[6]))
+print("phase 1: loads+scans", int(c[8]), "reflectors", int(c[9]), "deposit", int(c[10]))
+print("iterations, all:", int(c[:5].sum()), "per iteration:", {n: int(v / it) for n, v in zip(names, c[:5])})
+print("final solve", int(c[5]), "phase 3", int(c[11]), "unstamped rest", int(c[6] - c[:6].sum() - c[8:12].sum()))
