@@ -19,6 +19,8 @@
 #pragma once
 #include "dsge_device.hpp"
 
+#include <type_traits>
+
 #include "../../include/dsge_hip.h"
 
 namespace dsge {
@@ -80,11 +82,19 @@ __device__ __forceinline__ unsigned long long crd_static_mask(const double* __re
     const double* ap = A + off + cl;
     const double* cp = C + off + cl;
     double av[NM], cv[NM];
+    if (n == NM) {  // (round 13) the tile is full: compile-time row offsets, no clamp, no 64-bit address product per load
 #pragma unroll
-    for (int i = 0; i < NM; ++i) {
-      const int ri = i < n ? i : n - 1;
-      av[i] = ap[(size_t)ri * n];
-      cv[i] = cp[(size_t)ri * n];
+      for (int i = 0; i < NM; ++i) {
+        av[i] = ap[i * NM];
+        cv[i] = cp[i * NM];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NM; ++i) {
+        const int ri = i < n ? i : n - 1;
+        av[i] = ap[(size_t)ri * n];
+        cv[i] = cp[(size_t)ri * n];
+      }
     }
     // (without the barrier the scheduler, short of registers, pairs every load with its compare: 40 serial round
     // trips to HBM, 54k cycles)
@@ -98,6 +108,7 @@ __device__ __forceinline__ unsigned long long crd_static_mask(const double* __re
 
 // the first h set bits of a mask
 __device__ __forceinline__ unsigned long long crd_first_bits(unsigned long long mask, int h) {
+  if (__popcll(mask) == h) return mask;  // (round 13) exactly the hinted number of static variables: every draw of such a model
   unsigned long long keep = 0ull, rest = mask;
   for (int c = 0; c < h; ++c) {
     const unsigned long long low = rest & (~rest + 1ull);
@@ -154,17 +165,36 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
     cv[q] = c0 + 64 * q + lane;
     act[q] = crd_col_source(cv[q], A, B, C, D, off, offk, n, k, h, dyi, sti, src[q], ss[q]);
   }
+  // unconditional loads (inactive lanes walk a valid column, rows are clamped).  (round 13) Every lane walks its pointer by its
+  // column's stride -- one 64-bit add per load where `src[q][rr * ss[q]]` cost a clamp, a 64-bit product and the add; a full
+  // tile (n == NM, the SW-shaped systems) has no row to clamp.
+  auto load_rows = [&](auto full) {
+    const double* p[NC];
 #pragma unroll
-  for (int r = 0; r < NM; ++r) {  // unconditional loads (inactive lanes walk a valid column, rows are clamped)
-    const int rr = r < n ? r : n - 1;
+    for (int q = 0; q < NC; ++q) p[q] = src[q];
 #pragma unroll
-    for (int q = 0; q < NC; ++q) col[q][r] = src[q][(size_t)rr * ss[q]];
-  }
+    for (int r = 0; r < NM; ++r) {
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        col[q][r] = *p[q];
+        p[q] += (decltype(full)::value || r + 1 < n) ? ss[q] : 0;
+      }
+    }
+  };
+  if (n == NM)
+    load_rows(std::true_type{});
+  else
+    load_rows(std::false_type{});
   __builtin_amdgcn_sched_barrier(0);  // all NC * NM loads in flight before the first select waits for one
+  // Rows >= n are cleared (the deposit and the column scans rely on zeros below the reduced system); a full tile has none.
+  // (round 13) An inactive lane keeps what it loaded there: nothing of it is stored, deposited or scanned (wr, destination(),
+  // blk of the fused kernel are all false / -1 for it).
+  if (n != NM) {
 #pragma unroll
-  for (int r = 0; r < NM; ++r)
+    for (int r = 0; r < NM; ++r)
 #pragma unroll
-    for (int q = 0; q < NC; ++q) col[q][r] = (r < n && act[q]) ? col[q][r] : 0.0;
+      for (int q = 0; q < NC; ++q) col[q][r] = (r < n && act[q]) ? col[q][r] : 0.0;
+  }
   // skip_zero_ac: an all-zero column of A_dy or C_dy stays all-zero under the reflectors; its h top entries are not
   // written (the reader masks them: crd_inflate_* with the column masks) -- 30 of the 107 columns on the SW-shaped system
   bool wr[NC];
@@ -191,8 +221,13 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
   for (int j = 0; j < h; ++j) {
     double xn2 = 0.0, alpha;
     double d0[NC], d1[NC];
+    // (round 13) the lane index of this pass, from two mbcnt and opaque: at 256 registers the compiler keeps `lane` in scratch
+    // across the loop and reloaded it twice per pass, the first time with a full wait in front of the publish.  (Every kernel
+    // that comes here is one wavefront per workgroup: the count of lanes below is threadIdx.x.)
+    int lj;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lj));
     if (c0 == 0) {  // publish the pivot column (lane j of the first chunk)
-      if (lane == j) {
+      if (lj == j) {
         double2* vw = reinterpret_cast<double2*>(V + j * NM);
 #pragma unroll
         for (int r2 = 0; r2 < NM / 2; ++r2) vw[r2] = make_double2(col[0][2 * r2], col[0][2 * r2 + 1]);
@@ -228,13 +263,13 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       scal = 1.0 / (alpha - beta);
     }
     // w = -tau v'x; the pivot column (beta e_0 exactly) and the columns left of it (all zeros by now) are set directly
-    const bool left = (c0 == 0) && (lane <= j);
+    const bool left = (c0 == 0) && (lj <= j);
     const double2 t0 = vj2[0];
 #pragma unroll
     for (int q = 0; q < NC; ++q) {
       const bool lf = (q == 0) && left;
       const double w = lf ? 0.0 : -tj * fma(scal, d0[q] + d1[q], col[q][0]);
-      const double topv = lf ? ((lane == j) ? beta : 0.0) : col[q][0] + w;
+      const double topv = lf ? ((lj == j) ? beta : 0.0) : col[q][0] + w;
       if (wr[q]) tp[(size_t)j * ncols + cv[q]] = topv;
       const double ws = w * scal;
       // update and shift up by one row.  (round 12) No select on `lf` here: the registers of a column at or left of the pivot
@@ -415,7 +450,8 @@ template <int NMD, typename IT>
 __device__ __forceinline__ void crd_inflate_chunk(int c0, const double (&y)[NMD], const double* __restrict__ tp, int n, int k,
                                                   int h, int lane, const CrdInflateLds<NMD>& L, const IT* dyi, const IT* sti,
                                                   double* __restrict__ Tg, double* __restrict__ Rg,
-                                                  unsigned long long amask = ~0ull) {  // bit d: column d of Atop was stored
+                                                  unsigned long long amask = ~0ull,  // bit d: column d of Atop was stored
+                                                  long long* t_solved = nullptr) {  // debug stamp: in front of the scatter
   constexpr int HM = CRD_HMAX;
   const int nd = n - h, ncols = h + 3 * nd + k, ntot = nd + k;
   const int c = c0 + lane;
@@ -455,6 +491,7 @@ __device__ __forceinline__ void crd_inflate_chunk(int c0, const double (&y)[NMD]
       x[i] = acc * L.rinv[i];
     }
   }
+  if (t_solved) *t_solved = clock64();
   // scatter to the caller's variable order
   double* dcol = (c < nd) ? (Tg + dyi[act && c < nd ? c : 0]) : (Rg + (c - nd));
   const int ds = (c < nd) ? n : k;

@@ -9,7 +9,7 @@
 //            of A_dy and C_dy are found by a ballot over the column registers, not by a pass over global memory.
 //   phase 2  crc_iterate (the loop of cr_compact_kernel, unchanged) and the final solve  [T_dy[:,S] | R_dy] =
 //            -A1_hat^-1 [A_dy[:,S] | D_red]; the right-hand side of that solve is the one thing that has to survive the
-//            iteration outside the register blocks: it is parked in global scratch (nd x (s + k) doubles, 6 KB).
+//            iteration outside the register blocks: it is parked in global scratch (NPD x (s + k) doubles, 6 KB).
 //   phase 3  back-substitution of the static rows (crd_inflate_prepare / crd_inflate_chunk) with the columns of
 //            [T_dy | R_dy] read from LDS, scatter to the caller's variable order.
 //
@@ -40,9 +40,10 @@ struct CrfSmem {
   static constexpr size_t bytes = sizeof(double) * dbl + sizeof(int) * NPD + ((4 * NPD + 64 + HM + 15) & ~(size_t)15);
 };
 
-// per-draw global scratch: top block (crd_top_doubles) and the right-hand side of the final solve, NPD columns of nd
-// doubles (column-major; columns [A_dy[:,S] | D_red], s + k <= NPD of them are written)
-__host__ __device__ inline size_t crf_rhs_doubles(int nd, int npd) { return (size_t)nd * npd; }
+// per-draw global scratch: top block (crd_top_doubles) and the right-hand side of the final solve, NPD columns of NPD
+// doubles (column-major; columns [A_dy[:,S] | D_red], s + k <= NPD of them are written).  (round 13) The leading dimension is
+// NPD, not nd: the writer stores whole register columns (rows >= nd are zeros) under a compile-time bound
+__host__ __device__ inline size_t crf_rhs_doubles(int nd, int npd) { return (size_t)npd * npd; }
 
 // bit (lane + shift) of the result = bit lane of b, for any shift in (-64, 64)
 __device__ __forceinline__ unsigned long long crf_place(unsigned long long b, int shift) {
@@ -52,7 +53,9 @@ __device__ __forceinline__ unsigned long long crf_place(unsigned long long b, in
 // NC = columns of [B_st | B_dy | A_dy | C_dy | D] per lane: 2 for h + 3 nd + k <= 128, 3 up to 192 (n = 46 .. 64)
 // DBG (round 12): the stamped instance.  Shader cycles of draw 0 go to dbg (int64[16]): [0..4] the five stamps of crc_iterate,
 // [5] final solve, [6] total, [7] iterations, [8] phase-1 loads + scans (static mask, index tables, the columns' loads),
-// [9] the h reflectors, [10] deposit (column masks, tables, W, the parked right-hand sides, the register blocks), [11] phase 3.
+// [9] the h reflectors, [10] deposit (column masks, tables, W, the parked right-hand sides, the register blocks), [11] phase 3;
+// (round 13) [12] the static mask alone (part of [8]), and of phase 3: [13] the gather of y through prow, [14]
+// crd_inflate_prepare, [15] crd_inflate_chunk up to its scatter -- the rest of [11] is the zero and scatter stores.
 // With DBG = false nothing of it is compiled: the listing of the default instance is the one without the flag.
 template <int BSF, int BSD, int NC, bool DBG = false>
 __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, const double* __restrict__ B,
@@ -65,6 +68,7 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
                                               long long* __restrict__ dbg = nullptr) {
   using SM = CrfSmem<BSF, BSD>;
   constexpr int NMF = SM::NMF, NPD = SM::NPD, LDW = SM::LDW, HM = CRD_HMAX;
+  static_assert(NPD <= NMF, "the reduced tile is no larger than the full one");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* W = smem;
   double* G1 = W + NPD;
@@ -92,9 +96,10 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   if (colmask_out && lane == 0) colmask_out[draw] = ~0ull;  // "not known" until the solve has succeeded
 
   // ---- phase 1: deflation ----------------------------------------------------------------------------------------------
-  long long tk_start = 0, tk_ld = 0, tk_qr = 0;
+  long long tk_start = 0, tk_ld = 0, tk_qr = 0, tk_mask = 0;
   if constexpr (DBG) tk_start = clock64();
   unsigned long long smask = crd_static_mask<NMF>(A, C, off, n, lane);
+  if constexpr (DBG) tk_mask = clock64();
   if (__popcll(smask) < h) return hand_over();
   smask = crd_first_bits(smask, h);
   crd_index_tables(smask, n, lane, dyi, sti);
@@ -169,17 +174,18 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
       } else if (blk[q] == 3) {
         gcol = s + d;
       }
+      // (round 13) all NPD rows, a compile-time bound: rows nd .. NPD - 1 of the column registers are +0.0 by now (shifted in
+      // by the reflector passes, or cleared after the loads), W was zeroed just above, and the park's columns are NPD long --
+      // the same bytes as under the wave-uniform test `r < nd`, without a scalar compare and a branch per store
       if (lcol >= 0) {
         double* dst = W + lcol;
 #pragma unroll
-        for (int r = 0; r < NMF; ++r)
-          if (r < nd) dst[r * LDW] = col[q][r];
+        for (int r = 0; r < NPD; ++r) dst[r * LDW] = col[q][r];
       }
       if (gcol >= 0) {  // (column-major: a lane writes its column contiguously, unused columns are never touched)
-        double* dst = rh + (size_t)gcol * nd;
+        double* dst = rh + (size_t)gcol * NPD;
 #pragma unroll
-        for (int r = 0; r < NMF; ++r)
-          if (r < nd) dst[r] = col[q][r];
+        for (int r = 0; r < NPD; ++r) dst[r] = col[q][r];
       }
     }
   }
@@ -237,7 +243,7 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
 #pragma unroll
       for (int j = 0; j < BSD; ++j) {
         const int r = lr_s * BSD + i, c = lc_s * BSD + j;
-        t[i][j] = (r < nd && c < s + k) ? rh[(size_t)c * nd + r] : 0.0;
+        t[i][j] = (r < nd && c < s + k) ? rh[(size_t)c * NPD + r] : 0.0;
       }
     double inv_lo = 1e300, inv_hi = 0.0;  // (not looked at: the final solve is never refined)
     gauss_jordan_blocked_rhs<BSD>(W, LDW, nd, t, Lbuf, Ybuf, prow, lane_f, nullptr, inv_lo, inv_hi);
@@ -256,18 +262,33 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
     else if (lane < ntot)
       src = s + (lane - nd);
     // (read through prow where the elimination left the rows: no pass that restores the natural order)
+    // (round 13) prow is the same for every lane: four entries per LDS read, up front, not one read in front of every row
+    static_assert(SM::dbl % 2 == 0 && NPD % 4 == 0, "prow is read as int4");
+    int pr[NPD];
 #pragma unroll
-    for (int q = 0; q < NPD; ++q) y[q] = (q < nd && src >= 0) ? -G1[prow[q < nd ? q : 0] * LDW + src] : 0.0;
+    for (int q4 = 0; q4 < NPD / 4; ++q4) {
+      const int4 v = reinterpret_cast<const int4*>(prow)[q4];
+      pr[4 * q4] = v.x;
+      pr[4 * q4 + 1] = v.y;
+      pr[4 * q4 + 2] = v.z;
+      pr[4 * q4 + 3] = v.w;
+    }
+#pragma unroll
+    for (int q = 0; q < NPD; ++q) y[q] = (q < nd && src >= 0) ? -G1[(q < nd ? pr[q] : pr[0]) * LDW + src] : 0.0;
   }
   wave_sync();  // the solution is in registers: W becomes the work space of the back-substitution
+  long long tk_y = 0, tk_prep = 0, tk_z = 0, tk_x = 0;
+  if constexpr (DBG) tk_y = clock64();
   const CrdInflateLds<NPD> L(smem);
   if (!crd_inflate_prepare<NPD>(y, lane < nd + k, tp, n, k, h, lane, L, maskL_red)) return hand_over();
+  if constexpr (DBG) tk_prep = clock64();
   if (lane < n) {  // static columns of T are exact zeros
 #pragma unroll
     for (int s2 = 0; s2 < HM; ++s2)
       if (s2 < h) T_out[off + (size_t)lane * n + sti[s2]] = 0.0;
   }
-  crd_inflate_chunk<NPD>(0, y, tp, n, k, h, lane, L, dyi, sti, T_out + off, R_out + offk, maskS_red);
+  if constexpr (DBG) tk_z = clock64();
+  crd_inflate_chunk<NPD>(0, y, tp, n, k, h, lane, L, dyi, sti, T_out + off, R_out + offk, maskS_red, DBG ? &tk_x : nullptr);
   // every other column of T is exactly zero (written so): the filter kernel need not look for them
   if (colmask_out && lane == 0) colmask_out[draw] = state_cols;
   if constexpr (DBG) {
@@ -281,6 +302,10 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
       dbg[9] = tk_qr - tk_ld;
       dbg[10] = tk_dep - tk_qr;
       dbg[11] = tk_end - tk_fin;
+      dbg[12] = tk_mask - tk_start;
+      dbg[13] = tk_y - tk_fin;
+      dbg[14] = tk_prep - tk_y;
+      dbg[15] = tk_x - tk_z;
     }
   }
 }

@@ -382,7 +382,9 @@ int dsge_debug_cr_phases(int enable, long long* cycles_out);
 /* Debug hook: enable != 0 routes the fused deflation + cycle-reduction launch of the 33 .. 40 variable systems with a
  * reduced tile of 32 (two waves per SIMD) to its stamped instance, which records the shader cycles of draw 0:
  * [0..4] as above per iteration phase, [5] the final solve, [6] total, [7] = iterations, [8] phase-1 loads and scans,
- * [9] the Householder reflectors, [10] deposit of the reduced system, [11] phase 3 (static rows and scatter);
+ * [9] the Householder reflectors, [10] deposit of the reduced system, [11] phase 3 (static rows and scatter),
+ * [12] the static mask alone (part of [8]), and of [11]: [13] the gather of the solution, [14] the preparation and
+ * [15] the back-substitution of the static rows up to its scatter;
  * cycles_out (host int64[16], may be NULL).  Results are those of the default instance. */
 int dsge_debug_cr_fused_phases(int enable, long long* cycles_out);
 

@@ -23,3 +23,6 @@ print("iterations", int(c[7]), "total", int(c[6]))
 print("phase 1: loads+scans", int(c[8]), "reflectors", int(c[9]), "deposit", int(c[10]))
 print("iterations, all:", int(c[:5].sum()), "per iteration:", {n: int(v / it) for n, v in zip(names, c[:5])})
 print("final solve", int(c[5]), "phase 3", int(c[11]), "unstamped rest", int(c[6] - c[:6].sum() - c[8:12].sum()))
+print("loads+scans: static mask", int(c[12]), "tables + column loads", int(c[8] - c[12]))
+print("phase 3: gather of y", int(c[13]), "inflate_prepare", int(c[14]), "inflate_chunk", int(c[15]),
+      "zero + scatter stores", int(c[11] - c[13:16].sum()))
