@@ -431,6 +431,76 @@ __device__ __forceinline__ double dpp_move_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// ---- row broadcasts of a double inside the consuming instruction (gfx90a and later: the FP64 ALU's only DPP control) -----------
+// row_newbcast:J hands every lane the value lane J of its own 16-lane row holds (tools/dpp_probe/dpp_probe.hip checks that, the
+// in-place form d == row_src included, and gives the issue costs).  hipcc does not select these forms (update_dpp on the halves is
+// two v_mov_b32_dpp, v_fma_f64 stays VOP3), hence the assembly.  Conditions the CALLER keeps, the compiler's hazard handling does not
+// look into assembly text:
+//   * every lane is active (a masked-off source lane delivers nothing);
+//   * a DPP operand written by a VALU instruction needs two wait states before it is read: NOP = true puts an s_nop 1 in front,
+//     NOP = false is for operands whose last write lies at least two instructions back BY CONSTRUCTION (say how at the call).
+// the value of lane J of the own row (v_mov_b64_dpp)
+template <int J, bool NOP>
+__device__ __forceinline__ double row_bcast_f64(double row_src) {
+  static_assert(J >= 0 && J < 16, "lane of the row");
+  double d;
+  if constexpr (NOP)
+    asm("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(row_src), "n"(J));
+  else
+    asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(row_src), "n"(J));
+  return d;
+}
+
+// d = fma(row_src[lane J of the own row], s, d) in one v_fmac_f64_dpp: the same fused multiply-add on the same three values as
+// fma(readlane(row_src, 16 (lane / 16) + J), s, d)
+template <int J, bool NOP>
+__device__ __forceinline__ void fmac_row_bcast(double& d, double row_src, double s) {
+  static_assert(J >= 0 && J < 16, "lane of the row");
+  if constexpr (NOP)
+    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(row_src), "v"(s), "n"(J));
+  else
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(row_src), "v"(s), "n"(J));
+}
+
+// One pivot's update of the other seven columns of a row-per-lane 8 x 8 elimination whose rows are replicated over the 8-lane groups
+// (lane J of every row holds pivot row J): fr[q] = fma(-ci, fr[q] of lane J, fr[q]) for q != J, in ONE assembly statement and in
+// the order q = J + 1, J + 2, ... (mod 8).  The order is what keeps the DPP wait states without a nop (kalman_mf_kernel, phase c):
+// the column the NEXT pivot broadcasts first (J + 1) is written first, six instructions ahead of the statement's end, and the
+// column a select wrote last (J - 1: the previous pivot's own) is read last, six instructions behind its start.
+template <int J, bool NOP>
+__device__ __forceinline__ void pivot_row_bcast_update(double (&fr)[8], double ci) {
+  static_assert(J >= 0 && J < 8, "pivot");
+#define DSGE_PV(K) "v_fmac_f64_dpp %" #K ", %" #K ", -%7 row_newbcast:%8 row_mask:0xf bank_mask:0xf\n\t"
+  if constexpr (NOP)
+    asm("s_nop 1\n\t" DSGE_PV(0) DSGE_PV(1) DSGE_PV(2) DSGE_PV(3) DSGE_PV(4) DSGE_PV(5) DSGE_PV(6)
+        : "+v"(fr[(J + 1) & 7]), "+v"(fr[(J + 2) & 7]), "+v"(fr[(J + 3) & 7]), "+v"(fr[(J + 4) & 7]), "+v"(fr[(J + 5) & 7]),
+          "+v"(fr[(J + 6) & 7]), "+v"(fr[(J + 7) & 7])
+        : "v"(ci), "n"(J));
+  else
+    asm(DSGE_PV(0) DSGE_PV(1) DSGE_PV(2) DSGE_PV(3) DSGE_PV(4) DSGE_PV(5) DSGE_PV(6)
+        : "+v"(fr[(J + 1) & 7]), "+v"(fr[(J + 2) & 7]), "+v"(fr[(J + 3) & 7]), "+v"(fr[(J + 4) & 7]), "+v"(fr[(J + 5) & 7]),
+          "+v"(fr[(J + 6) & 7]), "+v"(fr[(J + 7) & 7])
+        : "v"(ci), "n"(J));
+#undef DSGE_PV
+}
+
+// The four running sums of a steady filter step over the eight entries of a vector v that sits in lanes 0..7 of every row:
+//   w0 = fma(f[o], v[o], w0), a0 = fma(k[o], v[o], a0) for o = 0, 2, 4, 6;  w1, a1 likewise for o = 1, 3, 5, 7,
+// each sum in that order.  v_own is the lane's own entry, written just before: the statement starts with the wait states.
+__device__ __forceinline__ void steady_sums_row_bcast(double& w0, double& w1, double& a0, double& a1, double v_own,
+                                                      const double (&f)[8], const double (&k)[8]) {
+#define DSGE_SS(O, O1, F0, F1, K0, K1)                                                       \
+  "v_fmac_f64_dpp %0, %4, %" #F0 " row_newbcast:" #O " row_mask:0xf bank_mask:0xf\n\t"    \
+  "v_fmac_f64_dpp %1, %4, %" #F1 " row_newbcast:" #O1 " row_mask:0xf bank_mask:0xf\n\t"  \
+  "v_fmac_f64_dpp %2, %4, %" #K0 " row_newbcast:" #O " row_mask:0xf bank_mask:0xf\n\t"    \
+  "v_fmac_f64_dpp %3, %4, %" #K1 " row_newbcast:" #O1 " row_mask:0xf bank_mask:0xf\n\t"
+  asm("s_nop 1\n\t" DSGE_SS(0, 1, 5, 6, 13, 14) DSGE_SS(2, 3, 7, 8, 15, 16) DSGE_SS(4, 5, 9, 10, 17, 18) DSGE_SS(6, 7, 11, 12, 19, 20)
+      : "+v"(w0), "+v"(w1), "+v"(a0), "+v"(a1)
+      : "v"(v_own), "v"(f[0]), "v"(f[1]), "v"(f[2]), "v"(f[3]), "v"(f[4]), "v"(f[5]), "v"(f[6]), "v"(f[7]), "v"(k[0]), "v"(k[1]),
+        "v"(k[2]), "v"(k[3]), "v"(k[4]), "v"(k[5]), "v"(k[6]), "v"(k[7]));
+#undef DSGE_SS
+}
+
 // sum over the 64 lanes (wave-uniform result): DPP row shifts + row broadcasts, no LDS traffic.
 // Lanes that receive nothing get +0.0 (identity).  Summation order differs from wave_sum().
 __device__ __forceinline__ double wave_sum_dpp(double v) {

@@ -373,8 +373,6 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
     }                                                   \
   } while (0)
     KMF_STORE_PZT();
-    const int v_zpos = (lane < p) ? zpos[lane] : 0;
-    const double v_zv = (lane < p) ? zv[lane] : 0.0, v_dd = (lane < 8) ? dd[lane & 7] : 0.0;
     wave_sync();
 
     const int r8 = lane & 7, g8 = lane >> 3;  // the update runs on 8 replicas of an 8-lane group: lane -> row r8 of F
@@ -463,7 +461,7 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
           for (int q = 0; q < 8; ++q) sg[RC::OFF_F + lane * 8 + q] = fr[q];
         }
       }
-      // ---- (c) Finv by Gauss-Jordan, one row per lane (SPD: no pivoting); the pivot row arrives through SGPRs ----------------
+      // ---- (c) Finv by Gauss-Jordan, one row per lane (SPD: no pivoting); the pivot row arrives by row broadcasts ------------
       double step_mant = 1.0, inv_own = 1.0;
       int step_exp = 0;
       // (p >= 7: pivots 0..6 unconditionally, pivot 7 only when there is an eighth observation: a row beyond p -- like the row of a missing
@@ -471,23 +469,26 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
       //  chain into basic blocks the scheduler could not overlap; one uniform branch at the end does not)
       auto pivot = [&](auto jt) {
         constexpr int j = decltype(jt)::value;
-        double rowj[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) rowj[q] = readlane_f64(fr[q], j);
+        // The rows are replicated over the 8-lane groups, so lane j of every 16-lane row holds pivot row j: its entries are taken
+        // inside the consuming instruction (row_newbcast, dsge_device.hpp), the pivot by one broadcast move, the other seven by the
+        // FMAs that use them -- fma(-ci, fr[q] of lane j, fr[q]), the operation it was with the row read into SGPR pairs first.
+        // Every lane is active here (the time loop's branches are wave-uniform).  DPP wait states, by construction: pivot 0 reads
+        // what the F build has just written and carries the nops (j == 0); a later pivot's move reads fr[j], the FIRST column the
+        // previous statement wrote (six FMAs behind it); its FMAs sit behind that move and the reciprocal chain, which depend on
+        // the previous statement, and fr[j - 1] -- the select below, which may be scheduled late -- is the LAST column they read.
+        const double pj = row_bcast_f64<j, j == 0>(fr[j]);
         // (ONE Newton step on v_rcp_f64: 2.2e-15 relative, tools/latency_probe/rcp_probe.hip -- the multipliers and the final
         //  row scaling of a 7 x 7 inverse whose conditioning costs more digits than that; the determinant takes the pivots
         //  themselves.  Two dependent FMAs less on the chain of every pivot)
-        double inv = __builtin_amdgcn_rcp(rowj[j]);
-        inv = inv * fma(-rowj[j], inv, 2.0);
+        double inv = __builtin_amdgcn_rcp(pj);
+        inv = inv * fma(-pj, inv, 2.0);
         const bool is_j = (r8 == j);
         const double ci = is_j ? 0.0 : fr[j] * inv;
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          if (q != j) fr[q] = fma(-ci, rowj[q], fr[q]);
+        pivot_row_bcast_update<j, j == 0>(fr, ci);
         fr[j] = is_j ? 1.0 : -ci;
         inv_own = is_j ? inv : inv_own;
         int e;
-        step_mant *= frexp(rowj[j], &e);
+        step_mant *= frexp(pj, &e);
         step_exp += e;
       };
       if (p >= 7) {
@@ -667,8 +668,11 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         }
         // What does not change while the loop runs (it runs while the mask is omask): which of this lane's entries is observed, the
         // intercept that goes with it, the 0 / 1 factor of the selector.
-        const bool obs_l = (lane < p) && ((omask >> lane) & 1ull);
-        const double d_l = (obs_l || !cv.mask_d) ? v_dd : 0.0, one_l = obs_l ? 1.0 : 0.0;
+        // The innovation is computed on lanes 0..p-1 of EVERY 16-lane row (there lane & 15 == r8, and y, the selector and the
+        // intercept are at hand per r8), so that the sums below take entry o from lane o of the lane's own row.
+        const bool in_p = (lane & 15) < p;
+        const bool obs_l = in_p && ((omask >> r8) & 1ull);
+        const double d_l = (obs_l || !cv.mask_d) ? r_dd : 0.0, one_l = obs_l ? 1.0 : 0.0;
         const unsigned long long pbits = (1ull << p) - 1ull;  // (p <= 8)
         // NC: columns of Tc the mean prediction runs over -- the padded state block, or two less when the last pair of columns is
         // padding (18 state variables in 20 columns: trow is +0 there and s0, s1 are never -0, so fma(+0, afi, acc) == acc).  That, and
@@ -689,19 +693,13 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
               if (lane < 8 * RBS) sgs[RC::OFF_A + lane] = av_reg;
               if (lane == 0) sgs[RC::OFF_SRC] = (double)seg_src;
             }
-            const double av_sel = __shfl(av_reg, v_zpos, 64);
-            const double v_s = (lane < p) ? (obs_l ? yt_s : 0.0) - (d_l + one_l * (v_zv * av_sel)) : 0.0;
-            double vsc[8];
-#pragma unroll
-            for (int o = 0; o < 8; ++o) vsc[o] = readlane_f64(v_s, o);
+            const double av_sel = __shfl(av_reg, r_zpos, 64);
+            const double v_s = in_p ? (obs_l ? yt_s : 0.0) - (d_l + one_l * (r_zv * av_sel)) : 0.0;
+            // w0 = fma(finv_row[o], v[o], w0), a0 = fma(kr_ss[o], v[o], a0) over o = 0, 2, 4, 6, w1 and a1 over o = 1, 3, 5, 7, with
+            // v[o] broadcast from lane o of the row inside the FMA.  (Rows 1..3 now hold v_s too: finv_row is zero there, their
+            // term of the quadratic form below is an exact zero for a finite v_s.)
             double w0 = 0.0, w1 = 0.0, a0 = av_reg, a1 = 0.0;
-#pragma unroll
-            for (int o = 0; o < 8; o += 2) {
-              w0 = fma(finv_row[o], vsc[o], w0);
-              w1 = fma(finv_row[o + 1], vsc[o + 1], w1);
-              a0 = fma(kr_ss[o], vsc[o], a0);
-              a1 = fma(kr_ss[o + 1], vsc[o + 1], a1);
-            }
+            steady_sums_row_bcast(w0, w1, a0, a1, v_s, finv_row, kr_ss);
             if (n_obs > 0) {
               const double yk = v_s * (w0 + w1) - quad_comp;  // lanes >= 8 hold finv_row = 0
               const double tk = quad_sum + yk;
