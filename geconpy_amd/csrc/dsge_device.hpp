@@ -501,6 +501,69 @@ __device__ __forceinline__ void steady_sums_row_bcast(double& w0, double& w1, do
 #undef DSGE_SS
 }
 
+// ---- a vector of up to 32 doubles, one per lane of rows 0 and 1, made readable by row broadcasts in BOTH of these rows ----------
+// v_permlane16_swap_b32 vdst, src (gfx950) exchanges the odd 16-lane rows of vdst with the even rows of src.  Started from two
+// copies of v, one swap per half of the double leaves
+//   x: rows 0 and 1 both hold v[0..15]  (rows 2 and 3: v[32..47]),     y: rows 0 and 1 both hold v[16..31]  (rows 2, 3: v[48..63]),
+// so that entry kk of v is lane kk & 15 of the own row of x (kk < 16) or y (kk >= 16) for every lane below 32
+// (tools/dpp_probe/dpp_probe.hip checks the pattern in all 64 lanes).  The builtin, not assembly: the compiler keeps the swap's own
+// wait states (a VALU write of either operand, two wait states, the swap) and makes the copies.  WITH_Y = false: y is not produced
+// (the second register of the swap is a scratch copy).
+template <bool WITH_Y>
+__device__ __forceinline__ void rows01_pair_f64(double v, double& x, double& y) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  x = __hiloint2double((int)h2[0], (int)l2[0]);
+  if constexpr (WITH_Y) y = __hiloint2double((int)h2[1], (int)l2[1]);
+}
+
+// The two running sums of a matrix-vector product, one row of the matrix per lane (t[kk]: this lane's entry of column kk), the
+// vector as rows01_pair_f64 left it:
+//   s0 = +0.0, s0 = fma(t[kk], v[kk], s0) for kk = 0, 2, 4, .., NC - 2 in that order,   s1 likewise for kk = 1, 3, .., NC - 1,
+// each the same fused multiply-add on the same values as with v[kk] read by read-lanes (the first term is an FMA as every other: a
+// product of -0 still rounds to +0).  Columns 0..15 broadcast from x, columns 16..NC - 1 from y (NC <= 16: y is not read, pass x).
+// ONE statement, and its order keeps the DPP wait states: x and y are VALU results (the swap writes both its registers) and may be
+// the instruction before -- the two moves that zero the sums stand between them and the first broadcast.
+#define DSGE_MV(ACC, SRC, T, J) "v_fmac_f64_dpp %" #ACC ", %" #SRC ", %" #T " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define DSGE_MV10                                                                                                               \
+  "v_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\t" DSGE_MV(0, 2, 4, 0) DSGE_MV(1, 2, 5, 1) DSGE_MV(0, 2, 6, 2) DSGE_MV(1, 2, 7, 3) DSGE_MV(0, 2, 8, 4) DSGE_MV(1, 2, 9, 5) \
+      DSGE_MV(0, 2, 10, 6) DSGE_MV(1, 2, 11, 7) DSGE_MV(0, 2, 12, 8) DSGE_MV(1, 2, 13, 9)
+#define DSGE_MV12 DSGE_MV10 DSGE_MV(0, 2, 14, 10) DSGE_MV(1, 2, 15, 11)
+#define DSGE_MV14 DSGE_MV12 DSGE_MV(0, 2, 16, 12) DSGE_MV(1, 2, 17, 13)
+#define DSGE_MV16 DSGE_MV14 DSGE_MV(0, 2, 18, 14) DSGE_MV(1, 2, 19, 15)
+#define DSGE_MV18 DSGE_MV16 DSGE_MV(0, 3, 20, 0) DSGE_MV(1, 3, 21, 1)
+#define DSGE_MV20 DSGE_MV18 DSGE_MV(0, 3, 22, 2) DSGE_MV(1, 3, 23, 3)
+#define DSGE_MV_T10 "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3]), "v"(t[4]), "v"(t[5]), "v"(t[6]), "v"(t[7]), "v"(t[8]), "v"(t[9])
+#define DSGE_MV_T12 DSGE_MV_T10, "v"(t[10]), "v"(t[11])
+#define DSGE_MV_T14 DSGE_MV_T12, "v"(t[12]), "v"(t[13])
+#define DSGE_MV_T16 DSGE_MV_T14, "v"(t[14]), "v"(t[15])
+#define DSGE_MV_T18 DSGE_MV_T16, "v"(t[16]), "v"(t[17])
+#define DSGE_MV_T20 DSGE_MV_T18, "v"(t[18]), "v"(t[19])
+template <int NC, int NT>
+__device__ __forceinline__ void matvec_sums_row_bcast(double& s0, double& s1, double x, double y, const double (&t)[NT]) {
+  static_assert(NC >= 10 && NC <= 20 && NC % 2 == 0 && NC <= NT, "columns");
+  if constexpr (NC == 10) asm(DSGE_MV10 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T10);
+  if constexpr (NC == 12) asm(DSGE_MV12 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T12);
+  if constexpr (NC == 14) asm(DSGE_MV14 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T14);
+  if constexpr (NC == 16) asm(DSGE_MV16 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T16);
+  if constexpr (NC == 18) asm(DSGE_MV18 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T18);
+  if constexpr (NC == 20) asm(DSGE_MV20 : "=&v"(s0), "=&v"(s1) : "v"(x), "v"(y), DSGE_MV_T20);
+}
+#undef DSGE_MV_T20
+#undef DSGE_MV_T18
+#undef DSGE_MV_T16
+#undef DSGE_MV_T14
+#undef DSGE_MV_T12
+#undef DSGE_MV_T10
+#undef DSGE_MV20
+#undef DSGE_MV18
+#undef DSGE_MV16
+#undef DSGE_MV14
+#undef DSGE_MV12
+#undef DSGE_MV10
+#undef DSGE_MV
+
 // sum over the 64 lanes (wave-uniform result): DPP row shifts + row broadcasts, no LDS traffic.
 // Lanes that receive nothing get +0.0 (identity).  Summation order differs from wave_sum().
 __device__ __forceinline__ double wave_sum_dpp(double v) {

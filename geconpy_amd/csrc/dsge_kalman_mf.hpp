@@ -679,6 +679,8 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         // the missing select on the predicted mean below, assume a FINITE filtered mean: with an Inf or NaN in afi the parent's
         // 0 * afi poisoned every lane's sum where this one skips the column, and lanes >= m (which the record's OFF_A store may cover)
         // hold NaN instead of 0.  Such a draw's likelihood is already non-finite and flagged DSGE_ST_FILTER_NONFINITE either way.
+        // (The row broadcasts of afi change nothing in that for lanes 0..31, which is all that is ever stored: column kk is the
+        // value of lane kk there, finite or not.  Lanes 32..63 multiply their zero row by the entries of lanes 32..63.)
         auto steady_loop = [&](auto nc_tag) {
           constexpr int NC = decltype(nc_tag)::value;
           while (t + 1 < T_len) {
@@ -712,23 +714,37 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
               n_obs_entries += n_obs;
             }
             const double afi = a0 + a1;
-            // the broadcasts of afi in batches of six to eight columns into SGPR pairs of their own -- the pairs vsc[] has just left --
-            // then the batch's FMAs in their order: a read-lane into the pair the previous FMA still reads needs a hazard nop in
-            // front of every FMA; all the columns at once would spill scalar registers elsewhere in the kernel
+            // a_pred = Tc afi with afi[kk] broadcast inside the FMA.  Entry kk of afi sits in lane kk, row kk / 16, and every lane
+            // below NM <= 28 (rows 0 and 1) consumes it: two lane swaps (one per half of the double) first give both rows both
+            // halves of afi -- ax: entries 0..15, ay: entries 16..31, needed beyond 16 columns only -- then s0 takes the even columns
+            // and s1 the odd ones, ascending, from +0.  Wait states: the sums are ONE statement that opens with the two moves zeroing
+            // s0 and s1 -- they stand between the swaps (VALU writes of ax and ay) and the first broadcast, whatever the compiler
+            // schedules around the statement.  All 64 lanes are active: the loop's branches are wave-uniform.
             double s0 = 0.0, s1 = 0.0;
+            if constexpr (TM < 7) {
+              double ax, ay;
+              rows01_pair_f64<(NC > 16)>(afi, ax, ay);
+              if constexpr (NC > 16) matvec_sums_row_bcast<NC>(s0, s1, ax, ay, trow);
+              else matvec_sums_row_bcast<NC>(s0, s1, ax, ax, trow);
+            } else {
+              // TM = 7 (256 registers, 84 bytes of scratch) keeps the read-lanes: with the swaps it spilled four bytes more.
+              // Batches of six to eight columns into SGPR pairs of their own, then the batch's FMAs in their order: a read-lane
+              // into the pair the previous FMA still reads needs a hazard nop in front of every FMA; all the columns at once
+              // would spill scalar registers elsewhere in the kernel.
 #pragma unroll
-            for (int b0 = 0; b0 < NC; b0 += 6) {
-              const int b1 = (NC - b0 <= 8) ? NC : b0 + 6;
-              double afs[8];
+              for (int b0 = 0; b0 < NC; b0 += 6) {
+                const int b1 = (NC - b0 <= 8) ? NC : b0 + 6;
+                double afs[8];
 #pragma unroll
-              for (int kk = b0; kk < b1; ++kk) afs[kk - b0] = readlane_f64(afi, kk);
+                for (int kk = b0; kk < b1; ++kk) afs[kk - b0] = readlane_f64(afi, kk);
 #pragma unroll
-              for (int kk = b0; kk < b1; kk += 2) {
-                s0 = fma(trow[kk], afs[kk - b0], s0);
-                s1 = fma(trow[kk + 1], afs[kk + 1 - b0], s1);
+                for (int kk = b0; kk < b1; kk += 2) {
+                  s0 = fma(trow[kk], afs[kk - b0], s0);
+                  s1 = fma(trow[kk + 1], afs[kk + 1 - b0], s1);
+                }
+                if (b1 == NC) break;
+                __builtin_amdgcn_sched_barrier(0);
               }
-              if (b1 == NC) break;
-              __builtin_amdgcn_sched_barrier(0);
             }
             av_reg = s0 + s1;  // (rows >= m of Tc are zero: +0 there for a finite afi, no select)
             if constexpr (DBG) ++ph[6];

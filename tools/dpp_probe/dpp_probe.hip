@@ -8,6 +8,10 @@
 // the read-lane form they replace (two v_readlane_b32 into an SGPR pair + v_fma_f64), each as a dependent chain and as eight
 // independent accumulators; then one whole pivot of the filter's 8 x 8 elimination (broadcast of the pivot, v_rcp_f64, Newton step,
 // multiplier, seven updates) in three forms: fused, one v_mov_b64_dpp per value + plain FMA, read-lanes + plain FMA.
+// Round 15 (profiles/r15/permlane_probe.txt): v_permlane16_swap_b32 on both halves of a double (rows01_pair_f64) -- the row pattern
+// it leaves in all 64 lanes against a host table, the builtin and the instruction in place -- the broadcast FMAs that read its
+// results two instructions behind them (matvec_sums_row_bcast, every column count), and the mean recursion of the filter's steady step in its
+// read-lane form and in the swap + broadcast form: ticks per step and the two forms' bits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -143,6 +147,87 @@ __global__ void pivots(double* out, long long* cyc, const double* mat) {
   if (lane == 0) cyc[0] = t1 - t0;
 }
 
+// ---- v_permlane16_swap_b32 in front of the row broadcasts (rows01_pair_f64, matvec_sums_row_bcast: the steady loop's mean) -------
+// Blocks of 64 doubles: 0 x, 1 y of rows01_pair_f64<true>(v); 2 x of rows01_pair_f64<false>(v); 3, 4 the instruction itself on the
+// halves of two DIFFERENT registers a = v, b = w, in place, behind its wait states (a: even rows own, odd rows b's even rows; b: even
+// rows a's odd rows, odd rows own); then for NC = 10, 12, .., 20 the sums s0, s1 of matvec_sums_row_bcast right behind the swaps.
+constexpr int SW_BLOCKS = 5 + 2 * 6;
+template <int NC>
+__device__ void swap_sums(double* out, int lane, double v, const double (&t)[20]) {
+  double s0 = 0.0, s1 = 0.0, x, y;
+  rows01_pair_f64<(NC > 16)>(v, x, y);
+  if constexpr (NC > 16) matvec_sums_row_bcast<NC>(s0, s1, x, y, t);
+  else matvec_sums_row_bcast<NC>(s0, s1, x, x, t);
+  out[lane] = s0;
+  out[64 + lane] = s1;
+}
+__global__ void swap_semantics(double* out, const double* vs, const double* ws, const double* ts) {
+  const int lane = threadIdx.x;
+  const double v = vs[lane], w = ws[lane];
+  double t[20];
+#pragma unroll
+  for (int kk = 0; kk < 20; ++kk) t[kk] = ts[lane * 20 + kk];
+  double x, y, x1, y1;
+  rows01_pair_f64<true>(v, x, y);
+  rows01_pair_f64<false>(v, x1, y1);
+  out[lane] = x, out[64 + lane] = y, out[128 + lane] = x1;
+  int alo = __double2loint(v), ahi = __double2hiint(v), blo = __double2loint(w), bhi = __double2hiint(w);
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3" : "+v"(alo), "+v"(ahi), "+v"(blo), "+v"(bhi));
+  out[192 + lane] = __hiloint2double(ahi, alo);
+  out[256 + lane] = __hiloint2double(bhi, blo);
+  swap_sums<10>(out + 5 * 64, lane, v, t);
+  swap_sums<12>(out + 7 * 64, lane, v, t);
+  swap_sums<14>(out + 9 * 64, lane, v, t);
+  swap_sums<16>(out + 11 * 64, lane, v, t);
+  swap_sums<18>(out + 13 * 64, lane, v, t);
+  swap_sums<20>(out + 15 * 64, lane, v, t);
+}
+
+// The mean recursion of the filter's steady step alone, NSTEP dependent steps: afi = av + c, av = sum over NC columns of t[kk] afi[kk]
+// in two running sums.  FORM 0: 2 NC read-lanes into SGPR pairs in batches of six to eight columns + NC v_fma_f64 (the present form,
+// its scheduling barriers included); FORM 1: two moves, two swaps, NC v_fmac_f64_dpp.
+constexpr int NSTEP = 4096;
+template <int FORM, int NC>
+__global__ void mean_step(double* out, long long* cyc, const double* ts) {
+  const int lane = threadIdx.x;
+  double t[20];
+#pragma unroll
+  for (int kk = 0; kk < 20; ++kk) t[kk] = (lane < 28) ? ts[lane * 20 + kk] : 0.0;
+  const double c = (lane < 28) ? 1.0 + 0.01 * lane : 0.0;
+  double av = 0.0;
+  __syncthreads();
+  const long long t0 = clock64();
+  for (int it = 0; it < NSTEP; ++it) {
+    const double afi = av + c;
+    double s0 = 0.0, s1 = 0.0;
+    if constexpr (FORM == 0) {
+#pragma unroll
+      for (int b0 = 0; b0 < NC; b0 += 6) {
+        const int b1 = (NC - b0 <= 8) ? NC : b0 + 6;
+        double afs[8];
+#pragma unroll
+        for (int kk = b0; kk < b1; ++kk) afs[kk - b0] = readlane_f64(afi, kk);
+#pragma unroll
+        for (int kk = b0; kk < b1; kk += 2) {
+          s0 = fma(t[kk], afs[kk - b0], s0);
+          s1 = fma(t[kk + 1], afs[kk + 1 - b0], s1);
+        }
+        if (b1 == NC) break;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      double x, y;
+      rows01_pair_f64<(NC > 16)>(afi, x, y);
+      if constexpr (NC > 16) matvec_sums_row_bcast<NC>(s0, s1, x, y, t);
+      else matvec_sums_row_bcast<NC>(s0, s1, x, x, t);
+    }
+    av = s0 + s1;
+  }
+  const long long t1 = clock64();
+  out[lane] = av;
+  if (lane == 0) cyc[0] = t1 - t0;
+}
+
 #define CHECK(e)                                                                    \
   do {                                                                              \
     hipError_t err_ = (e);                                                          \
@@ -226,5 +311,71 @@ int main() {
   printf("  16 x v_readlane_b32 + 7 v_fma_f64 (present form)         %8.1f\n", (double)p2 / (7.0 * NP));
   const bool same = std::memcmp(r0.data(), r2.data(), 4096) == 0 && std::memcmp(r1.data(), r2.data(), 4096) == 0;
   printf("  the three forms' results (64 lanes x 8 entries of the scaled inverse): %s\n", same ? "bit-identical" : "DIFFER");
-  return (bad_total || !same) ? 1 : 0;
+  // ---- lane swap + row broadcasts: the steady loop's mean --------------------------------------------------------------------
+  std::vector<double> v(64), w(64), ts(64 * 20), sw(SW_BLOCKS * 64);
+  for (int l = 0; l < 64; ++l) {
+    v[l] = (l % 5 == 2 ? -1.0 : 1.0) * (0.37 * l + 1.0 / 7.0), w[l] = 1000.0 + l / 3.0;
+    for (int kk = 0; kk < 20; ++kk) ts[l * 20 + kk] = 0.04 * std::sin(1.0 + 0.7 * l + 1.3 * kk);
+  }
+  v[0] = -0.0, v[1] = -0.0;  // (first terms t v = -0 where t > 0: the sums must still start as +0, as the host's fma(t, v, +0) does)
+  double *dv, *dw, *dts;
+  CHECK(hipMalloc(&dv, 512));
+  CHECK(hipMalloc(&dw, 512));
+  CHECK(hipMalloc(&dts, sizeof(double) * ts.size()));
+  CHECK(hipMemcpy(dv, v.data(), 512, hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(dw, w.data(), 512, hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(dts, ts.data(), sizeof(double) * ts.size(), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(swap_semantics, dim3(1), dim3(64), 0, 0, d_out, dv, dw, dts);
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipMemcpy(sw.data(), d_out, sizeof(double) * sw.size(), hipMemcpyDeviceToHost));
+  printf("\nv_permlane16_swap_b32 on both halves of a double, against a host table, compared bit for bit in 64 lanes\n");
+  int sw_bad_total = 0;
+  auto sw_check = [&](const char* what, int block, auto want_of_lane) {
+    int bad = 0;
+    for (int l = 0; l < 64; ++l) {
+      const double g = sw[block * 64 + l], want = want_of_lane(l);
+      if (std::memcmp(&g, &want, 8) != 0 && bad++ < 3) printf("    lane %d: got %.17g, want %.17g\n", l, g, want);
+    }
+    printf("  %-76s %2d of 64 mismatches\n", what, bad);
+    sw_bad_total += bad;
+  };
+  sw_check("rows01_pair_f64<true>  x: v[32 (lane / 32) + (lane & 15)]", 0, [&](int l) { return v[32 * (l / 32) + (l & 15)]; });
+  sw_check("rows01_pair_f64<true>  y: v[32 (lane / 32) + 16 + (lane & 15)]", 1, [&](int l) { return v[32 * (l / 32) + 16 + (l & 15)]; });
+  sw_check("rows01_pair_f64<false> x", 2, [&](int l) { return v[32 * (l / 32) + (l & 15)]; });
+  sw_check("in place, a = v, b = w: a keeps its even rows, odd rows = b's even rows", 3,
+           [&](int l) { return ((l >> 4) & 1) ? w[l - 16] : v[l]; });
+  sw_check("in place, a = v, b = w: b keeps its odd rows, even rows = a's odd rows", 4,
+           [&](int l) { return ((l >> 4) & 1) ? w[l] : v[l + 16]; });
+  for (int nc = 10; nc <= 20; nc += 2) {
+    for (int par = 0; par < 2; ++par) {
+      char what[96];
+      snprintf(what, sizeof what, "matvec_sums_row_bcast<%d> right behind the swaps, s%d", nc, par);
+      sw_check(what, 5 + (nc - 10) + par, [&](int l) {
+        double s = 0.0;
+        for (int kk = par; kk < nc; kk += 2) s = std::fma(ts[l * 20 + kk], v[32 * (l / 32) + kk], s);
+        return s;
+      });
+    }
+  }
+  printf("swap semantics %s\n", sw_bad_total ? "FAILED" : "ok");
+  printf("\nthe mean recursion of one steady step (afi = av + c; av = two running sums over NC columns), %d dependent steps, clock64 ticks per step\n",
+         NSTEP);
+  std::vector<double> m0(64), m1(64);
+  bool mean_same = true;
+  auto mean_pair = [&](int nc, auto k0, auto k1) {
+    const long long c0 = timed(k0, (const double*)dts);
+    if (hipMemcpy(m0.data(), d_out, 512, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    const long long c1 = timed(k1, (const double*)dts);
+    if (hipMemcpy(m1.data(), d_out, 512, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    const bool eq = std::memcmp(m0.data(), m1.data(), 512) == 0;
+    printf("  NC = %2d   %2d x v_readlane_b32 + %2d v_fma_f64 (present form) %8.1f     2 moves + 2 swaps + %2d v_fmac_f64_dpp %8.1f     results %s\n",
+           nc, 2 * nc, nc, (double)c0 / NSTEP, nc, (double)c1 / NSTEP, eq ? "bit-identical" : "DIFFER");
+    mean_same = mean_same && eq && c0 > 0 && c1 > 0;
+    return true;
+  };
+  mean_pair(10, mean_step<0, 10>, mean_step<1, 10>);
+  mean_pair(16, mean_step<0, 16>, mean_step<1, 16>);
+  mean_pair(18, mean_step<0, 18>, mean_step<1, 18>);
+  mean_pair(20, mean_step<0, 20>, mean_step<1, 20>);
+  return (bad_total || !same || sw_bad_total || !mean_same) ? 1 : 0;
 }
