@@ -309,6 +309,11 @@ int dsge_debug_adjoint_refine(int mode) {
   g_adj_refine_mode = mode;
   return DSGE_SUCCESS;
 }
+int dsge_debug_cr_static_rows(int mode) {
+  if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
+  g_cr_static_rows_mode = mode;
+  return DSGE_SUCCESS;
+}
 int dsge_forget_measured_shapes(void) {
   cr_deflation_reset();
   gensys_shape_reset();
@@ -1160,8 +1165,13 @@ int dsge_host::pipeline_unchunked(const double* A, const double* B, const double
       int deflated = 0;
       // static variables deflated first (the iteration then runs on n - h variables); not when the caller asks for the
       // iteration counts or the residual, whose contract is the full-size iteration
-      if (fuse_R && !n_iter_out &&
-          (rc = launch_cr_deflated(A, B, C, D, batch, n, k, max_iter, tol, Tw, Rw, status_out, it_w, st, &deflated, cm_w)))
+      // (round 16) T and R in the arena: the filter below is their only reader, and it reads the states and the observed variables
+      // only -- the one-launch kernel is told the observation model and leaves the static rows of a draw that observes none of
+      // its deflated variables at zero (dsge_cr_fused.hpp, phase 3).  A caller who receives T or R gets every row.
+      const bool rows_unread = g_cr_static_rows_mode == 2 || (g_cr_static_rows_mode == 0 && !T_out && !R_out);
+      const ObsModel* skip_obs = (rows_unread && o.Z && p >= 1 && p <= 8) ? &o : nullptr;
+      if (fuse_R && !n_iter_out && (rc = launch_cr_deflated(A, B, C, D, batch, n, k, max_iter, tol, Tw, Rw, status_out, it_w, st,
+                                                            &deflated, cm_w, skip_obs)))
         return rc;
       have_colmask = deflated == 2;
       if (!deflated)

@@ -72,9 +72,14 @@ __device__ __forceinline__ void crd_index_tables(unsigned long long smask, int n
 }
 
 // which variables are static: lane j looks down column j of A and C (all rows in flight); bit j of the result
+// (round 16) obs != nullptr: Zg is this draw's observation matrix (p x n, p <= 8) and *obs gets bit j <=> column j of Z has a
+// non-zero entry, i.e. variable j is observed -- lane j reads column j with the rows clamped to p, unconditionally and in
+// flight with the loads of A and C, as the filter's prologue reads it
 template <int NM>
 __device__ __forceinline__ unsigned long long crd_static_mask(const double* __restrict__ A, const double* __restrict__ C,
-                                                              size_t off, int n, int lane) {
+                                                              size_t off, int n, int lane,
+                                                              const double* __restrict__ Zg = nullptr, int p = 0,
+                                                              unsigned long long* obs = nullptr) {
   int nz = 0;
   {
     // unconditional loads (clamped indices): conditional ones compile to one exec-masked block per load
@@ -82,6 +87,12 @@ __device__ __forceinline__ unsigned long long crd_static_mask(const double* __re
     const double* ap = A + off + cl;
     const double* cp = C + off + cl;
     double av[NM], cv[NM];
+    double zv[8];
+    if (obs) {
+      const double* zp = Zg + cl;
+#pragma unroll
+      for (int o = 0; o < 8; ++o) zv[o] = zp[(size_t)(o < p ? o : (p > 0 ? p - 1 : 0)) * n];
+    }
     if (n == NM) {  // (round 13) the tile is full: compile-time row offsets, no clamp, no 64-bit address product per load
 #pragma unroll
       for (int i = 0; i < NM; ++i) {
@@ -101,6 +112,12 @@ __device__ __forceinline__ unsigned long long crd_static_mask(const double* __re
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NM; ++i) nz |= ((av[i] != 0.0) | (cv[i] != 0.0)) ? 1 : 0;
+    if (obs) {
+      int zn = 0;
+#pragma unroll
+      for (int o = 0; o < 8; ++o) zn |= (o < p && zv[o] != 0.0) ? 1 : 0;
+      *obs = __ballot(zn != 0 && lane < n);
+    }
   }
   const unsigned long long nmask = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
   return ~__ballot(nz != 0) & nmask;
@@ -150,13 +167,17 @@ __device__ __forceinline__ bool crd_col_source(int cv, const double* __restrict_
 // for systems with more columns than one pass holds) reads it as a broadcast; no wave reductions anywhere.  Rows 0..h-1 of
 // Q'[...] go to `tp` (h x ncols, row-major); on return col[q] holds the rows of the REDUCED system (rows 0..nd-1, zeros
 // below) for every column but the h columns of B_st, which have none: their registers hold nothing of use.
+// (round 16) write_top = false (wave-uniform): nothing goes to `tp` -- the caller will not form the static rows.  *rst_bad then
+// still carries the verdict the reader of the top block would have reached (crd_inflate_prepare): some diagonal entry of R_st
+// -- the beta of reflector j, the same value in every lane -- fails fabs(d) > 1e-300.
 template <int NM, int NC, typename IT>
 __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const double* __restrict__ B,
                                              const double* __restrict__ C, const double* __restrict__ D, size_t off,
                                              size_t offk, int n, int k, int h, int c0, const IT* dyi, const IT* sti,
                                              double* V, double* __restrict__ tp, int lane, double (&col)[NC][NM],
                                              bool (&act)[NC], bool skip_zero_ac = false,
-                                             long long* t_loaded = nullptr) {  // debug stamp: the columns have arrived
+                                             long long* t_loaded = nullptr,  // debug stamp: the columns have arrived
+                                             bool write_top = true, bool* rst_bad = nullptr) {
   const int ncols = h + 3 * (n - h) + k;
   const double* src[NC];
   int ss[NC], cv[NC];
@@ -209,7 +230,9 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       const bool ac = cv[q] >= h + nd_ && cv[q] < h + 3 * nd_;
       wr[q] = act[q] && (nz || !ac);
     }
+    wr[q] = wr[q] && write_top;
   }
+  bool bad = false;
   if (t_loaded) *t_loaded = clock64();
   // Row j is final once reflector j has been applied: it goes straight to the top block and the columns are shifted
   // up by one row, so that the pivot is always register row 0 (no index-dependent selects, which cost a scalar lane
@@ -262,6 +285,7 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       tj = (beta - alpha) / beta;
       scal = 1.0 / (alpha - beta);
     }
+    if (rst_bad) bad = bad || !(fabs(beta) > 1e-300);
     // w = -tau v'x; the pivot column (beta e_0 exactly) and the columns left of it (all zeros by now) are set directly
     const bool left = (c0 == 0) && (lj <= j);
     const double2 t0 = vj2[0];
@@ -270,7 +294,9 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       const bool lf = (q == 0) && left;
       const double w = lf ? 0.0 : -tj * fma(scal, d0[q] + d1[q], col[q][0]);
       const double topv = lf ? ((lj == j) ? beta : 0.0) : col[q][0] + w;
-      if (wr[q]) tp[(size_t)j * ncols + cv[q]] = topv;
+      // (round 16) the column index from this pass's own lane index, not cv[q]: that one lived across the loop in scratch (one
+      // reload per pass) and kept the caller's lane index alive, reloaded in front of every use, with it
+      if (wr[q]) tp[(size_t)j * ncols + (c0 + 64 * q + lj)] = topv;
       const double ws = w * scal;
       // update and shift up by one row.  (round 12) No select on `lf` here: the registers of a column at or left of the pivot
       // are dead -- lane j published its column before reflector j, B_st has no rows in the reduced system (no caller deposits
@@ -285,6 +311,7 @@ __device__ __forceinline__ void crd_qr_chunk(const double* __restrict__ A, const
       col[q][NM - 1] = 0.0;
     }
   }
+  if (rst_bad) *rst_bad = bad;
 }
 
 template <int BS>
@@ -499,6 +526,29 @@ __device__ __forceinline__ void crd_inflate_chunk(int c0, const double (&y)[NMD]
 #pragma unroll
     for (int s2 = 0; s2 < HM; ++s2)
       if (s2 < h) dcol[(size_t)sti[s2] * ds] = -x[s2];
+#pragma unroll
+    for (int q = 0; q < NMD; ++q)
+      if (q < nd) dcol[(size_t)dyi[q] * ds] = y[q];
+  }
+}
+
+// (round 16) crd_inflate_chunk without the static rows: column c = c0 + lane of [T_dy | R_dy] scattered to the caller's variable
+// order -- the same values to the same addresses -- and +0.0 where the chunk writes the static rows (as many stores, no load, no
+// top block, no LDS arrays).  For a caller nobody asks for the static variables' own values: they feed nothing (their columns of T
+// are zero), so T and R with these rows zeroed describe the same model with those variables identically zero.
+template <int NMD, typename IT>
+__device__ __forceinline__ void crd_scatter_dynamic(int c0, const double (&y)[NMD], int n, int k, int h, int lane, const IT* dyi,
+                                                    const IT* sti, double* __restrict__ Tg, double* __restrict__ Rg) {
+  constexpr int HM = CRD_HMAX;
+  const int nd = n - h, ntot = nd + k;
+  const int c = c0 + lane;
+  const bool act = c < ntot;
+  double* dcol = (c < nd) ? (Tg + dyi[act && c < nd ? c : 0]) : (Rg + (c - nd));
+  const int ds = (c < nd) ? n : k;
+  if (act) {
+#pragma unroll
+    for (int s2 = 0; s2 < HM; ++s2)
+      if (s2 < h) dcol[(size_t)sti[s2] * ds] = 0.0;
 #pragma unroll
     for (int q = 0; q < NMD; ++q)
       if (q < nd) dcol[(size_t)dyi[q] * ds] = y[q];

@@ -11,7 +11,12 @@
 //            -A1_hat^-1 [A_dy[:,S] | D_red]; the right-hand side of that solve is the one thing that has to survive the
 //            iteration outside the register blocks: it is parked in global scratch (NPD x (s + k) doubles, 6 KB).
 //   phase 3  back-substitution of the static rows (crd_inflate_prepare / crd_inflate_chunk) with the columns of
-//            [T_dy | R_dy] read from LDS, scatter to the caller's variable order.
+//            [T_dy | R_dy] read from LDS, scatter to the caller's variable order.  (round 16) The top block and with it
+//            the static rows are CONDITIONAL: given the caller's observation matrix Z (the fused likelihood call with T
+//            and R in the library's arena), a draw none of whose h deflated variables is observed writes no top block in
+//            phase 1 and +0.0 into the static rows here (crd_scatter_dynamic) -- the filter gathers T and R over states
+//            and observed variables only, and a static variable, with zero columns in A and C, is never a state.  The
+//            hand-over for a singular R_st is then decided from the reflectors' betas.  Z = nullptr: always computed.
 //
 // Against the three launches (SW-shaped 40-variable system, 10 static, 4096 draws): no reduced A, B, C, D, T_dy, R_dy in HBM
 // (131 MB written and read back twice), two launches and their tails less.  Draws the fused kernel cannot take -- fewer
@@ -56,6 +61,7 @@ __device__ __forceinline__ unsigned long long crf_place(unsigned long long b, in
 // [9] the h reflectors, [10] deposit (column masks, tables, W, the parked right-hand sides, the register blocks), [11] phase 3;
 // (round 13) [12] the static mask alone (part of [8]), and of phase 3: [13] the gather of y through prow, [14]
 // crd_inflate_prepare, [15] crd_inflate_chunk up to its scatter -- the rest of [11] is the zero and scatter stores.
+// (round 16) A draw that skips the static rows stamps the same places: [14] and [15] then read next to nothing.
 // With DBG = false nothing of it is compiled: the listing of the default instance is the one without the flag.
 template <int BSF, int BSD, int NC, bool DBG = false>
 __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, const double* __restrict__ B,
@@ -65,6 +71,7 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
                                               double* __restrict__ R_out, int32_t* __restrict__ status,
                                               int32_t* __restrict__ n_iter_out,
                                               unsigned long long* __restrict__ colmask_out,
+                                              const double* __restrict__ Z, int z_batched, int p,
                                               long long* __restrict__ dbg = nullptr) {
   using SM = CrfSmem<BSF, BSD>;
   constexpr int NMF = SM::NMF, NPD = SM::NPD, LDW = SM::LDW, HM = CRD_HMAX;
@@ -98,11 +105,22 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   // ---- phase 1: deflation ----------------------------------------------------------------------------------------------
   long long tk_start = 0, tk_ld = 0, tk_qr = 0, tk_mask = 0;
   if constexpr (DBG) tk_start = clock64();
-  unsigned long long smask = crd_static_mask<NMF>(A, C, off, n, lane);
+  // (round 16) which variables the caller's filter observes: the loads of Z ride with the ones of A and C (a null Z reads row 0
+  // of A in their place and the verdict below is "not skipped")
+  unsigned long long obs = 0ull;
+  unsigned long long smask = crd_static_mask<NMF>(A, C, off, n, lane, Z ? Z + (z_batched ? (size_t)draw * p * n : 0) : A + off,
+                                                  Z ? p : 0, &obs);
   if constexpr (DBG) tk_mask = clock64();
   if (__popcll(smask) < h) return hand_over();
   smask = crd_first_bits(smask, h);
-  crd_index_tables(smask, n, lane, dyi, sti);
+  // no deflated variable is observed: nobody reads the static rows of T and R (header comment, phase 3)
+  const bool skip = Z != nullptr && (smask & obs) == 0ull;
+  // (round 16) the lane index of the tables and the column sources, from two mbcnt and opaque (as in the reflector pass): at 256
+  // registers `lane` is in scratch across the static mask, and with the Z registers live there the compiler reloaded it in front
+  // of every use below, nine waits of a scratch round trip in a row
+  int lane_t;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_t));
+  crd_index_tables(smask, n, lane_t, dyi, sti);
   double* tp = top + (size_t)draw * crd_top_doubles(n, k, h);
   double* rh = rhs + (size_t)draw * crf_rhs_doubles(nd, NPD);
   int s, l;
@@ -110,8 +128,16 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   {
     double col[NC][NMF];
     bool act[NC];
-    crd_qr_chunk<NMF, NC>(A, B, C, D, off, offk, n, k, h, 0, dyi, sti, /*V=*/smem, tp, lane, col, act,
-                          /*skip_zero_ac=*/true, DBG ? &tk_ld : nullptr);
+    bool rst_bad = false;
+    int lane_c;  // (a copy of its own for the column sources: two short live ranges, not one across both)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_c));
+    crd_qr_chunk<NMF, NC>(A, B, C, D, off, offk, n, k, h, 0, dyi, sti, /*V=*/smem, tp, lane_c, col, act,
+                          /*skip_zero_ac=*/true, DBG ? &tk_ld : nullptr, /*write_top=*/!skip, &rst_bad);
+    // (round 16) the verdict for phase 3, parked in the one spare slot of the tables (h >= 1: dyi holds nd <= 63 entries) -- a
+    // value carried across crc_iterate in a register is a register the iteration does not have.  Bit 0: skip the static rows,
+    // bit 1: R_st is numerically singular, what crd_inflate_prepare would have found in the top block that was not written
+    const bool rst_singular = __ballot(rst_bad) != 0ull;  // (every lane holds the same verdict: wave-uniform for the compiler)
+    if (lane == 0) dyi[63] = (idx_t)(skip ? (rst_singular ? 3 : 1) : 0);
     if constexpr (DBG) tk_qr = clock64();
     // block (0 B, 1 A, 2 C, 3 D, -1 none) and column inside the block of this lane's columns 64 q + lane
     int blk[NC], dcol[NC];
@@ -253,8 +279,12 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
 
   // ---- phase 3: the static rows, scatter to the caller's variable order -------------------------------------------------
   if constexpr (DBG) tk_fin = clock64();
+  // (round 16) The verdict of phase 1 first (bit 0: skip the static rows, bit 1: R_st singular), then ONE branch around the whole
+  // phase: the full path below is the code it was -- the gather, the loads of the top block and the LDS arrays scheduled as one
+  // piece -- and the skipping path is the gather and the stores.
+  const int verdict = __builtin_amdgcn_readfirstlane((int)dyi[63]);
   double y[NPD];  // column `lane` of [T_dy | R_dy]: T_dy[:, v] = -X[:, posS(v)] for a state v, zero otherwise
-  {
+  auto gather_y = [&]() {
     const int ntot = nd + k;
     int src = -1;
     if (lane < nd)
@@ -275,20 +305,33 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
     }
 #pragma unroll
     for (int q = 0; q < NPD; ++q) y[q] = (q < nd && src >= 0) ? -G1[(q < nd ? pr[q] : pr[0]) * LDW + src] : 0.0;
-  }
-  wave_sync();  // the solution is in registers: W becomes the work space of the back-substitution
-  long long tk_y = 0, tk_prep = 0, tk_z = 0, tk_x = 0;
-  if constexpr (DBG) tk_y = clock64();
-  const CrdInflateLds<NPD> L(smem);
-  if (!crd_inflate_prepare<NPD>(y, lane < nd + k, tp, n, k, h, lane, L, maskL_red)) return hand_over();
-  if constexpr (DBG) tk_prep = clock64();
-  if (lane < n) {  // static columns of T are exact zeros
+  };
+  auto zero_static_columns = [&]() {  // static columns of T are exact zeros
+    if (lane < n) {
 #pragma unroll
-    for (int s2 = 0; s2 < HM; ++s2)
-      if (s2 < h) T_out[off + (size_t)lane * n + sti[s2]] = 0.0;
+      for (int s2 = 0; s2 < HM; ++s2)
+        if (s2 < h) T_out[off + (size_t)lane * n + sti[s2]] = 0.0;
+    }
+  };
+  long long tk_y = 0, tk_prep = 0, tk_z = 0, tk_x = 0;
+  if (verdict != 0) {
+    if (verdict & 2) return hand_over();  // (as the full path: before anything is written to T_out or R_out)
+    gather_y();
+    if constexpr (DBG) tk_y = tk_prep = clock64();
+    zero_static_columns();
+    if constexpr (DBG) tk_z = tk_x = clock64();
+    crd_scatter_dynamic<NPD>(0, y, n, k, h, lane, dyi, sti, T_out + off, R_out + offk);
+  } else {
+    gather_y();
+    wave_sync();  // the solution is in registers: W becomes the work space of the back-substitution
+    if constexpr (DBG) tk_y = clock64();
+    const CrdInflateLds<NPD> L(smem);
+    if (!crd_inflate_prepare<NPD>(y, lane < nd + k, tp, n, k, h, lane, L, maskL_red)) return hand_over();
+    if constexpr (DBG) tk_prep = clock64();
+    zero_static_columns();
+    if constexpr (DBG) tk_z = clock64();
+    crd_inflate_chunk<NPD>(0, y, tp, n, k, h, lane, L, dyi, sti, T_out + off, R_out + offk, maskS_red, DBG ? &tk_x : nullptr);
   }
-  if constexpr (DBG) tk_z = clock64();
-  crd_inflate_chunk<NPD>(0, y, tp, n, k, h, lane, L, dyi, sti, T_out + off, R_out + offk, maskS_red, DBG ? &tk_x : nullptr);
   // every other column of T is exactly zero (written so): the filter kernel need not look for them
   if (colmask_out && lane == 0) colmask_out[draw] = state_cols;
   if constexpr (DBG) {
@@ -317,8 +360,10 @@ __global__ __launch_bounds__(64) void cr_fused_kernel(const double* __restrict__
                                                        double* __restrict__ top, double* __restrict__ rhs,
                                                        double* __restrict__ T_out, double* __restrict__ R_out,
                                                        int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
-                                                       unsigned long long* __restrict__ colmask_out) {
-  cr_fused_body<BSF, BSD, NC>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out);
+                                                       unsigned long long* __restrict__ colmask_out,
+                                                       const double* __restrict__ Z, int z_batched, int p) {
+  cr_fused_body<BSF, BSD, NC>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out,
+                              Z, z_batched, p);
 }
 
 // the register budget of two waves per SIMD for the 4 x 4 reduced tile (see cr_compact_kernel_occ2)
@@ -327,8 +372,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ C, const double* __restrict__ D,
     int batch, int n, int k, int h, int max_iter, double tol, double* __restrict__ top, double* __restrict__ rhs,
     double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
-    unsigned long long* __restrict__ colmask_out) {
-  cr_fused_body<BSF, BSD, 2>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out);
+    unsigned long long* __restrict__ colmask_out, const double* __restrict__ Z, int z_batched, int p) {
+  cr_fused_body<BSF, BSD, 2>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out,
+                             Z, z_batched, p);
 }
 
 // The stamped instance of the kernel above (body flag DBG; dsge_debug_cr_fused_phases).  A kernel of its own because of the
@@ -338,9 +384,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ C, const double* __restrict__ D,
     int batch, int n, int k, int h, int max_iter, double tol, double* __restrict__ top, double* __restrict__ rhs,
     double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
-    unsigned long long* __restrict__ colmask_out, long long* __restrict__ dbg) {
+    unsigned long long* __restrict__ colmask_out, const double* __restrict__ Z, int z_batched, int p,
+    long long* __restrict__ dbg) {
   cr_fused_body<BSF, BSD, 2, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out,
-                                   colmask_out, dbg);
+                                   colmask_out, Z, z_batched, p, dbg);
 }
 
 }  // namespace dsge

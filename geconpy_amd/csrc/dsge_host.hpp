@@ -230,8 +230,11 @@ int launch_big_compress(const double* T, const double* R, const double* Z, int z
                         const unsigned char* idx, int u, double* T_r, double* R_r, double* Z_r, hipStream_t st);
 int launch_cr_deflated(const double* A, const double* B, const double* C, const double* D, int batch, int n, int k,
                        int max_iter, double tol, double* T_out, double* R_out, int32_t* status, int32_t* n_iter,
-                       hipStream_t st, int* used, unsigned long long* colmask = nullptr);
+                       hipStream_t st, int* used, unsigned long long* colmask = nullptr, const ObsModel* skip_obs = nullptr);
 // (*used = 2: the one-launch kernel ran and colmask[draw] holds the non-zero columns of T_out[draw], ~0 = not known)  // static-variable deflation + cycle reduction on the reduced system
+// skip_obs (p <= 8; the one-launch kernel only): T_out and R_out are read by a filter with this observation model and by nobody
+// else -- a draw none of whose deflated static variables is observed gets zeros in the static rows of T_out and R_out
+// (dsge_cr_fused.hpp, phase 3).  Null: every row is computed.
 void cr_deflation_reset();
 void gensys_shape_reset();  // launch_gensys.hip
 int launch_bdirect(const double* A, const double* B, const double* D, int batch, int n, int k, double* T_out,
@@ -470,6 +473,7 @@ extern long long* g_shock_decomp_dbg;  // launch_shock_decomp.hip: debug phase c
 extern long long* g_condfc_dbg;        // launch_condfc.hip: debug phase counters of the two conditional-forecast kernels
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
 extern long long* g_cr_fused_dbg;      // launch_solvers.hip: debug phase counters of the fused CR kernel (stamped instance)
+extern int g_cr_static_rows_mode;      // launch_solvers.hip: 0 = static rows skipped where nobody reads them, 1 = never, 2 = also into T_out / R_out (debug)
 extern long long* g_big_dbg;         // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
 extern long long* g_gensys_win_dbg;   // launch_gensys.hip: debug phase stamps of the window kernels (device int64[32])

@@ -13,6 +13,7 @@ namespace dsge_host {
 
 long long* g_cr_dbg = nullptr;  // debug: device int64[8], phase cycles of draw 0 of the compact kernel
 long long* g_cr_fused_dbg = nullptr;  // debug: device int64[16], phase cycles of draw 0 of cr_fused_kernel_occ2_dbg<5, 4>
+int g_cr_static_rows_mode = 0;        // debug: dsge_debug_cr_static_rows
 
 int launch_cr(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol,
               double* T_out, int32_t* status, int32_t* n_iter, hipStream_t st, int scan_mode, const double* D, int k,
@@ -80,7 +81,7 @@ namespace {
 template <int BSF, int BSD, int NC>
 int launch_cr_fused_inst(const double* A, const double* B, const double* C, const double* D, int batch, int n, int k, int h,
                          int max_iter, double tol, double* top, double* rhs, double* T_out, double* R_out, int32_t* status,
-                         int32_t* n_iter, hipStream_t st, unsigned long long* colmask) {
+                         int32_t* n_iter, hipStream_t st, unsigned long long* colmask, const double* Z, int z_batched, int p) {
   using SM = dsge::CrfSmem<BSF, BSD>;
   int rc;
   if constexpr (BSD == 4 && NC == 2) {
@@ -89,21 +90,21 @@ int launch_cr_fused_inst(const double* A, const double* B, const double* C, cons
         if (g_cr_fused_dbg) {
           if ((rc = set_lds(dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>, SM::bytes))) return rc;
           hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n,
-                             k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, g_cr_fused_dbg);
+                             k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, Z, z_batched, p, g_cr_fused_dbg);
           HIP_TRY(hipGetLastError());
           return DSGE_SUCCESS;
         }
       }
       if ((rc = set_lds(dsge::cr_fused_kernel_occ2<BSF, BSD>, SM::bytes))) return rc;
       hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n, k, h,
-                         max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask);
+                         max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, Z, z_batched, p);
       HIP_TRY(hipGetLastError());
       return DSGE_SUCCESS;
     }
   }
   if ((rc = set_lds(dsge::cr_fused_kernel<BSF, BSD, NC>, SM::bytes))) return rc;
   hipLaunchKernelGGL((dsge::cr_fused_kernel<BSF, BSD, NC>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n, k, h,
-                     max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask);
+                     max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, Z, z_batched, p);
   HIP_TRY(hipGetLastError());
   return DSGE_SUCCESS;
 }
@@ -111,7 +112,7 @@ int launch_cr_fused_inst(const double* A, const double* B, const double* C, cons
 
 int launch_cr_fused(const double* A, const double* B, const double* C, const double* D, int batch, int n, int k, int h,
                     int max_iter, double tol, double* T_out, double* R_out, int32_t* status, int32_t* n_iter, hipStream_t st,
-                    int* done, unsigned long long* colmask) {
+                    int* done, unsigned long long* colmask, const ObsModel* skip_obs) {
   *done = 0;
   const int nd = n - h, bsf = tile_bs(n), bsd = tile_bs(nd);
   const int ncol = h + 3 * nd + k, nc = ncol <= 128 ? 2 : 3;  // columns of [B_st | B_dy | A_dy | C_dy | D] per lane
@@ -130,7 +131,8 @@ int launch_cr_fused(const double* A, const double* B, const double* C, const dou
 #define FUSED_CASE(F, D_, N_)                                                                                          \
   if (bsf == F && bsd == D_ && nc == N_)                                                                               \
     rc = launch_cr_fused_inst<F, D_, N_>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, st, \
-                                         colmask)
+                                         colmask, skip_obs ? skip_obs->Z : nullptr, skip_obs ? skip_obs->z_batched : 0,  \
+                                         skip_obs ? skip_obs->p : 0)
   rc = DSGE_ERR_INVALID;
   FUSED_CASE(3, 2, 2);
   FUSED_CASE(3, 3, 2);
@@ -163,7 +165,7 @@ int launch_cr_fused(const double* A, const double* B, const double* C, const dou
 // *used = 0: nothing done (deflation off, too few static variables, ...): the caller runs launch_cr on the full system.
 int launch_cr_deflated(const double* A, const double* B, const double* C, const double* D, int batch, int n, int k,
                        int max_iter, double tol, double* T_out, double* R_out, int32_t* status, int32_t* n_iter,
-                       hipStream_t st, int* used, unsigned long long* colmask) {
+                       hipStream_t st, int* used, unsigned long long* colmask, const ObsModel* skip_obs) {
   *used = 0;
   if (!opt().cr_deflation || !D || !R_out || n < 8 || n > 64 || batch < 1) return DSGE_SUCCESS;
   int rc;
@@ -213,7 +215,7 @@ int launch_cr_deflated(const double* A, const double* B, const double* C, const 
     // one launch (dsge_cr_fused.hpp); the (full tile, reduced tile) pairs built are the ones the deflation test above lets
     // through for n <= 48
     int done = 0;
-    if ((rc = launch_cr_fused(A, B, C, D, batch, n, k, h, max_iter, tol, T_out, R_out, status, n_iter, st, &done, colmask)))
+    if ((rc = launch_cr_fused(A, B, C, D, batch, n, k, h, max_iter, tol, T_out, R_out, status, n_iter, st, &done, colmask, skip_obs)))
       return rc;
     if (done) {
       *used = colmask ? 2 : 1;  // 2: colmask[draw] holds the non-zero columns of T (or ~0: not known)

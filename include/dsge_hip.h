@@ -567,6 +567,12 @@ int dsge_policy_adjoints_batched_host(const double* B, const double* C, const do
  * residual = T_bar + M' S + C' S T'): the level of the reference's Kronecker LU (shared.py:53-71).  Debug hook for the tests:
  * mode 0 = that rule (default), 1 = refine every draw, 2 = never refine.  Process-wide. */
 int dsge_debug_adjoint_refine(int mode);
+/* The fused likelihood call (dsge_solve_kalman_logp_batched and its twins) keeps T and R in the library's arena when the caller asks
+ * for neither; its filter reads the state variables and the observed variables only, so the one-launch deflated cycle reduction
+ * leaves the rows of T and R of the deflated static variables at zero for every draw that observes none of them (p <= 8; decided
+ * per draw on the device).  Debug hook for the tests: mode 0 = that rule (default), 1 = always compute the static rows, 2 = apply
+ * the rule also when the caller receives T_out / R_out (their static rows are then zeros where it fired).  Process-wide. */
+int dsge_debug_cr_static_rows(int mode);
 
 /*
  * Pullback of the shock-impact matrix.  The reference's R = -solve(C @ T + B, D) is plain differentiable pytensor
