@@ -116,6 +116,7 @@ _DEVICE_ENTRIES = {
     "dsge_debug_gensys_stage_ms": "enable ms_out",
     "dsge_debug_adjoint_refine": "mode",
     "dsge_debug_cr_static_rows": "mode",
+    "dsge_debug_cr_refine": "mode",
     "dsge_debug_second_order_phases": "enable cycles_out",
     "dsge_debug_pruned_phases": "enable cycles_out",
     "dsge_debug_shock_decomp_phases": "enable cycles_out",

@@ -299,7 +299,7 @@ static int debug_counters(long long** slot, int count, int enable, long long* cy
   return DSGE_SUCCESS;
 }
 int dsge_debug_cr_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_dbg, 8, enable, cycles_out); }
-int dsge_debug_cr_fused_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_fused_dbg, 16, enable, cycles_out); }
+int dsge_debug_cr_fused_phases(int enable, long long* cycles_out) { return debug_counters(&g_cr_fused_dbg, 24, enable, cycles_out); }
 int dsge_debug_second_order_phases(int enable, long long* cycles_out) { return debug_counters(&g_so_dbg, 8, enable, cycles_out); }
 int dsge_debug_pruned_phases(int enable, long long* cycles_out) { return debug_counters(&g_pruned_dbg, 8, enable, cycles_out); }
 int dsge_debug_shock_decomp_phases(int enable, long long* cycles_out) { return debug_counters(&g_shock_decomp_dbg, 8, enable, cycles_out); }
@@ -312,6 +312,11 @@ int dsge_debug_adjoint_refine(int mode) {
 int dsge_debug_cr_static_rows(int mode) {
   if (mode < 0 || mode > 2) return fail(DSGE_ERR_INVALID, "mode out of range (0..2)");
   g_cr_static_rows_mode = mode;
+  return DSGE_SUCCESS;
+}
+int dsge_debug_cr_refine(int mode) {
+  if (mode < 0 || mode > 1) return fail(DSGE_ERR_INVALID, "mode out of range (0..1)");
+  g_cr_refine_mode = mode;
   return DSGE_SUCCESS;
 }
 int dsge_forget_measured_shapes(void) {

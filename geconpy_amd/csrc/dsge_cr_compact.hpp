@@ -81,7 +81,18 @@ __device__ __forceinline__ unsigned long long blk_colmask(const double (&x)[BS][
 // as the products' left operands only: the elimination works on the register block).
 // ph (nullable): debug stamps [0] GJ panels, [1] GJ trailing updates, [2] row gather + staging, [3] products,
 // [4] scatter/update/norms.
-template <int BS, typename IT>
+// RM (round 17), the measuring forms of the refinement branch, each compiled into an instance of its own: CRC_REFINE_NEVER leaves
+// the branch out (dsge_debug_cr_refine: it changes results), CRC_REFINE_STAMPED counts and stamps it -- ph[8] refinements of the
+// draw, ph[9] cycles of their residuals, ph[10] of their second eliminations, ph[11] of the whole branch (ph then holds 12).
+// With CRC_REFINE_RULE nothing of either is compiled.
+enum { CRC_REFINE_RULE = 0, CRC_REFINE_NEVER = 1, CRC_REFINE_STAMPED = 2 };
+// REPLAY (round 17): refine by replaying the recorded elimination instead of eliminating a second time.  Both give the same bits,
+// so the choice is per INSTANCE and free.  It is on for the instances with the register budget of two waves per SIMD
+// (cr_compact_kernel_occ2, cr_fused_kernel_occ2*): the bench's instance, where it was measured to pay -- the launch ends with
+// the draws that refine -- and its siblings, none of which gains scratch with it.  Everywhere else the record's row stores
+// per panel would be paid by every draw for nothing measured (24 variables: +0.8 % of the full_nk step) and the wide tiles
+// spill more with it: those keep the second elimination and the parent's code.
+template <int BS, int RM = CRC_REFINE_RULE, bool REPLAY = false, typename IT>
 __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[BS][BS], double (&Rb)[BS][BS], double* W,
                                             double* Lbuf, double* Ybuf, int* prow, const IT* cmap, IT* rsrc,
                                             const IT* posS, const IT* posL, int n, int s, int l, int max_iter,
@@ -111,7 +122,8 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     }
     blk_store_lds<BS>(Rb, G1, LDW, lr, lc);
     double inv_lo = 1e300, inv_hi = 0.0;
-    gauss_jordan_blocked_rhs<BS>(W, LDW, n, Rb, Lbuf, Ybuf, prow, lane, ph, inv_lo, inv_hi);  // syncs on entry and exit
+    // (round 17, REPLAY) ... and leaves its multipliers in the dead panel columns of W, for the refinement below
+    gauss_jordan_blocked_rhs<BS, REPLAY>(W, LDW, n, Rb, Lbuf, Ybuf, prow, lane, ph, inv_lo, inv_hi);  // syncs on entry and exit
     // One step of iterative refinement, X += A1^-1 (R - A1 X), in every iteration whose pivots span more than
     // CR_REFINE_PIVOT_RATIO: the blocked Gauss-Jordan loses ~1e-15 x cond(A1) where the reference's LAPACK LU
     // (cycle_reduction.py:150-160) keeps 1e-10, and the worst A1 of a draw may come as late as the third or fourth iteration
@@ -120,9 +132,17 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
     // branch in some iteration; the others are untouched (bit-identical).  The residual is formed in twice the working
     // precision (mm_residual_dot2): the corrected X is then better than the reference's own LU on the systems where float64
     // algorithms cannot agree to 1e-9 (cond(A1) ~ 1e6: tools/cr_accuracy_study.py, tests/golden/cr_ill_conditioned_54.npz).
-    if (__builtin_amdgcn_readfirstlane((int)(inv_hi > cr_refine_ratio<BS>() * inv_lo))) {
+    if (RM != CRC_REFINE_NEVER && __builtin_amdgcn_readfirstlane((int)(inv_hi > cr_refine_ratio<BS>() * inv_lo))) {
+      long long tk_r0 = 0, tk_r1 = 0, tk_r2 = 0;
+      if constexpr (RM == CRC_REFINE_STAMPED) tk_r0 = clock64();
+      // (round 17) The correction A1^-1 (R - A1 X) used to be a second elimination of [A1 | R - A1 X]: the pivot search, the 8 BS
+      // pivots and the multipliers of the one just done, all over again.  It is now that elimination REPLAYED on the residual
+      // (gj_replay: the trailing update's FMAs on the same operands in the same order, bit-identical).  Its record is in column
+      // group 0 of W, which the residual needs for X and A1: it waits in a register block meanwhile -- rows lr BS .. of panel lc,
+      // each lane the block it is about to overwrite -- and goes back once the residual is formed and A1 in LDS is dead.
       // X (registers, pivot order) -> natural row order through the dead column group 0; Rb takes the original R back from G1
-      double xh[BS][BS], rr[BS][BS];
+      double xh[BS][BS], rr[BS][BS], rec[BS][BS];  // (rec: REPLAY only)
+      if constexpr (REPLAY) blk_load_lds<BS>(rec, W, LDW, lr, lc);
       blk_store_lds<BS>(Rb, W, LDW, lr, lc);
       wave_sync();
 #pragma unroll
@@ -141,10 +161,26 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
         for (int i = 0; i < BS; ++i) W[(lr * BS + i) * LDW + lc * BS + i] = A1[i][i] + 1e-16;
       }
       wave_sync();
+      if constexpr (RM == CRC_REFINE_STAMPED) tk_r1 = clock64();
       mm_residual_dot2<BS>(rr, Rb, W, LDW, G1, LDW, n, lr, lc);  // R - A1 X, inner products in twice the working precision
       wave_sync();
-      blk_store_lds<BS>(rr, G1, LDW, lr, lc);
-      gauss_jordan_blocked<BS>(W, LDW, n, 2, Lbuf, Ybuf, prow, lane);  // [A1 | R - A1 X] -> the correction (syncs on entry and exit)
+      if constexpr (RM == CRC_REFINE_STAMPED) tk_r2 = clock64();
+      if constexpr (REPLAY) {
+        blk_load_lds<BS>(xh, G1, LDW, lr, lc);  // (X again: with the record in registers there is no room for it across the residual)
+        blk_store_lds<BS>(rr, G1, LDW, lr, lc);
+        blk_store_lds<BS>(rec, W, LDW, lr, lc);
+        gj_replay<BS, true>(G1, LDW, n, W, prow, Ybuf, lane);  // R - A1 X -> the correction (syncs on entry and exit)
+      } else {
+        blk_store_lds<BS>(rr, G1, LDW, lr, lc);
+        gauss_jordan_blocked<BS>(W, LDW, n, 2, Lbuf, Ybuf, prow, lane);  // [A1 | R - A1 X] -> the correction (syncs on entry and exit)
+      }
+      if constexpr (RM == CRC_REFINE_STAMPED) {
+        const long long tk_r3 = clock64();
+        ph[8] += 1;
+        ph[9] += tk_r2 - tk_r1;
+        ph[10] += tk_r3 - tk_r2;
+        ph[11] -= tk_r0;  // (the end of the branch is added below)
+      }
       gj_unpermute<BS>(W, LDW, n, 1, 2, prow, lane);
       blk_load_lds<BS>(rr, G1, LDW, lr, lc);
       wave_sync();
@@ -155,6 +191,7 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
         for (int j = 0; j < BS; ++j) Rb[i][j] = xh[i][j] + rr[i][j];  // the solution, where the common path expects it
       if (lane < NP) prow[lane] = lane;  // it sits in natural row order now
       wave_sync();
+      if constexpr (RM == CRC_REFINE_STAMPED) ph[11] += clock64();
     }
     long long tk0 = ph ? clock64() : 0;
     // the solution -> dead column group 0, its rows S then L gathered there into compact order: XC[r] = X[cmap[r]]
@@ -238,7 +275,7 @@ __device__ __forceinline__ void crc_iterate(double (&A1)[BS][BS], double (&Ah)[B
   }
 }
 
-template <int BS>
+template <int BS, bool REPLAY = false>
 __device__ __forceinline__ void cr_compact_body(const double* __restrict__ A, const double* __restrict__ B,
                                                 const double* __restrict__ C, int batch, int n, int max_iter,
                                                 double tol, double* __restrict__ T_out,
@@ -319,8 +356,8 @@ __device__ __forceinline__ void cr_compact_body(const double* __restrict__ A, co
     // [4] scatter/update/norms, [5] final solve, [6] total
     long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const long long tk_start = dbg ? clock64() : 0;
-    crc_iterate<BS>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, n, s, l, max_iter, tol, scan_mode, lane,
-                    dbg ? ph : nullptr, it, converged, saw_nan);
+    crc_iterate<BS, CRC_REFINE_RULE, REPLAY>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, n, s, l, max_iter, tol,
+                                             scan_mode, lane, dbg ? ph : nullptr, it, converged, saw_nan);
     const long long tk_fin = dbg ? clock64() : 0;
 
     double Tb[BS][BS];
@@ -420,7 +457,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ C, int batch, int n, int max_iter,
     double tol, double* __restrict__ T_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
     long long* __restrict__ dbg, int scan_mode, const double* __restrict__ D, int k, double* __restrict__ R_out) {
-  cr_compact_body<BS>(A, B, C, batch, n, max_iter, tol, T_out, status, n_iter_out, dbg, scan_mode, D, k, R_out);
+  cr_compact_body<BS, true>(A, B, C, batch, n, max_iter, tol, T_out, status, n_iter_out, dbg, scan_mode, D, k, R_out);
 }
 
 }  // namespace dsge

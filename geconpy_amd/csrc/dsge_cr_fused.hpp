@@ -62,8 +62,13 @@ __device__ __forceinline__ unsigned long long crf_place(unsigned long long b, in
 // (round 13) [12] the static mask alone (part of [8]), and of phase 3: [13] the gather of y through prow, [14]
 // crd_inflate_prepare, [15] crd_inflate_chunk up to its scatter -- the rest of [11] is the zero and scatter stores.
 // (round 16) A draw that skips the static rows stamps the same places: [14] and [15] then read next to nothing.
+// (round 17) The refinement branch of the iterations is counted over the WHOLE batch, not draw 0 (a few draws in a thousand take
+// it): atomic adds of every draw that refined into [16] draws, [17] refinements, [18] cycles of the residuals, [19] of the
+// second eliminations, [20] of the whole branch, [21] / [22] / [23] draws that refined in one / two / three or more iterations.
 // With DBG = false nothing of it is compiled: the listing of the default instance is the one without the flag.
-template <int BSF, int BSD, int NC, bool DBG = false>
+// NOREFINE (round 17): the iteration without its refinement branch (dsge_debug_cr_refine(1), a measuring tool: results change).
+// REPLAY (round 17): crc_iterate's, on for the instances of two waves per SIMD.
+template <int BSF, int BSD, int NC, bool DBG = false, bool NOREFINE = false, bool REPLAY = false>
 __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, const double* __restrict__ B,
                                               const double* __restrict__ C, const double* __restrict__ D, int batch, int n,
                                               int k, int h, int max_iter, double tol, double* __restrict__ top,
@@ -234,12 +239,20 @@ __device__ __forceinline__ void cr_fused_body(const double* __restrict__ A, cons
   wave_sync();
   bool converged, saw_nan;
   int it;
-  long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long ph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   long long tk_dep = 0, tk_it = 0, tk_fin = 0;
   if constexpr (DBG) tk_dep = clock64();
-  crc_iterate<BSD>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, nd, s, l, max_iter, tol, 0, lane,
+  crc_iterate<BSD, DBG ? CRC_REFINE_STAMPED : (NOREFINE ? CRC_REFINE_NEVER : CRC_REFINE_RULE), REPLAY>(A1, Ah, Rb, W, Lbuf, Ybuf, prow, cmap, rsrc, posS, posL, nd, s, l, max_iter, tol, 0, lane,
                    DBG ? ph : nullptr, it, converged, saw_nan);
-  if constexpr (DBG) tk_it = clock64();
+  if constexpr (DBG) {
+    tk_it = clock64();
+    if (dbg && lane == 0 && ph[8] > 0) {  // (before the early return of a draw that did not converge)
+      unsigned long long* cnt = reinterpret_cast<unsigned long long*>(dbg);
+      atomicAdd(cnt + 16, 1ull);
+      for (int q = 0; q < 4; ++q) atomicAdd(cnt + 17 + q, (unsigned long long)ph[8 + q]);
+      atomicAdd(cnt + (ph[8] >= 3 ? 23 : 20 + (int)ph[8]), 1ull);
+    }
+  }
   if (lane == 0) {
     status[draw] = converged ? DSGE_ST_OK : (DSGE_ST_NOT_CONVERGED | (saw_nan ? DSGE_ST_NAN : 0));
     if (n_iter_out) n_iter_out[draw] = it;
@@ -373,8 +386,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     int batch, int n, int k, int h, int max_iter, double tol, double* __restrict__ top, double* __restrict__ rhs,
     double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
     unsigned long long* __restrict__ colmask_out, const double* __restrict__ Z, int z_batched, int p) {
-  cr_fused_body<BSF, BSD, 2>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out, colmask_out,
-                             Z, z_batched, p);
+  cr_fused_body<BSF, BSD, 2, false, false, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status,
+                                                 n_iter_out, colmask_out, Z, z_batched, p);
+}
+
+// (round 17) ... and without the refinement branch of the iterations: what dsge_debug_cr_refine(1) launches to measure the
+// branch's share of the launch.  Results differ from the default instance's on every draw that would have refined.
+template <int BSF, int BSD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void cr_fused_kernel_occ2_norefine(
+    const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ C, const double* __restrict__ D,
+    int batch, int n, int k, int h, int max_iter, double tol, double* __restrict__ top, double* __restrict__ rhs,
+    double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
+    unsigned long long* __restrict__ colmask_out, const double* __restrict__ Z, int z_batched, int p) {
+  cr_fused_body<BSF, BSD, 2, false, true, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status,
+                                                n_iter_out, colmask_out, Z, z_batched, p);
 }
 
 // The stamped instance of the kernel above (body flag DBG; dsge_debug_cr_fused_phases).  A kernel of its own because of the
@@ -386,8 +411,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     double* __restrict__ T_out, double* __restrict__ R_out, int32_t* __restrict__ status, int32_t* __restrict__ n_iter_out,
     unsigned long long* __restrict__ colmask_out, const double* __restrict__ Z, int z_batched, int p,
     long long* __restrict__ dbg) {
-  cr_fused_body<BSF, BSD, 2, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter_out,
-                                   colmask_out, Z, z_batched, p, dbg);
+  cr_fused_body<BSF, BSD, 2, true, false, true>(A, B, C, D, batch, n, k, h, max_iter, tol, top, rhs, T_out, R_out, status,
+                                                n_iter_out, colmask_out, Z, z_batched, p, dbg);
 }
 
 }  // namespace dsge

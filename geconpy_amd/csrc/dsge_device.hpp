@@ -634,7 +634,11 @@ __device__ __forceinline__ constexpr double cr_refine_ratio() {
 
 // RHS_REG (round 9, gauss_jordan_blocked_rhs below): the right-hand sides -- column group 1 of two -- live in the caller's
 // register block Rg instead of W; false is the LDS form every other caller uses, which never touches Rg.
-template <int BS, bool RHS_REG>
+// REC_W (round 17, register form only): the multipliers of panel kb are kept in the panel's own block column of W -- columns
+// kb BS .. kb BS + BS - 1 of rows < n, dead once the panel is done: the trailing updates skip them, the pivot-row copies to Ybuf
+// read them for nothing -- as -Lhat, the very values Lbuf holds for one panel.  gj_replay<BS, true> applies the elimination to
+// one more right-hand-side group from there.  Two LDS stores of a row per lane and panel; nothing else changes.
+template <int BS, bool RHS_REG, bool REC_W = false>
 __device__ __forceinline__ void gauss_jordan_blocked_impl(double* W, int ldw, int n, int ngroups, double* Lbuf, double* Ybuf,
                                                           int* prow, int lane, long long* ph, double& inv_min, double& inv_max,
                                                           double* rec_L, double (&Rg)[BS][BS]) {
@@ -731,6 +735,10 @@ __device__ __forceinline__ void gauss_jordan_blocked_impl(double* W, int ldw, in
         }
 #pragma unroll
         for (int b = 0; b < BS; ++b) Lbuf[lane * BS + b] = nl[b];
+        if constexpr (REC_W) {  // (every slot of the row, as Lbuf: a partial panel's are signed zeros the FMAs see)
+#pragma unroll
+          for (int b = 0; b < BS; ++b) W[lane * ldw + j0 + b] = nl[b];
+        }
         if (rec_L) {  // (Lhat itself: gj_replay negates)
 #pragma unroll
           for (int b = 0; b < BS; ++b) rec_L[((size_t)kb * NP + lane) * BS + b] = -nl[b];
@@ -801,6 +809,10 @@ __device__ __forceinline__ void gauss_jordan_blocked_impl(double* W, int ldw, in
       for (int b = 0; b < BS; ++b) nl[i][b] = Lbuf[(lr * BS + i) * BS + b];
     for (int g = 0; g < (RHS_REG ? 1 : ngroups); ++g) {
       // block columns at or left of the panel inside the matrix part are dead (never read again)
+      // (round 17) REC_W RESTS ON THIS: the record of panel kb sits in block column kb of group 0, and the pivot-row copies above
+      // carry it into Ybuf -- columns < (kb + 1) BS of Ybuf and of W's group 0 must stay unread by every update from here to the
+      // end of the elimination, and whatever follows the elimination overwrites group 0 entirely before reading it (crc_iterate).
+      // A change that reads those columns breaks the bit-identity of gj_replay<BS, true> without any test of the plain path failing.
       if (g == 0 && lc <= kb) continue;
       const int c0 = g * NP + lc * BS;
       double wb[BS][BS], yb[BS][BS];
@@ -862,11 +874,12 @@ __device__ __forceinline__ void gauss_jordan_blocked(double* W, int ldw, int n, 
 // there is no row swap).  Ybuf as for two groups.  Every FMA of the LDS form with its operands and its order: bit-identical.
 // What it saves is LDS traffic: per panel the block of group 1 is neither loaded nor stored (BS rows each way), and only the
 // BS pivot rows go through Ybuf, one exec-masked row store each.
-template <int BS>
+// (round 17) REC_W: the elimination's multipliers stay behind in column group 0 of W (gauss_jordan_blocked_impl).
+template <int BS, bool REC_W = false>
 __device__ __forceinline__ void gauss_jordan_blocked_rhs(double* W, int ldw, int n, double (&Rg)[BS][BS], double* Lbuf,
                                                          double* Ybuf, int* prow, int lane, long long* ph, double& inv_min,
                                                          double& inv_max) {
-  gauss_jordan_blocked_impl<BS, true>(W, ldw, n, 2, Lbuf, Ybuf, prow, lane, ph, inv_min, inv_max, nullptr, Rg);
+  gauss_jordan_blocked_impl<BS, true, REC_W>(W, ldw, n, 2, Lbuf, Ybuf, prow, lane, ph, inv_min, inv_max, nullptr, Rg);
 }
 
 // The elimination recorded by gauss_jordan_blocked (rec_L, prow) applied to ONE more right-hand-side column group Wg (NP columns,
@@ -874,7 +887,10 @@ __device__ __forceinline__ void gauss_jordan_blocked_rhs(double* W, int ldw, int
 // by operation (same multipliers, same pivot rows, same order of the FMAs): the result is bit-identical to eliminating
 // [A | Wg] again, at the cost of the rank-BS updates alone -- no pivot search, no panel, nothing on the matrix part.
 // Ybuf2: BS x NP doubles of scratch.  Syncs on entry and exit.
-template <int BS>
+// IN_W (round 17): the record is the one gauss_jordan_blocked_rhs<BS, true> leaves in W -- rec_L = W, row stride ldw, panel kb in
+// columns kb BS ..., holding -Lhat: the factor the trailing update multiplies by, so nothing is negated here (the same FMA,
+// operand for operand).  Rows >= n of it were not written: they are the -0.0 rows of Lbuf.
+template <int BS, bool IN_W = false>
 __device__ __forceinline__ void gj_replay(double* Wg, int ldw, int n, const double* rec_L, const int* prow, double* Ybuf2,
                                           int lane) {
   constexpr int NP = 8 * BS;
@@ -893,7 +909,12 @@ __device__ __forceinline__ void gj_replay(double* Wg, int ldw, int n, const doub
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll
-      for (int b = 0; b < BS; ++b) lh[i][b] = rec_L[((size_t)kb * NP + lr * BS + i) * BS + b];
+      for (int b = 0; b < BS; ++b) {
+        if constexpr (IN_W)
+          lh[i][b] = (lr * BS + i < n) ? rec_L[(lr * BS + i) * ldw + j0 + b] : -0.0;
+        else
+          lh[i][b] = rec_L[((size_t)kb * NP + lr * BS + i) * BS + b];
+      }
     const int c0 = lc * BS;
 #pragma unroll
     for (int i = 0; i < BS; ++i)
@@ -908,7 +929,7 @@ __device__ __forceinline__ void gj_replay(double* Wg, int ldw, int n, const doub
 #pragma unroll
       for (int i = 0; i < BS; ++i)
 #pragma unroll
-        for (int j = 0; j < BS; ++j) wb[i][j] = fma(-lh[i][b], yb[b][j], wb[i][j]);
+        for (int j = 0; j < BS; ++j) wb[i][j] = fma(IN_W ? lh[i][b] : -lh[i][b], yb[b][j], wb[i][j]);
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll

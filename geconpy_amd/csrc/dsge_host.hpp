@@ -474,6 +474,7 @@ extern long long* g_condfc_dbg;        // launch_condfc.hip: debug phase counter
 extern long long* g_cr_dbg;            // launch_solvers.hip: debug phase counters of the compact CR kernel
 extern long long* g_cr_fused_dbg;      // launch_solvers.hip: debug phase counters of the fused CR kernel (stamped instance)
 extern int g_cr_static_rows_mode;      // launch_solvers.hip: 0 = static rows skipped where nobody reads them, 1 = never, 2 = also into T_out / R_out (debug)
+extern int g_cr_refine_mode;           // launch_solvers.hip: 0 = the refinement rule, 1 = never refine on cr_fused_kernel_occ2<5, 4> (debug, changes results)
 extern long long* g_big_dbg;         // launch_big.hip: debug phase cycles of cr_big_kernel
 extern long long* g_kalman_dbg;       // launch_kalman.hip: debug buffer for per-phase cycles of draw 0
 extern long long* g_gensys_win_dbg;   // launch_gensys.hip: debug phase stamps of the window kernels (device int64[32])

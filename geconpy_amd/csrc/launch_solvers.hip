@@ -12,7 +12,8 @@
 namespace dsge_host {
 
 long long* g_cr_dbg = nullptr;  // debug: device int64[8], phase cycles of draw 0 of the compact kernel
-long long* g_cr_fused_dbg = nullptr;  // debug: device int64[16], phase cycles of draw 0 of cr_fused_kernel_occ2_dbg<5, 4>
+long long* g_cr_fused_dbg = nullptr;  // debug: device int64[24], phase cycles of draw 0 of cr_fused_kernel_occ2_dbg<5, 4> and the batch's refinements
+int g_cr_refine_mode = 0;             // debug: dsge_debug_cr_refine
 int g_cr_static_rows_mode = 0;        // debug: dsge_debug_cr_static_rows
 
 int launch_cr(const double* A, const double* B, const double* C, int batch, int n, int max_iter, double tol,
@@ -91,6 +92,13 @@ int launch_cr_fused_inst(const double* A, const double* B, const double* C, cons
           if ((rc = set_lds(dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>, SM::bytes))) return rc;
           hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2_dbg<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch, n,
                              k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, Z, z_batched, p, g_cr_fused_dbg);
+          HIP_TRY(hipGetLastError());
+          return DSGE_SUCCESS;
+        }
+        if (g_cr_refine_mode == 1) {  // the measuring instance without the refinement branch
+          if ((rc = set_lds(dsge::cr_fused_kernel_occ2_norefine<BSF, BSD>, SM::bytes))) return rc;
+          hipLaunchKernelGGL((dsge::cr_fused_kernel_occ2_norefine<BSF, BSD>), dim3(batch), dim3(64), SM::bytes, st, A, B, C, D, batch,
+                             n, k, h, max_iter, tol, top, rhs, T_out, R_out, status, n_iter, colmask, Z, z_batched, p);
           HIP_TRY(hipGetLastError());
           return DSGE_SUCCESS;
         }

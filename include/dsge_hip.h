@@ -384,8 +384,11 @@ int dsge_debug_cr_phases(int enable, long long* cycles_out);
  * [0..4] as above per iteration phase, [5] the final solve, [6] total, [7] = iterations, [8] phase-1 loads and scans,
  * [9] the Householder reflectors, [10] deposit of the reduced system, [11] phase 3 (static rows and scatter),
  * [12] the static mask alone (part of [8]), and of [11]: [13] the gather of the solution, [14] the preparation and
- * [15] the back-substitution of the static rows up to its scatter;
- * cycles_out (host int64[16], may be NULL).  Results are those of the default instance. */
+ * [15] the back-substitution of the static rows up to its scatter.  The refinement branch of the iteration, summed over EVERY
+ * draw of the launches since enable (atomic adds): [16] draws that refined, [17] refinements, [18] cycles of their residuals,
+ * [19] of their second eliminations, [20] of the whole branch (the rest: stores and reordering), [21], [22], [23] draws that
+ * refined in one, two, three or more iterations;
+ * cycles_out (host int64[24], may be NULL).  Results are those of the default instance. */
 int dsge_debug_cr_fused_phases(int enable, long long* cycles_out);
 
 /*
@@ -573,6 +576,14 @@ int dsge_debug_adjoint_refine(int mode);
  * per draw on the device).  Debug hook for the tests: mode 0 = that rule (default), 1 = always compute the static rows, 2 = apply
  * the rule also when the caller receives T_out / R_out (their static rows are then zeros where it fired).  Process-wide. */
 int dsge_debug_cr_static_rows(int mode);
+/* Cycle reduction refines the solve of an iteration whose pivots span more than the tile's ratio (one step of iterative
+ * refinement, csrc/dsge_cr_compact.hpp).  Measuring switch for what that costs on the bench's one-launch instance (33 .. 40
+ * variables, reduced tile of 32, two waves per SIMD): mode 0 = that rule (default), 1 = never refine -- an instance of its own
+ * without the branch; every other instance keeps the rule.  That instance is the default one's body otherwise: its eliminations
+ * still keep the record the replay needs, so mode 0 against mode 1 is "what refining costs on this build", not the build without
+ * the record -- profiles/r17/refine_cost.txt was taken before the record existed and is not comparable.  Mode 1 CHANGES RESULTS: nothing but tools/cr_refine_cost.py uses
+ * it.  The stamped instance (dsge_debug_cr_fused_phases) takes precedence over it.  Process-wide. */
+int dsge_debug_cr_refine(int mode);
 
 /*
  * Pullback of the shock-impact matrix.  The reference's R = -solve(C @ T + B, D) is plain differentiable pytensor
