@@ -419,6 +419,126 @@ def forecast(b, name, T, R, Q, a0, *, P0, n_steps, Z, d, Hdiag, q_mode, covarian
     return res
 
 
+SEGMENT_OUTPUTS = ("logp", "ll", "a_last", "P_last")
+
+
+def segment_starts(seg_start, T_len):
+    """The dated breaks as the library takes them -- a HOST int32 list with seg_start[0] == 0, strictly increasing, every entry
+    < T_len (when T_len > 0), 1 .. ``_lib.MAX_SEGMENTS`` entries -- checked as ``check_kalman_segments`` (csrc/dsge_host.hpp) checks."""
+    if seg_start is None:
+        raise ValueError("seg_start is required")
+    raw = np.asarray(seg_start)
+    if raw.ndim != 1 or (raw.size and raw.dtype.kind not in "iu"):
+        raise ValueError("seg_start must be a 1-d list of integers")
+    seg = np.ascontiguousarray(raw, dtype=np.int32)
+    if not 1 <= seg.size <= _lib.MAX_SEGMENTS:
+        raise ValueError(f"seg_start has {seg.size} entries; 1 .. {_lib.MAX_SEGMENTS} segments")
+    if seg[0] != 0:
+        raise ValueError("seg_start[0] must be 0")
+    if np.any(np.diff(seg) <= 0):
+        raise ValueError("seg_start must be strictly increasing")
+    if T_len > 0 and seg[-1] >= T_len:
+        raise ValueError(f"seg_start: every entry must be < T_len = {T_len}")
+    return seg
+
+
+def segment_q_layout(shape, q_mode, nb, S, k):
+    """``q_layout`` with a segment axis behind the draw axis: (S, k), (batch, S, k), (S, k, k) or (batch, S, k, k)."""
+    shape = tuple(shape)
+    want = {_lib.Q_DIAG_SHARED: (S, k), _lib.Q_DIAG_BATCHED: (nb, S, k), _lib.Q_FULL_SHARED: (S, k, k), _lib.Q_FULL_BATCHED: (nb, S, k, k)}
+    if q_mode is None:
+        codes = [code for code, w in want.items() if w == shape]
+        if len(codes) != 1:
+            raise ValueError(f"cannot infer the layout of Q with shape {shape} (batch={nb}, segments={S}, k={k}); pass q_mode")
+        return codes[0]
+    code = Q_MODES[q_mode] if isinstance(q_mode, str) else int(q_mode)
+    if shape != want[code]:
+        raise ValueError(f"Q has shape {shape}, q_mode needs {want[code]}")
+    return code
+
+
+def kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0, shift, q_mode, status, jitter, missing_fill, options,
+                         outputs=SEGMENT_OUTPUTS, out=None):
+    """``dsge_kalman_logp_segments_batched``: T (batch, S, m, m), R (batch, S, m, k), every other per-segment array with the segment
+    axis behind the draw axis.  ``outputs``: which of ``SEGMENT_OUTPUTS`` are computed (logp always is); ``out``: buffers to reuse."""
+    T, R = b.inp(T), b.inp(R)
+    if T is None or R is None or Q is None or Z is None or y is None:
+        raise ValueError(f"{name}: T, R, Q, Z and y are required")
+    T, R, y = _nd(T, 4), _nd(R, 4), _nd(b.inp(y), 2)
+    nb, S, m, m2 = T.shape
+    k = R.shape[3]
+    if m != m2 or m < 1 or tuple(R.shape[:3]) != (nb, S, m) or k < 1:
+        raise ValueError(f"T must be (batch, S, m, m) and R (batch, S, m, k); got {tuple(T.shape)}, {tuple(R.shape)}")
+    T_len, p = y.shape
+    seg = segment_starts(seg_start, T_len)
+    if seg.size != S:
+        raise ValueError(f"seg_start has {seg.size} entries, T has {S} segments")
+    Q = b.inp(Q)
+    code = segment_q_layout(Q.shape, q_mode, nb, S, k)
+    Z, d, Hdiag = b.inp(Z), b.inp(d), b.inp(Hdiag)
+    zb = shared_or_batched(Z, nb, (S, p, m), "Z", "(S, p, m) or (batch, S, p, m)")
+    db, hb = (0 if x is None else shared_or_batched(x, nb, (S, p), nm, "(S, p) or (batch, S, p)") for x, nm in ((d, "d"), (Hdiag, "Hdiag")))
+    a0 = None if a0 is None else _is(b.inp(a0), (nb, m), "a0")
+    P0 = None if P0 is None else _is(b.inp(P0), (nb, m, m), "P0")
+    shift = None if shift is None else _is(b.inp(shift), (nb, S, m), "shift", "(batch, S, m)")
+    outputs = tuple(outputs)
+    if not set(outputs) <= set(SEGMENT_OUTPUTS):
+        raise ValueError(f"outputs must be among {SEGMENT_OUTPUTS}; got {outputs}")
+    st = check_status(b.status_io(status, nb), nb)
+    out = out or {}
+    res = dict(logp=_out(b, out.get("logp"), (nb,)), status=st)
+    for key, shape in (("ll", (nb, T_len)), ("a_last", (nb, m)), ("P_last", (nb, m, m))):
+        res[key] = _out(b, out.get(key), shape) if key in outputs or out.get(key) is not None else None
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        call(b, "dsge_kalman_logp_segments_batched", T=T, R=R, Q=Q, q_mode=code, Z=Z, z_batched=zb, d=d, d_batched=db, Hdiag=Hdiag,
+             h_batched=hb, a0=a0, P0=P0, shift=shift, y=y, seg_start=seg.ctypes.data, n_seg=S, batch=nb, m=m, k=k, p=p, T_len=T_len,
+             jitter=jitter, missing_fill=missing_fill, logp_out=res["logp"], ll_out=res["ll"], a_last_out=res["a_last"],
+             P_last_out=res["P_last"], status_io=st)
+    return res
+
+
+def solve_kalman_logp_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, solver, tol, max_iter, n_lead_hint, options, **filter_kw):
+    """A .. D (batch, S, n, n | k): every (draw, segment) solved by the EXISTING solver entry on the flattened batch, the segments'
+    status words ORed per draw (array operations of the backend: no host round trip on the device), then the filter above.  Returns
+    its dict plus T (batch, S, n, n) and R (batch, S, n, k); a draw whose solve fails in any segment gets -inf and the OR of the bits."""
+    A, B, C, D = (b.inp(x) for x in (A, B, C, D))
+    if any(x is None for x in (A, B, C, D, Q, Z, y)):
+        raise ValueError(f"{name}: A, B, C, D, Q, Z and y are required")
+    A, D = _nd(A, 4), _nd(D, 4)
+    nb, S, n, n2 = A.shape
+    k = D.shape[3]
+    if n != n2 or tuple(B.shape) != tuple(A.shape) or tuple(C.shape) != tuple(A.shape) or tuple(D.shape[:3]) != (nb, S, n) or k < 1:
+        raise ValueError(f"A, B, C must be (batch, S, n, n) and D (batch, S, n, k); got {tuple(A.shape)}, {tuple(B.shape)}, "
+                         f"{tuple(C.shape)}, {tuple(D.shape)}")
+    if solver not in ("cycle_reduction", "gensys", "backward_direct"):
+        raise ValueError(f"solver must be cycle_reduction, gensys or backward_direct; got {solver!r}")
+    segment_starts(seg_start, _nd(b.inp(y), 2).shape[0])  # (refused before the solver runs)
+    flat = nb * S
+    Af, Bf, Cf, Df = A.reshape(flat, n, n), B.reshape(flat, n, n), C.reshape(flat, n, n), D.reshape(flat, n, k)
+    T, R, st = b.empty((flat, n, n)), b.empty((flat, n, k)), b.empty((flat,), "int32")
+    with _lib.options_scope(options):
+        if solver == "cycle_reduction":
+            call(b, "dsge_cycle_reduction_batched", A=Af, B=Bf, C=Cf, batch=flat, n=n, max_iter=max_iter, tol=tol, T_out=T, status=st,
+                 n_iter=None)
+            call(b, "dsge_selection_batched", A=None, B=Bf, C=Cf, D=Df, T=T, batch=flat, n=n, k=k, R_out=R, resid_out=None)
+        elif solver == "gensys":
+            eu = b.empty((flat, 3), "int32")
+            call(b, "dsge_gensys_batched", A=Af, B=Bf, C=Cf, D=Df, batch=flat, n=n, k=k, tol=tol, n_lead_hint=n_lead_hint, T_out=T,
+                 R_out=R, eu_out=eu, status=st)
+        else:
+            call(b, "dsge_backward_direct_batched", A=Af, B=Bf, D=Df, batch=flat, n=n, k=k, T_out=T, R_out=R)
+            st = st * 0  # (this solver reports nothing)
+    st2 = st.reshape(nb, S)
+    acc = st2[:, 0] * 1
+    for s in range(1, S):
+        acc = acc | st2[:, s]
+    acc = b.inp(acc if b.host else acc.contiguous(), "int32")
+    T, R = T.reshape(nb, S, n, n), R.reshape(nb, S, n, k)
+    res = kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, status=acc, options=options, **filter_kw)
+    res.update(T=T, R=R)
+    return res
+
+
 def shock_groups(groups, k):
     """``groups`` (None, or a sequence of sequences of shock indices that partitions 0 .. k-1) -> (group_of_shock int32 (k,), g)."""
     if groups is None:

@@ -19,6 +19,7 @@ MAX_N_CR = 64
 MAX_N_GENSYS = 64
 MAX_N_BIG = 96  # cycle reduction, selection and the fused solve + Kalman logp with a cycle-reduction solver (csrc/dsge_big.hpp)
 MAX_P = 16
+MAX_SEGMENTS = 8  # DSGE_MAX_SEGMENTS: segments of dsge_kalman_logp_segments_batched
 
 ST_OK = 0
 ST_NOT_CONVERGED = 1
@@ -83,7 +84,7 @@ class GensysForward(C.Structure):
 # host or device address) otherwise; a leading "*" marks the two names that are a pointer here and an int elsewhere.
 _INTS = ("N T_len batch bound_batched c c_batched correlation cv_batched cv_paths d_batched device enable eps_batched "
          "eta_batched full_cov h_batched horizon k lag_step m max_iter mode n n_cond n_eta n_filter_hint n_grid n_groups n_lags "
-         "n_lead n_lead_hint n_links n_out n_paths n_ret n_shock_steps n_state n_state_hint n_steps nnz p q_batched q_mode "
+         "n_lead n_lead_hint n_links n_out n_paths n_ret n_seg n_shock_steps n_state n_state_hint n_steps nnz p q_batched q_mode "
          "remainder reps s_batched shock solver w_batched x0_batched x0_paths z_batched z_selector_hint")
 _KINDS = {**dict.fromkeys(_INTS.split(), C.c_int), **dict.fromkeys("jitter missing_fill rank_tol tol".split(), C.c_double),
           "scratch_limit_bytes": C.c_size_t}
@@ -138,6 +139,8 @@ _DEVICE_ENTRIES = {
     "dsge_autocorrelation_batched": "T R Q q_mode Z Hdiag batch m k p n_lags lag_step correlation acf_out Sigma_out status stream",
     "dsge_kalman_logp_batched": f"{_FILTER} n_state_hint z_selector_hint logp_out status_io stream",
     "dsge_kalman_filter_outputs_batched": f"{_FILTER} ll_out a_pred_out a_filt_out p_pred_out p_filt_out full_cov status_io stream",
+    "dsge_kalman_logp_segments_batched": (f"T R Q q_mode {_OBS} a0 P0 shift y seg_start n_seg batch m k p T_len jitter missing_fill "
+                                          "logp_out ll_out a_last_out P_last_out status_io stream"),
     "dsge_kalman_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes ll_out a_smooth_out p_smooth_out eps_smooth_out "
                                      "full_cov status_io stream"),
     "dsge_simulation_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes x0 x0_batched eps eps_batched eta eta_batched "

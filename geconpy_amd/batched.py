@@ -442,6 +442,36 @@ def kalman_filter_outputs_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None
     return out
 
 
+def kalman_logp_segments_batched(T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None, jitter=JITTER_DEFAULT,
+                                 missing_fill_value=MISSING_FILL, options=None, outputs=F.SEGMENT_OUTPUTS, q_mode=None, status=None):
+    """Kalman log-likelihood across DATED STRUCTURAL BREAKS per draw (include/dsge_hip.h, ``dsge_kalman_logp_segments_batched``;
+    docs/design/segmented_filter.md): the system matrices are piecewise constant in time, segment s from period ``seg_start[s]``
+    on (``seg_start[0] == 0``, strictly increasing, shared by all draws, at most ``_lib.MAX_SEGMENTS`` entries).  ``T``
+    (batch, S, m, m), ``R`` (batch, S, m, k); ``q`` (S, k), (batch, S, k), (S, k, k) or (batch, S, k, k); ``Z`` (S, p, m) or
+    (batch, S, p, m); ``d``, ``Hdiag``: None, (S, p) or (batch, S, p); ``a0`` (batch, m): the predicted mean of period 0 (None: 0);
+    ``P0`` (batch, m, m): its covariance (None: the stationary covariance of segment 0); ``shift`` (batch, S, m): added to the
+    filtered mean once, at the boundary into segment s, before the product with ``T_s`` (row 0 is never read).  ``outputs``: which
+    of logp, ll, a_last, P_last are computed.  Returns dict(logp (batch,), ll (batch, T_len), a_last (batch, m), P_last
+    (batch, m, m): the FILTERED moments of the last period, what ``forecast_batched`` takes as ``a0``, ``P0``; status)."""
+    return F.kalman_logp_segments(HOST, "kalman_logp_segments_batched", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d, a0=a0, P0=P0,
+                                  shift=shift, q_mode=q_mode, status=status, jitter=jitter, missing_fill=missing_fill_value,
+                                  options=options, outputs=outputs)
+
+
+def solve_kalman_logp_segments_batched(A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                       solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                       missing_fill_value=MISSING_FILL, options=None, outputs=F.SEGMENT_OUTPUTS, q_mode=None,
+                                       n_lead_hint=0):
+    """``A .. D`` (batch, S, n, n | k) -> ``T``, ``R`` of every (draw, segment) by the solver entry ``solver`` names
+    ("cycle_reduction", "gensys", "backward_direct") on the flattened batch, then ``kalman_logp_segments_batched``.  A draw whose
+    solve fails in any segment gets ``logp = -inf`` and the OR of the segments' status bits.  Returns the filter's dict plus
+    ``T`` (batch, S, n, n) and ``R`` (batch, S, n, k)."""
+    return F.solve_kalman_logp_segments(HOST, "solve_kalman_logp_segments_batched", A, B, C, D, q, Z, y, seg_start, solver=solver,
+                                        tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options, Hdiag=Hdiag, d=d, a0=a0,
+                                        P0=P0, shift=shift, q_mode=q_mode, jitter=jitter, missing_fill=missing_fill_value,
+                                        outputs=outputs)
+
+
 def smoother_scratch_bytes_per_draw(m, T_len):
     """Bytes of library scratch the smoother's forward pass stores per draw (what ``scratch_limit_bytes`` counts):
     ``2 T_len m^2 + 2 T_len m`` doubles."""

@@ -558,6 +558,59 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
                                status_io, st);
 }
 
+// The likelihood across dated breaks (dsge_kalman_seg.hpp), a chain on the caller's stream: sym(R Q R') of every (draw, segment) by the
+// launch dsge_lyapunov_batched uses (the layouts flatten to batch * S draws; a shared Q is first repeated per draw), P0 of segment 0
+// by the Lyapunov launch on T_0 and sym(R_0 Q_0 R_0') (gathered when S > 1) unless the caller gave P0, then the filter.
+int dsge_kalman_logp_segments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                      const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                      int batch, int m, int k, int p, int T_len, double jitter, double missing_fill, double* logp_out,
+                                      double* ll_out, double* a_last_out, double* P_last_out, int32_t* status_io, void* stream) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman_segments(batch, m, k, obs, q, seg_start, n_seg, T && R && logp_out && status_io);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned flat = 0;
+  if ((rc = batch_grid(batch, n_seg, "segmented filter: batch * n_seg exceeds 2^31 - 1", &flat))) return rc;
+  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "segmented filter: LDS budget exceeded");
+  const size_t mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k;
+  const bool gather = !P0 && n_seg > 1;
+  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, flat * mm);
+  if (!q.batched()) lay.add(&Qx, flat * qw);
+  if (gather) {
+    lay.add(&T0, batch * mm);
+    lay.add(&G0, batch * mm);
+  }
+  if (!P0) lay.add(&P0s, batch * mm);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  ShockCov qe = q;
+  if (!q.batched()) {
+    if ((rc = launch_segment_rows(Qx, Q, flat, (int)qw, n_seg, 1, st))) return rc;
+    qe = ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+  }
+  // (no status here: a skipped draw's product is never read, and the words are per draw, not per (draw, segment))
+  if ((rc = assemble_rqr(R, qe, (int)flat, m, k, RQR, nullptr, st))) return rc;
+  if (!P0) {
+    const double* Ts = T;
+    double* Gs = RQR;
+    if (gather) {
+      if ((rc = launch_segment_rows(T0, T, (size_t)batch, (int)mm, batch, n_seg, st))) return rc;
+      if ((rc = launch_segment_rows(G0, RQR, (size_t)batch, (int)mm, batch, n_seg, st))) return rc;
+      Ts = T0;
+      Gs = G0;
+    }
+    if ((rc = assemble_p0_from_rqr(Ts, Gs, batch, m, P0s, status_io, false, st))) return rc;
+    P0 = P0s;
+  }
+  return launch_kalman_segments(T, RQR, P0, a0, shift, obs, seg_start, n_seg, batch, m, logp_out, ll_out, a_last_out, P_last_out,
+                                status_io, st);
+}
+
 // Smoothed states, covariances and shocks (dsge_kalman_smooth.hpp): the forward pass is launch_kalman_outputs with full
 // covariances into library scratch, one contiguous chunk of draws after the other on the caller's stream.
 int dsge_kalman_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

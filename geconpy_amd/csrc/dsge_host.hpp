@@ -282,6 +282,15 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                   int rerun_all = 0);  // 1: every launch is a second pass -- only the draws flagged DSGE_ST_INTERNAL_RERUN are filtered
 int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, double* ll,
                           double* a_pred, double* a_filt, double* p_pred, double* p_filt, int full_cov, int32_t* status, hipStream_t st);
+// launch_kalman_seg.hip (dsge_kalman_seg.hpp): the filter across dated breaks.  T, RQR: [batch][S][m][m]; of o: Z, d, Hdiag with a
+// segment axis behind the draw axis; seg_start: HOST list, already checked; a0, shift, ll, a_last, P_last may be null
+int launch_kalman_segments(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
+                           const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* logp, double* ll,
+                           double* a_last, double* P_last, int32_t* status, hipStream_t st);
+size_t kalman_segments_lds_bytes(int m, int p);
+// dst[r][0 .. width-1] = src[(r % mod) * mul][0 .. width-1], r = 0 .. rows-1: a shared [S][width] repeated per draw (mod = S, mul = 1),
+// segment 0 of every draw out of [batch][S][width] (mod = rows, mul = S)
+int launch_segment_rows(double* dst, const double* src, size_t rows, int width, int mod, int mul, hipStream_t st);
 // launch_smooth.hip (dsge_kalman_smooth.hpp): basis of range(P_pred) per draw (U, UT, UR: [batch] images of smoother_image_doubles(m)
 // doubles, rank: [batch]) and the backward pass over the stored outputs of launch_kalman_outputs (full covariances)
 size_t smoother_image_doubles(int m);
@@ -567,6 +576,21 @@ inline int check_smoother(int batch, int m, int k, const ObsModel& o, const Shoc
   int rc = check_kalman(batch, m, k, o, q, others);
   if (rc) return rc;
   return any_output ? DSGE_SUCCESS : fail(DSGE_ERR_INVALID, "no smoothed output requested");
+}
+// the likelihood across dated breaks: the sizes first (DSGE_ERR_TOO_LARGE), then the filter's own checks, then the HOST list of
+// segment starts -- n_seg in 1 .. DSGE_MAX_SEGMENTS, seg_start[0] == 0, strictly increasing, every entry < T_len (when T_len > 0)
+inline int check_kalman_segments(int batch, int m, int k, const ObsModel& o, const ShockCov& q, const int32_t* seg_start, int n_seg,
+                                 bool others) {
+  if (m > DSGE_MAX_N || o.p > DSGE_MAX_P)
+    return fail(DSGE_ERR_TOO_LARGE, "segmented filter: m exceeds DSGE_MAX_N or p exceeds DSGE_MAX_P");
+  int rc = check_kalman(batch, m, k, o, q, others && seg_start);
+  if (rc) return rc;
+  if (n_seg < 1 || n_seg > DSGE_MAX_SEGMENTS) return fail(DSGE_ERR_INVALID, "n_seg out of range (1..DSGE_MAX_SEGMENTS)");
+  if (seg_start[0] != 0) return fail(DSGE_ERR_INVALID, "seg_start[0] must be 0");
+  for (int s = 1; s < n_seg; ++s)
+    if (seg_start[s] <= seg_start[s - 1]) return fail(DSGE_ERR_INVALID, "seg_start must be strictly increasing");
+  if (o.T_len > 0 && seg_start[n_seg - 1] >= o.T_len) return fail(DSGE_ERR_INVALID, "seg_start: every entry must be < T_len");
+  return DSGE_SUCCESS;
 }
 inline int check_simulation_smoother(int batch, int m, int k, const ObsModel& o, const ShockCov& q, bool others, int n_paths,
                                      const double* eps, const double* eta, bool any_output) {

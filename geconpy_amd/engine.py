@@ -237,6 +237,29 @@ class LogpEngine:
                                  jitter=jitter, missing_fill=missing_fill_value, cov=covariances, full=full_covariances,
                                  rank_tol=rank_tol, scratch_limit_bytes=scratch_limit_bytes, options=options)
 
+    def kalman_logp_segments(self, T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                             jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, options=None, outputs=F.SEGMENT_OUTPUTS,
+                             q_mode=None, status=None, out=None):
+        """Kalman log-likelihood across dated structural breaks of the whole batch (``dsge_kalman_logp_segments_batched``; see
+        ``batched.kalman_logp_segments_batched``) from device tensors, on torch's current stream.  ``seg_start`` is a HOST list
+        (passed to the kernel by value: the call is a pure enqueue).  ``out``: optional dict with preallocated ``logp`` / ``ll`` /
+        ``a_last`` / ``P_last``.  Returns dict(logp, ll, a_last, P_last, status) of device tensors; asynchronous."""
+        return F.kalman_logp_segments(self.backend, "kalman_logp_segments", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d, a0=a0, P0=P0,
+                                      shift=shift, q_mode=q_mode, status=status, jitter=jitter, missing_fill=missing_fill_value,
+                                      options=options, outputs=outputs, out=out)
+
+    def solve_kalman_logp_segments(self, A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                   solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                   missing_fill_value=MISSING_FILL, options=None, outputs=F.SEGMENT_OUTPUTS, q_mode=None,
+                                   n_lead_hint=0, out=None):
+        """``A .. D`` [batch][S][n][n|k] -> T, R per (draw, segment) by the existing solver entries on the flattened batch, the
+        segments' status words ORed per draw with tensor operations, then ``kalman_logp_segments``
+        (``batched.solve_kalman_logp_segments_batched``).  Returns its dict plus ``T`` and ``R``; asynchronous."""
+        return F.solve_kalman_logp_segments(self.backend, "solve_kalman_logp_segments", A, B, C, D, q, Z, y, seg_start, solver=solver,
+                                            tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options, Hdiag=Hdiag, d=d,
+                                            a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter, missing_fill=missing_fill_value,
+                                            outputs=outputs, out=out)
+
     def stationary_factor(self, T, R, Q, q_mode=None):
         """F [batch][m][m] with F F' = P0 per draw (``batched.stationary_factor``) from device tensors: ``dsge_lyapunov_batched``
         and a batched ``torch.linalg.eigh``, on torch's current stream."""

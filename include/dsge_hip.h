@@ -56,6 +56,9 @@ extern "C" {
 /* ABI 18: dsge_constrained_paths_batched (+ _host) and the status bit DSGE_ST_CONSTRAINT_UNRESOLVED are new (new entry and status
  * bit, nothing else changed). */
 /* ABI 19: dsge_constrained_simulate_batched (+ _host) and the path bit DSGE_OBC_HORIZON_SHORT are new; nothing else changed. */
+/* Still ABI 19: dsge_kalman_logp_segments_batched (+ _host) and DSGE_MAX_SEGMENTS were added WITHOUT a new version number -- two new
+ * symbols and one constant, nothing else changed; a caller built against the earlier ABI 19 header runs unchanged (backward
+ * compatible), a caller of the new entry must load a library that exports it. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -67,6 +70,7 @@ extern "C" {
                                   variables, of which there may be at most 64 (else DSGE_ERR_TOO_LARGE); every other entry point
                                   keeps the limits above */
 #define DSGE_MAX_P 16      /* observed series */
+#define DSGE_MAX_SEGMENTS 8 /* dsge_kalman_logp_segments_batched: segments of piecewise constant system matrices */
 #define DSGE_SPECTRAL_MAX_K 32     /* dsge_spectral_moments_batched: shocks */
 #define DSGE_SPECTRAL_MAX_P 64     /* dsge_spectral_moments_batched: rows of Z */
 #define DSGE_SPECTRAL_MAX_GRID 4096 /* dsge_spectral_moments_batched: grid points N */
@@ -713,6 +717,48 @@ int dsge_kalman_filter_outputs_batched_host(const double* T, const double* R, co
                                             const double* y, int batch, int m, int k, int p, int T_len, double jitter,
                                             double missing_fill, double* ll_out, double* a_pred_out, double* a_filt_out,
                                             double* p_pred_out, double* p_filt_out, int full_cov, int32_t* status_io);
+
+/*
+ * Kalman log-likelihood ACROSS DATED STRUCTURAL BREAKS per draw (csrc/dsge_kalman_seg.hpp, docs/design/segmented_filter.md): the
+ * system matrices are piecewise constant in time, with the switches at dates the caller knows -- a variance break, a change of the
+ * policy rule or of the steady state, a pegged rate over a known spell, a few periods of scaled shock variances.  S = n_seg segments,
+ * 1 <= S <= DSGE_MAX_SEGMENTS; seg_start [S] (int32) with seg_start[0] == 0, strictly increasing, every entry < T_len, shared by all
+ * draws and HOST memory in the device entry too (passed to the kernel by value: the call stays a pure enqueue).  Period t belongs
+ * to segment s(t) = max{s : seg_start[s] <= t}; the matrices of segment s drive the transition INTO every period of s and the
+ * observation OF every period of s:
+ *     a_{0|-1} = a0 (NULL: 0)      P_{0|-1} = P0 (NULL: the stationary covariance of segment 0, dlyap(T_0, R_0 Q_0 R_0'))
+ *     period t, s = s(t): the measurement update of dsge_kalman_filter_outputs_batched with Z_s, d_s, H_s under the filter
+ *                         conventions of the call (dsge_options_push / dsge_options_pop; missing entries as there)
+ *     s' = s(t+1):        a_{t+1|t} = T_s' (a_{t|t} + [t+1 == seg_start[s']] shift_s')
+ *                         P_{t+1|t} = sym(T_s' P_{t|t} T_s'') + sym(R_s' Q_s' R_s'')
+ *     logp = sum_t ll_t
+ * shift re-expresses the state when the point it is measured from moves (a new steady state); it is added once, at the boundary,
+ * and row 0 is never read.  Nothing beyond segment 0 has to be stationary (and not segment 0 when P0 is given).  With S = 1 and
+ * a0 = P0 = shift = NULL this is the recursion of dsge_kalman_filter_outputs_batched.
+ *   T [batch][S][m][m], R [batch][S][m][k];  Q by q_mode with a segment axis behind the draw axis: [S][k], [batch][S][k], [S][k][k],
+ *   [batch][S][k][k];  Z [S][p][m] or [batch][S][p][m];  d, Hdiag: NULL, [S][p] or [batch][S][p];  a0 [batch][m], P0 [batch][m][m],
+ *   shift [batch][S][m]: each may be NULL;  y [T_len][p]
+ *   logp_out [batch] (required);  ll_out [batch][T_len], a_last_out [batch][m], P_last_out [batch][m][m]: may be NULL.  a_last_out
+ *   and P_last_out are the FILTERED moments of the last period, a_{n-1|n-1} and P_{n-1|n-1}: what dsge_forecast_batched takes as a0, P0
+ *   status_io [batch] in/out: a draw with a non-zero incoming status is skipped -- logp = -inf, every other requested output NaN; a
+ *   Lyapunov failure on segment 0 sets DSGE_ST_LYAP_FAIL (logp = -inf), a filter that goes non-finite DSGE_ST_FILTER_NONFINITE;
+ *   every other draw is untouched, bit for bit
+ * m <= DSGE_MAX_N and p <= DSGE_MAX_P, else DSGE_ERR_TOO_LARGE.  DSGE_ERR_INVALID before any device is touched: n_seg outside
+ * 1 .. DSGE_MAX_SEGMENTS, seg_start[0] != 0, seg_start not strictly increasing, an entry >= T_len (when T_len > 0), a required
+ * pointer NULL.  batch == 0 or T_len == 0: success, nothing touched.  No host synchronisation and no atomics: two calls give the same
+ * bits, any subset of the outputs gives the bits of the full call.
+ */
+int dsge_kalman_logp_segments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                      const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                      const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                      int batch, int m, int k, int p, int T_len, double jitter, double missing_fill, double* logp_out,
+                                      double* ll_out, double* a_last_out, double* P_last_out, int32_t* status_io, void* stream);
+int dsge_kalman_logp_segments_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                           int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                           const double* a0, const double* P0, const double* shift, const double* y,
+                                           const int32_t* seg_start, int n_seg, int batch, int m, int k, int p, int T_len,
+                                           double jitter, double missing_fill, double* logp_out, double* ll_out, double* a_last_out,
+                                           double* P_last_out, int32_t* status_io);
 
 /*
  * Fixed-interval (Rauch-Tung-Striebel) SMOOTHER over the stored outputs of the filter above, batched over draws: the smoothed

@@ -8,6 +8,7 @@
     python tools/dynamics_time.py --anticipated [draws ...]       the anticipated-shock rows alone
     python tools/dynamics_time.py --constrained [draws ...]       the occasionally-binding-bound rows alone
     python tools/dynamics_time.py --stochastic-bound [draws ...]  the rows of the stochastic simulation at the bound alone
+    python tools/dynamics_time.py --segmented [draws ...]         the rows of the Kalman likelihood across dated breaks alone
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -49,6 +50,10 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     on eps + nu e_s) around a torch loop of batched torch.linalg.solve on the identity-padded systems with the same updates of S,
     one host round trip per iteration -- with the agreement of the two routes, the parts of the entry timed apart through its own
     subsets of outputs and the anticipated-shock entry, and the mean and largest iters.
+  * --segmented (csrc/dsge_kalman_seg.hpp), m = 40, k = 7, T_len = 200, p and Z of bench.py's workload: the median of five timings
+    of >= 1 s each of LogpEngine.kalman_logp_segments with S = 1, S = 3 (breaks at 80 and 140) and S = 8, against
+    dsge_kalman_filter_outputs_batched with ll alone and, for scale, dsge_kalman_logp_batched with kalman_steady_tol = 0 and at its
+    default.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -589,9 +594,70 @@ def stochastic_bound_rows(eng, sizes, n_steps=N_STEPS, n_paths=16, horizon=32, s
               f"entry less that {t_entry - t_mz:8.3f} ms")
 
 
+def segmented_rows(eng, sizes, T_len=200, repeats=5):
+    """The Kalman likelihood across dated breaks (csrc/dsge_kalman_seg.hpp) on the SW-shaped batch (n = 40, T_len = 200, p and Z of
+    bench.py's workload): S = 1, S = 3 with breaks at 80 and 140, S = 8, against the full recursions a caller had before it --
+    dsge_kalman_filter_outputs_batched with ll alone, and for scale dsge_kalman_logp_batched with kalman_steady_tol = 0 and at its
+    default.  Segment s of draw b is draw (b + s) mod 64 of the generator."""
+    lib = _lib.load()
+    b = wl.sw_shaped_batch(64)
+    om = wl.sw_shaped_observation_model()
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p = 40, 7, om["y"].shape[1]
+    y, H1, Z1 = eng.to_device(om["y"][:T_len]), om["Hdiag"], om["Z"]
+    breaks = {1: (0,), 3: (0, 80, 140), 8: tuple(range(0, T_len, T_len // 8))[:8]}
+    ns, zs = int(np.count_nonzero(np.any(b["T_star"] != 0, axis=(0, 1)))), 1
+    print(f"segmented filter, SW shape m={m} k={k} p={p}, T_len={T_len}; median of {repeats} timings of >= 1 s each")
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    for nb in sizes:
+        idx = np.arange(nb) % 64
+        T, R, q = eng.to_device(b["T_star"][idx]), eng.to_device(R64[idx]), eng.to_device(b["sigma"][idx] ** 2)
+        Z, H = eng.to_device(Z1), eng.to_device(H1)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        ll, logp = mk(nb, T_len), mk(nb)
+        st = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+
+        def filter_outputs():
+            _lib.check(lib.dsge_kalman_filter_outputs_batched(
+                T.data_ptr(), R.data_ptr(), q.data_ptr(), 1, Z.data_ptr(), 0, None, 0, H.data_ptr(), 0, y.data_ptr(), nb, m, k, p,
+                T_len, 1e-8, -9999.0, ll.data_ptr(), None, None, None, None, 0, st.data_ptr(), eng._stream()))
+
+        def fast(options):
+            with _lib.options_scope(options):
+                _lib.check(lib.dsge_kalman_logp_batched(
+                    T.data_ptr(), R.data_ptr(), q.data_ptr(), 1, Z.data_ptr(), 0, None, 0, H.data_ptr(), 0, y.data_ptr(), nb, m, k, p,
+                    T_len, 1e-8, -9999.0, ns, zs, logp.data_ptr(), st.data_ptr(), eng._stream()))
+
+        t_ko = med(filter_outputs)
+        ll_ko = ll.clone()
+        no_steady = _lib.make_options(kalman_steady_tol=0.0)
+        t_full, t_fast = med(lambda: fast(no_steady)), med(lambda: fast(None))
+        assert int(st.abs().max().item()) == 0
+        print(f"draws={nb:5d} filter outputs, ll alone: {t_ko:9.3f} ms | kalman_logp, no steady state: {t_full:8.3f} ms | "
+              f"kalman_logp, default: {t_fast:8.3f} ms")
+        t_one = None
+        for S, starts in breaks.items():
+            pick = (np.arange(nb)[:, None] + np.arange(S)[None, :]) % 64
+            Ts, Rs, qs = eng.to_device(b["T_star"][pick]), eng.to_device(R64[pick]), eng.to_device(b["sigma"][pick] ** 2)
+            Zs, Hs = eng.to_device(np.tile(Z1, (S, 1, 1))), eng.to_device(np.tile(H1, (S, 1)))
+            out = dict(logp=logp)
+            call = lambda outputs, out: eng.kalman_logp_segments(Ts, Rs, qs, Zs, y, starts, Hdiag=Hs, q_mode="diag_batched",  # noqa: E731
+                                                                  outputs=outputs, out=out, status=st)
+            t_lp = med(lambda: call(("logp",), out))
+            t_ll = med(lambda: call(("logp", "ll"), dict(logp=logp, ll=ll)))
+            assert int(st.abs().max().item()) == 0
+            if S == 1:
+                t_one = t_lp
+                agree = float((ll - ll_ko).abs().max() / ll_ko.abs().max())
+                print(f"draws={nb:5d} S=1 against the filter outputs, largest |ll difference| / max |ll|: {agree:.2e}")
+            print(f"draws={nb:5d} segments S={S} breaks {starts if S < 8 else 'every ' + str(T_len // 8)}: logp alone {t_lp:9.3f} ms, "
+                  f"with ll {t_ll:9.3f} ms | / S=1: {t_lp / t_one:5.3f} | / filter outputs: {t_lp / t_ko:5.3f} | "
+                  f"/ kalman_logp no steady: {t_lp / t_full:6.2f} | / default: {t_lp / t_fast:6.2f}")
+
+
 def main():
     args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated",
-                                                 "--constrained", "--stochastic-bound")]
+                                                 "--constrained", "--stochastic-bound", "--segmented")]
     sizes = [int(a) for a in args] or [256, 4096]
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
@@ -607,6 +673,8 @@ def main():
         return constrained_rows(LogpEngine(0), sizes)
     if "--stochastic-bound" in sys.argv:
         return stochastic_bound_rows(LogpEngine(0), sizes)
+    if "--segmented" in sys.argv:
+        return segmented_rows(LogpEngine(0), sizes)
     eng = LogpEngine(0)
     lib = _lib.load()
     b = wl.sw_shaped_batch(64)
