@@ -457,10 +457,8 @@ def segment_q_layout(shape, q_mode, nb, S, k):
     return code
 
 
-def kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0, shift, q_mode, status, jitter, missing_fill, options,
-                         outputs=SEGMENT_OUTPUTS, out=None):
-    """``dsge_kalman_logp_segments_batched``: T (batch, S, m, m), R (batch, S, m, k), every other per-segment array with the segment
-    axis behind the draw axis.  ``outputs``: which of ``SEGMENT_OUTPUTS`` are computed (logp always is); ``out``: buffers to reuse."""
+def _segment_inputs(b, name, T, R, Q, Z, y, seg_start, Hdiag, d, a0, P0, shift, q_mode):
+    """The inputs the entries across dated breaks share, validated -> the named arguments they make (``T`` .. ``T_len``)."""
     T, R = b.inp(T), b.inp(R)
     if T is None or R is None or Q is None or Z is None or y is None:
         raise ValueError(f"{name}: T, R, Q, Z and y are required")
@@ -481,6 +479,17 @@ def kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0,
     a0 = None if a0 is None else _is(b.inp(a0), (nb, m), "a0")
     P0 = None if P0 is None else _is(b.inp(P0), (nb, m, m), "P0")
     shift = None if shift is None else _is(b.inp(shift), (nb, S, m), "shift", "(batch, S, m)")
+    # (``_seg``: keeps the host list alive for the call)
+    return dict(T=T, R=R, Q=Q, q_mode=code, Z=Z, z_batched=zb, d=d, d_batched=db, Hdiag=Hdiag, h_batched=hb, a0=a0, P0=P0, shift=shift,
+                y=y, seg_start=seg.ctypes.data, n_seg=S, batch=nb, m=m, k=k, p=p, T_len=T_len), seg
+
+
+def kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0, shift, q_mode, status, jitter, missing_fill, options,
+                         outputs=SEGMENT_OUTPUTS, out=None):
+    """``dsge_kalman_logp_segments_batched``: T (batch, S, m, m), R (batch, S, m, k), every other per-segment array with the segment
+    axis behind the draw axis.  ``outputs``: which of ``SEGMENT_OUTPUTS`` are computed (logp always is); ``out``: buffers to reuse."""
+    a, _seg = _segment_inputs(b, name, T, R, Q, Z, y, seg_start, Hdiag, d, a0, P0, shift, q_mode)
+    nb, m, T_len = a["batch"], a["m"], a["T_len"]
     outputs = tuple(outputs)
     if not set(outputs) <= set(SEGMENT_OUTPUTS):
         raise ValueError(f"outputs must be among {SEGMENT_OUTPUTS}; got {outputs}")
@@ -490,17 +499,58 @@ def kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0,
     for key, shape in (("ll", (nb, T_len)), ("a_last", (nb, m)), ("P_last", (nb, m, m))):
         res[key] = _out(b, out.get(key), shape) if key in outputs or out.get(key) is not None else None
     with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
-        call(b, "dsge_kalman_logp_segments_batched", T=T, R=R, Q=Q, q_mode=code, Z=Z, z_batched=zb, d=d, d_batched=db, Hdiag=Hdiag,
-             h_batched=hb, a0=a0, P0=P0, shift=shift, y=y, seg_start=seg.ctypes.data, n_seg=S, batch=nb, m=m, k=k, p=p, T_len=T_len,
-             jitter=jitter, missing_fill=missing_fill, logp_out=res["logp"], ll_out=res["ll"], a_last_out=res["a_last"],
-             P_last_out=res["P_last"], status_io=st)
+        call(b, "dsge_kalman_logp_segments_batched", **a, jitter=jitter, missing_fill=missing_fill, logp_out=res["logp"],
+             ll_out=res["ll"], a_last_out=res["a_last"], P_last_out=res["P_last"], status_io=st)
     return res
 
 
-def solve_kalman_logp_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, solver, tol, max_iter, n_lead_hint, options, **filter_kw):
+SEGMENT_SMOOTHER_OUTPUTS = ("ll", "a_pred", "a_filt", "P_pred", "P_filt", "smoothed_states", "smoothed_covs", "smoothed_shocks")
+_SEGMENT_SMOOTHER_ARGS = dict(ll="ll_out", a_pred="a_pred_out", a_filt="a_filt_out", P_pred="p_pred_out", P_filt="p_filt_out",
+                              smoothed_states="a_smooth_out", smoothed_covs="p_smooth_out", smoothed_shocks="eps_smooth_out")
+
+
+def segment_smoother_scratch_bytes_per_draw(m, T_len, n_seg):
+    """What ``scratch_limit_bytes`` counts per draw: ``2 T_len m^2 + 2 T_len m`` doubles of the stored forward pass and the
+    ``3 n_seg`` basis images (``ks_mat(m)``: 16 ceil(m / 16) rows of two doubles more)."""
+    mp = 16 * ((m + 15) // 16)
+    return 8 * (2 * T_len * m * m + 2 * T_len * m + 3 * n_seg * mp * (mp + 2))
+
+
+def kalman_smoother_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0, shift, q_mode, status, jitter, missing_fill, full,
+                             rank_tol, scratch_limit_bytes, options, outputs=SEGMENT_SMOOTHER_OUTPUTS, out=None):
+    """``dsge_kalman_smoother_segments_batched``: the inputs of ``kalman_logp_segments``.  ``outputs``: which of
+    ``SEGMENT_SMOOTHER_OUTPUTS`` are computed (at least one; without "smoothed_covs" the covariance recursion is skipped); ``full``:
+    covariances as full matrices; ``out``: buffers to reuse."""
+    a, _seg = _segment_inputs(b, name, T, R, Q, Z, y, seg_start, Hdiag, d, a0, P0, shift, q_mode)
+    nb, m, k, T_len = a["batch"], a["m"], a["k"], a["T_len"]
+    if m > _lib.MAX_N:
+        raise ValueError(f"{name}: m = {m}, the smoother takes at most {_lib.MAX_N} variables")
+    out = out or {}
+    outputs = tuple(outputs)
+    if not set(outputs) <= set(SEGMENT_SMOOTHER_OUTPUTS):
+        raise ValueError(f"outputs must be among {SEGMENT_SMOOTHER_OUTPUTS}; got {outputs}")
+    if not outputs and all(out.get(key) is None for key in SEGMENT_SMOOTHER_OUTPUTS):
+        raise ValueError(f"{name}: at least one output is required")
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    st = check_status(b.status_io(status, nb), nb)
+    cov = (nb, T_len, m, m) if full else (nb, T_len, m)
+    shapes = dict(ll=(nb, T_len), a_pred=(nb, T_len, m), a_filt=(nb, T_len, m), P_pred=cov, P_filt=cov, smoothed_states=(nb, T_len, m),
+                  smoothed_covs=cov, smoothed_shocks=(nb, T_len, k))
+    res = {key: _out(b, out.get(key), shape) if key in outputs or out.get(key) is not None else None for key, shape in shapes.items()}
+    res["status"] = st
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        call(b, "dsge_kalman_smoother_segments_batched", **a, jitter=jitter, missing_fill=missing_fill,
+             rank_tol=0.0 if rank_tol is None else rank_tol, scratch_limit_bytes=limit, full_cov=bool(full), status_io=st,
+             **{arg: res[key] for key, arg in _SEGMENT_SMOOTHER_ARGS.items()})
+    return res
+
+
+def _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options):
     """A .. D (batch, S, n, n | k): every (draw, segment) solved by the EXISTING solver entry on the flattened batch, the segments'
-    status words ORed per draw (array operations of the backend: no host round trip on the device), then the filter above.  Returns
-    its dict plus T (batch, S, n, n) and R (batch, S, n, k); a draw whose solve fails in any segment gets -inf and the OR of the bits."""
+    status words ORed per draw (array operations of the backend: no host round trip on the device).  Returns T (batch, S, n, n),
+    R (batch, S, n, k) and the status (batch,)."""
     A, B, C, D = (b.inp(x) for x in (A, B, C, D))
     if any(x is None for x in (A, B, C, D, Q, Z, y)):
         raise ValueError(f"{name}: A, B, C, D, Q, Z and y are required")
@@ -533,8 +583,23 @@ def solve_kalman_logp_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, solve
     for s in range(1, S):
         acc = acc | st2[:, s]
     acc = b.inp(acc if b.host else acc.contiguous(), "int32")
-    T, R = T.reshape(nb, S, n, n), R.reshape(nb, S, n, k)
+    return T.reshape(nb, S, n, n), R.reshape(nb, S, n, k), acc
+
+
+def solve_kalman_logp_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, solver, tol, max_iter, n_lead_hint, options, **filter_kw):
+    """``_solve_segments``, then the filter above.  Returns its dict plus T and R; a draw whose solve fails in any segment gets -inf
+    and the OR of the bits."""
+    T, R, acc = _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options)
     res = kalman_logp_segments(b, name, T, R, Q, Z, y, seg_start, status=acc, options=options, **filter_kw)
+    res.update(T=T, R=R)
+    return res
+
+
+def solve_kalman_smoother_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, solver, tol, max_iter, n_lead_hint, options, **smoother_kw):
+    """``_solve_segments``, then the smoother across breaks.  Returns its dict plus T and R; a draw whose solve fails in any segment
+    has NaN in every output and the OR of the bits."""
+    T, R, acc = _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options)
+    res = kalman_smoother_segments(b, name, T, R, Q, Z, y, seg_start, status=acc, options=options, **smoother_kw)
     res.update(T=T, R=R)
     return res
 

@@ -494,6 +494,42 @@ def kalman_smoother_batched(T, R, Q, Z, y, d=None, Hdiag=None, q_mode=None, stat
                              scratch_limit_bytes=scratch_limit_bytes, options=options)
 
 
+segment_smoother_scratch_bytes_per_draw = F.segment_smoother_scratch_bytes_per_draw
+
+
+def kalman_smoother_segments_batched(T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None, jitter=JITTER_DEFAULT,
+                                     missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None, scratch_limit_bytes=None,
+                                     options=None, outputs=F.SEGMENT_SMOOTHER_OUTPUTS, q_mode=None, status=None):
+    """Smoothed states, covariances and structural shocks ACROSS DATED STRUCTURAL BREAKS per draw, with the per-step filter outputs
+    they stand on (include/dsge_hip.h, ``dsge_kalman_smoother_segments_batched``; docs/design/segmented_smoother.md): the
+    counterpart of ``kalman_smoother_batched`` for the inputs of ``kalman_logp_segments_batched`` (same arguments, same layouts).
+    Step t of the backward pass uses the matrices of the segment of period t + 1; ``smoothed_states[:, t]`` is in the coordinates of
+    the segment of period t, ``smoothed_shocks[:, 0]`` is NaN by definition.  ``outputs``: which of ll (batch, T_len), a_pred, a_filt
+    (batch, T_len, m), P_pred, P_filt, smoothed_covs (diagonals (batch, T_len, m) or, with ``full_covariances``, (batch, T_len, m,
+    m)), smoothed_states (batch, T_len, m), smoothed_shocks (batch, T_len, k) are computed -- without smoothed_covs the covariance
+    recursion is skipped.  ``scratch_limit_bytes`` (default 2 GiB) counts ``segment_smoother_scratch_bytes_per_draw`` per draw.
+    Returns a dict of the outputs (None where not asked for) and status."""
+    return F.kalman_smoother_segments(HOST, "kalman_smoother_segments_batched", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d, a0=a0,
+                                      P0=P0, shift=shift, q_mode=q_mode, status=status, jitter=jitter,
+                                      missing_fill=missing_fill_value, full=full_covariances, rank_tol=rank_tol,
+                                      scratch_limit_bytes=scratch_limit_bytes, options=options, outputs=outputs)
+
+
+def solve_kalman_smoother_segments_batched(A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                           solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                           missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None,
+                                           scratch_limit_bytes=None, options=None, outputs=F.SEGMENT_SMOOTHER_OUTPUTS, q_mode=None,
+                                           n_lead_hint=0):
+    """``A .. D`` (batch, S, n, n | k) -> ``T``, ``R`` of every (draw, segment) as ``solve_kalman_logp_segments_batched`` solves
+    them, then ``kalman_smoother_segments_batched``.  A draw whose solve fails in any segment has NaN in every output and the OR of
+    the segments' status bits.  Returns the smoother's dict plus ``T`` and ``R``."""
+    return F.solve_kalman_smoother_segments(HOST, "solve_kalman_smoother_segments_batched", A, B, C, D, q, Z, y, seg_start,
+                                            solver=solver, tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options,
+                                            Hdiag=Hdiag, d=d, a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter,
+                                            missing_fill=missing_fill_value, full=full_covariances, rank_tol=rank_tol,
+                                            scratch_limit_bytes=scratch_limit_bytes, outputs=outputs)
+
+
 simulation_smoother_scratch_bytes_per_draw = F.simulation_smoother_scratch_bytes_per_draw
 
 

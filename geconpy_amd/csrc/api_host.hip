@@ -620,6 +620,57 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
   return hc.finish();
 }
 
+int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                               int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                               const double* a0, const double* P0, const double* shift, const double* y,
+                                               const int32_t* seg_start, int n_seg, int batch, int m, int k, int p, int T_len,
+                                               double jitter, double missing_fill, double rank_tol, size_t scratch_limit_bytes,
+                                               int full_cov, double* ll_out, double* a_pred_out, double* a_filt_out,
+                                               double* p_pred_out, double* p_filt_out, double* a_smooth_out, double* p_smooth_out,
+                                               double* eps_smooth_out, int32_t* status_io) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_smoother_segments(batch, m, k, obs, q, seg_start, n_seg, T && R && status_io,
+                                   ll_out || a_pred_out || a_filt_out || p_pred_out || p_filt_out || a_smooth_out || p_smooth_out ||
+                                       eps_smooth_out);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  // staged as the likelihood's twin stages them: batch * S "draws" (the shared ones as S)
+  const size_t S = (size_t)n_seg, flat = (size_t)batch * S, mm = (size_t)m * m, tm = (size_t)batch * T_len * m;
+  const size_t qw = q.diag() ? (size_t)k : (size_t)k * k, tc = full_cov ? tm * m : tm;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0, *dsh, *dy;
+  double *dll, *dap, *daf, *dpp, *dpf, *das, *dps, *des;
+  int32_t* dS;
+  hc.in(&dT, T, flat * mm);
+  hc.in(&dR, R, flat * m * k);
+  hc.in(&dQ, Q, (q.batched() ? flat : S) * qw);
+  hc.in(&dZ, Z, (z_batched ? flat : S) * p * m);
+  hc.in(&dd, d, (d_batched ? flat : S) * p);
+  hc.in(&dH, Hdiag, (h_batched ? flat : S) * p);
+  hc.in(&da0, a0, (size_t)batch * m);
+  hc.in(&dP0, P0, (size_t)batch * mm);
+  hc.in(&dsh, shift, flat * m);
+  hc.in(&dy, y, (size_t)T_len * p);
+  hc.io(&dS, status_io, (size_t)batch);
+  hc.out(&dll, ll_out, (size_t)batch * T_len);
+  hc.out(&dap, a_pred_out, tm);
+  hc.out(&daf, a_filt_out, tm);
+  hc.out(&dpp, p_pred_out, tc);
+  hc.out(&dpf, p_filt_out, tc);
+  hc.out(&das, a_smooth_out, tm);
+  hc.out(&dps, p_smooth_out, tc);
+  hc.out(&des, eps_smooth_out, (size_t)batch * T_len * k);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_kalman_smoother_segments_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dsh, dy,
+                                                  seg_start, n_seg, batch, m, k, p, T_len, jitter, missing_fill, rank_tol,
+                                                  scratch_limit_bytes, full_cov, dll, dap, daf, dpp, dpf, das, dps, des, dS,
+                                                  hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_simulation_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
                                           int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,

@@ -666,6 +666,94 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   return DSGE_SUCCESS;
 }
 
+// The smoother across dated breaks (docs/design/segmented_smoother.md), per chunk of draws on the caller's stream: the chain of
+// dsge_kalman_logp_segments_batched up to P0, the storing instantiation of its filter (full covariances into library scratch, the
+// per-step outputs the caller asked for next to them), the basis of every (draw, segment) and the backward pass.
+int dsge_kalman_smoother_segments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                          const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                          int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                          double rank_tol, size_t scratch_limit_bytes, int full_cov, double* ll_out,
+                                          double* a_pred_out, double* a_filt_out, double* p_pred_out, double* p_filt_out,
+                                          double* a_smooth_out, double* p_smooth_out, double* eps_smooth_out, int32_t* status_io,
+                                          void* stream) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_smoother_segments(batch, m, k, obs, q, seg_start, n_seg, T && R && status_io,
+                                   ll_out || a_pred_out || a_filt_out || p_pred_out || p_filt_out || a_smooth_out || p_smooth_out ||
+                                       eps_smooth_out);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned flat_all = 0;
+  if ((rc = batch_grid(batch, n_seg, "segmented smoother: batch * n_seg exceeds 2^31 - 1", &flat_all))) return rc;
+  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT || smoother_lds_bytes(m) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "segmented smoother: LDS budget exceeded");
+  if (!(rank_tol > 0.0)) rank_tol = 1e-10;
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  const size_t S = (size_t)n_seg, mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k, tm = (size_t)T_len * m;
+  const size_t per_draw = (2 * tm * m + 2 * tm + 3 * S * smoother_image_doubles(m)) * sizeof(double);
+  const size_t fit = scratch_limit_bytes / per_draw;
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const size_t cf = (size_t)chunk * S, img = cf * smoother_image_doubles(m);
+  const bool gather = !P0 && n_seg > 1, smooth = a_smooth_out || p_smooth_out || eps_smooth_out;
+  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr;
+  double *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
+  int32_t *rank = nullptr, *sflat = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, cf * mm);
+  if (!q.batched()) lay.add(&Qx, cf * qw);
+  if (gather) {
+    lay.add(&T0, chunk * mm);
+    lay.add(&G0, chunk * mm);
+  }
+  if (!P0) lay.add(&P0s, chunk * mm);
+  lay.add(&U, img);
+  lay.add(&UT, img);
+  lay.add(&UR, img);
+  lay.add(&ap, chunk * tm);
+  lay.add(&af, chunk * tm);
+  lay.add(&pp, chunk * tm * m);
+  lay.add(&pf, chunk * tm * m);
+  lay.add(&rank, cf);
+  lay.add(&sflat, cf);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  // (a shared Q repeats with period S: its first nb * S rows serve every chunk)
+  if (!q.batched() && (rc = launch_segment_rows(Qx, Q, cf, (int)qw, n_seg, 1, st))) return rc;
+  const size_t tc = full_cov ? tm * m : tm;
+  auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const size_t o = (size_t)c0, fo = o * S, nf = (size_t)nb * S;
+    const double *Tc = T + fo * mm, *Rc = R + fo * m * k, *P0c = P0 ? P0 + o * mm : nullptr;
+    const ShockCov qe = q.batched() ? q.at(fo, k) : ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+    int32_t* sc = status_io + o;
+    if ((rc = assemble_rqr(Rc, qe, (int)nf, m, k, RQR, nullptr, st))) return rc;
+    if (!P0c) {
+      const double* Ts = Tc;
+      double* Gs = RQR;
+      if (gather) {
+        if ((rc = launch_segment_rows(T0, Tc, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
+        if ((rc = launch_segment_rows(G0, RQR, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
+        Ts = T0;
+        Gs = G0;
+      }
+      if ((rc = assemble_p0_from_rqr(Ts, Gs, nb, m, P0s, sc, false, st))) return rc;
+      P0c = P0s;
+    }
+    if ((rc = launch_kalman_segments_store(Tc, RQR, P0c, a0 ? a0 + o * m : nullptr, shift ? shift + fo * m : nullptr, obs.at(fo, m),
+                                           seg_start, n_seg, nb, m, at(ll_out, o * T_len), ap, af, pp, pf, at(a_pred_out, o * tm),
+                                           at(a_filt_out, o * tm), at(p_pred_out, o * tc), at(p_filt_out, o * tc), full_cov, sc, st)))
+      return rc;
+    if (smooth && (rc = launch_kalman_smoother_segments(Tc, Rc, qe, seg_start, n_seg, nb, m, k, T_len, rank_tol, U, UT, UR, rank, sflat,
+                                                        ap, af, pp, pf, at(a_smooth_out, o * tm), at(p_smooth_out, o * tc),
+                                                        at(eps_smooth_out, o * T_len * k), full_cov, sc, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
 // Joint posterior draws of the state path and the shocks (dsge_simsmooth.hpp): the smoother's forward pass and basis per chunk of
 // draws, x+ of every path through the propagation kernel, then the two path kernels -- all on the caller's stream.
 int dsge_simulation_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

@@ -300,6 +300,20 @@ int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, 
                            int32_t* status, hipStream_t st);
 int launch_smoother_basis(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, double rank_tol, double* U,
                           double* UT, double* UR, int32_t* rank, int32_t* status, hipStream_t st);  // the basis alone
+size_t smoother_lds_bytes(int m);
+// the smoother across dated breaks.  launch_kalman_seg_store.hip: the filter of launch_kalman_segments that also stores the moments
+// of every period -- ap_s .. pf_s: [batch][T_len][m] / [batch][T_len][m][m] scratch; ap_o .. pf_o: the caller's, each may be null,
+// covariances as diagonals or full by full_cov.  launch_smooth.hip: the bases and the backward pass over that scratch -- T, R, U, UT,
+// UR: [batch][S] problems; q: a *_BATCHED layout over batch * S; rank, status_flat: [batch * S] scratch
+int launch_kalman_segments_store(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
+                                 const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* ll, double* ap_s,
+                                 double* af_s, double* pp_s, double* pf_s, double* ap_o, double* af_o, double* pp_o, double* pf_o,
+                                 int full_cov, int32_t* status, hipStream_t st);
+int launch_kalman_smoother_segments(const double* T, const double* R, const ShockCov& q, const int32_t* seg_start, int n_seg, int batch,
+                                    int m, int k, int T_len, double rank_tol, double* U, double* UT, double* UR, int32_t* rank,
+                                    int32_t* status_flat, const double* a_pred, const double* a_filt, const double* p_pred,
+                                    const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov, int32_t* status,
+                                    hipStream_t st);
 // launch_simsmooth.hip (dsge_simsmooth.hpp): the simulation smoother's forward (filter means of n_paths transformed data sets per
 // draw over the stored P_pred) and backward pass (smoother means, x+ / eps+ added) for groups of 16 paths per draw.  xp, a_pred,
 // a_filt: [batch][n_paths][T_len][m] (a_pred, a_filt: scratch); eps / eta: draw strides, 0 = shared; snap: [batch] scratch
@@ -591,6 +605,12 @@ inline int check_kalman_segments(int batch, int m, int k, const ObsModel& o, con
     if (seg_start[s] <= seg_start[s - 1]) return fail(DSGE_ERR_INVALID, "seg_start must be strictly increasing");
   if (o.T_len > 0 && seg_start[n_seg - 1] >= o.T_len) return fail(DSGE_ERR_INVALID, "seg_start: every entry must be < T_len");
   return DSGE_SUCCESS;
+}
+inline int check_smoother_segments(int batch, int m, int k, const ObsModel& o, const ShockCov& q, const int32_t* seg_start, int n_seg,
+                                   bool others, bool any_output) {
+  int rc = check_kalman_segments(batch, m, k, o, q, seg_start, n_seg, others);
+  if (rc) return rc;
+  return any_output ? DSGE_SUCCESS : fail(DSGE_ERR_INVALID, "no output requested");
 }
 inline int check_simulation_smoother(int batch, int m, int k, const ObsModel& o, const ShockCov& q, bool others, int n_paths,
                                      const double* eps, const double* eta, bool any_output) {

@@ -13,6 +13,8 @@
 // L2) and adds shift_s to the filtered mean before the product with T_s.  LDS at m = 64, p = 16: three images (101 376 bytes) + Z
 // (8 320) + P Zm' and K (8 704 each) + vectors (5 696) = 132 800 of the 160 KiB (kseg_lds_doubles).
 #pragma once
+#include <type_traits>
+
 #include "dsge_postsolve.hpp"
 
 namespace dsge {
@@ -41,6 +43,15 @@ struct KsegArgs {
   double missing_fill;
 };
 
+// The STORING variant of the kernel (kalman_seg_kernel<true>, the forward pass of the smoother across breaks,
+// dsge_kalman_smooth.hpp) also writes the moments of every period: into the smoother's scratch as full matrices, and into the
+// caller's arrays (each may be null; covariances as diagonals or full by full_cov).  logp, a_last and P_last may then be null.
+struct KsegStoreArgs : KsegArgs {
+  double *ap_s, *af_s, *pp_s, *pf_s;  // [batch][T_len][m], [batch][T_len][m][m]: scratch, required
+  double *ap_o, *af_o, *pp_o, *pf_o;  // [batch][T_len][m]; [batch][T_len][m] or [batch][T_len][m][m]
+  int full_cov;
+};
+
 __host__ __device__ inline int kseg_zld(int m) { return m | 1; }  // row stride of Z in LDS (odd)
 __host__ __device__ inline size_t kseg_lds_doubles(int m, int p) {
   return 3 * ks_mat(m) + (size_t)p * kseg_zld(m) + 2 * (size_t)ks_mp(m) * KSEG_PLD + 2 * 64 + 2 * KSEG_PMAX * KSEG_PMAX +
@@ -58,7 +69,8 @@ __device__ __forceinline__ int kseg_start(const KsegArgs& a, int s) {
 
 // rows of a source laid out by (row % mod) * mul into consecutive rows of dst: the shared shock covariances [S][w] repeated for
 // every draw (mod = S, mul = 1), and segment 0 of every draw gathered out of [batch][S][w] (mod = rows, mul = S)
-__global__ __launch_bounds__(256) void kseg_rows_kernel(double* __restrict__ dst, const double* __restrict__ src, long long rows,
+// (static: this header is included by two translation units, and only launch_kalman_seg.hip launches it)
+static __global__ __launch_bounds__(256) void kseg_rows_kernel(double* __restrict__ dst, const double* __restrict__ src, long long rows,
                                                         int width, int mod, int mul) {
   const long long n = rows * width;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long long)gridDim.x * 256) {
@@ -68,7 +80,28 @@ __global__ __launch_bounds__(256) void kseg_rows_kernel(double* __restrict__ dst
   }
 }
 
-__global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
+// the predicted moments of period t (vector av, LDS image P) into the scratch and, where asked for, the caller's arrays
+__device__ __forceinline__ void kseg_store(const KsegStoreArgs& a, int draw, int t, const ks_lds* av, const ks_lds* P, int ld, double* vs,
+                                           double* ms, double* vo, double* mo, int tid) {
+  const int m = a.m, mm = m * m;
+  const size_t o = ((size_t)draw * a.T_len + t) * m;
+  if (tid < m) {
+    vs[o + tid] = av[tid];
+    if (vo) vo[o + tid] = av[tid];
+  }
+  for (int idx = tid; idx < mm; idx += KSEG_THREADS) {
+    const int i = idx / m, j = idx - i * m;
+    const double v = P[i * ld + j];
+    ms[o * m + idx] = v;
+    if (mo) {
+      if (a.full_cov) mo[o * m + idx] = v;
+      else if (i == j) mo[o + i] = v;
+    }
+  }
+}
+
+template <bool STORE>
+__global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(typename std::conditional<STORE, KsegStoreArgs, KsegArgs>::type a) {
   constexpr int NT = KSEG_THREADS, PM = KSEG_PMAX, PL = KSEG_PLD;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, draw = blockIdx.x, m = a.m, p = a.p, mm = m * m, n = a.T_len, S = a.n_seg;
@@ -77,7 +110,14 @@ __global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
   double* al_o = a.a_last ? a.a_last + (size_t)draw * m : nullptr;
   double* pl_o = a.P_last ? a.P_last + (size_t)draw * mm : nullptr;
   if (a.status[draw] != 0) {  // failed solve or Lyapunov iteration: no filter -- logp = -inf, EVERY other requested output NaN
-    if (tid == 0) a.logp[draw] = -INFINITY;
+    if constexpr (STORE) {  // (the scratch of such a draw is never read: the backward pass skips it too)
+      const size_t nv = (size_t)n * m, ncv = a.full_cov ? nv * m : nv;
+      if (a.ap_o) ps_fill_nan(a.ap_o + (size_t)draw * nv, nv, tid, NT);
+      if (a.af_o) ps_fill_nan(a.af_o + (size_t)draw * nv, nv, tid, NT);
+      if (a.pp_o) ps_fill_nan(a.pp_o + (size_t)draw * ncv, ncv, tid, NT);
+      if (a.pf_o) ps_fill_nan(a.pf_o + (size_t)draw * ncv, ncv, tid, NT);
+      if (tid == 0 && a.logp) a.logp[draw] = -INFINITY;
+    } else if (tid == 0) a.logp[draw] = -INFINITY;
     if (ll_o) ps_fill_nan(ll_o, n, tid, NT);
     if (al_o) ps_fill_nan(al_o, m, tid, NT);
     if (pl_o) ps_fill_nan(pl_o, mm, tid, NT);
@@ -132,6 +172,7 @@ __global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
   bool finite = true;
   double ll_sum = 0.0;
   for (int t = 0; t < n; ++t) {
+    if constexpr (STORE) kseg_store(a, draw, t, (const ks_lds*)av, (const ks_lds*)P, ld, a.ap_s, a.pp_s, a.ap_o, a.pp_o, tid);  // predicted
     int mask = 0;  // (every thread reads the p entries itself: uniform, no barrier)
     for (int o = 0; o < p; ++o) {
       const double yo = a.y[(size_t)t * p + o];
@@ -210,6 +251,11 @@ __global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
       double acc = av[i];
       for (int o = 0; o < p; ++o) acc = fma(Kg[i * PL + o], vv[o], acc);
       af[i] = acc;
+      if constexpr (STORE) {  // (before a boundary adds shift: a_filt is in the coordinates of the period's own segment)
+        const size_t o = ((size_t)draw * n + t) * m + i;
+        a.af_s[o] = acc;
+        if (a.af_o) a.af_o[o] = acc;
+      }
     }
     __syncthreads();
     for (int idx = tid; idx < mm; idx += NT) {  // P+ -> W
@@ -220,7 +266,16 @@ __global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
         acc = fma(ki, fma(a.cv.jit_V, kj, PZ[j * PL + o]), acc);
         acc = fma(kj, fma(a.cv.jit_V, ki, PZ[i * PL + o]), acc);
       }
-      W[i * ld + j] = P[i * ld + j] - 0.5 * acc + (i == j ? a.cv.jit_P : 0.0);
+      const double pf = P[i * ld + j] - 0.5 * acc + (i == j ? a.cv.jit_P : 0.0);
+      W[i * ld + j] = pf;
+      if constexpr (STORE) {
+        const size_t o = ((size_t)draw * n + t) * m;
+        a.pf_s[o * m + idx] = pf;
+        if (a.pf_o) {
+          if (a.full_cov) a.pf_o[o * m + idx] = pf;
+          else if (i == j) a.pf_o[o + i] = pf;
+        }
+      }
     }
     if (t == n - 1) {  // the filtered moments of the last period: what dsge_forecast_batched takes as a0, P0
       __syncthreads();
@@ -260,7 +315,7 @@ __global__ __launch_bounds__(KSEG_THREADS) void kalman_seg_kernel(KsegArgs a) {
     __syncthreads();
   }
   if (tid == 0) {
-    a.logp[draw] = ll_sum;
+    if (!STORE || a.logp) a.logp[draw] = ll_sum;
     if (!finite || !((ll_sum == ll_sum) && (fabs(ll_sum) < 1.797e308))) a.status[draw] |= DSGE_ST_FILTER_NONFINITE;
   }
 }

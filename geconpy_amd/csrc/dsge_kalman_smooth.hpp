@@ -62,6 +62,31 @@ struct KsArgs {
   double rank_tol;
 };
 
+// ACROSS DATED BREAKS (kalman_smoother_kernel<UG, true>; docs/design/segmented_smoother.md): the stored forward pass is that of
+// kalman_seg_kernel<true> (dsge_kalman_seg.hpp) and step t uses the matrices of s' = s(t+1).  The range of P_pred[t+1] is fixed per
+// (draw, segment), so U, UT, UR are [batch][S] images, rank is [batch][S] and Q is per (draw, segment) (a *_BATCHED layout over
+// batch * S): the basis kernel runs unchanged on the flattened batch.  Walking back over a boundary (t + 1 == seg_start[s']) the
+// workgroup re-stages the three LDS images (m <= 48) or moves its three pointers (m >= 49), and reads r and the diagonal of Q anew.
+struct KsSegArgs : KsArgs {
+  int n_seg;
+  int seg_start[DSGE_MAX_SEGMENTS];
+};
+
+// first period of segment s (constant indices only: the list lives in the kernel arguments)
+__device__ __forceinline__ int ks_seg_start(const KsSegArgs& a, int s) {
+  int v = 0;
+#pragma unroll
+  for (int q = 0; q < DSGE_MAX_SEGMENTS; ++q)
+    if (q == s) v = a.seg_start[q];
+  return v;
+}
+
+// the draw's status word repeated for each of its segments: what the basis kernel reads on the flattened batch
+__global__ __launch_bounds__(256) void ks_seg_status_kernel(int32_t* __restrict__ dst, const int32_t* __restrict__ src, long long flat,
+                                                            int n_seg) {
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < flat; idx += (long long)gridDim.x * 256) dst[idx] = src[idx / n_seg];
+}
+
 // ---- basis of [T | R_J] and U'T, once per draw ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(KS_THREADS) void smoother_basis_kernel(KsArgs a) {
   constexpr int NT = KS_THREADS;
@@ -176,8 +201,8 @@ __global__ __launch_bounds__(KS_THREADS) void smoother_basis_kernel(KsArgs a) {
   if (tid == 0) a.rank[draw] = r;
 }
 
-template <bool UG>
-__global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
+template <bool UG, bool SEG = false>
+__global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(typename std::conditional<SEG, KsSegArgs, KsArgs>::type a) {
   constexpr int NT = KS_THREADS;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, draw = blockIdx.x, m = a.m, k = a.k, mm = m * m, n = a.T_len;
@@ -195,7 +220,15 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
   }
   const int ld = ks_ld(m), mp = ks_mp(m), mt = mp / 16, m4 = ps_r4(m);
   const size_t MAT = ks_mat(m);
-  const int r = a.rank[draw], rt = (r + 15) / 16, r4 = ps_r4(r);
+  // the problem whose basis, rank and Q the step uses: the draw, or (draw, segment) -- the last segment first
+  int seg = 0, seg_first = 0;
+  size_t prob = (size_t)draw;
+  if constexpr (SEG) {
+    seg = a.n_seg - 1;
+    seg_first = ks_seg_start(a, seg);
+    prob = (size_t)draw * a.n_seg + seg;
+  }
+  typename std::conditional<SEG, int, const int>::type r = a.rank[prob], rt = (r + 15) / 16, r4 = ps_r4(r);
   const bool cov = ps_o != nullptr;
   ks_lds* V = (ks_lds*)smem;
   ks_lds* Pf = V + MAT;
@@ -204,18 +237,19 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
   ks_lds* pl = W + MAT;
   typedef typename std::conditional<UG, const ks_glb*, const ks_lds*>::type UPtr;
   UPtr U, UT, UR;
+  ks_lds *Ul = nullptr, *UTl = nullptr, *URl = nullptr;
   if constexpr (UG) {
-    U = (const ks_glb*)(a.U + (size_t)draw * MAT);
-    UT = (const ks_glb*)(a.UT + (size_t)draw * MAT);
-    UR = (const ks_glb*)(a.UR + (size_t)draw * MAT);
+    U = (const ks_glb*)(a.U + prob * MAT);
+    UT = (const ks_glb*)(a.UT + prob * MAT);
+    UR = (const ks_glb*)(a.UR + prob * MAT);
   } else {
-    ks_lds* Ul = pl; pl += MAT;
-    ks_lds* UTl = pl; pl += MAT;
-    ks_lds* URl = pl; pl += MAT;
+    Ul = pl; pl += MAT;
+    UTl = pl; pl += MAT;
+    URl = pl; pl += MAT;
     for (size_t idx = tid; idx < MAT; idx += NT) {
-      Ul[idx] = a.U[(size_t)draw * MAT + idx];
-      UTl[idx] = a.UT[(size_t)draw * MAT + idx];
-      URl[idx] = a.UR[(size_t)draw * MAT + idx];
+      Ul[idx] = a.U[prob * MAT + idx];
+      UTl[idx] = a.UT[prob * MAT + idx];
+      URl[idx] = a.UR[prob * MAT + idx];
     }
     U = Ul;
     UT = UTl;
@@ -231,7 +265,7 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
   ks_lds* afv = pl; pl += 64;   // a_filt[t]
   ks_lds* qd = pl; pl += 64;    // diagonal Q
   bool qf;
-  const double* Qg = ps_q_slice(a.Q, a.q_mode, draw, k, &qf);
+  const double* Qg = ps_q_slice(a.Q, a.q_mode, prob, k, &qf);
   const double* apg = a.a_pred + (size_t)draw * nv;
   const double* afg = a.a_filt + (size_t)draw * nv;
   const double* ppg = a.p_pred + (size_t)draw * nv * m;
@@ -431,6 +465,29 @@ __global__ __launch_bounds__(KS_THREADS) void kalman_smoother_kernel(KsArgs a) {
       if (tid < m) {
         apv[tid] = apr;
         afv[tid] = afr;
+      }
+    }
+    if constexpr (SEG) {
+      if (t + 1 == seg_first) {  // (uniform) period t belongs to the segment before: its basis, rank and Q from here on.  Nobody
+        --seg;                   // reads the old ones any more, and the barrier that opens the next step publishes the new ones
+        seg_first = ks_seg_start(a, seg);
+        prob = (size_t)draw * a.n_seg + seg;
+        r = a.rank[prob];
+        rt = (r + 15) / 16;
+        r4 = ps_r4(r);
+        Qg = ps_q_slice(a.Q, a.q_mode, prob, k, &qf);
+        if (tid < k) qd[tid] = qf ? Qg[tid * k + tid] : Qg[tid];
+        if constexpr (UG) {
+          U = (const ks_glb*)(a.U + prob * MAT);
+          UT = (const ks_glb*)(a.UT + prob * MAT);
+          UR = (const ks_glb*)(a.UR + prob * MAT);
+        } else {
+          for (size_t idx = tid; idx < MAT; idx += NT) {
+            Ul[idx] = a.U[prob * MAT + idx];
+            UTl[idx] = a.UT[prob * MAT + idx];
+            URl[idx] = a.UR[prob * MAT + idx];
+          }
+        }
       }
     }
   }

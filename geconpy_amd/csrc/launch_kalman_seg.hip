@@ -28,7 +28,7 @@ int launch_kalman_segments(const double* T, const double* RQR, const double* P0,
   for (int s = 0; s < DSGE_MAX_SEGMENTS; ++s) a.seg_start[s] = s < n_seg ? seg_start[s] : 0x7fffffff;
   a.cv = filter_conv(o.jitter);
   a.missing_fill = o.missing_fill;
-  return launch_with_lds(dsge::kalman_seg_kernel, batch, dsge::KSEG_THREADS, kalman_segments_lds_bytes(m, o.p), st, a,
+  return launch_with_lds(dsge::kalman_seg_kernel<false>, batch, dsge::KSEG_THREADS, kalman_segments_lds_bytes(m, o.p), st, a,
                          "segmented filter: LDS budget exceeded");
 }
 

@@ -260,6 +260,33 @@ class LogpEngine:
                                             a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter, missing_fill=missing_fill_value,
                                             outputs=outputs, out=out)
 
+    def kalman_smoother_segments(self, T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                 jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None,
+                                 scratch_limit_bytes=None, options=None, outputs=F.SEGMENT_SMOOTHER_OUTPUTS, q_mode=None, status=None,
+                                 out=None):
+        """Smoothed states, covariances and shocks across dated structural breaks, with the per-step filter outputs
+        (``dsge_kalman_smoother_segments_batched``; see ``batched.kalman_smoother_segments_batched``) from device tensors, on torch's
+        current stream.  ``seg_start`` is a HOST list.  ``out``: optional dict of preallocated outputs, by the names of ``outputs``.
+        ``status``: optional int32 tensor [batch] of incoming status words (updated in place).  Returns a dict of device tensors
+        (None where not asked for) and status; asynchronous."""
+        return F.kalman_smoother_segments(self.backend, "kalman_smoother_segments", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d, a0=a0,
+                                          P0=P0, shift=shift, q_mode=q_mode, status=status, jitter=jitter,
+                                          missing_fill=missing_fill_value, full=full_covariances, rank_tol=rank_tol,
+                                          scratch_limit_bytes=scratch_limit_bytes, options=options, outputs=outputs, out=out)
+
+    def solve_kalman_smoother_segments(self, A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                       solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                       missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None,
+                                       scratch_limit_bytes=None, options=None, outputs=F.SEGMENT_SMOOTHER_OUTPUTS, q_mode=None,
+                                       n_lead_hint=0, out=None):
+        """``A .. D`` [batch][S][n][n|k] solved as ``solve_kalman_logp_segments`` solves them, then ``kalman_smoother_segments``
+        (``batched.solve_kalman_smoother_segments_batched``).  Returns its dict plus ``T`` and ``R``; asynchronous."""
+        return F.solve_kalman_smoother_segments(self.backend, "solve_kalman_smoother_segments", A, B, C, D, q, Z, y, seg_start,
+                                                solver=solver, tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options,
+                                                Hdiag=Hdiag, d=d, a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter,
+                                                missing_fill=missing_fill_value, full=full_covariances, rank_tol=rank_tol,
+                                                scratch_limit_bytes=scratch_limit_bytes, outputs=outputs, out=out)
+
     def stationary_factor(self, T, R, Q, q_mode=None):
         """F [batch][m][m] with F F' = P0 per draw (``batched.stationary_factor``) from device tensors: ``dsge_lyapunov_batched``
         and a batched ``torch.linalg.eigh``, on torch's current stream."""

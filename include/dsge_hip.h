@@ -58,7 +58,8 @@ extern "C" {
 /* ABI 19: dsge_constrained_simulate_batched (+ _host) and the path bit DSGE_OBC_HORIZON_SHORT are new; nothing else changed. */
 /* Still ABI 19: dsge_kalman_logp_segments_batched (+ _host) and DSGE_MAX_SEGMENTS were added WITHOUT a new version number -- two new
  * symbols and one constant, nothing else changed; a caller built against the earlier ABI 19 header runs unchanged (backward
- * compatible), a caller of the new entry must load a library that exports it. */
+ * compatible), a caller of the new entry must load a library that exports it.  dsge_kalman_smoother_segments_batched (+ _host)
+ * followed the same way: two new symbols, nothing else changed. */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -797,6 +798,53 @@ int dsge_kalman_smoother_batched_host(const double* T, const double* R, const do
                                       int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
                                       double rank_tol, size_t scratch_limit_bytes, double* ll_out, double* a_smooth_out,
                                       double* p_smooth_out, double* eps_smooth_out, int full_cov, int32_t* status_io);
+
+/*
+ * The SMOOTHER ACROSS DATED STRUCTURAL BREAKS per draw, with the per-step filter outputs it stands on (docs/design/
+ * segmented_smoother.md): the counterpart of dsge_kalman_smoother_batched for the piecewise constant system of
+ * dsge_kalman_logp_segments_batched.  Segments, seg_start (HOST memory), s(t), a0, P0, shift, the filter conventions, missing data
+ * and the forward recursion are exactly those of that entry; a_pred, P_pred, a_filt, P_filt are the moments of its forward pass
+ * (a_pred[0] = a0 or 0, P_pred[0] = P0 or the stationary covariance of segment 0; a_pred[t+1] holds shift at a boundary).  With
+ * n = T_len:
+ *     as[n-1] = a_filt[n-1], V[n-1] = P_filt[n-1];   for t = n-2 .. 0, with s' = s(t+1) and Pp = P_pred[t+1]:
+ *     w = Pp^+ (as[t+1] - a_pred[t+1]);  as[t] = a_filt[t] + P_filt[t] T_s'' w;  eps[t+1] = Q_s' R_s'' w;
+ *     G = P_filt[t] T_s'' Pp^+;  V[t] = P_filt[t] + sym(G (V[t+1] - Pp) G');      eps[0] = NaN BY DEFINITION (also with a0 / P0)
+ * as[t] is in the coordinates of segment s(t); shift is deterministic and enters through a_pred alone.  Pp^+ comes from the range
+ * as in dsge_kalman_smoother_batched, fixed per (draw, SEGMENT): range(P_pred[t+1]) = range(T_s') + range(R_s',J), J = {j :
+ * Q_s',jj > 0}, under that entry's two assumptions -- one basis and one rank per (draw, segment); the ranks of a draw's segments
+ * may differ.  With S = 1 and a0 = P0 = shift = NULL this is dsge_kalman_smoother_batched.  Arguments T .. missing_fill as
+ * dsge_kalman_logp_segments_batched, rank_tol and scratch_limit_bytes as dsge_kalman_smoother_batched (the per-draw figure is
+ * 2 T_len m^2 + 2 T_len m doubles of the stored forward pass plus the 3 S basis images), plus
+ *   ll_out                   : [batch][T_len]
+ *   a_pred_out, a_filt_out   : [batch][T_len][m]
+ *   p_pred_out, p_filt_out   : [batch][T_len][m] diagonals, or [..][m][m] with full_cov != 0
+ *   a_smooth_out             : [batch][T_len][m]      p_smooth_out : as p_pred_out; without it the covariance recursion is skipped
+ *   eps_smooth_out           : [batch][T_len][k]
+ *   each may be NULL, at least one must be given; any subset gives the bits of the full call, and so does a chunked call
+ *   status_io                : [batch] in/out, as in the two entries: a non-zero incoming status or DSGE_ST_LYAP_FAIL on segment 0
+ *                              gives NaN in every requested output, DSGE_ST_FILTER_NONFINITE NaN in every smoothed output,
+ *                              DSGE_ST_SMOOTHER_SINGULAR NaN for that step and all earlier ones (the later steps stay); every other
+ *                              draw is untouched, bit for bit
+ * m <= DSGE_MAX_N, p <= DSGE_MAX_P (else DSGE_ERR_TOO_LARGE), S <= DSGE_MAX_SEGMENTS; refusals as dsge_kalman_logp_segments_batched.
+ * batch == 0 or T_len == 0: success, nothing touched.  T_len == 1: smoothed = filtered, shocks NaN.  No host synchronisation, no
+ * atomics: a pure enqueue on the caller's stream.  Added WITHOUT a new ABI version number, like the likelihood across breaks.
+ */
+int dsge_kalman_smoother_segments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                          const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                          const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                          int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                          double rank_tol, size_t scratch_limit_bytes, int full_cov, double* ll_out,
+                                          double* a_pred_out, double* a_filt_out, double* p_pred_out, double* p_filt_out,
+                                          double* a_smooth_out, double* p_smooth_out, double* eps_smooth_out, int32_t* status_io,
+                                          void* stream);
+int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                               int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                               const double* a0, const double* P0, const double* shift, const double* y,
+                                               const int32_t* seg_start, int n_seg, int batch, int m, int k, int p, int T_len,
+                                               double jitter, double missing_fill, double rank_tol, size_t scratch_limit_bytes,
+                                               int full_cov, double* ll_out, double* a_pred_out, double* a_filt_out,
+                                               double* p_pred_out, double* p_filt_out, double* a_smooth_out, double* p_smooth_out,
+                                               double* eps_smooth_out, int32_t* status_io);
 
 /*
  * SIMULATION SMOOTHER (ABI 12; csrc/dsge_simsmooth.hpp, docs/design/simulation_smoother.md): n_paths JOINT posterior draws of the

@@ -9,6 +9,7 @@
     python tools/dynamics_time.py --constrained [draws ...]       the occasionally-binding-bound rows alone
     python tools/dynamics_time.py --stochastic-bound [draws ...]  the rows of the stochastic simulation at the bound alone
     python tools/dynamics_time.py --segmented [draws ...]         the rows of the Kalman likelihood across dated breaks alone
+    python tools/dynamics_time.py --segmented-smoother [--library PATH] [--scratch-limit-gib G] [draws ...]   the smoother across breaks
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -54,6 +55,10 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     of >= 1 s each of LogpEngine.kalman_logp_segments with S = 1, S = 3 (breaks at 80 and 140) and S = 8, against
     dsge_kalman_filter_outputs_batched with ll alone and, for scale, dsge_kalman_logp_batched with kalman_steady_tol = 0 and at its
     default.
+  * --segmented-smoother [--library PATH] [--scratch-limit-gib G] (docs/design/segmented_smoother.md), the batch of --segmented: the median of five timings
+    of >= 1 s each of LogpEngine.kalman_smoother_segments (ll, smoothed states and shocks; with diagonal covariances and without
+    covariances) with S = 1, S = 3 and S = 8, against dsge_kalman_smoother_batched on the inputs of S = 1 -- of this build and of
+    the library at PATH (a build of another commit) in the same run -- with the cost per boundary and whether S = 1 has its bits.
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -655,10 +660,89 @@ def segmented_rows(eng, sizes, T_len=200, repeats=5):
                   f"/ kalman_logp no steady: {t_lp / t_full:6.2f} | / default: {t_lp / t_fast:6.2f}")
 
 
+def segmented_smoother_rows(eng, sizes, other_lib=None, scratch_limit=0, T_len=200, repeats=5):
+    """The smoother across dated breaks (docs/design/segmented_smoother.md) on the SW-shaped batch of ``segmented_rows``: S = 1,
+    S = 3 with breaks at 80 and 140, S = 8, with diagonal covariances and without covariances (ll, states and shocks in both),
+    against dsge_kalman_smoother_batched on the inputs of S = 1 -- of this build and, with ``--library PATH``, of the libdsge_hip.so
+    at PATH (a build of the parent commit) loaded next to it.  ``scratch_limit`` (``--scratch-limit-gib``; 0: the library's 2 GiB)
+    is the ``scratch_limit_bytes`` of every call: the stored forward pass takes 5.3 MB per draw at this shape, so by default the
+    batch goes in chunks of about 400 draws (fewer with more segments: their bases count too)."""
+    import ctypes
+
+    libs = {"this build": _lib.load()}
+    if other_lib:
+        libs[other_lib] = ctypes.CDLL(other_lib)
+        libs[other_lib].dsge_kalman_smoother_batched.argtypes = _lib.PROTOTYPES["dsge_kalman_smoother_batched"]
+    b = wl.sw_shaped_batch(64)
+    om = wl.sw_shaped_observation_model()
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p = 40, 7, om["y"].shape[1]
+    y, H1, Z1 = eng.to_device(om["y"][:T_len]), om["Hdiag"], om["Z"]
+    breaks = {1: (0,), 3: (0, 80, 140), 8: tuple(range(0, T_len, T_len // 8))[:8]}
+    print(f"segmented smoother, SW shape m={m} k={k} p={p}, T_len={T_len}, scratch_limit_bytes={scratch_limit}; median of {repeats} "
+          "timings of >= 1 s each")
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    for nb in sizes:
+        idx = np.arange(nb) % 64
+        T, R, q = eng.to_device(b["T_star"][idx]), eng.to_device(R64[idx]), eng.to_device(b["sigma"][idx] ** 2)
+        Z, H = eng.to_device(Z1), eng.to_device(H1)
+        mk = lambda *sh: torch.empty(sh, dtype=torch.float64, device=eng.device)  # noqa: E731
+        ll, a_s, p_s, e_s = mk(nb, T_len), mk(nb, T_len, m), mk(nb, T_len, m), mk(nb, T_len, k)
+        st = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+        plain, kept = {}, {}
+        for name, lib in libs.items():
+            def smoother(cov, lib=lib):
+                _lib.check(lib.dsge_kalman_smoother_batched(
+                    T.data_ptr(), R.data_ptr(), q.data_ptr(), 1, Z.data_ptr(), 0, None, 0, H.data_ptr(), 0, y.data_ptr(), nb, m, k, p,
+                    T_len, 1e-8, -9999.0, 0.0, scratch_limit, ll.data_ptr(), a_s.data_ptr(), p_s.data_ptr() if cov else None, e_s.data_ptr(), 0,
+                    st.data_ptr(), eng._stream()))
+
+            plain[name] = (med(lambda: smoother(True)), med(lambda: smoother(False)))
+            smoother(True)
+            kept[name] = [x.clone() for x in (ll, a_s, p_s, e_s)]
+            assert int(st.abs().max().item()) == 0
+            print(f"draws={nb:5d} kalman_smoother_batched of {name}: diagonal covariances {plain[name][0]:9.3f} ms, "
+                  f"no covariances {plain[name][1]:9.3f} ms")
+        base = plain[other_lib] if other_lib else plain["this build"]
+        one = None
+        for S, starts in breaks.items():
+            pick = (np.arange(nb)[:, None] + np.arange(S)[None, :]) % 64
+            Ts, Rs, qs = eng.to_device(b["T_star"][pick]), eng.to_device(R64[pick]), eng.to_device(b["sigma"][pick] ** 2)
+            Zs, Hs = eng.to_device(np.tile(Z1, (S, 1, 1))), eng.to_device(np.tile(H1, (S, 1)))
+            out = dict(ll=ll, smoothed_states=a_s, smoothed_covs=p_s, smoothed_shocks=e_s)
+            lean = {key: v for key, v in out.items() if key != "smoothed_covs"}
+            call = lambda out: eng.kalman_smoother_segments(Ts, Rs, qs, Zs, y, starts, Hdiag=Hs, q_mode="diag_batched",  # noqa: E731
+                                                            outputs=tuple(out), out=out, status=st,
+                                                            scratch_limit_bytes=scratch_limit)
+            t = (med(lambda: call(out)), med(lambda: call(lean)))
+            assert int(st.abs().max().item()) == 0
+            if S == 1:
+                one = t
+                call(out)
+                for name, ref in kept.items():
+                    same = [bool(torch.equal(torch.nan_to_num(x), torch.nan_to_num(r))) for x, r in zip((ll, a_s, p_s, e_s), ref)]
+                    print(f"draws={nb:5d} S=1 against kalman_smoother_batched of {name}, bit-identical (ll, states, covs, shocks): {same}")
+            print(f"draws={nb:5d} segments S={S} breaks {starts if S < 8 else 'every ' + str(T_len // 8)}: diagonal covariances "
+                  f"{t[0]:9.3f} ms, no covariances {t[1]:9.3f} ms | / S=1: {t[0] / one[0]:5.3f}, {t[1] / one[1]:5.3f} | "
+                  f"/ kalman_smoother_batched: {t[0] / base[0]:5.3f}, {t[1] / base[1]:5.3f} | per boundary: "
+                  f"{(t[0] - one[0]) / max(S - 1, 1) * 1e3:8.1f} us, {(t[1] - one[1]) / max(S - 1, 1) * 1e3:8.1f} us")
+
+
 def main():
+    other_lib, scratch_limit = None, 0
+    for flag in ("--library", "--scratch-limit-gib"):
+        if flag in sys.argv:
+            at = sys.argv.index(flag)
+            if flag == "--library":
+                other_lib = sys.argv[at + 1]
+            else:
+                scratch_limit = int(float(sys.argv[at + 1]) * 2 ** 30)
+            del sys.argv[at:at + 2]
     args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated",
-                                                 "--constrained", "--stochastic-bound", "--segmented")]
+                                                 "--constrained", "--stochastic-bound", "--segmented", "--segmented-smoother")]
     sizes = [int(a) for a in args] or [256, 4096]
+    if "--segmented-smoother" in sys.argv:
+        return segmented_smoother_rows(LogpEngine(0), sizes, other_lib, scratch_limit)
     if "--second-order" in sys.argv:
         return second_order_rows(LogpEngine(0), sizes)
     if "--decomposition" in sys.argv:
