@@ -547,6 +547,16 @@ def kalman_smoother_segments(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0,
     return res
 
 
+def _or_over_segments(b, st, nb, S):
+    """The status words of the flattened (draw, segment) problems ORed per draw -> a fresh contiguous int32 (batch,) of the backend
+    (neither numpy nor torch reduces with a bitwise OR under one name: the at most 8 columns are folded)."""
+    st2 = st.reshape(nb, S)
+    acc = st2[:, 0] * 1
+    for s in range(1, S):
+        acc = acc | st2[:, s]
+    return b.inp(acc if b.host else acc.contiguous(), "int32")
+
+
 def _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options):
     """A .. D (batch, S, n, n | k): every (draw, segment) solved by the EXISTING solver entry on the flattened batch, the segments'
     status words ORed per draw (array operations of the backend: no host round trip on the device).  Returns T (batch, S, n, n),
@@ -578,11 +588,7 @@ def _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_it
         else:
             call(b, "dsge_backward_direct_batched", A=Af, B=Bf, D=Df, batch=flat, n=n, k=k, T_out=T, R_out=R)
             st = st * 0  # (this solver reports nothing)
-    st2 = st.reshape(nb, S)
-    acc = st2[:, 0] * 1
-    for s in range(1, S):
-        acc = acc | st2[:, s]
-    acc = b.inp(acc if b.host else acc.contiguous(), "int32")
+    acc = _or_over_segments(b, st, nb, S)
     return T.reshape(nb, S, n, n), R.reshape(nb, S, n, k), acc
 
 
@@ -601,6 +607,94 @@ def solve_kalman_smoother_segments(b, name, A, B, C, D, Q, Z, y, seg_start, *, s
     T, R, acc = _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options)
     res = kalman_smoother_segments(b, name, T, R, Q, Z, y, seg_start, status=acc, options=options, **smoother_kw)
     res.update(T=T, R=R)
+    return res
+
+
+SEGMENT_GRADIENT_OUTPUTS = ("T_bar", "R_bar", "q_bar", "Z_bar", "d_bar", "h_bar", "shift_bar", "a0_bar", "P0_bar")
+MAX_N_ADJOINT = 56  # dsge_selection_adjoints_batched, dsge_policy_adjoints_batched
+
+
+def segment_gradient_scratch_bytes_per_draw(m, T_len, n_seg):
+    """What ``scratch_limit_bytes`` of the gradient across breaks counts per draw: ``2 T_len m^2 + 2 T_len m`` doubles of the stored
+    forward pass and ``2 n_seg m^2`` of the accumulators of ``T_bar`` and of the cotangent of ``sym(R Q R')``."""
+    return 8 * (2 * T_len * m * m + 2 * T_len * m + 2 * n_seg * m * m)
+
+
+def kalman_logp_segments_grad(b, name, T, R, Q, Z, y, seg_start, *, Hdiag, d, a0, P0, shift, q_mode, status, jitter, missing_fill,
+                              scratch_limit_bytes, options, outputs=SEGMENT_GRADIENT_OUTPUTS, out=None):
+    """``dsge_kalman_logp_segments_grad_batched``: the inputs of ``kalman_logp_segments``.  ``outputs``: which of
+    ``SEGMENT_GRADIENT_OUTPUTS`` are computed (logp always is; "Q_bar" is accepted for "q_bar"); ``out``: buffers to reuse.  The
+    cotangent of the shock covariance is returned as ``q_bar`` (batch, S, k) for a diagonal layout and as ``Q_bar`` (batch, S, k, k)
+    for a full one, per draw also when the covariance is shared."""
+    a, _seg = _segment_inputs(b, name, T, R, Q, Z, y, seg_start, Hdiag, d, a0, P0, shift, q_mode)
+    nb, S, m, k, p = a["batch"], a["n_seg"], a["m"], a["k"], a["p"]
+    if m > _lib.MAX_N or p > _lib.MAX_P:
+        raise ValueError(f"{name}: m = {m}, p = {p}; the gradient takes at most {_lib.MAX_N} variables and {_lib.MAX_P} series")
+    full = a["q_mode"] in (_lib.Q_FULL_SHARED, _lib.Q_FULL_BATCHED)
+    qkey = "Q_bar" if full else "q_bar"
+    outputs = tuple("q_bar" if key == "Q_bar" else key for key in outputs)
+    if not set(outputs) <= set(SEGMENT_GRADIENT_OUTPUTS):
+        raise ValueError(f"outputs must be among {SEGMENT_GRADIENT_OUTPUTS}; got {outputs}")
+    limit = 0 if scratch_limit_bytes is None else int(scratch_limit_bytes)
+    if limit < 0:
+        raise ValueError("scratch_limit_bytes must be >= 0")
+    st = check_status(b.status_io(status, nb), nb)
+    out = dict(out or {})
+    if "Q_bar" in out:
+        out["q_bar"] = out.pop("Q_bar")
+    shapes = dict(T_bar=(nb, S, m, m), R_bar=(nb, S, m, k), q_bar=(nb, S, k, k) if full else (nb, S, k), Z_bar=(nb, S, p, m),
+                  d_bar=(nb, S, p), h_bar=(nb, S, p), shift_bar=(nb, S, m), a0_bar=(nb, m), P0_bar=(nb, m, m))
+    res = {key: _out(b, out.get(key), shape) if key in outputs or out.get(key) is not None else None for key, shape in shapes.items()}
+    logp = _out(b, out.get("logp"), (nb,))
+    with _lib.options_scope(options):  # (the filter conventions: _lib.filter_conventions)
+        call(b, "dsge_kalman_logp_segments_grad_batched", **a, jitter=jitter, missing_fill=missing_fill, scratch_limit_bytes=limit,
+             logp_out=logp, T_bar=res["T_bar"], R_bar=res["R_bar"], Q_bar=res["q_bar"], Z_bar=res["Z_bar"], d_bar=res["d_bar"],
+             h_bar=res["h_bar"], shift_bar=res["shift_bar"], a0_bar=res["a0_bar"], P0_bar=res["P0_bar"], status_io=st)
+    res[qkey] = res.pop("q_bar")
+    res.update(logp=logp, status=st)
+    return res
+
+
+def solve_kalman_logp_segments_grad(b, name, A, B, C, D, Q, Z, y, seg_start, *, solver, tol, max_iter, n_lead_hint, options,
+                                    **grad_kw):
+    """``_solve_segments``, the gradient across breaks, then the pullbacks of R = -(C T + B)^-1 D and of the policy function on the
+    flattened batch (``dsge_selection_adjoints_batched``, ``dsge_policy_adjoints_batched``, the cotangents of T summed between
+    them).  Returns the gradient's dict plus ``A_bar``, ``B_bar``, ``C_bar`` (batch, S, n, n), ``D_bar`` (batch, S, n, k), ``T`` and
+    ``R``.  A draw whose solve or adjoint fails in any segment gets -inf, the OR of the bits and zero cotangents."""
+    if solver == "backward_direct":
+        raise ValueError(f"{name}: backward_direct has no adjoint entry; the solvers are cycle_reduction and gensys")
+    Ash = () if A is None else tuple(b.inp(A).shape)
+    if len(Ash) == 4 and Ash[2] > MAX_N_ADJOINT:
+        raise ValueError(f"{name}: n = {Ash[2]}, the adjoint entries take at most {MAX_N_ADJOINT} variables")
+    T, R, acc = _solve_segments(b, name, A, B, C, D, Q, Z, y, seg_start, solver, tol, max_iter, n_lead_hint, options)
+    grad_kw["outputs"] = tuple(dict.fromkeys((*grad_kw.get("outputs", SEGMENT_GRADIENT_OUTPUTS), "T_bar", "R_bar")))
+    res = kalman_logp_segments_grad(b, name, T, R, Q, Z, y, seg_start, status=acc, options=options, **grad_kw)
+    nb, S, n, _ = T.shape
+    k, flat = R.shape[3], nb * S
+    Bf, Cf = (b.inp(x).reshape(flat, n, n) for x in (B, C))
+    Tf, Rf = T.reshape(flat, n, n), R.reshape(flat, n, k)
+    Bs, Cs, Ts = (b.empty((flat, n, n)) for _ in range(3))
+    Db = b.empty((flat, n, k))
+    call(b, "dsge_selection_adjoints_batched", B=Bf, C=Cf, T=Tf, R=Rf, R_bar=res["R_bar"].reshape(flat, n, k), batch=flat, n=n, k=k,
+         B_bar=Bs, C_bar=Cs, D_bar=Db, T_bar=Ts)
+    Tsum = Ts + res["T_bar"].reshape(flat, n, n)
+    Ab, Bb, Cb = (b.empty((flat, n, n)) for _ in range(3))
+    ast = b.empty((flat,), "int32")
+    call(b, "dsge_policy_adjoints_batched", B=Bf, C=Cf, T=Tf, T_bar=b.inp(Tsum if b.host else Tsum.contiguous()), batch=flat, n=n,
+         A_bar=Ab, B_bar=Bb, C_bar=Cb, status=ast)
+    Bb, Cb = Bb + Bs, Cb + Cs
+    # a failed draw: the OR of the bits, -inf, zeros -- with array operations of the backend (no host round trip on the device)
+    xp = b.xp
+    # (the adjoint of a draw the filter skipped ran on zeros: its word says nothing, the draw keeps the filter's)
+    st = xp.where(res["status"] != 0, res["status"], _or_over_segments(b, ast, nb, S))
+    res["status"] = st
+    bad = st != 0
+    res["logp"][...] = xp.where(bad, xp.full_like(res["logp"], -np.inf), res["logp"])
+    res.update(A_bar=Ab.reshape(nb, S, n, n), B_bar=Bb.reshape(nb, S, n, n), C_bar=Cb.reshape(nb, S, n, n),
+               D_bar=Db.reshape(nb, S, n, k), T=T, R=R)
+    for key, val in res.items():
+        if key.endswith("_bar") and val is not None:
+            val[...] = xp.where(bad.reshape((nb,) + (1,) * (val.ndim - 1)), xp.zeros_like(val), val)
     return res
 
 

@@ -146,6 +146,9 @@ _DEVICE_ENTRIES = {
     "dsge_kalman_smoother_segments_batched": (f"T R Q q_mode {_OBS} a0 P0 shift y seg_start n_seg batch m k p T_len jitter missing_fill "
                                               "rank_tol scratch_limit_bytes full_cov ll_out a_pred_out a_filt_out p_pred_out p_filt_out "
                                               "a_smooth_out p_smooth_out eps_smooth_out status_io stream"),
+    "dsge_kalman_logp_segments_grad_batched": (f"T R Q q_mode {_OBS} a0 P0 shift y seg_start n_seg batch m k p T_len jitter missing_fill "
+                                               "scratch_limit_bytes logp_out T_bar R_bar Q_bar Z_bar d_bar h_bar shift_bar a0_bar P0_bar "
+                                               "status_io stream"),
     "dsge_simulation_smoother_batched": (f"{_FILTER} rank_tol scratch_limit_bytes x0 x0_batched eps eps_batched eta eta_batched "
                                          "n_paths ll_out x_out eps_out status_io stream"),
     "dsge_simulate_batched": "T R eps eps_batched x0 x0_batched status batch m k n_paths n_steps n_shock_steps x_out stream",

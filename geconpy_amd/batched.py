@@ -472,6 +472,43 @@ def solve_kalman_logp_segments_batched(A, B, C, D, q, Z, y, seg_start, Hdiag=Non
                                         outputs=outputs)
 
 
+segment_gradient_scratch_bytes_per_draw = F.segment_gradient_scratch_bytes_per_draw
+
+
+def kalman_logp_segments_grad_batched(T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None, jitter=JITTER_DEFAULT,
+                                      missing_fill_value=MISSING_FILL, scratch_limit_bytes=None, options=None,
+                                      outputs=F.SEGMENT_GRADIENT_OUTPUTS, q_mode=None, status=None, out=None):
+    """``logp`` of ``kalman_logp_segments_batched`` (same arguments, same layouts, the same bits) and its GRADIENT with respect to
+    every entry of every input, by a hand-written reverse sweep on the device (include/dsge_hip.h,
+    ``dsge_kalman_logp_segments_grad_batched``; docs/design/segmented_gradient.md).  ``outputs``: which of T_bar (batch, S, m, m),
+    R_bar (batch, S, m, k), q_bar (batch, S, k) -- returned as Q_bar (batch, S, k, k), the symmetric convention, for a full
+    covariance --, Z_bar (batch, S, p, m), d_bar, h_bar (batch, S, p), shift_bar (batch, S, m; row 0 zero), a0_bar (batch, m),
+    P0_bar (batch, m, m; zero unless ``P0`` is given) are computed; any subset has the bits of the full call.  Cotangents are per
+    draw also for shared inputs (sum over the batch).  A failed draw gets ``logp = -inf`` and zeros.  ``scratch_limit_bytes``
+    (default 2 GiB) counts ``segment_gradient_scratch_bytes_per_draw`` per draw.  Returns a dict of logp, the cotangents (None
+    where not asked for) and status."""
+    return F.kalman_logp_segments_grad(HOST, "kalman_logp_segments_grad_batched", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d, a0=a0,
+                                       P0=P0, shift=shift, q_mode=q_mode, status=status, jitter=jitter,
+                                       missing_fill=missing_fill_value, scratch_limit_bytes=scratch_limit_bytes, options=options,
+                                       outputs=outputs, out=out)
+
+
+def solve_kalman_logp_segments_grad_batched(A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                            solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                            missing_fill_value=MISSING_FILL, scratch_limit_bytes=None, options=None,
+                                            outputs=F.SEGMENT_GRADIENT_OUTPUTS, q_mode=None, n_lead_hint=0, out=None):
+    """``A .. D`` (batch, S, n, n | k), n <= 56, solved per (draw, segment) as ``solve_kalman_logp_segments_batched`` solves them
+    (``solver``: "cycle_reduction" or "gensys"; "backward_direct" has no adjoint and is refused), ``kalman_logp_segments_grad_batched``,
+    then the pullbacks through R and the policy function on the flattened batch.  Returns that dict plus A_bar, B_bar, C_bar
+    (batch, S, n, n), D_bar (batch, S, n, k), T and R.  A draw whose solve or adjoint fails in any segment gets ``-inf``, the OR of
+    the status bits and zero cotangents."""
+    return F.solve_kalman_logp_segments_grad(HOST, "solve_kalman_logp_segments_grad_batched", A, B, C, D, q, Z, y, seg_start,
+                                             solver=solver, tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options,
+                                             Hdiag=Hdiag, d=d, a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter,
+                                             missing_fill=missing_fill_value, scratch_limit_bytes=scratch_limit_bytes,
+                                             outputs=outputs, out=out)
+
+
 def smoother_scratch_bytes_per_draw(m, T_len):
     """Bytes of library scratch the smoother's forward pass stores per draw (what ``scratch_limit_bytes`` counts):
     ``2 T_len m^2 + 2 T_len m`` doubles."""

@@ -671,6 +671,55 @@ int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R,
   return hc.finish();
 }
 
+int dsge_kalman_logp_segments_grad_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                                int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                                const double* a0, const double* P0, const double* shift, const double* y,
+                                                const int32_t* seg_start, int n_seg, int batch, int m, int k, int p, int T_len,
+                                                double jitter, double missing_fill, size_t scratch_limit_bytes, double* logp_out,
+                                                double* T_bar, double* R_bar, double* Q_bar, double* Z_bar, double* d_bar,
+                                                double* h_bar, double* shift_bar, double* a0_bar, double* P0_bar, int32_t* status_io) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman_segments(batch, m, k, obs, q, seg_start, n_seg, T && R && logp_out && status_io);
+  if (rc) return rc;
+  HostCall hc;
+  if ((rc = hc.begin())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  // staged as the likelihood's twin stages them: batch * S "draws" (the shared ones as S); Q_bar is per draw in every layout
+  const size_t S = (size_t)n_seg, flat = (size_t)batch * S, mm = (size_t)m * m;
+  const size_t qw = q.diag() ? (size_t)k : (size_t)k * k;
+  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0, *dsh, *dy;
+  double *dlp, *dTb, *dRb, *dQb, *dZb, *ddb, *dhb, *dsb, *dab, *dPb;
+  int32_t* dS;
+  hc.in(&dT, T, flat * mm);
+  hc.in(&dR, R, flat * m * k);
+  hc.in(&dQ, Q, (q.batched() ? flat : S) * qw);
+  hc.in(&dZ, Z, (z_batched ? flat : S) * p * m);
+  hc.in(&dd, d, (d_batched ? flat : S) * p);
+  hc.in(&dH, Hdiag, (h_batched ? flat : S) * p);
+  hc.in(&da0, a0, (size_t)batch * m);
+  hc.in(&dP0, P0, (size_t)batch * mm);
+  hc.in(&dsh, shift, flat * m);
+  hc.in(&dy, y, (size_t)T_len * p);
+  hc.io(&dS, status_io, (size_t)batch);
+  hc.out(&dlp, logp_out, (size_t)batch);
+  hc.out(&dTb, T_bar, flat * mm);
+  hc.out(&dRb, R_bar, flat * m * k);
+  hc.out(&dQb, Q_bar, flat * qw);
+  hc.out(&dZb, Z_bar, flat * p * m);
+  hc.out(&ddb, d_bar, flat * p);
+  hc.out(&dhb, h_bar, flat * p);
+  hc.out(&dsb, shift_bar, flat * m);
+  hc.out(&dab, a0_bar, (size_t)batch * m);
+  hc.out(&dPb, P0_bar, (size_t)batch * mm);
+  if ((rc = hc.stage())) return rc;
+  if ((rc = dsge_kalman_logp_segments_grad_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dsh, dy,
+                                                   seg_start, n_seg, batch, m, k, p, T_len, jitter, missing_fill, scratch_limit_bytes,
+                                                   dlp, dTb, dRb, dQb, dZb, ddb, dhb, dsb, dab, dPb, dS, hc.stream())))
+    return rc;
+  return hc.finish();
+}
+
 int dsge_simulation_smoother_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* y,
                                           int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,

@@ -754,6 +754,100 @@ int dsge_kalman_smoother_segments_batched(const double* T, const double* R, cons
   return DSGE_SUCCESS;
 }
 
+// The gradient of the likelihood across dated breaks (docs/design/segmented_gradient.md), per chunk of draws on the caller's stream:
+// the chain of dsge_kalman_logp_segments_batched up to P0, the storing instantiation of its filter (logp, and the moments of every
+// period into library scratch), the reverse sweep over them, then R_bar / Q_bar from the cotangent of sym(R Q R').
+int dsge_kalman_logp_segments_grad_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                           const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                           int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                           size_t scratch_limit_bytes, double* logp_out, double* T_bar, double* R_bar, double* Q_bar,
+                                           double* Z_bar, double* d_bar, double* h_bar, double* shift_bar, double* a0_bar, double* P0_bar,
+                                           int32_t* status_io, void* stream) {
+  const ObsModel obs{Z, z_batched, d, d_batched, Hdiag, h_batched, y, p, T_len, jitter, missing_fill};
+  const ShockCov q{Q, q_mode};
+  int rc = check_kalman_segments(batch, m, k, obs, q, seg_start, n_seg, T && R && logp_out && status_io);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned flat_all = 0;
+  if ((rc = batch_grid(batch, n_seg, "segmented gradient: batch * n_seg exceeds 2^31 - 1", &flat_all))) return rc;
+  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT || kalman_segments_grad_lds_bytes(m, p) > LDS_LIMIT)
+    return fail(DSGE_ERR_TOO_LARGE, "segmented gradient: LDS budget exceeded");
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  const size_t S = (size_t)n_seg, mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k, tm = (size_t)T_len * m;
+  // per draw: the stored forward pass and the accumulators of Tbar and Gbar (Tbar's are counted also when the caller's T_bar serves)
+  const size_t per_draw = (2 * tm * m + 2 * tm + 2 * S * mm) * sizeof(double);
+  const size_t fit = scratch_limit_bytes / per_draw;
+  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const size_t cf = (size_t)chunk * S;
+  const bool gather = !P0 && n_seg > 1;
+  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr, *Tb = nullptr, *Gb = nullptr;
+  double *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
+  ScratchLayout lay;
+  lay.add(&RQR, cf * mm);
+  if (!q.batched()) lay.add(&Qx, cf * qw);
+  if (gather) {
+    lay.add(&T0, chunk * mm);
+    lay.add(&G0, chunk * mm);
+  }
+  if (!P0) lay.add(&P0s, chunk * mm);
+  if (!T_bar) lay.add(&Tb, cf * mm);
+  lay.add(&Gb, cf * mm);
+  lay.add(&ap, chunk * tm);
+  lay.add(&af, chunk * tm);
+  lay.add(&pp, chunk * tm * m);
+  lay.add(&pf, chunk * tm * m);
+  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
+  // (a shared Q repeats with period S: its first nb * S rows serve every chunk)
+  if (!q.batched() && (rc = launch_segment_rows(Qx, Q, cf, (int)qw, n_seg, 1, st))) return rc;
+  // every cotangent the sweep adds to, or writes for healthy draws only, starts from zero: a failed draw keeps the zeros
+  const size_t fa = (size_t)batch * S;
+  if (T_bar) HIP_TRY(hipMemsetAsync(T_bar, 0, sizeof(double) * fa * mm, st));
+  if (Z_bar) HIP_TRY(hipMemsetAsync(Z_bar, 0, sizeof(double) * fa * p * m, st));
+  if (d_bar) HIP_TRY(hipMemsetAsync(d_bar, 0, sizeof(double) * fa * p, st));
+  if (h_bar) HIP_TRY(hipMemsetAsync(h_bar, 0, sizeof(double) * fa * p, st));
+  if (shift_bar) HIP_TRY(hipMemsetAsync(shift_bar, 0, sizeof(double) * fa * m, st));
+  if (a0_bar) HIP_TRY(hipMemsetAsync(a0_bar, 0, sizeof(double) * (size_t)batch * m, st));
+  if (P0_bar) HIP_TRY(hipMemsetAsync(P0_bar, 0, sizeof(double) * (size_t)batch * mm, st));
+  auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
+  for (int c0 = 0; c0 < batch; c0 += chunk) {
+    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const size_t o = (size_t)c0, fo = o * S, nf = (size_t)nb * S;
+    const double *Tc = T + fo * mm, *Rc = R + fo * m * k, *P0c = P0 ? P0 + o * mm : nullptr;
+    const ShockCov qe = q.batched() ? q.at(fo, k) : ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+    int32_t* sc = status_io + o;
+    if ((rc = assemble_rqr(Rc, qe, (int)nf, m, k, RQR, nullptr, st))) return rc;
+    if (!P0c) {
+      const double* Ts = Tc;
+      double* Gs = RQR;
+      if (gather) {
+        if ((rc = launch_segment_rows(T0, Tc, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
+        if ((rc = launch_segment_rows(G0, RQR, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
+        Ts = T0;
+        Gs = G0;
+      }
+      if ((rc = assemble_p0_from_rqr(Ts, Gs, nb, m, P0s, sc, false, st))) return rc;
+      P0c = P0s;
+    }
+    const ObsModel oc = obs.at(fo, m);
+    if ((rc = launch_kalman_segments_grad_forward(Tc, RQR, P0c, a0 ? a0 + o * m : nullptr, shift ? shift + fo * m : nullptr, oc,
+                                                  seg_start, n_seg, nb, m, logp_out + o, ap, af, pp, pf, sc, st)))
+      return rc;
+    double* Tbc = T_bar ? T_bar + fo * mm : Tb;
+    if (!T_bar) HIP_TRY(hipMemsetAsync(Tb, 0, sizeof(double) * nf * mm, st));
+    if ((rc = launch_kalman_segments_grad(Tc, shift ? shift + fo * m : nullptr, oc, seg_start, n_seg, nb, m, P0 != nullptr, ap, af, pp,
+                                          pf, Tbc, Gb, at(Z_bar, fo * p * m), at(d_bar, fo * p), at(h_bar, fo * p),
+                                          at(shift_bar, fo * m), at(a0_bar, o * m), at(P0_bar, o * mm), sc, st)))
+      return rc;
+    if ((rc = launch_kalman_segments_grad_rq(Gb, Rc, qe, (int)nf, n_seg, m, k, at(R_bar, fo * m * k), at(Q_bar, fo * qw),
+                                             logp_out + o, sc, st)))
+      return rc;
+  }
+  return DSGE_SUCCESS;
+}
+
 // Joint posterior draws of the state path and the shocks (dsge_simsmooth.hpp): the smoother's forward pass and basis per chunk of
 // draws, x+ of every path through the propagation kernel, then the two path kernels -- all on the caller's stream.
 int dsge_simulation_smoother_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,

@@ -314,6 +314,20 @@ int launch_kalman_smoother_segments(const double* T, const double* R, const Shoc
                                     int32_t* status_flat, const double* a_pred, const double* a_filt, const double* p_pred,
                                     const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov, int32_t* status,
                                     hipStream_t st);
+// launch_kalman_seg_grad.hip (dsge_kalman_seg_grad.hpp): the gradient of the likelihood across dated breaks.  The storing forward
+// pass with logp; the reverse sweep over its scratch (Tbar: [batch][S][m][m] zeroed, the caller's or scratch; Gbar: scratch; the
+// other cotangents: the caller's, zeroed, each may be null); R_bar, Q_bar of the flattened batch * S from Gbar (q: a *_BATCHED
+// layout over it), zeros and logp = -inf for a failed draw
+size_t kalman_segments_grad_lds_bytes(int m, int p);
+int launch_kalman_segments_grad_forward(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
+                                        const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* logp,
+                                        double* ap_s, double* af_s, double* pp_s, double* pf_s, int32_t* status, hipStream_t st);
+int launch_kalman_segments_grad(const double* T, const double* shift, const ObsModel& o, const int32_t* seg_start, int n_seg, int batch,
+                                int m, int p0_given, const double* ap, const double* af, const double* pp, const double* pf,
+                                double* Tbar, double* Gbar, double* Zbar, double* dbar, double* hbar, double* shbar, double* a0bar,
+                                double* P0bar, const int32_t* status, hipStream_t st);
+int launch_kalman_segments_grad_rq(const double* Gbar, const double* R, const ShockCov& q, int flat, int n_seg, int m, int k,
+                                   double* Rbar, double* Qbar, double* logp, const int32_t* status, hipStream_t st);
 // launch_simsmooth.hip (dsge_simsmooth.hpp): the simulation smoother's forward (filter means of n_paths transformed data sets per
 // draw over the stored P_pred) and backward pass (smoother means, x+ / eps+ added) for groups of 16 paths per draw.  xp, a_pred,
 // a_filt: [batch][n_paths][T_len][m] (a_pred, a_filt: scratch); eps / eta: draw strides, 0 = shared; snap: [batch] scratch

@@ -58,8 +58,10 @@ __host__ __device__ inline size_t kseg_lds_doubles(int m, int p) {
          4 * KSEG_PMAX + 8;
 }
 
-// first period of segment s, or "never" behind the last one (constant indices only: the list lives in the kernel arguments)
-__device__ __forceinline__ int kseg_start(const KsegArgs& a, int s) {
+// first period of segment s, or "never" behind the last one (constant indices only: the list lives in the kernel arguments);
+// A: any argument struct with n_seg and seg_start[DSGE_MAX_SEGMENTS] (the filter's, and the reverse sweep's of dsge_kalman_seg_grad.hpp)
+template <class A>
+__device__ __forceinline__ int kseg_start(const A& a, int s) {
   int v = 0x7fffffff;
 #pragma unroll
   for (int q = 0; q < DSGE_MAX_SEGMENTS; ++q)

@@ -260,6 +260,31 @@ class LogpEngine:
                                             a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter, missing_fill=missing_fill_value,
                                             outputs=outputs, out=out)
 
+    def kalman_logp_segments_grad(self, T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                  jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, scratch_limit_bytes=None, options=None,
+                                  outputs=F.SEGMENT_GRADIENT_OUTPUTS, q_mode=None, status=None, out=None):
+        """``logp`` across dated structural breaks and its gradient with respect to every input
+        (``dsge_kalman_logp_segments_grad_batched``; see ``batched.kalman_logp_segments_grad_batched``) from device tensors, on
+        torch's current stream.  ``seg_start`` is a HOST list.  ``out``: optional dict of preallocated outputs (``logp`` and the
+        names of ``outputs``).  Returns a dict of device tensors (None where not asked for) and status; asynchronous."""
+        return F.kalman_logp_segments_grad(self.backend, "kalman_logp_segments_grad", T, R, q, Z, y, seg_start, Hdiag=Hdiag, d=d,
+                                           a0=a0, P0=P0, shift=shift, q_mode=q_mode, status=status, jitter=jitter,
+                                           missing_fill=missing_fill_value, scratch_limit_bytes=scratch_limit_bytes,
+                                           options=options, outputs=outputs, out=out)
+
+    def solve_kalman_logp_segments_grad(self, A, B, C, D, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
+                                        solver="cycle_reduction", tol=1e-6, max_iter=50, jitter=JITTER_DEFAULT,
+                                        missing_fill_value=MISSING_FILL, scratch_limit_bytes=None, options=None,
+                                        outputs=F.SEGMENT_GRADIENT_OUTPUTS, q_mode=None, n_lead_hint=0, out=None):
+        """``A .. D`` [batch][S][n][n|k] (n <= 56) solved as ``solve_kalman_logp_segments`` solves them, ``kalman_logp_segments_grad``,
+        then the adjoint entries on the flattened batch (``batched.solve_kalman_logp_segments_grad_batched``): its dict plus
+        ``A_bar`` .. ``D_bar``, ``T`` and ``R``.  Failed draws are ORed and zeroed with tensor operations; asynchronous."""
+        return F.solve_kalman_logp_segments_grad(self.backend, "solve_kalman_logp_segments_grad", A, B, C, D, q, Z, y, seg_start,
+                                                 solver=solver, tol=tol, max_iter=max_iter, n_lead_hint=n_lead_hint, options=options,
+                                                 Hdiag=Hdiag, d=d, a0=a0, P0=P0, shift=shift, q_mode=q_mode, jitter=jitter,
+                                                 missing_fill=missing_fill_value, scratch_limit_bytes=scratch_limit_bytes,
+                                                 outputs=outputs, out=out)
+
     def kalman_smoother_segments(self, T, R, q, Z, y, seg_start, Hdiag=None, d=None, a0=None, P0=None, shift=None,
                                  jitter=JITTER_DEFAULT, missing_fill_value=MISSING_FILL, full_covariances=False, rank_tol=None,
                                  scratch_limit_bytes=None, options=None, outputs=F.SEGMENT_SMOOTHER_OUTPUTS, q_mode=None, status=None,

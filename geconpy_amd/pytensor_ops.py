@@ -350,6 +350,112 @@ class HipSolveKalmanLogpGrad(Op):
             cell[0] = out[key]
 
 
+class _SegmentsOp(Op):
+    """What the two Ops across dated breaks share: the data, the break dates, the conventions and the layout of the shock
+    covariance are PROPS (constants of the model; ``y`` is kept as bytes so that the Op hashes), the system matrices are inputs."""
+
+    __props__ = ("y_shape", "y_bytes", "seg_start", "q_mode", "jitter", "missing_fill_value", "conventions")
+
+    def __init__(self, y, seg_start, q_mode=None, jitter=batched.JITTER_DEFAULT, missing_fill_value=batched.MISSING_FILL,
+                 conventions=None):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 2:
+            raise ValueError(f"y must be (T_len, p); got {y.shape}")
+        self.y_shape, self.y_bytes = tuple(y.shape), y.tobytes()
+        self.seg_start = tuple(int(s) for s in batched.F.segment_starts(seg_start, y.shape[0]))
+        if q_mode is not None and q_mode not in batched.F.Q_MODES:
+            raise ValueError(f"q_mode must be one of {tuple(batched.F.Q_MODES)} or None; got {q_mode!r}")
+        self.q_mode = q_mode
+        self.jitter = jitter
+        self.missing_fill_value = missing_fill_value
+        self.conventions = _conventions_prop(conventions)
+        if _HAVE_PYTENSOR:
+            super().__init__()
+
+    @property
+    def y(self):
+        return np.frombuffer(self.y_bytes, dtype=np.float64).reshape(self.y_shape)
+
+    def _kwargs(self):
+        return dict(q_mode=self.q_mode, jitter=self.jitter, missing_fill_value=self.missing_fill_value,
+                    options=_conventions_options(self.conventions))
+
+
+class HipKalmanLogpSegments(_SegmentsOp):
+    """Log-likelihood across dated structural breaks per draw: ``logp = Op(T, R, q, Z, d, Hdiag, shift)``
+    (``batched.kalman_logp_segments_batched``; a0 = 0 and the stationary P0 of segment 0).  T: (batch, S, m, m); R: (batch, S, m, k);
+    q: (S, k), (batch, S, k), (S, k, k) or (batch, S, k, k); Z: (S, p, m) or (batch, S, p, m); d, Hdiag: (S, p) or (batch, S, p);
+    shift: (batch, S, m).  Failed draws give -inf.  ``pullback`` runs the device's reverse sweep (``HipKalmanLogpSegmentsGrad``)."""
+
+    def make_node(self, T, R, q, Z, d, Hdiag, shift):
+        _require()
+        inputs = [pt.as_tensor(x) for x in (T, R, q, Z, d, Hdiag, shift)]
+        return Apply(self, inputs, [pt.tensor("logp", dtype="float64", shape=inputs[0].type.shape[:1])])
+
+    def infer_shape(self, fgraph, node, input_shapes):
+        return [(input_shapes[0][0],)]
+
+    def perform(self, node, inputs, outputs):
+        T, R, q, Z, d, Hdiag, shift = inputs
+        out = batched.kalman_logp_segments_batched(T, R, q, Z, self.y, self.seg_start, Hdiag=Hdiag, d=d, shift=shift, outputs=("logp",),
+                                                   **self._kwargs())
+        outputs[0][0] = out["logp"]
+
+    def pullback(self, inputs, outputs, cotangents):
+        """Cotangents of T, R, q, Z, d, Hdiag, shift: the per-draw ones of the reverse sweep times the cotangent of logp; an input
+        shared by the draws (no leading draw axis) receives the sum over the batch."""
+        T, R, q, Z, d, Hdiag, shift = inputs
+        g = cotangents[0]
+        bars = HipKalmanLogpSegmentsGrad(self.y, self.seg_start, q_mode=self.q_mode, jitter=self.jitter,
+                                         missing_fill_value=self.missing_fill_value,
+                                         conventions=None if self.conventions is None else dict(self.conventions))(*inputs)
+        out = []
+        for x, bar in zip(inputs, bars):
+            w = bar * g.reshape((-1,) + (1,) * (bar.type.ndim - 1))
+            out.append(w.sum(axis=0) if x.type.ndim < bar.type.ndim else w)
+        return out
+
+
+class HipKalmanLogpSegmentsGrad(_SegmentsOp):
+    """``T_bar, R_bar, q_bar, Z_bar, d_bar, h_bar, shift_bar = Op(T, R, q, Z, d, Hdiag, shift)`` per draw, for a unit cotangent of
+    logp (``batched.kalman_logp_segments_grad_batched``): every output has the leading draw axis, also where its input is shared;
+    q_bar is (batch, S, k) for a diagonal covariance and (batch, S, k, k), the symmetric convention, for a full one."""
+
+    def make_node(self, T, R, q, Z, d, Hdiag, shift):
+        _require()
+        inputs = [pt.as_tensor(x) for x in (T, R, q, Z, d, Hdiag, shift)]
+        T_ = inputs[0]
+        b = T_.type.shape[:1]
+        full = self._q_full(len(inputs[2].type.shape))
+        outputs = []
+        for x, name, nd in zip(inputs, ("T_bar", "R_bar", "q_bar", "Z_bar", "d_bar", "h_bar", "shift_bar"), (4, 4, 4 if full else 3, 4, 3, 3, 3)):
+            shape = tuple(x.type.shape)
+            outputs.append(pt.tensor(name, dtype="float64", shape=shape if len(shape) == nd else b + shape))
+        return Apply(self, inputs, outputs)
+
+    def _q_full(self, ndim):
+        """Whether q is a full covariance: by ``q_mode``, else by its number of axes -- (S, k) and (batch, S, k, k) are unambiguous,
+        three axes are (batch, S, k) or (S, k, k) and need ``q_mode``."""
+        if self.q_mode is not None:
+            return self.q_mode in ("full", "full_batched")
+        if ndim == 3:
+            raise ValueError("q with three axes is (batch, S, k) or (S, k, k): pass q_mode")
+        return ndim == 4
+
+    def infer_shape(self, fgraph, node, input_shapes):
+        b = input_shapes[0][0]
+        return [tuple(s) if len(s) == out.type.ndim else (b, *s) for s, out in zip(input_shapes, node.outputs)]
+
+    def perform(self, node, inputs, outputs):
+        T, R, q, Z, d, Hdiag, shift = inputs
+        out = batched.kalman_logp_segments_grad_batched(T, R, q, Z, self.y, self.seg_start, Hdiag=Hdiag, d=d, shift=shift,
+                                                        outputs=("T_bar", "R_bar", "q_bar", "Z_bar", "d_bar", "h_bar", "shift_bar"),
+                                                        **self._kwargs())
+        qb = out["Q_bar"] if "Q_bar" in out else out["q_bar"]
+        for cell, val in zip(outputs, (out["T_bar"], out["R_bar"], qb, out["Z_bar"], out["d_bar"], out["h_bar"], out["shift_bar"])):
+            cell[0] = val
+
+
 class HipGensys(Op):
     """Drop-in for ``GensysWrapper`` (gEconpy/solvers/gensys.py:634-676): ``T, success = Op(A, B, C, D)``
     with ``__props__ = ("tol",)``, the same ``gufunc_signature``, ``T`` (n, n) of dtype floatX (as upstream) and a boolean

@@ -59,7 +59,7 @@ extern "C" {
 /* Still ABI 19: dsge_kalman_logp_segments_batched (+ _host) and DSGE_MAX_SEGMENTS were added WITHOUT a new version number -- two new
  * symbols and one constant, nothing else changed; a caller built against the earlier ABI 19 header runs unchanged (backward
  * compatible), a caller of the new entry must load a library that exports it.  dsge_kalman_smoother_segments_batched (+ _host)
- * followed the same way: two new symbols, nothing else changed. */
+ * followed the same way: two new symbols, nothing else changed; so did dsge_kalman_logp_segments_grad_batched (+ _host). */
 
 /* limits of this build */
 #define DSGE_MAX_N 64      /* model variables n == Kalman states m */
@@ -845,6 +845,47 @@ int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R,
                                                int full_cov, double* ll_out, double* a_pred_out, double* a_filt_out,
                                                double* p_pred_out, double* p_filt_out, double* a_smooth_out, double* p_smooth_out,
                                                double* eps_smooth_out, int32_t* status_io);
+
+/*
+ * The GRADIENT OF THE LIKELIHOOD ACROSS DATED STRUCTURAL BREAKS per draw (docs/design/segmented_gradient.md): logp of
+ * dsge_kalman_logp_segments_batched and its cotangent with respect to every entry of every input, each entry taken as independent,
+ * by a hand-written reverse sweep over the stored forward pass (csrc/dsge_kalman_seg_grad.hpp).  Arguments T .. missing_fill as
+ * dsge_kalman_logp_segments_batched (same layouts, seg_start in HOST memory), scratch_limit_bytes as
+ * dsge_kalman_smoother_segments_batched (0: 2 GiB; at least one draw per chunk; the per-draw figure is 2 T_len m^2 + 2 T_len m
+ * doubles of the stored forward pass plus 2 S m^2 of the accumulators), plus
+ *   logp_out         : [batch], required: the bits of dsge_kalman_logp_segments_batched on the same inputs
+ *   T_bar, R_bar     : [batch][S][m][m], [batch][S][m][k]
+ *   Q_bar            : [batch][S][k] for the diagonal modes, [batch][S][k][k] for the full ones -- ALWAYS per draw, also for a shared Q
+ *                      (the caller sums).  Full: R_s' sym(Gbar_s) R_s, Gbar_s the cotangent of sym(R_s Q_s R_s'): the gradient of the
+ *                      symmetric parametrisation, as q_bar of dsge_solve_kalman_logp_grad_batched
+ *   Z_bar            : [batch][S][p][m]                      (per draw also for shared Z, d, Hdiag)
+ *   d_bar, h_bar     : [batch][S][p]; computed whether or not d / Hdiag were NULL (the gradient at 0)
+ *   shift_bar        : [batch][S][m]; row 0 is zero
+ *   a0_bar, P0_bar   : [batch][m], [batch][m][m]; a0_bar also when a0 was NULL (the gradient at 0); P0_bar is the symmetric
+ *                      cotangent of a symmetric P0 and is written only when P0 is given (else zeros: P0 is dlyap(T_0, .), whose
+ *                      adjoint has gone into T_bar, R_bar and Q_bar of segment 0)
+ *   every cotangent may be NULL; any subset gives the bits of the full call, and so does a chunked call
+ *   status_io        : [batch] in/out.  A draw with a non-zero incoming status, DSGE_ST_LYAP_FAIL or DSGE_ST_FILTER_NONFINITE gets
+ *                      logp = -inf and ZERO cotangents (the convention of dsge_solve_kalman_logp_grad_batched); every other draw is
+ *                      untouched, bit for bit
+ * m <= DSGE_MAX_N, p <= DSGE_MAX_P (else DSGE_ERR_TOO_LARGE), S <= DSGE_MAX_SEGMENTS; refusals as dsge_kalman_logp_segments_batched.
+ * batch == 0 or T_len == 0: success, nothing touched.  No host synchronisation, no atomics: a pure enqueue on the caller's stream,
+ * two calls give the same bits.  Added WITHOUT a new ABI version number, like the two entries across breaks before it.
+ */
+int dsge_kalman_logp_segments_grad_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
+                                           const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
+                                           const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
+                                           int batch, int m, int k, int p, int T_len, double jitter, double missing_fill,
+                                           size_t scratch_limit_bytes, double* logp_out, double* T_bar, double* R_bar, double* Q_bar,
+                                           double* Z_bar, double* d_bar, double* h_bar, double* shift_bar, double* a0_bar, double* P0_bar,
+                                           int32_t* status_io, void* stream);
+int dsge_kalman_logp_segments_grad_batched_host(const double* T, const double* R, const double* Q, int q_mode, const double* Z,
+                                                int z_batched, const double* d, int d_batched, const double* Hdiag, int h_batched,
+                                                const double* a0, const double* P0, const double* shift, const double* y,
+                                                const int32_t* seg_start, int n_seg, int batch, int m, int k, int p, int T_len,
+                                                double jitter, double missing_fill, size_t scratch_limit_bytes, double* logp_out,
+                                                double* T_bar, double* R_bar, double* Q_bar, double* Z_bar, double* d_bar,
+                                                double* h_bar, double* shift_bar, double* a0_bar, double* P0_bar, int32_t* status_io);
 
 /*
  * SIMULATION SMOOTHER (ABI 12; csrc/dsge_simsmooth.hpp, docs/design/simulation_smoother.md): n_paths JOINT posterior draws of the

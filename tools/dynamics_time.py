@@ -10,6 +10,7 @@
     python tools/dynamics_time.py --stochastic-bound [draws ...]  the rows of the stochastic simulation at the bound alone
     python tools/dynamics_time.py --segmented [draws ...]         the rows of the Kalman likelihood across dated breaks alone
     python tools/dynamics_time.py --segmented-smoother [--library PATH] [--scratch-limit-gib G] [draws ...]   the smoother across breaks
+    python tools/dynamics_time.py --segmented-gradient [--library PATH] [--scratch-limit-gib G] [draws ...]   the gradient across breaks
 
 Per batch size, with device-resident inputs and outputs, after a warm-up and over >= 1 s of timed work each:
   * LogpEngine.impulse_response (unit impulses, c = 7) and LogpEngine.simulate (16 paths, shocks at every step), each against a
@@ -59,6 +60,11 @@ Per batch size, with device-resident inputs and outputs, after a warm-up and ove
     of >= 1 s each of LogpEngine.kalman_smoother_segments (ll, smoothed states and shocks; with diagonal covariances and without
     covariances) with S = 1, S = 3 and S = 8, against dsge_kalman_smoother_batched on the inputs of S = 1 -- of this build and of
     the library at PATH (a build of another commit) in the same run -- with the cost per boundary and whether S = 1 has its bits.
+  * --segmented-gradient [--library PATH] [--scratch-limit-gib G] (docs/design/segmented_gradient.md), the batch of --segmented: the
+    median of five timings of >= 1 s each of LogpEngine.kalman_logp_segments_grad (every cotangent) with S = 1, S = 3 and S = 8, next
+    to dsge_kalman_logp_segments_batched (logp alone) on the same inputs -- of the library at PATH (a build of the parent commit)
+    loaded in the same process, else of this build -- with the ratio gradient / likelihood, whether logp has the likelihood's
+    bits, and for scale the cost of the same gradient of T alone by central differences (stated, not run).
 Kernel times proper: rocprofv3 --kernel-trace --stats -- python tools/dynamics_time.py 4096."""
 import os
 import sys
@@ -728,6 +734,60 @@ def segmented_smoother_rows(eng, sizes, other_lib=None, scratch_limit=0, T_len=2
                   f"{(t[0] - one[0]) / max(S - 1, 1) * 1e3:8.1f} us, {(t[1] - one[1]) / max(S - 1, 1) * 1e3:8.1f} us")
 
 
+def segmented_gradient_rows(eng, sizes, other_lib=None, scratch_limit=0, T_len=200, repeats=5):
+    """The gradient of the likelihood across dated breaks (docs/design/segmented_gradient.md) on the SW-shaped batch of
+    ``segmented_rows``: every cotangent, S = 1, S = 3 with breaks at 80 and 140, S = 8, next to dsge_kalman_logp_segments_batched
+    (logp alone) of the library at ``--library PATH`` (a build of the parent commit; this build's without it) on the same inputs."""
+    import ctypes
+
+    name = "dsge_kalman_logp_segments_batched"
+    lib = _lib.load()
+    if other_lib:
+        lib = ctypes.CDLL(other_lib)
+        getattr(lib, name).argtypes = _lib.PROTOTYPES[name]
+    b = wl.sw_shaped_batch(64)
+    om = wl.sw_shaped_observation_model()
+    R64 = np.stack([oracle.compute_selection_matrix(b["B"][i], b["C"][i], b["D"][i], b["T_star"][i]) for i in range(64)])
+    m, k, p = 40, 7, om["y"].shape[1]
+    y, H1, Z1 = eng.to_device(om["y"][:T_len]), om["Hdiag"], om["Z"]
+    breaks = {1: (0,), 3: (0, 80, 140), 8: tuple(range(0, T_len, T_len // 8))[:8]}
+    print(f"segmented gradient, SW shape m={m} k={k} p={p}, T_len={T_len}, scratch_limit_bytes={scratch_limit}; median of {repeats} "
+          f"timings of >= 1 s each; likelihood: {name} of {other_lib or 'this build'}")
+    med = lambda fn: float(np.median([timed(fn) for _ in range(repeats)]))  # noqa: E731
+    for nb in sizes:
+        for S, starts in breaks.items():
+            pick = (np.arange(nb)[:, None] + np.arange(S)[None, :]) % 64
+            Ts, Rs, qs = eng.to_device(b["T_star"][pick]), eng.to_device(R64[pick]), eng.to_device(b["sigma"][pick] ** 2)
+            Zs, Hs = eng.to_device(np.tile(Z1, (S, 1, 1))), eng.to_device(np.tile(H1, (S, 1)))
+            seg = np.ascontiguousarray(starts, dtype=np.int32)
+            logp = torch.empty(nb, dtype=torch.float64, device=eng.device)
+            st = torch.zeros(nb, dtype=torch.int32, device=eng.device)
+
+            def likelihood():
+                _lib.check(getattr(lib, name)(
+                    Ts.data_ptr(), Rs.data_ptr(), qs.data_ptr(), 1, Zs.data_ptr(), 0, None, 0, Hs.data_ptr(), 0, None, None, None,
+                    y.data_ptr(), seg.ctypes.data, S, nb, m, k, p, T_len, 1e-8, -9999.0, logp.data_ptr(), None, None, None, st.data_ptr(),
+                    eng._stream()))
+
+            t_lp = med(likelihood)
+            likelihood()
+            lp_kept = logp.clone()
+            out = {}
+
+            def gradient():
+                out.update(eng.kalman_logp_segments_grad(Ts, Rs, qs, Zs, y, starts, Hdiag=Hs, q_mode="diag_batched", status=st,
+                                                         scratch_limit_bytes=scratch_limit, out={key: v for key, v in out.items()
+                                                                                                  if key != "status"}))
+
+            t_g = med(gradient)
+            assert int(st.abs().max().item()) == 0
+            same = bool(torch.equal(out["logp"], lp_kept))
+            n_fd = 2 * m * m
+            print(f"draws={nb:5d} segments S={S} breaks {starts if S < 8 else 'every ' + str(T_len // 8)}: likelihood {t_lp:9.3f} ms | "
+                  f"gradient, every cotangent {t_g:9.3f} ms | gradient / likelihood {t_g / t_lp:6.2f} | logp bit-identical: {same} | "
+                  f"one T_s alone by central differences: {n_fd} likelihood calls = {n_fd * t_lp * 1e-3:9.1f} s (stated, not run)")
+
+
 def main():
     other_lib, scratch_limit = None, 0
     for flag in ("--library", "--scratch-limit-gib"):
@@ -739,8 +799,11 @@ def main():
                 scratch_limit = int(float(sys.argv[at + 1]) * 2 ** 30)
             del sys.argv[at:at + 2]
     args = [a for a in sys.argv[1:] if a not in ("--second-order", "--decomposition", "--conditional", "--spectral", "--anticipated",
-                                                 "--constrained", "--stochastic-bound", "--segmented", "--segmented-smoother")]
+                                                 "--constrained", "--stochastic-bound", "--segmented", "--segmented-smoother",
+                                                 "--segmented-gradient")]
     sizes = [int(a) for a in args] or [256, 4096]
+    if "--segmented-gradient" in sys.argv:
+        return segmented_gradient_rows(LogpEngine(0), sizes, other_lib, scratch_limit)
     if "--segmented-smoother" in sys.argv:
         return segmented_smoother_rows(LogpEngine(0), sizes, other_lib, scratch_limit)
     if "--second-order" in sys.argv:
