@@ -97,6 +97,23 @@ class HostCall {
     *dev = host;
     member(&dev->Q, host.Q, host.elems(batch, k), upload || !host.batched());
   }
+  // The ten inputs of a filter problem across dated breaks: every per-draw array carries the segment axis behind the draw axis, so
+  // they are staged as batch * S "draws" (the shared ones as S).  seg_start stays the HOST list.
+  void in(SegmentedProblem* dev, const SegmentedProblem& host) {
+    *dev = host;
+    const ObsModel& o = host.obs;
+    const size_t b = (size_t)host.batch, S = (size_t)host.n_seg, flat = host.flat(), m = (size_t)host.m, mm = m * m, p = (size_t)o.p;
+    in(&dev->T, host.T, flat * mm);
+    in(&dev->R, host.R, flat * m * host.k);
+    in(&dev->q.Q, host.q.Q, (host.q.batched() ? flat : S) * host.q_width());
+    in(&dev->obs.Z, o.Z, (o.z_batched ? flat : S) * p * m);
+    in(&dev->obs.d, o.d, (o.d_batched ? flat : S) * p);
+    in(&dev->obs.Hdiag, o.Hdiag, (o.h_batched ? flat : S) * p);
+    in(&dev->a0, host.a0, b * m);
+    in(&dev->P0, host.P0, b * mm);
+    in(&dev->shift, host.shift, flat * m);
+    in(&dev->obs.y, o.y, (size_t)o.T_len * p);
+  }
 
   // Ends the declarations: leases an arena that holds every declared buffer (each rounded up to 256 bytes), assigns the
   // addresses in declaration order and enqueues the uploads on stream 0.
@@ -555,31 +572,19 @@ int dsge_kalman_logp_segments_batched_host(const double* T, const double* R, con
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
-  // every per-draw array carries the segment axis behind the draw axis: staged as batch * S "draws" (the shared ones as S)
-  const size_t S = (size_t)n_seg, flat = (size_t)batch * S, mm = (size_t)m * m;
-  const size_t qw = q.diag() ? (size_t)k : (size_t)k * k;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0, *dsh, *dy;
+  SegmentedProblem ds;
   double *dlp, *dll, *dal, *dpl;
   int32_t* dS;
-  hc.in(&dT, T, flat * mm);
-  hc.in(&dR, R, flat * m * k);
-  hc.in(&dQ, Q, (q.batched() ? flat : S) * qw);
-  hc.in(&dZ, Z, (z_batched ? flat : S) * p * m);
-  hc.in(&dd, d, (d_batched ? flat : S) * p);
-  hc.in(&dH, Hdiag, (h_batched ? flat : S) * p);
-  hc.in(&da0, a0, (size_t)batch * m);
-  hc.in(&dP0, P0, (size_t)batch * mm);
-  hc.in(&dsh, shift, flat * m);
-  hc.in(&dy, y, (size_t)T_len * p);
+  hc.in(&ds, SegmentedProblem{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k});
   hc.io(&dS, status_io, (size_t)batch);
   hc.out(&dlp, logp_out, (size_t)batch);
   hc.out(&dll, ll_out, (size_t)batch * T_len);
   hc.out(&dal, a_last_out, (size_t)batch * m);
-  hc.out(&dpl, P_last_out, (size_t)batch * mm);
+  hc.out(&dpl, P_last_out, (size_t)batch * m * m);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_logp_segments_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dsh, dy,
-                                              seg_start, n_seg, batch, m, k, p, T_len, jitter, missing_fill, dlp, dll, dal, dpl, dS,
-                                              hc.stream())))
+  if ((rc = dsge_kalman_logp_segments_batched(ds.T, ds.R, ds.q.Q, q_mode, ds.obs.Z, z_batched, ds.obs.d, d_batched, ds.obs.Hdiag,
+                                              h_batched, ds.a0, ds.P0, ds.shift, ds.obs.y, seg_start, n_seg, batch, m, k, p, T_len,
+                                              jitter, missing_fill, dlp, dll, dal, dpl, dS, hc.stream())))
     return rc;
   return hc.finish();
 }
@@ -637,22 +642,11 @@ int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R,
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
-  // staged as the likelihood's twin stages them: batch * S "draws" (the shared ones as S)
-  const size_t S = (size_t)n_seg, flat = (size_t)batch * S, mm = (size_t)m * m, tm = (size_t)batch * T_len * m;
-  const size_t qw = q.diag() ? (size_t)k : (size_t)k * k, tc = full_cov ? tm * m : tm;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0, *dsh, *dy;
+  const size_t tm = (size_t)batch * T_len * m, tc = full_cov ? tm * m : tm;
+  SegmentedProblem ds;
   double *dll, *dap, *daf, *dpp, *dpf, *das, *dps, *des;
   int32_t* dS;
-  hc.in(&dT, T, flat * mm);
-  hc.in(&dR, R, flat * m * k);
-  hc.in(&dQ, Q, (q.batched() ? flat : S) * qw);
-  hc.in(&dZ, Z, (z_batched ? flat : S) * p * m);
-  hc.in(&dd, d, (d_batched ? flat : S) * p);
-  hc.in(&dH, Hdiag, (h_batched ? flat : S) * p);
-  hc.in(&da0, a0, (size_t)batch * m);
-  hc.in(&dP0, P0, (size_t)batch * mm);
-  hc.in(&dsh, shift, flat * m);
-  hc.in(&dy, y, (size_t)T_len * p);
+  hc.in(&ds, SegmentedProblem{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k});
   hc.io(&dS, status_io, (size_t)batch);
   hc.out(&dll, ll_out, (size_t)batch * T_len);
   hc.out(&dap, a_pred_out, tm);
@@ -663,10 +657,10 @@ int dsge_kalman_smoother_segments_batched_host(const double* T, const double* R,
   hc.out(&dps, p_smooth_out, tc);
   hc.out(&des, eps_smooth_out, (size_t)batch * T_len * k);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_smoother_segments_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dsh, dy,
-                                                  seg_start, n_seg, batch, m, k, p, T_len, jitter, missing_fill, rank_tol,
-                                                  scratch_limit_bytes, full_cov, dll, dap, daf, dpp, dpf, das, dps, des, dS,
-                                                  hc.stream())))
+  if ((rc = dsge_kalman_smoother_segments_batched(ds.T, ds.R, ds.q.Q, q_mode, ds.obs.Z, z_batched, ds.obs.d, d_batched, ds.obs.Hdiag,
+                                                  h_batched, ds.a0, ds.P0, ds.shift, ds.obs.y, seg_start, n_seg, batch, m, k, p,
+                                                  T_len, jitter, missing_fill, rank_tol, scratch_limit_bytes, full_cov, dll, dap, daf,
+                                                  dpp, dpf, das, dps, des, dS, hc.stream())))
     return rc;
   return hc.finish();
 }
@@ -685,22 +679,13 @@ int dsge_kalman_logp_segments_grad_batched_host(const double* T, const double* R
   HostCall hc;
   if ((rc = hc.begin())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
-  // staged as the likelihood's twin stages them: batch * S "draws" (the shared ones as S); Q_bar is per draw in every layout
-  const size_t S = (size_t)n_seg, flat = (size_t)batch * S, mm = (size_t)m * m;
-  const size_t qw = q.diag() ? (size_t)k : (size_t)k * k;
-  const double *dT, *dR, *dQ, *dZ, *dd, *dH, *da0, *dP0, *dsh, *dy;
+  // the cotangents carry the segment axis as the inputs do; Q_bar is per draw in every layout
+  const SegmentedProblem hs{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k};
+  const size_t flat = hs.flat(), mm = (size_t)m * m, qw = hs.q_width();
+  SegmentedProblem ds;
   double *dlp, *dTb, *dRb, *dQb, *dZb, *ddb, *dhb, *dsb, *dab, *dPb;
   int32_t* dS;
-  hc.in(&dT, T, flat * mm);
-  hc.in(&dR, R, flat * m * k);
-  hc.in(&dQ, Q, (q.batched() ? flat : S) * qw);
-  hc.in(&dZ, Z, (z_batched ? flat : S) * p * m);
-  hc.in(&dd, d, (d_batched ? flat : S) * p);
-  hc.in(&dH, Hdiag, (h_batched ? flat : S) * p);
-  hc.in(&da0, a0, (size_t)batch * m);
-  hc.in(&dP0, P0, (size_t)batch * mm);
-  hc.in(&dsh, shift, flat * m);
-  hc.in(&dy, y, (size_t)T_len * p);
+  hc.in(&ds, hs);
   hc.io(&dS, status_io, (size_t)batch);
   hc.out(&dlp, logp_out, (size_t)batch);
   hc.out(&dTb, T_bar, flat * mm);
@@ -713,9 +698,10 @@ int dsge_kalman_logp_segments_grad_batched_host(const double* T, const double* R
   hc.out(&dab, a0_bar, (size_t)batch * m);
   hc.out(&dPb, P0_bar, (size_t)batch * mm);
   if ((rc = hc.stage())) return rc;
-  if ((rc = dsge_kalman_logp_segments_grad_batched(dT, dR, dQ, q_mode, dZ, z_batched, dd, d_batched, dH, h_batched, da0, dP0, dsh, dy,
-                                                   seg_start, n_seg, batch, m, k, p, T_len, jitter, missing_fill, scratch_limit_bytes,
-                                                   dlp, dTb, dRb, dQb, dZb, ddb, dhb, dsb, dab, dPb, dS, hc.stream())))
+  if ((rc = dsge_kalman_logp_segments_grad_batched(ds.T, ds.R, ds.q.Q, q_mode, ds.obs.Z, z_batched, ds.obs.d, d_batched, ds.obs.Hdiag,
+                                                   h_batched, ds.a0, ds.P0, ds.shift, ds.obs.y, seg_start, n_seg, batch, m, k, p,
+                                                   T_len, jitter, missing_fill, scratch_limit_bytes, dlp, dTb, dRb, dQb, dZb, ddb, dhb,
+                                                   dsb, dab, dPb, dS, hc.stream())))
     return rc;
   return hc.finish();
 }

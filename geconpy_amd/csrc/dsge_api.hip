@@ -272,6 +272,68 @@ thread_local ThreadStream t_chunk[MAX_CHUNK_STREAMS];
 // Scratch of the device entry points (one arena per (device, stream), StreamArenaPool)
 StreamArenaPool g_scratch_pool;
 StreamArenaPool g_aug_big_pool;  // the gathered model of the augmented route beyond 64 states
+
+// The chain every entry across dated breaks (dsge_kalman_seg.hpp) runs up to P0, on the caller's stream: sym(R Q R') of every (draw,
+// segment) by the launch dsge_lyapunov_batched uses (the layouts flatten to batch * S draws; a shared Q is first repeated per draw),
+// P0 of segment 0 by the Lyapunov launch on T_0 and sym(R_0 Q_0 R_0') (gathered when S > 1) unless the caller gave P0.
+//
+//   SegmentChain ch;
+//   if ((rc = ch.declare(s, chunk, "segmented ...", other_lds_bytes))) return rc;  // the refusals; the chain's scratch at the head of ch.lay
+//   ch.lay.add(...);                                                               // the entry's own scratch behind it
+//   if ((rc = ch.reserve(s, st))) return rc;
+//   per chunk c = s.at(c0, nb):  if ((rc = ch.run(c, status_io + c0, st))) return rc;  then the filter on ch.RQR, ch.P0 (and ch.qe)
+struct SegmentChain {
+  ScratchLayout lay;
+  double* RQR = nullptr;     // [chunk][S][m][m]
+  const double* P0 = nullptr;  // after run(): the caller's P0 of the chunk, or the chain's
+  ShockCov qe;               // after run(): the chunk's Q in a *_BATCHED layout over its (draw, segment) problems
+
+  // `name` prefixes the refusals (DSGE_ERR_TOO_LARGE); other_lds_bytes: the LDS image of the entry's own kernel behind the filter
+  int declare(const SegmentedProblem& s, int chunk, const char* name, size_t other_lds_bytes) {
+    unsigned flat_all = 0;
+    if (int rc = batch_grid(s.batch, s.n_seg, (std::string(name) + ": batch * n_seg exceeds 2^31 - 1").c_str(), &flat_all)) return rc;
+    if (kalman_segments_lds_bytes(s.m, s.obs.p) > LDS_LIMIT || other_lds_bytes > LDS_LIMIT)
+      return fail(DSGE_ERR_TOO_LARGE, std::string(name) + ": LDS budget exceeded");
+    const size_t mm = (size_t)s.m * s.m;
+    rows_ = (size_t)chunk * s.n_seg;
+    lay.add(&RQR, rows_ * mm);
+    if (!s.q.batched()) lay.add(&Qx_, rows_ * s.q_width());
+    if (!s.P0 && s.n_seg > 1) {
+      lay.add(&T0_, chunk * mm);
+      lay.add(&G0_, chunk * mm);
+    }
+    if (!s.P0) lay.add(&P0s_, chunk * mm);
+    return DSGE_SUCCESS;
+  }
+  int reserve(const SegmentedProblem& s, hipStream_t st) {
+    if (int rc = lay.reserve(g_scratch_pool, st)) return rc;
+    // (a shared Q repeats with period S: its first nb * S rows serve every chunk)
+    return s.q.batched() ? DSGE_SUCCESS : launch_segment_rows(Qx_, s.q.Q, rows_, (int)s.q_width(), s.n_seg, 1, st);
+  }
+  int run(const SegmentedProblem& c, int32_t* status, hipStream_t st) {
+    const int mm = c.m * c.m;
+    int rc;
+    qe = c.q.batched() ? c.q : ShockCov{Qx_, c.q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+    // (no status here: a skipped draw's product is never read, and the words are per draw, not per (draw, segment))
+    if ((rc = assemble_rqr(c.R, qe, (int)c.flat(), c.m, c.k, RQR, nullptr, st))) return rc;
+    P0 = c.P0;
+    if (P0) return DSGE_SUCCESS;
+    const double* Ts = c.T;
+    double* Gs = RQR;
+    if (c.n_seg > 1) {
+      if ((rc = launch_segment_rows(T0_, c.T, (size_t)c.batch, mm, c.batch, c.n_seg, st))) return rc;
+      if ((rc = launch_segment_rows(G0_, RQR, (size_t)c.batch, mm, c.batch, c.n_seg, st))) return rc;
+      Ts = T0_;
+      Gs = G0_;
+    }
+    P0 = P0s_;
+    return assemble_p0_from_rqr(Ts, Gs, c.batch, c.m, P0s_, status, false, st);
+  }
+
+ private:
+  double *Qx_ = nullptr, *T0_ = nullptr, *G0_ = nullptr, *P0s_ = nullptr;
+  size_t rows_ = 0;  // (draw, segment) problems of a full chunk
+};
 }  // namespace
 
 extern "C" {
@@ -558,9 +620,8 @@ int dsge_kalman_filter_outputs_batched(const double* T, const double* R, const d
                                status_io, st);
 }
 
-// The likelihood across dated breaks (dsge_kalman_seg.hpp), a chain on the caller's stream: sym(R Q R') of every (draw, segment) by the
-// launch dsge_lyapunov_batched uses (the layouts flatten to batch * S draws; a shared Q is first repeated per draw), P0 of segment 0
-// by the Lyapunov launch on T_0 and sym(R_0 Q_0 R_0') (gathered when S > 1) unless the caller gave P0, then the filter.
+// The likelihood across dated breaks (dsge_kalman_seg.hpp), a chain on the caller's stream: SegmentChain on the whole batch, then the
+// filter.
 int dsge_kalman_logp_segments_batched(const double* T, const double* R, const double* Q, int q_mode, const double* Z, int z_batched,
                                       const double* d, int d_batched, const double* Hdiag, int h_batched, const double* a0,
                                       const double* P0, const double* shift, const double* y, const int32_t* seg_start, int n_seg,
@@ -573,42 +634,12 @@ int dsge_kalman_logp_segments_batched(const double* T, const double* R, const do
   if ((rc = ensure_device())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  unsigned flat = 0;
-  if ((rc = batch_grid(batch, n_seg, "segmented filter: batch * n_seg exceeds 2^31 - 1", &flat))) return rc;
-  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT) return fail(DSGE_ERR_TOO_LARGE, "segmented filter: LDS budget exceeded");
-  const size_t mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k;
-  const bool gather = !P0 && n_seg > 1;
-  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr;
-  ScratchLayout lay;
-  lay.add(&RQR, flat * mm);
-  if (!q.batched()) lay.add(&Qx, flat * qw);
-  if (gather) {
-    lay.add(&T0, batch * mm);
-    lay.add(&G0, batch * mm);
-  }
-  if (!P0) lay.add(&P0s, batch * mm);
-  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  ShockCov qe = q;
-  if (!q.batched()) {
-    if ((rc = launch_segment_rows(Qx, Q, flat, (int)qw, n_seg, 1, st))) return rc;
-    qe = ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
-  }
-  // (no status here: a skipped draw's product is never read, and the words are per draw, not per (draw, segment))
-  if ((rc = assemble_rqr(R, qe, (int)flat, m, k, RQR, nullptr, st))) return rc;
-  if (!P0) {
-    const double* Ts = T;
-    double* Gs = RQR;
-    if (gather) {
-      if ((rc = launch_segment_rows(T0, T, (size_t)batch, (int)mm, batch, n_seg, st))) return rc;
-      if ((rc = launch_segment_rows(G0, RQR, (size_t)batch, (int)mm, batch, n_seg, st))) return rc;
-      Ts = T0;
-      Gs = G0;
-    }
-    if ((rc = assemble_p0_from_rqr(Ts, Gs, batch, m, P0s, status_io, false, st))) return rc;
-    P0 = P0s;
-  }
-  return launch_kalman_segments(T, RQR, P0, a0, shift, obs, seg_start, n_seg, batch, m, logp_out, ll_out, a_last_out, P_last_out,
-                                status_io, st);
+  const SegmentedProblem s{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k};
+  SegmentChain ch;
+  if ((rc = ch.declare(s, batch, "segmented filter", 0))) return rc;
+  if ((rc = ch.reserve(s, st))) return rc;
+  if ((rc = ch.run(s, status_io, st))) return rc;
+  return launch_kalman_segments(s, ch.RQR, ch.P0, logp_out, ll_out, a_last_out, P_last_out, status_io, st);
 }
 
 // Smoothed states, covariances and shocks (dsge_kalman_smooth.hpp): the forward pass is launch_kalman_outputs with full
@@ -626,11 +657,9 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   if (!(rank_tol > 0.0)) rank_tol = 1e-10;
-  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
   // the per-step filter outputs of one draw (the limit counts these; the per-draw matrices next to them are a few m^2)
   const size_t tm = (size_t)T_len * m, per_draw = (2 * tm * m + 2 * tm) * sizeof(double);
-  size_t fit = scratch_limit_bytes / per_draw;
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const int chunk = chunk_for(scratch_limit_bytes, per_draw, batch);
   const size_t mm = (size_t)chunk * m * m, img = (size_t)chunk * smoother_image_doubles(m);
   double *RQR = nullptr, *P0 = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr, *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
   double* ll = nullptr;
@@ -650,7 +679,7 @@ int dsge_kalman_smoother_batched(const double* T, const double* R, const double*
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   const size_t tc = full_cov ? tm * m : tm;
   for (int c0 = 0; c0 < batch; c0 += chunk) {
-    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const int nb = chunk_draws(batch, c0, chunk);
     const size_t o = (size_t)c0;
     const double *Tc = T + o * m * m, *Rc = R + o * m * k;
     const ShockCov qc = q.at(o, k);
@@ -686,68 +715,39 @@ int dsge_kalman_smoother_segments_batched(const double* T, const double* R, cons
   if ((rc = ensure_device())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  unsigned flat_all = 0;
-  if ((rc = batch_grid(batch, n_seg, "segmented smoother: batch * n_seg exceeds 2^31 - 1", &flat_all))) return rc;
-  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT || smoother_lds_bytes(m) > LDS_LIMIT)
-    return fail(DSGE_ERR_TOO_LARGE, "segmented smoother: LDS budget exceeded");
+  const SegmentedProblem s{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k};
   if (!(rank_tol > 0.0)) rank_tol = 1e-10;
-  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
-  const size_t S = (size_t)n_seg, mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k, tm = (size_t)T_len * m;
+  const size_t S = (size_t)n_seg, tm = (size_t)T_len * m;
   const size_t per_draw = (2 * tm * m + 2 * tm + 3 * S * smoother_image_doubles(m)) * sizeof(double);
-  const size_t fit = scratch_limit_bytes / per_draw;
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const int chunk = chunk_for(scratch_limit_bytes, per_draw, batch);
   const size_t cf = (size_t)chunk * S, img = cf * smoother_image_doubles(m);
-  const bool gather = !P0 && n_seg > 1, smooth = a_smooth_out || p_smooth_out || eps_smooth_out;
-  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr;
-  double *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
+  const bool smooth = a_smooth_out || p_smooth_out || eps_smooth_out;
+  double *U = nullptr, *UT = nullptr, *UR = nullptr, *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
   int32_t *rank = nullptr, *sflat = nullptr;
-  ScratchLayout lay;
-  lay.add(&RQR, cf * mm);
-  if (!q.batched()) lay.add(&Qx, cf * qw);
-  if (gather) {
-    lay.add(&T0, chunk * mm);
-    lay.add(&G0, chunk * mm);
-  }
-  if (!P0) lay.add(&P0s, chunk * mm);
-  lay.add(&U, img);
-  lay.add(&UT, img);
-  lay.add(&UR, img);
-  lay.add(&ap, chunk * tm);
-  lay.add(&af, chunk * tm);
-  lay.add(&pp, chunk * tm * m);
-  lay.add(&pf, chunk * tm * m);
-  lay.add(&rank, cf);
-  lay.add(&sflat, cf);
-  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  // (a shared Q repeats with period S: its first nb * S rows serve every chunk)
-  if (!q.batched() && (rc = launch_segment_rows(Qx, Q, cf, (int)qw, n_seg, 1, st))) return rc;
+  SegmentChain ch;
+  if ((rc = ch.declare(s, chunk, "segmented smoother", smoother_lds_bytes(m)))) return rc;
+  ch.lay.add(&U, img);
+  ch.lay.add(&UT, img);
+  ch.lay.add(&UR, img);
+  ch.lay.add(&ap, chunk * tm);
+  ch.lay.add(&af, chunk * tm);
+  ch.lay.add(&pp, chunk * tm * m);
+  ch.lay.add(&pf, chunk * tm * m);
+  ch.lay.add(&rank, cf);
+  ch.lay.add(&sflat, cf);
+  if ((rc = ch.reserve(s, st))) return rc;
   const size_t tc = full_cov ? tm * m : tm;
   auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
   for (int c0 = 0; c0 < batch; c0 += chunk) {
-    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
-    const size_t o = (size_t)c0, fo = o * S, nf = (size_t)nb * S;
-    const double *Tc = T + fo * mm, *Rc = R + fo * m * k, *P0c = P0 ? P0 + o * mm : nullptr;
-    const ShockCov qe = q.batched() ? q.at(fo, k) : ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+    const size_t o = (size_t)c0;
+    const SegmentedProblem c = s.at(o, chunk_draws(batch, c0, chunk));
     int32_t* sc = status_io + o;
-    if ((rc = assemble_rqr(Rc, qe, (int)nf, m, k, RQR, nullptr, st))) return rc;
-    if (!P0c) {
-      const double* Ts = Tc;
-      double* Gs = RQR;
-      if (gather) {
-        if ((rc = launch_segment_rows(T0, Tc, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
-        if ((rc = launch_segment_rows(G0, RQR, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
-        Ts = T0;
-        Gs = G0;
-      }
-      if ((rc = assemble_p0_from_rqr(Ts, Gs, nb, m, P0s, sc, false, st))) return rc;
-      P0c = P0s;
-    }
-    if ((rc = launch_kalman_segments_store(Tc, RQR, P0c, a0 ? a0 + o * m : nullptr, shift ? shift + fo * m : nullptr, obs.at(fo, m),
-                                           seg_start, n_seg, nb, m, at(ll_out, o * T_len), ap, af, pp, pf, at(a_pred_out, o * tm),
+    if ((rc = ch.run(c, sc, st))) return rc;
+    if ((rc = launch_kalman_segments_store(c, ch.RQR, ch.P0, nullptr, at(ll_out, o * T_len), ap, af, pp, pf, at(a_pred_out, o * tm),
                                            at(a_filt_out, o * tm), at(p_pred_out, o * tc), at(p_filt_out, o * tc), full_cov, sc, st)))
       return rc;
-    if (smooth && (rc = launch_kalman_smoother_segments(Tc, Rc, qe, seg_start, n_seg, nb, m, k, T_len, rank_tol, U, UT, UR, rank, sflat,
-                                                        ap, af, pp, pf, at(a_smooth_out, o * tm), at(p_smooth_out, o * tc),
+    if (smooth && (rc = launch_kalman_smoother_segments(c.T, c.R, ch.qe, seg_start, n_seg, c.batch, m, k, T_len, rank_tol, U, UT, UR, rank,
+                                                        sflat, ap, af, pp, pf, at(a_smooth_out, o * tm), at(p_smooth_out, o * tc),
                                                         at(eps_smooth_out, o * T_len * k), full_cov, sc, st)))
       return rc;
   }
@@ -771,37 +771,22 @@ int dsge_kalman_logp_segments_grad_batched(const double* T, const double* R, con
   if ((rc = ensure_device())) return rc;
   if (batch == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  unsigned flat_all = 0;
-  if ((rc = batch_grid(batch, n_seg, "segmented gradient: batch * n_seg exceeds 2^31 - 1", &flat_all))) return rc;
-  if (kalman_segments_lds_bytes(m, p) > LDS_LIMIT || kalman_segments_grad_lds_bytes(m, p) > LDS_LIMIT)
-    return fail(DSGE_ERR_TOO_LARGE, "segmented gradient: LDS budget exceeded");
-  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
-  const size_t S = (size_t)n_seg, mm = (size_t)m * m, qw = q.diag() ? (size_t)k : (size_t)k * k, tm = (size_t)T_len * m;
+  const SegmentedProblem s{T, R, q, obs, a0, P0, shift, seg_start, n_seg, batch, m, k};
+  const size_t S = (size_t)n_seg, mm = (size_t)m * m, qw = s.q_width(), tm = (size_t)T_len * m;
   // per draw: the stored forward pass and the accumulators of Tbar and Gbar (Tbar's are counted also when the caller's T_bar serves)
   const size_t per_draw = (2 * tm * m + 2 * tm + 2 * S * mm) * sizeof(double);
-  const size_t fit = scratch_limit_bytes / per_draw;
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const int chunk = chunk_for(scratch_limit_bytes, per_draw, batch);
   const size_t cf = (size_t)chunk * S;
-  const bool gather = !P0 && n_seg > 1;
-  double *RQR = nullptr, *Qx = nullptr, *T0 = nullptr, *G0 = nullptr, *P0s = nullptr, *Tb = nullptr, *Gb = nullptr;
-  double *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
-  ScratchLayout lay;
-  lay.add(&RQR, cf * mm);
-  if (!q.batched()) lay.add(&Qx, cf * qw);
-  if (gather) {
-    lay.add(&T0, chunk * mm);
-    lay.add(&G0, chunk * mm);
-  }
-  if (!P0) lay.add(&P0s, chunk * mm);
-  if (!T_bar) lay.add(&Tb, cf * mm);
-  lay.add(&Gb, cf * mm);
-  lay.add(&ap, chunk * tm);
-  lay.add(&af, chunk * tm);
-  lay.add(&pp, chunk * tm * m);
-  lay.add(&pf, chunk * tm * m);
-  if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
-  // (a shared Q repeats with period S: its first nb * S rows serve every chunk)
-  if (!q.batched() && (rc = launch_segment_rows(Qx, Q, cf, (int)qw, n_seg, 1, st))) return rc;
+  double *Tb = nullptr, *Gb = nullptr, *ap = nullptr, *af = nullptr, *pp = nullptr, *pf = nullptr;
+  SegmentChain ch;
+  if ((rc = ch.declare(s, chunk, "segmented gradient", kalman_segments_grad_lds_bytes(m, p)))) return rc;
+  if (!T_bar) ch.lay.add(&Tb, cf * mm);
+  ch.lay.add(&Gb, cf * mm);
+  ch.lay.add(&ap, chunk * tm);
+  ch.lay.add(&af, chunk * tm);
+  ch.lay.add(&pp, chunk * tm * m);
+  ch.lay.add(&pf, chunk * tm * m);
+  if ((rc = ch.reserve(s, st))) return rc;
   // every cotangent the sweep adds to, or writes for healthy draws only, starts from zero: a failed draw keeps the zeros
   const size_t fa = (size_t)batch * S;
   if (T_bar) HIP_TRY(hipMemsetAsync(T_bar, 0, sizeof(double) * fa * mm, st));
@@ -813,35 +798,20 @@ int dsge_kalman_logp_segments_grad_batched(const double* T, const double* R, con
   if (P0_bar) HIP_TRY(hipMemsetAsync(P0_bar, 0, sizeof(double) * (size_t)batch * mm, st));
   auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
   for (int c0 = 0; c0 < batch; c0 += chunk) {
-    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
-    const size_t o = (size_t)c0, fo = o * S, nf = (size_t)nb * S;
-    const double *Tc = T + fo * mm, *Rc = R + fo * m * k, *P0c = P0 ? P0 + o * mm : nullptr;
-    const ShockCov qe = q.batched() ? q.at(fo, k) : ShockCov{Qx, q.diag() ? DSGE_Q_DIAG_BATCHED : DSGE_Q_FULL_BATCHED};
+    const size_t o = (size_t)c0, fo = o * S;
+    const SegmentedProblem c = s.at(o, chunk_draws(batch, c0, chunk));
     int32_t* sc = status_io + o;
-    if ((rc = assemble_rqr(Rc, qe, (int)nf, m, k, RQR, nullptr, st))) return rc;
-    if (!P0c) {
-      const double* Ts = Tc;
-      double* Gs = RQR;
-      if (gather) {
-        if ((rc = launch_segment_rows(T0, Tc, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
-        if ((rc = launch_segment_rows(G0, RQR, (size_t)nb, (int)mm, nb, n_seg, st))) return rc;
-        Ts = T0;
-        Gs = G0;
-      }
-      if ((rc = assemble_p0_from_rqr(Ts, Gs, nb, m, P0s, sc, false, st))) return rc;
-      P0c = P0s;
-    }
-    const ObsModel oc = obs.at(fo, m);
-    if ((rc = launch_kalman_segments_grad_forward(Tc, RQR, P0c, a0 ? a0 + o * m : nullptr, shift ? shift + fo * m : nullptr, oc,
-                                                  seg_start, n_seg, nb, m, logp_out + o, ap, af, pp, pf, sc, st)))
+    if ((rc = ch.run(c, sc, st))) return rc;
+    // (the forward pass: logp alone goes to the caller, the moments of every period into scratch)
+    if ((rc = launch_kalman_segments_store(c, ch.RQR, ch.P0, logp_out + o, nullptr, ap, af, pp, pf, nullptr, nullptr, nullptr, nullptr, 0,
+                                           sc, st)))
       return rc;
     double* Tbc = T_bar ? T_bar + fo * mm : Tb;
-    if (!T_bar) HIP_TRY(hipMemsetAsync(Tb, 0, sizeof(double) * nf * mm, st));
-    if ((rc = launch_kalman_segments_grad(Tc, shift ? shift + fo * m : nullptr, oc, seg_start, n_seg, nb, m, P0 != nullptr, ap, af, pp,
-                                          pf, Tbc, Gb, at(Z_bar, fo * p * m), at(d_bar, fo * p), at(h_bar, fo * p),
+    if (!T_bar) HIP_TRY(hipMemsetAsync(Tb, 0, sizeof(double) * c.flat() * mm, st));
+    if ((rc = launch_kalman_segments_grad(c, ap, af, pp, pf, Tbc, Gb, at(Z_bar, fo * p * m), at(d_bar, fo * p), at(h_bar, fo * p),
                                           at(shift_bar, fo * m), at(a0_bar, o * m), at(P0_bar, o * mm), sc, st)))
       return rc;
-    if ((rc = launch_kalman_segments_grad_rq(Gb, Rc, qe, (int)nf, n_seg, m, k, at(R_bar, fo * m * k), at(Q_bar, fo * qw),
+    if ((rc = launch_kalman_segments_grad_rq(Gb, c.R, ch.qe, (int)c.flat(), n_seg, m, k, at(R_bar, fo * m * k), at(Q_bar, fo * qw),
                                              logp_out + o, sc, st)))
       return rc;
   }
@@ -864,12 +834,10 @@ int dsge_simulation_smoother_batched(const double* T, const double* R, const dou
   if (batch == 0 || n_paths == 0 || T_len == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   if (!(rank_tol > 0.0)) rank_tol = 1e-10;
-  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
   // per draw: the per-step filter outputs of the smoother entry (an upper bound: the means of y are not stored here), and x+,
   // a*_pred, a*_filt of every path
   const size_t tm = (size_t)T_len * m, ptm = (size_t)n_paths * tm, per_draw = (2 * tm * m + 2 * tm + 3 * ptm) * sizeof(double);
-  size_t fit = scratch_limit_bytes / per_draw;
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const int chunk = chunk_for(scratch_limit_bytes, per_draw, batch);
   const size_t mm = (size_t)chunk * m * m, img = (size_t)chunk * smoother_image_doubles(m);
   double *RQR = nullptr, *P0 = nullptr, *U = nullptr, *UT = nullptr, *UR = nullptr, *pp = nullptr, *pf = nullptr;
   double *xp = nullptr, *asp = nullptr, *asf = nullptr, *ll = nullptr;
@@ -892,7 +860,7 @@ int dsge_simulation_smoother_batched(const double* T, const double* R, const dou
   const long long eps_path = (long long)T_len * k, eps_draw = eps_batched ? n_paths * eps_path : 0;
   const long long eta_draw = eta_batched ? (long long)n_paths * T_len * p : 0, x0_draw = x0_batched ? (long long)n_paths * m : 0;
   for (int c0 = 0; c0 < batch; c0 += chunk) {
-    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const int nb = chunk_draws(batch, c0, chunk);
     const size_t o = (size_t)c0;
     const double *Tc = T + o * m * m, *Rc = R + o * m * k;
     const ShockCov qc = q.at(o, k);
@@ -960,8 +928,8 @@ int dsge_irf_batched(const double* T, const double* R, const double* S, int s_ba
 static constexpr size_t PRUNED_SCRATCH_BYTES = (size_t)1 << 30;
 static int pruned_run(const PrunedProblem& p, int batch, const double* eps, const double* xf0, const double* xs0, const double* imp,
                       const int32_t* status, double* x_out, double* xf_out, double* xs_out, double* girf_out, hipStream_t st) {
-  const size_t pd = pruned_panel_doubles(p.n, p.s, p.k), fit = PRUNED_SCRATCH_BYTES / (pd * sizeof(double));
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const size_t pd = pruned_panel_doubles(p.n, p.s, p.k);
+  const int chunk = chunk_for(PRUNED_SCRATCH_BYTES, pd * sizeof(double), batch);
   double* panel = nullptr;
   ScratchLayout lay;
   lay.add(&panel, (size_t)chunk * pd);
@@ -969,7 +937,7 @@ static int pruned_run(const PrunedProblem& p, int batch, const double* eps, cons
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   const size_t n = p.n, s = p.s, k = p.k, sim = (size_t)p.n_paths * p.n_steps * n, gi = (size_t)p.c * p.n_steps * n;
   for (int c0 = 0; c0 < batch; c0 += chunk) {
-    const int nb = batch - c0 < chunk ? batch - c0 : chunk;
+    const int nb = chunk_draws(batch, c0, chunk);
     const size_t o = (size_t)c0;
     PrunedProblem q = p;
     q.T += o * n * n; q.R += o * n * k; q.gyy += o * n * s * s; q.gyu += o * n * s * k; q.guu += o * n * k * k; q.gss += o * n;
@@ -1071,11 +1039,9 @@ int dsge_spectral_moments_batched(const double* T, const double* R, const double
   if ((rc = ensure_device())) return rc;
   if (batch == 0) return DSGE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
   const size_t dim = Z ? p : m, nf = (size_t)n_grid / 2 + 1, dd = dim * dim;
   const size_t per_draw = acov_out ? 2 * nf * dd * sizeof(double) : sizeof(int32_t);
-  const size_t fit = scratch_limit_bytes / per_draw;
-  const int chunk = fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+  const int chunk = chunk_for(scratch_limit_bytes, per_draw, batch);
   double* F = nullptr;
   int32_t* flag = nullptr;
   ScratchLayout lay;
@@ -1084,7 +1050,7 @@ int dsge_spectral_moments_batched(const double* T, const double* R, const double
   if ((rc = lay.reserve(g_scratch_pool, st))) return rc;
   for (int c0 = 0; c0 < batch; c0 += chunk) {
     const size_t o = (size_t)c0;
-    s.batch = batch - c0 < chunk ? batch - c0 : chunk;
+    s.batch = chunk_draws(batch, c0, chunk);
     if ((rc = launch_spectral(s, T + o * m * m, R + o * m * k, q.at(o, k), Z && z_batched ? Z + o * p * m : Z,
                               Hdiag && h_batched ? Hdiag + o * p : Hdiag, gain, status_io ? status_io + o : nullptr, flag, F,
                               acov_out ? acov_out + o * (n_lags + 1) * dd : nullptr,

@@ -142,6 +142,42 @@ struct ShockCov {
   size_t elems(int batch, int k) const { return (size_t)(batched() ? batch : 1) * k * (diag() ? 1 : k); }
   ShockCov at(size_t c0, int k) const { return ShockCov{batched() ? Q + c0 * elems(1, k) : Q, mode}; }
 };
+// The filter problem across dated breaks (dsge_kalman_seg.hpp), as the likelihood, the smoother and the gradient receive it.  The
+// segment axis stands behind the draw axis: T, R, shift and the per-draw members of q and obs are [batch][S] problems, the shared
+// members of q and obs [S] ones; a0, P0: [batch].  a0, P0 and shift may be null; seg_start: HOST list of S entries, already checked
+struct SegmentedProblem {
+  const double *T, *R;
+  ShockCov q;
+  ObsModel obs;
+  const double *a0, *P0, *shift;
+  const int32_t* seg_start;
+  int n_seg, batch, m, k;
+  size_t flat() const { return (size_t)batch * n_seg; }                      // (draw, segment) problems
+  size_t q_width() const { return q.diag() ? (size_t)k : (size_t)k * k; }    // doubles of one Q
+  // the same description for the nb draws from c0 on: the per-draw members move by c0, the per-(draw, segment) ones by c0 * S
+  SegmentedProblem at(size_t c0, int nb) const {
+    SegmentedProblem c = *this;
+    const size_t fo = c0 * n_seg, mm = (size_t)m * m;
+    c.T += fo * mm;
+    c.R += fo * m * k;
+    c.q = q.at(fo, k);
+    c.obs = obs.at(fo, m);
+    if (a0) c.a0 += c0 * m;
+    if (P0) c.P0 += c0 * mm;
+    if (shift) c.shift += fo * m;
+    c.batch = nb;
+    return c;
+  }
+};
+
+// An entry that runs its batch in contiguous chunks of draws under the caller's scratch limit (0 = 2 GiB): the draws of a chunk at
+// per_draw_bytes of scratch each (at least one, at most the batch), and the draws of the chunk that starts at c0
+inline int chunk_for(size_t scratch_limit_bytes, size_t per_draw_bytes, int batch) {
+  if (scratch_limit_bytes == 0) scratch_limit_bytes = (size_t)2 << 30;
+  const size_t fit = scratch_limit_bytes / per_draw_bytes;
+  return fit < 1 ? 1 : (fit > (size_t)batch ? batch : (int)fit);
+}
+inline int chunk_draws(int batch, int c0, int chunk) { return batch - c0 < chunk ? batch - c0 : chunk; }
 
 int ensure_device();  // lazy check for a gfx950 device: nothing touches HIP before the first call
 // The fused solve + filter pipeline of ONE batch on ONE stream: what dsge_solve_kalman_logp_batched runs when it does not
@@ -282,11 +318,10 @@ int launch_kalman(const double* T, double* RQR, double* P0, int p0_valid, const 
                   int rerun_all = 0);  // 1: every launch is a second pass -- only the draws flagged DSGE_ST_INTERNAL_RERUN are filtered
 int launch_kalman_outputs(const double* T, const double* RQR, const double* P0, const ObsModel& o, int batch, int m, double* ll,
                           double* a_pred, double* a_filt, double* p_pred, double* p_filt, int full_cov, int32_t* status, hipStream_t st);
-// launch_kalman_seg.hip (dsge_kalman_seg.hpp): the filter across dated breaks.  T, RQR: [batch][S][m][m]; of o: Z, d, Hdiag with a
-// segment axis behind the draw axis; seg_start: HOST list, already checked; a0, shift, ll, a_last, P_last may be null
-int launch_kalman_segments(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
-                           const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* logp, double* ll,
-                           double* a_last, double* P_last, int32_t* status, hipStream_t st);
+// launch_kalman_seg.hip (dsge_kalman_seg.hpp): the filter across dated breaks.  Of s: T, a0, shift, obs, seg_start and the sizes;
+// RQR: [batch][S][m][m]; P0: [batch][m][m], the caller's or the chain's; ll, a_last, P_last may be null
+int launch_kalman_segments(const SegmentedProblem& s, const double* RQR, const double* P0, double* logp, double* ll, double* a_last,
+                           double* P_last, int32_t* status, hipStream_t st);
 size_t kalman_segments_lds_bytes(int m, int p);
 // dst[r][0 .. width-1] = src[(r % mod) * mul][0 .. width-1], r = 0 .. rows-1: a shared [S][width] repeated per draw (mod = S, mul = 1),
 // segment 0 of every draw out of [batch][S][width] (mod = rows, mul = S)
@@ -301,29 +336,25 @@ int launch_kalman_smoother(const double* T, const double* R, const ShockCov& q, 
 int launch_smoother_basis(const double* T, const double* R, const ShockCov& q, int batch, int m, int k, double rank_tol, double* U,
                           double* UT, double* UR, int32_t* rank, int32_t* status, hipStream_t st);  // the basis alone
 size_t smoother_lds_bytes(int m);
-// the smoother across dated breaks.  launch_kalman_seg_store.hip: the filter of launch_kalman_segments that also stores the moments
-// of every period -- ap_s .. pf_s: [batch][T_len][m] / [batch][T_len][m][m] scratch; ap_o .. pf_o: the caller's, each may be null,
-// covariances as diagonals or full by full_cov.  launch_smooth.hip: the bases and the backward pass over that scratch -- T, R, U, UT,
-// UR: [batch][S] problems; q: a *_BATCHED layout over batch * S; rank, status_flat: [batch * S] scratch
-int launch_kalman_segments_store(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
-                                 const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* ll, double* ap_s,
-                                 double* af_s, double* pp_s, double* pf_s, double* ap_o, double* af_o, double* pp_o, double* pf_o,
-                                 int full_cov, int32_t* status, hipStream_t st);
+// launch_kalman_seg_store.hip: the filter of launch_kalman_segments that also stores the moments of every period, the forward pass
+// of the smoother and of the gradient across dated breaks -- logp, ll: may be null; ap_s .. pf_s: [batch][T_len][m] /
+// [batch][T_len][m][m] scratch; ap_o .. pf_o: the caller's, each may be null, covariances as diagonals or full by full_cov.
+// launch_smooth.hip: the bases and the backward pass of the smoother over that scratch -- T, R, U, UT, UR: [batch][S] problems; q: a
+// *_BATCHED layout over batch * S; rank, status_flat: [batch * S] scratch
+int launch_kalman_segments_store(const SegmentedProblem& s, const double* RQR, const double* P0, double* logp, double* ll,
+                                 double* ap_s, double* af_s, double* pp_s, double* pf_s, double* ap_o, double* af_o, double* pp_o,
+                                 double* pf_o, int full_cov, int32_t* status, hipStream_t st);
 int launch_kalman_smoother_segments(const double* T, const double* R, const ShockCov& q, const int32_t* seg_start, int n_seg, int batch,
                                     int m, int k, int T_len, double rank_tol, double* U, double* UT, double* UR, int32_t* rank,
                                     int32_t* status_flat, const double* a_pred, const double* a_filt, const double* p_pred,
                                     const double* p_filt, double* a_s, double* p_s, double* e_s, int full_cov, int32_t* status,
                                     hipStream_t st);
-// launch_kalman_seg_grad.hip (dsge_kalman_seg_grad.hpp): the gradient of the likelihood across dated breaks.  The storing forward
-// pass with logp; the reverse sweep over its scratch (Tbar: [batch][S][m][m] zeroed, the caller's or scratch; Gbar: scratch; the
-// other cotangents: the caller's, zeroed, each may be null); R_bar, Q_bar of the flattened batch * S from Gbar (q: a *_BATCHED
-// layout over it), zeros and logp = -inf for a failed draw
+// launch_kalman_seg_grad.hip (dsge_kalman_seg_grad.hpp): the gradient of the likelihood across dated breaks.  The reverse sweep over
+// the scratch of launch_kalman_segments_store (of s: T, shift, obs, seg_start, the sizes, and whether P0 is the caller's; Tbar:
+// [batch][S][m][m] zeroed, the caller's or scratch; Gbar: scratch; the other cotangents: the caller's, zeroed, each may be null);
+// R_bar, Q_bar of the flattened batch * S from Gbar (q: a *_BATCHED layout over it), zeros and logp = -inf for a failed draw
 size_t kalman_segments_grad_lds_bytes(int m, int p);
-int launch_kalman_segments_grad_forward(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
-                                        const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* logp,
-                                        double* ap_s, double* af_s, double* pp_s, double* pf_s, int32_t* status, hipStream_t st);
-int launch_kalman_segments_grad(const double* T, const double* shift, const ObsModel& o, const int32_t* seg_start, int n_seg, int batch,
-                                int m, int p0_given, const double* ap, const double* af, const double* pp, const double* pf,
+int launch_kalman_segments_grad(const SegmentedProblem& s, const double* ap, const double* af, const double* pp, const double* pf,
                                 double* Tbar, double* Gbar, double* Zbar, double* dbar, double* hbar, double* shbar, double* a0bar,
                                 double* P0bar, const int32_t* status, hipStream_t st);
 int launch_kalman_segments_grad_rq(const double* Gbar, const double* R, const ShockCov& q, int flat, int n_seg, int m, int k,
@@ -573,6 +604,18 @@ inline dsge::FilterConv filter_conv(double jitter) {
   cv.ll_mode = o.ll_constant;
   cv.mask_d = o.mask_d ? 1 : 0;
   return cv;
+}
+// what every kernel of the family across dated breaks reads of the problem, into its argument struct (KsegArgs, KsegStoreArgs,
+// KsegGradArgs): the list of starts padded with 0x7fffffff, as kseg_start reads it
+template <typename A>
+void fill_segment_args(A& a, const SegmentedProblem& s) {
+  const ObsModel& o = s.obs;
+  a.T = s.T; a.shift = s.shift; a.Z = o.Z; a.d = o.d; a.Hdiag = o.Hdiag; a.y = o.y;
+  a.batch = s.batch; a.m = s.m; a.p = o.p; a.T_len = o.T_len; a.n_seg = s.n_seg;
+  a.z_batched = o.z_batched; a.d_batched = o.d_batched; a.h_batched = o.h_batched;
+  for (int i = 0; i < DSGE_MAX_SEGMENTS; ++i) a.seg_start[i] = i < s.n_seg ? s.seg_start[i] : 0x7fffffff;
+  a.cv = filter_conv(o.jitter);
+  a.missing_fill = o.missing_fill;
 }
 
 // ---- Argument checks, each written ONCE for a device entry (dsge_api.hip) and its host twin (api_host.hip): both run them before

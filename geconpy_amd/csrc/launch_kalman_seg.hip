@@ -18,17 +18,12 @@ int launch_segment_rows(double* dst, const double* src, size_t rows, int width, 
 
 size_t kalman_segments_lds_bytes(int m, int p) { return dsge::kseg_lds_doubles(m, p) * sizeof(double); }
 
-int launch_kalman_segments(const double* T, const double* RQR, const double* P0, const double* a0, const double* shift,
-                           const ObsModel& o, const int32_t* seg_start, int n_seg, int batch, int m, double* logp, double* ll,
-                           double* a_last, double* P_last, int32_t* status, hipStream_t st) {
+int launch_kalman_segments(const SegmentedProblem& s, const double* RQR, const double* P0, double* logp, double* ll, double* a_last,
+                           double* P_last, int32_t* status, hipStream_t st) {
   dsge::KsegArgs a{};
-  a.T = T; a.RQR = RQR; a.P0 = P0; a.a0 = a0; a.shift = shift; a.Z = o.Z; a.d = o.d; a.Hdiag = o.Hdiag; a.y = o.y; a.logp = logp;
-  a.ll = ll; a.a_last = a_last; a.P_last = P_last; a.status = status; a.batch = batch; a.m = m; a.p = o.p; a.T_len = o.T_len;
-  a.n_seg = n_seg; a.z_batched = o.z_batched; a.d_batched = o.d_batched; a.h_batched = o.h_batched;
-  for (int s = 0; s < DSGE_MAX_SEGMENTS; ++s) a.seg_start[s] = s < n_seg ? seg_start[s] : 0x7fffffff;
-  a.cv = filter_conv(o.jitter);
-  a.missing_fill = o.missing_fill;
-  return launch_with_lds(dsge::kalman_seg_kernel<false>, batch, dsge::KSEG_THREADS, kalman_segments_lds_bytes(m, o.p), st, a,
+  fill_segment_args(a, s);
+  a.RQR = RQR; a.P0 = P0; a.a0 = s.a0; a.logp = logp; a.ll = ll; a.a_last = a_last; a.P_last = P_last; a.status = status;
+  return launch_with_lds(dsge::kalman_seg_kernel<false>, s.batch, dsge::KSEG_THREADS, kalman_segments_lds_bytes(s.m, s.obs.p), st, a,
                          "segmented filter: LDS budget exceeded");
 }
 

@@ -170,6 +170,17 @@ def test_every_front_end_every_subset_and_every_chunking_has_the_same_bits():
     _same_bits(_run(c, scratch_limit_bytes=2 * per), want, every)  # chunks of two draws and one
     nop0 = dict(c, P0=None)  # (the Lyapunov adjoint, chunked)
     _same_bits(_run(nop0, scratch_limit_bytes=2 * per), _run(nop0), every)
+    # a shared Q, repeated per draw once for all chunks, with P0 from the gathered segment 0 of every chunk, the partial last one included
+    for q_mode in ("diag", "full"):
+        s = K.build("dense5", nb=3, seg_start=(0, 4, 9), n=12, q_mode=q_mode)
+        assert s["P0"] is None and s["q"].shape[0] == 3 and s["T"].shape[:3] == (3, 3, 5)
+        whole = _run(s)
+        assert not whole["status"].any()
+        _same_bits(_run(s, scratch_limit_bytes=2 * batched.segment_gradient_scratch_bytes_per_draw(5, 12, 3)), whole,
+                   _keys(s) + ("logp", "status"))
+        like = batched.kalman_logp_segments_batched(s["T"], s["R"], s["q"], s["Z"], s["y"], s["seg_start"], Hdiag=s["H"], d=s["d"],
+                                                    q_mode=q_mode, outputs=("logp",))
+        assert np.array_equal(whole["logp"], like["logp"]) and np.array_equal(whole["status"], like["status"])
     eng = LogpEngine(0)
     dev = lambda x: None if x is None else eng.to_device(x)  # noqa: E731
     head = [dev(c[key]) for key in ("T", "R", "q", "Z", "y")]

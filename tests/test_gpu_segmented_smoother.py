@@ -141,6 +141,16 @@ def test_every_front_end_subset_and_chunking_has_the_same_bits():
     _same_bits(_run(K.build("sw17", nb=3), scratch_limit_bytes=2 * batched.segment_smoother_scratch_bytes_per_draw(17, 8, 3)),
                _run(K.build("sw17", nb=3)))  # chunks of two draws and one
     assert per_draw == 8 * (2 * 8 * m * m + 2 * 8 * m + 3 * S * 48 * 50)
+    # a shared Q, repeated per draw once for all chunks, with P0 from the gathered segment 0 of every chunk, the partial last one included
+    for q_mode in ("diag", "full"):
+        s = K.build("dense5", nb=3, seg_start=(0, 4, 9), n=12, q_mode=q_mode)
+        assert s["P0"] is None and s["q"].shape[0] == 3 and s["T"].shape[:3] == (3, 3, 5)
+        whole = _run(s)
+        assert not whole["status"].any()
+        _same_bits(_run(s, scratch_limit_bytes=2 * batched.segment_smoother_scratch_bytes_per_draw(5, 12, 3)), whole)
+        like = batched.kalman_logp_segments_batched(s["T"], s["R"], s["q"], s["Z"], s["y"], s["seg_start"], Hdiag=s["H"], d=s["d"],
+                                                    q_mode=q_mode)
+        assert np.array_equal(whole["ll"], like["ll"]) and np.array_equal(whole["status"], like["status"])
     eng = LogpEngine(0)
     dev = lambda x: None if x is None else eng.to_device(x)  # noqa: E731
     head = [dev(c[key]) for key in ("T", "R", "q", "Z", "y")]

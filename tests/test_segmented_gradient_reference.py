@@ -170,12 +170,18 @@ def test_no_new_kernel_uses_scratch_memory(tmp_path):
 
     from geconpy_amd import build
 
-    out = subprocess.run([build._hipcc(), *build.CFLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", str(tmp_path / "a.o"),
-                          os.path.join(build.CSRC, "launch_kalman_seg_grad.hip")], cwd=build.CSRC, capture_output=True, text=True, check=True)
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    sizes = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)
-    assert len(names) == len(sizes)
-    found = dict(zip(names, sizes))
-    for kernel in ("kalman_seg_grad_kernel", "kseg_grad_rq_kernel", "kalman_seg_kernelILb1E"):
-        assert [n for n in found if kernel in n], (kernel, sorted(found))
-    assert all(size == "0" for size in found.values()), found
+    # the reverse sweep and R_bar / Q_bar in the gradient's unit, the storing forward pass in the unit the smoother launches it from
+    found = {}
+    for unit in ("launch_kalman_seg_grad.hip", "launch_kalman_seg_store.hip"):
+        out = subprocess.run([build._hipcc(), *build.CFLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", str(tmp_path / "a.o"),
+                              os.path.join(build.CSRC, unit)], cwd=build.CSRC, capture_output=True, text=True, check=True)
+        names = re.findall(r"Function Name: (\S+)", out.stderr)
+        sizes = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)
+        assert len(names) == len(sizes)
+        found[unit] = dict(zip(names, sizes))
+    grad, store = found["launch_kalman_seg_grad.hip"], found["launch_kalman_seg_store.hip"]
+    for kernel in ("kalman_seg_grad_kernel", "kseg_grad_rq_kernel"):
+        assert [n for n in grad if kernel in n], (kernel, sorted(grad))
+    assert [n for n in store if "kalman_seg_kernelILb1E" in n], sorted(store)
+    assert not [n for n in grad if "kalman_seg_kernel" in n], sorted(grad)  # one kernel, compiled once
+    assert all(size == "0" for unit in found.values() for size in unit.values()), found
