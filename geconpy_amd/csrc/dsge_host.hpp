@@ -717,6 +717,10 @@ inline int check_second_order(int batch, int n, int k, const ObsModel& o, const 
   if (rc) return rc;
   if (s < 1 || s > 24) return fail(DSGE_ERR_INVALID, "second order: n_state out of range (1..24)");
   if (l < 0 || l > n || u < s || u > n) return fail(DSGE_ERR_INVALID, "second order: n_lead / n_ret out of range");
+  // (the limits of launch_second_order, here as well: a refused call must not have run the first-order solver into status_out,
+  //  T_out and R_out.  The set-up kernel's LDS limit alone stays with the launcher, which owns the layout)
+  if (u > 40 || k > 12 || k > s) return fail(DSGE_ERR_INVALID, "second order: sizes out of range (s <= u <= 40, k <= min(s, 12))");
+  if (2 * u + s * (s + 1) / 2 > 208) return fail(DSGE_ERR_INVALID, "second order: pruned state 2 u + s (s + 1) / 2 exceeds 208");
   if (solver != DSGE_SOLVER_CYCLE_REDUCTION && solver != DSGE_SOLVER_GENSYS)
     return fail(DSGE_ERR_INVALID, "second order: solver must be cycle reduction or gensys");
   for (int i = 0; i < s; ++i)
@@ -725,6 +729,8 @@ inline int check_second_order(int batch, int n, int k, const ObsModel& o, const 
     if (L[i] < 0 || L[i] >= n) return fail(DSGE_ERR_INVALID, "lead_idx out of range");
   for (int i = 0; i < u; ++i)
     if (U[i] < 0 || U[i] >= n) return fail(DSGE_ERR_INVALID, "ret_idx out of range");
+  for (int i = 0; i < s; ++i)
+    if (U[i] != S[i]) return fail(DSGE_ERR_INVALID, "second order: the retained variables must list the states first");
   return DSGE_SUCCESS;
 }
 // the dynamics entries (DSGE_ERR_TOO_LARGE: a well-formed call beyond a capacity)

@@ -122,8 +122,9 @@ def test_generated_theta_kernels_fuzz(seed):
 @pytest.mark.parametrize("seed", [1, 2])
 def test_second_order_fuzz(seed):
     """The second-order path at random sizes / structures (tools/fuzz_second_order.py: 4..34 variables, pruned states up to
-    208, observed non-states, missing observations, samples that reach the steady-state switch): coefficients to 1e-9 and the
-    pruned quasi-likelihood to 1e-8 against oracle/second_order.py (parity unpinned against the reference, which raises)."""
+    208, up to 12 shocks and 8 observables, observed non-states, rows with two loadings, missing observations, samples that reach the
+    steady-state switch): every coefficient to 1e-9 of its block's largest reference entry and the pruned quasi-likelihood to 1e-8
+    against oracle/second_order.py (parity unpinned against the reference, which raises)."""
     import fuzz_second_order
 
     assert fuzz_second_order.run(seed, 10, verbose=False) == 0

@@ -1,6 +1,7 @@
 """GPU box: the second-order path (coefficients + pruned-state-space likelihood) at random sizes and structures against
-oracle/second_order.py: 4..34 variables, 1..14 states (pruned state up to 208), observed states and non-states, missing
-observations, short and long samples (the steady-state switch), with and without an observation intercept."""
+oracle/second_order.py: 4..34 variables, 1..14 states (pruned state up to 208), up to 12 shocks and 8 observables, observed states
+and non-states, rows with one or two loadings, missing observations, short and long samples (the steady-state switch), with and without
+an observation intercept.  Coefficients: every entry to 1e-9 of its block's largest reference entry; logp: 1e-8 relative."""
 import os
 import sys
 
@@ -18,10 +19,13 @@ def run(seed, trials, verbose=True):
         n = int(rng.integers(4, 35))
         ns = int(rng.integers(1, min(15, max(2, n // 2)) + 0))
         nl = int(rng.integers(1, max(2, n // 3)))
-        k = int(rng.integers(1, min(ns, 6) + 1))
-        p = int(rng.integers(1, min(5, n) + 1))
+        k = int(rng.integers(1, min(ns, 12) + 1))
+        p = int(rng.integers(1, min(8, n) + 1))
         obs = np.sort(rng.choice(n, size=p, replace=False))
-        u = ns + int(np.sum(obs >= ns))  # the generator puts the states first
+        second = np.where(rng.random(p) < 0.5, rng.integers(0, n, p), -1)  # a second loading per row with probability 1/2
+        second[second == obs] = -1
+        loaded = np.union1d(obs, second[second >= 0])
+        u = ns + int(np.sum(loaded >= ns))  # the generator puts the states first
         if 2 * u + ns * (ns + 1) // 2 > 208 or u > 40:
             continue
         nb = 2
@@ -36,6 +40,8 @@ def run(seed, trials, verbose=True):
         q = rng.uniform(0.5e-4, 4e-4, (nb, k))
         Z = np.zeros((p, n))
         Z[np.arange(p), obs] = rng.choice([1.0, 0.5, 2.0], size=p)
+        rows = np.flatnonzero(second >= 0)
+        Z[rows, second[rows]] = rng.choice([0.25, -0.5, 1.0], size=len(rows))
         T_len = int(rng.choice([12, 40, 120]))
         y = rng.normal(0, 0.02, (T_len, p))
         if T_len > 12:
@@ -46,10 +52,10 @@ def run(seed, trials, verbose=True):
         out = batched.second_order_logp_batched(A, B, C, D, idx, val, q, Z, y, d=d, Hdiag=H, tol=1e-12, return_solution=True)
         for i in range(nb):
             r = so.solve_second_order_logp(A[i], B[i], C[i], D[i], idx, val[i], np.diag(q[i]), Z, y, H=np.diag(H), d=d, tol=1e-12)
-            errs = {key: float(np.abs(out[key][i] - r["sol"][key]).max() / max(1.0, np.abs(r["sol"][key]).max()))
+            errs = {key: float(np.abs(out[key][i] - r["sol"][key]).max() / np.abs(r["sol"][key]).max())
                     for key in ("g_yy", "g_yu", "g_uu", "g_ss")}
             el = abs(out["logp"][i] - r["logp"]) / abs(r["logp"])
-            if out["status"][i] != 0 or max(errs.values()) > 1e-9 or not el <= 1e-8:
+            if out["status"][i] != 0 or not max(errs.values()) <= 1e-9 or not el <= 1e-8:  # (NaN -- a zero reference block -- counts)
                 bad += 1
                 if verbose:
                     print("MISMATCH", dict(n=n, ns=ns, nl=nl, k=k, p=p, T_len=T_len, draw=i), int(out["status"][i]), errs, el)
