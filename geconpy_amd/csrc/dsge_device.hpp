@@ -431,6 +431,45 @@ __device__ __forceinline__ double dpp_move_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// A double moved between lanes by a DPP control under which EVERY lane has a source lane (quad_perm, row_mirror, row_half_mirror,
+// row_ror, all rows and banks enabled): no old value exists to keep, so none is handed over -- dpp_move_f64 zeroes the destination
+// first (two v_mov_b32 per double) for the controls that leave lanes without a source.  Same two v_mov_b32_dpp, same values.
+template <int CTRL>
+__device__ __forceinline__ double dpp_perm_f64(double v) {
+  static_assert((CTRL >= 0 && CTRL <= 0xFF) || CTRL == 0x140 || CTRL == 0x141 || (CTRL >= 0x121 && CTRL <= 0x12F),
+                "a control that gives every lane a source");
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// max over the 64 lanes of doubles that are >= +0 and not NaN, where only the lanes with (lane & 3) == (lane >> 4) may hold anything but
+// +0: the diagonal positions of the 4 x 4 tile layout (dsge_mfma4.hpp: lane l holds row l >> 4 and column l & 3 of its block).  Two
+// row rotations (by 4 and by 8 lanes) leave the maximum of 16-lane row k in every lane of that row with (lane & 3) == k, lane 17 k among
+// them; the four row maxima are read from there and folded in.  A maximum of such values is exact in any order: the same double as
+// wave_max_u32 on the high word followed by wave_max_u32 on the low words of the lanes that reach it, in four lane moves, eight
+// read-lanes and six v_max_f64 instead of twelve DPP maxima with a wait state in front of each.  Wave-uniform result; every lane
+// active.  The maxima are assembly: fmax() puts a canonicalising v_max_f64 in front of every operand it cannot prove quiet, and these
+// operands come out of integer moves.  Wait states: the lane moves and read-lanes are builtins, the compiler keeps theirs (it takes an
+// assembly statement's outputs as VALU writes); the last statement opens with the two a VALU read of a scalar register needs behind
+// the read-lane that wrote it (gfx940 and later), which it does not add in front of assembly text.
+__device__ __forceinline__ double tile_diag_wave_max(double v) {
+  double t = dpp_perm_f64<0x124>(v);  // row_ror:4
+  asm("v_max_f64 %0, %1, %2" : "=v"(v) : "v"(v), "v"(t));
+  t = dpp_perm_f64<0x128>(v);  // row_ror:8
+  asm("v_max_f64 %0, %1, %2" : "=v"(v) : "v"(v), "v"(t));
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  double r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, 17 * k), __builtin_amdgcn_readlane(lo, 17 * k));
+  double mx;
+  asm("s_nop 1\n\tv_max_f64 %0, %1, %2\n\tv_max_f64 %0, %0, %3\n\tv_max_f64 %0, %0, %4\n\tv_max_f64 %0, %0, %5"
+      : "=&v"(mx)
+      : "v"(v), "s"(r[0]), "s"(r[1]), "s"(r[2]), "s"(r[3]));
+  return mx;
+}
+
 // ---- row broadcasts of a double inside the consuming instruction (gfx90a and later: the FP64 ALU's only DPP control) -----------
 // row_newbcast:J hands every lane the value lane J of its own 16-lane row holds (tools/dpp_probe/dpp_probe.hip checks that, the
 // in-place form d == row_src included, and gives the issue costs).  hipcc does not select these forms (update_dpp on the halves is

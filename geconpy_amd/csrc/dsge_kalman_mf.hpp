@@ -436,10 +436,15 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         double pscale = 0.0;
 #pragma unroll
         for (int g = 0; g < NG; ++g) pscale = fmax(pscale, (rr[g] == cc[g]) ? fabs(Pt[g]) : 0.0);
-        const unsigned hi = (unsigned)__double2hiint(pscale), lo = (unsigned)__double2loint(pscale);
-        const unsigned mhi = wave_max_u32(hi);
-        const unsigned mlo = wave_max_u32(hi == mhi ? lo : 0u);
-        pm = __hiloint2double((int)mhi, (int)mlo);
+        if constexpr (!LEAN) {
+          // (rr == cc only where lane & 3 == lane >> 4, every other lane holds +0; fmax has dropped a NaN diagonal)
+          pm = tile_diag_wave_max(pscale);
+        } else {  // (seven groups: the scale in a scalar register pair, the vector pair would be eight bytes of scratch more)
+          const unsigned hi = (unsigned)__double2hiint(pscale), lo = (unsigned)__double2loint(pscale);
+          const unsigned mhi = wave_max_u32(hi);
+          const unsigned mlo = wave_max_u32(hi == mhi ? lo : 0u);
+          pm = __hiloint2double((int)mhi, (int)mlo);
+        }
       }
       // ---- (b) innovation v[r8] and row r8 of F = Zm P Zm' + Hm + jitter I, replicated over the eight 8-lane groups ----------
       const double c_r = obs ? r_zv : 0.0;
@@ -452,8 +457,10 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
       for (int q = 0; q < 8; ++q) {
         const double tq = (q & 1) ? fr2[q >> 1].y : fr2[q >> 1].x;
         const double wq = ((omask >> q) & 1ull) ? 1.0 : 0.0;  // wave-uniform
-        const double f = (c_r * tq) * wq;
-        fr[q] = (q == r8) ? f + dg : f;
+        // F[r8][q] = (c_r tq) wq, + dg on the diagonal, as ONE fused multiply-add with the addend selected: on the diagonal the
+        // contraction the compiler made of `f + dg` anyway (now spelled out), elsewhere x wq + (-0.0) == x wq bit for bit for every x
+        // (a zero product keeps its sign against -0.0, everything else is the rounded product) -- a multiply per column less
+        fr[q] = fma(c_r * tq, wq, (q == r8) ? dg : -0.0);
       }
       if constexpr (REC) {
         if (lane < 8) {
@@ -485,7 +492,9 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         const bool is_j = (r8 == j);
         const double ci = is_j ? 0.0 : fr[j] * inv;
         pivot_row_bcast_update<j, j == 0>(fr, ci);
-        fr[j] = is_j ? 1.0 : -ci;
+        // fr[j] = is_j ? 1.0 : -ci.  The low word is ci's own (ci is +0.0 in the pivot lane, and 1.0 ends in 32 zero bits): one
+        // select, on the high word, instead of two
+        fr[j] = __hiloint2double(is_j ? 0x3ff00000 : (__double2hiint(ci) ^ (int)0x80000000), __double2loint(ci));
         inv_own = is_j ? inv : inv_own;
         int e;
         step_mant *= frexp(pj, &e);
@@ -558,9 +567,9 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
         Ks[i * PS + r8] = kk;
         Vs[i * PS + r8] = -fma(cv.jit_V, kk, obs ? pzo[ps] : 0.0);
         double part = kk * v_r;
-        part += dpp_move_f64<0xB1, 0xf>(part);
-        part += dpp_move_f64<0x4E, 0xf>(part);
-        part += dpp_move_f64<0x141, 0xf>(part);
+        part += dpp_perm_f64<0xB1>(part);   // quad_perm [1,0,3,2]
+        part += dpp_perm_f64<0x4E>(part);   // quad_perm [2,3,0,1]
+        part += dpp_perm_f64<0x141>(part);  // row_half_mirror: the other quad of the 8-lane group
         af[(r8 == 0) ? i : NR] = avi[ps] + part;  // (entry NR: a slot for the lanes that own nothing -- no branch)
       }
       wave_sync();  // #2
@@ -643,7 +652,9 @@ __global__ __launch_bounds__(64, KMF_WAVES) void kalman_mf_kernel(
                                       [&](int g, double d) {
                                         // column m: the predicted mean (Q is zero there); everything else outside m x m: padding
                                         const bool is_mean = fold_a && cc[g] == m && rr[g] < m && up[g];
-                                        avd[is_mean ? rr[g] : NR] = is_mean ? d : 0.0;  // (entry NR: a slot of its own for the rest)
+                                        // (entry NR: a slot of its own for the rest, which nothing reads -- whatever they hold;
+                                        //  seven groups: the zero, that form is four bytes of scratch less there)
+                                        avd[is_mean ? rr[g] : NR] = (LEAN && !is_mean) ? 0.0 : d;
                                         Pt[g] = inm[g] ? d : 0.0;
                                       });
       KMF_STORE_PZT();
